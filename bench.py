@@ -17,8 +17,12 @@ node, so for N > 1 the default is **strong** scaling: `--records` is the GLOBAL 
 records on every GPU instead (global = records x N).  At N = 1 the two coincide.  The JSON line names the mode, the
 per-rank shard sizes, the slowest and fastest rank's kernel times and the time of the one cross-GPU exchange.
 
-On one GPU a short second leg runs BASELINE configs[2] (bc_len = umi_len = 32, the maximum width) and is reported
-under `config2_32_32`; it is outside the timed region of the headline value.
+A plain run does only what the headline needs: it places and fills the arrays, warms up, times the steps, writes the
+outputs of the last step when `--dump-outputs DIR` is given, and prints the line.  Everything else it measures or checks
+runs with `--full` only: the first-placement figure, the copy ceiling, the full round-trip verification and the global
+totals, and on one GPU the side legs — BASELINE configs[2] (bc_len = umi_len = 32, the maximum width, reported under
+`config2_32_32`), the sort, the file -> result legs and the CPU baseline.  All of them are outside the timed region of
+the headline value.
 
 Output: one JSON line on rank 0.
 """
@@ -42,15 +46,23 @@ def parse(argv=None):
                         "exit code.  Default: WORLD_SIZE, or 1")
     p.add_argument("--steps", type=int, default=10)
     p.add_argument("--warmup", type=int, default=2)
+    p.add_argument("--full", action="store_true",
+                   help="also run everything beyond the headline: first-placement figure, copy ceiling, round-trip verification, "
+                        "global totals, and on one GPU the (32,32), sort, e2e legs and the CPU baseline (the --no-* options below "
+                        "still drop single legs)")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="after the timed steps, write what the last step computed to DIR/<name>.npy (float32 / float64): the "
+                        "barcode, UMI and index columns of the decode and the re-encoded records, at a fixed seeded sample of "
+                        "record indices (sample_index.npy); rank r > 0 adds _rank<r> to every name")
     p.add_argument("--records", type=float, default=1e9,
                    help="strong scaling: records in the whole stream; weak scaling: records per GPU")
     p.add_argument("--scaling", choices=["strong", "weak"], default="strong",
                    help="strong (default): --records is the global count, range-sharded over the ranks (configs[3]); "
                         "weak: --records per GPU")
-    p.add_argument("--no-wide-leg", action="store_true", help="skip the (32,32) leg (configs[2]) on one GPU")
+    p.add_argument("--no-wide-leg", action="store_true", help="skip the (32,32) leg (configs[2]) on one GPU (with --full)")
     p.add_argument("--wide-records", type=float, default=0, help="records of the (32,32) leg (0 = same as --records)")
-    p.add_argument("--no-sort-leg", action="store_true", help="skip the sort + per-barcode aggregation leg on one GPU")
-    p.add_argument("--no-e2e-leg", action="store_true", help="skip the file -> result (PCIe-inclusive) leg on one GPU")
+    p.add_argument("--no-sort-leg", action="store_true", help="skip the sort + per-barcode aggregation leg on one GPU (with --full)")
+    p.add_argument("--no-e2e-leg", action="store_true", help="skip the file -> result (PCIe-inclusive) leg on one GPU (with --full)")
     p.add_argument("--e2e-records", type=float, default=1e8, help="records of the e2e leg's file (24 B each)")
     p.add_argument("--bgzf-large-records", type=float, default=5e8,
                    help="records of the e2e leg's LARGE BGZF file (ibu_load_bgzf_to_device with its decoder launched ahead of the copies, beside "
@@ -68,8 +80,8 @@ def parse(argv=None):
                         "others freed) BEFORE the timed region; every probe is printed.  0 (default) = as many as fit, at most "
                         "16: 3-5 for the arrays of 1e9 records on one GPU, 16 for the shards of an 8-GPU run.  1 = no bench-side "
                         "probing: on one GPU the arrays then come from plain ibu_device_alloc calls under the LIBRARY's default "
-                        "option (alloc_probe_tries = auto since round 5), on several GPUs from plain hipMalloc.  Every run also "
-                        "reports value_first_placement (plain hipMalloc) and, on one GPU, value_library_default_placement.  "
+                        "option (alloc_probe_tries = auto since round 5), on several GPUs from plain hipMalloc.  A run on one GPU "
+                        "also reports value_library_default_placement, a --full run value_first_placement (plain hipMalloc).  "
                         "See place_leg()")
     # rehearsal of the N>1 code path on a box with fewer GPUs than ranks (never used by the driver):
     p.add_argument("--backend", default="nccl", choices=["nccl", "gloo"], help="gloo: collectives on CPU tensors")
@@ -236,7 +248,7 @@ def traffic_from_profile(bc_len, umi_len, n):
         return None, None
 
 
-def place_leg(make, tries, set_bytes, torch, dev, sharers=1, ctx=None, library_default=False):
+def place_leg(make, tries, set_bytes, torch, dev, records, sharers=1, ctx=None, library_default=False, first_placement=True):
     """Placement probing — since round 3 a LIBRARY call, not bench-side logic.  On this part the rate of a read+write
     streaming kernel depends on WHERE the driver put the arrays' physical pages: the same kernel on the same GPU runs
     9.4 ... 11.3 ms from one allocation to the next (profiles/README.md: pool survey, r02_placement_pmc, r02_ag — physical
@@ -250,22 +262,29 @@ def place_leg(make, tries, set_bytes, torch, dev, sharers=1, ctx=None, library_d
     `value_first_placement`; (1b, one GPU) the same from plain `ibu_device_alloc` calls under the library's DEFAULT option (auto
     probing: `value_library_default_placement`); (2) unless --placement-tries 1, every array is allocated again through the probing
     call with as many candidates as fit, and the faster of that set and the library-default set (same decode + encode probe) is
-    what the timed region runs on.  All of it happens before the timed region; every candidate's time is in the line (`placement`)."""
+    what the timed region runs on.  All of it happens before the timed region; every candidate's time is in the line (`placement`).
+
+    Step (1) never decides which arrays the timed region runs on (its set is freed before that choice), so it runs only when
+    `first_placement` is set (bench.py --full); `records` is the n of the sets `make` builds."""
     free_b, _ = torch.cuda.mem_get_info(dev)
-    if ctx is not None:
-        ctx.set_option("alloc_probe_tries", 1)           # plain hipMalloc: what the library did by default until round 4
-    first = make(1)
-    if ctx is not None:
-        ctx.set_option("alloc_probe_tries", 0)           # back to the library's default (auto)
-    first_probe = first.probe()
-    bytes_per_launch = first.n * (24 + first.bc_len + first.umi_len + 8)
-    info = {"tries": 1, "first_placement_probe_ms_decode_encode": [round(v, 3) for v in first_probe],
-            "first_placement_decode_frac": round(bytes_per_launch / (first_probe[0] * 1e-3) / 1e9 / HBM_PEAK_GBPS, 4),
-            "first_placement_records_per_s": first.n / ((first_probe[0] + first_probe[1]) * 1e-3)}
+    info = {"tries": 1}
+    first = None
+    if first_placement:
+        if ctx is not None:
+            ctx.set_option("alloc_probe_tries", 1)       # plain hipMalloc: what the library did by default until round 4
+        first = make(1)
+        if ctx is not None:
+            ctx.set_option("alloc_probe_tries", 0)       # back to the library's default (auto)
+        first_probe = first.probe()
+        bytes_per_launch = first.n * (24 + first.bc_len + first.umi_len + 8)
+        info.update(first_placement_probe_ms_decode_encode=[round(v, 3) for v in first_probe],
+                    first_placement_decode_frac=round(bytes_per_launch / (first_probe[0] * 1e-3) / 1e9 / HBM_PEAK_GBPS, 4),
+                    first_placement_records_per_s=first.n / ((first_probe[0] + first_probe[1]) * 1e-3))
     if library_default:
         # (1b) what a caller of ibu_device_alloc gets under the library's DEFAULT option (round 5: "alloc_probe_tries" = 0 = auto —
         # arrays of 1 GiB and more draw up to four candidates when three fit): the same five arrays from plain ctx.alloc calls
-        first.free()
+        if first is not None:
+            first.free()
         t0 = time.perf_counter()
         try:
             first = make(1)
@@ -276,6 +295,7 @@ def place_leg(make, tries, set_bytes, torch, dev, sharers=1, ctx=None, library_d
             ctx.set_option("alloc_probe_tries", 0)
         alloc_s = time.perf_counter() - t0
         dprobe = first.probe()
+        bytes_per_launch = first.n * (24 + first.bc_len + first.umi_len + 8)
         info.update(library_default_probe_ms_decode_encode=[round(v, 3) for v in dprobe],
                     library_default_decode_frac=round(bytes_per_launch / (dprobe[0] * 1e-3) / 1e9 / HBM_PEAK_GBPS, 4),
                     library_default_records_per_s=first.n / ((dprobe[0] + dprobe[1]) * 1e-3),
@@ -283,7 +303,7 @@ def place_leg(make, tries, set_bytes, torch, dev, sharers=1, ctx=None, library_d
                     library_default_option='alloc_probe_tries = 0 (auto): ibu_device_alloc of >= 1 GiB draws up to 4 candidates when 3 fit')
     # 0 = auto: as many candidates as fit beside the arrays already chosen, at most 16.  The largest array (24 B/record)
     # sets the bound: the other arrays of the set stay allocated while it is probed.
-    biggest = max(24 * first.n, 1)
+    biggest = max(24 * records, 1)
     # On one GPU the library-default set STAYS while the probed set is built (two sets resident: 168 GB of the 288 at 1e9 records),
     # and the faster of the two — by the same decode + encode probe, before the timed region — is the one the headline runs on: the
     # per-array probe (a write and a read over each array alone) removes bad draws but does not rank good ones (profiles/README.md
@@ -293,8 +313,14 @@ def place_leg(make, tries, set_bytes, torch, dev, sharers=1, ctx=None, library_d
     fit = int((free_b * 0.94 / max(sharers, 1) - resident) // biggest) + 1
     tries = max(1, min(tries or 16, fit, 16))
     if tries == 1:
+        if first is None:                                # no first set was built: the plain arrays step (1) would have made
+            if ctx is not None:
+                ctx.set_option("alloc_probe_tries", 1)
+            first = make(1)
+            if ctx is not None:
+                ctx.set_option("alloc_probe_tries", 0)
         return first, info
-    if hold is None:
+    if hold is None and first is not None:
         first.free()
     first = None
     leg = make(tries)
@@ -832,6 +858,32 @@ class Leg:
                 raise SystemExit("round trip encode(decode(x)) != x")
         return red, ok
 
+    def dump(self, out_dir, seed, k, suffix=""):
+        """What the last step left for a caller — the decoded barcode / UMI / index columns and the re-encoded records — at `k`
+        record indices drawn with a fixed seed (the first and the last record always among them), as .npy files: bytes as
+        float32, the index column as float64 (exact below 2^53).  Outside every timed region."""
+        import numpy as np
+
+        torch, n = self.torch, self.n
+        sel = np.unique(np.concatenate([[0, n - 1], np.random.default_rng(seed).integers(0, n, size=max(k - 2, 0))]))
+        it = torch.as_tensor(sel, dtype=torch.int64, device=self.dev)
+
+        def rows(buf, width):
+            t = torch.as_tensor(buf, device=self.dev)[:n * width].view(n, width)
+            return t.index_select(0, it).cpu().numpy()
+
+        arrays = {
+            "sample_index": sel.astype(np.float64),
+            "barcode_ascii": rows(self.bc, self.bc_len).astype(np.float32),
+            "umi_ascii": rows(self.umi, self.umi_len).astype(np.float32),
+            "index": rows(self.idx, 8).view(np.uint64).reshape(-1).astype(np.float64),
+            "records_reencoded": rows(self.back, 24).astype(np.float32),
+        }
+        os.makedirs(out_dir, exist_ok=True)
+        for name, a in arrays.items():
+            np.save(os.path.join(out_dir, f"{name}{suffix}.npy"), a)
+        return sorted(arrays)
+
     def free(self):
         for b in (self.recs, self.back, self.bc, self.umi, self.idx):
             if b is not None:
@@ -891,9 +943,12 @@ def main():
             dist.barrier()
 
     leg, placement = place_leg(lambda tries: Leg(ctx, torch, dev, st, args.seed, first, n, bc_len, umi_len, tries), args.placement_tries,
-                               n * (48 + bc_len + umi_len + 8), torch, dev, sharers=world if args.share_gpu else 1, ctx=ctx,
-                               library_default=(world == 1))
+                               n * (48 + bc_len + umi_len + 8), torch, dev, n, sharers=world if args.share_gpu else 1, ctx=ctx,
+                               library_default=(world == 1), first_placement=args.full)
     elapsed, dec_ms, enc_ms = leg.timed(args.steps, args.warmup, barrier)
+    dumped = None
+    if args.dump_outputs:                            # before anything below overwrites the columns (copy_ceiling does)
+        dumped = leg.dump(args.dump_outputs, args.seed, max(2, (1 << 17) // world), "" if rank == 0 else f"_rank{rank}")
     per_rank = [[float(n), dec_ms, enc_ms, elapsed]]
     if use_dist:
         t = torch.tensor([elapsed], dtype=torch.float64, device=coll_dev)
@@ -904,28 +959,30 @@ def main():
         per_rank = [p.tolist() for p in parts]
         elapsed = float(t.item())
 
-    copy_GBps = leg.copy_ceiling()
-    red, verified = leg.verify(not args.no_verify)
-    # the one cross-GPU exchange: global count + wrapping field sums (4 x i64 over RCCL); timed on its second call
-    # (the first pays the communicator's lazy set-up)
-    g = sharding.global_totals(red, device=coll_dev, force=args.force_dist)
-    torch.cuda.synchronize()
-    barrier()
-    t0 = time.perf_counter()
-    g = sharding.global_totals(red, device=coll_dev, force=args.force_dist)
-    torch.cuda.synchronize()
-    allreduce_ms = (time.perf_counter() - t0) * 1e3
-    tot = [g["count"]] + g["sum"]
-    assert tot[0] == n_global
-    assert tot[3] == sharding.expected_index_sum(n_global)  # index column is 0..n_global-1
+    copy_GBps = verified = allreduce_ms = tot = None
+    if args.full:
+        copy_GBps = leg.copy_ceiling()
+        red, verified = leg.verify(not args.no_verify)
+        # the one cross-GPU exchange: global count + wrapping field sums (4 x i64 over RCCL); timed on its second call
+        # (the first pays the communicator's lazy set-up)
+        g = sharding.global_totals(red, device=coll_dev, force=args.force_dist)
+        torch.cuda.synchronize()
+        barrier()
+        t0 = time.perf_counter()
+        g = sharding.global_totals(red, device=coll_dev, force=args.force_dist)
+        torch.cuda.synchronize()
+        allreduce_ms = (time.perf_counter() - t0) * 1e3
+        tot = [g["count"]] + g["sum"]
+        assert tot[0] == n_global
+        assert tot[3] == sharding.expected_index_sum(n_global)  # index column is 0..n_global-1
 
     wide = None
-    if world == 1 and not args.no_wide_leg and (bc_len, umi_len) != (32, 32):
+    if args.full and world == 1 and not args.no_wide_leg and (bc_len, umi_len) != (32, 32):
         # BASELINE configs[2]: maximum width, encode+decode on one GPU — a short leg outside the headline's timed region
         leg.free()
         nw = int(args.wide_records) or n
         wl, w_placement = place_leg(lambda tries: Leg(ctx, torch, dev, st, 0x1B00002, 0, nw, 32, 32, tries), min(args.placement_tries or 2, 2),
-                                    nw * (48 + 72), torch, dev, ctx=ctx)
+                                    nw * (48 + 72), torch, dev, nw, ctx=ctx)
         w_steps = max(1, min(args.steps, 5))
         w_el, w_dec, w_enc = wl.timed(w_steps, 1, barrier)
         _, w_ok = wl.verify(not args.no_verify)
@@ -942,7 +999,7 @@ def main():
         wl.free()
 
     sort_leg = None
-    if world == 1 and not args.no_sort_leg:
+    if args.full and world == 1 and not args.no_sort_leg:
         # SURVEY 8f-2 / 8f-3 on the same box: device sort by (barcode, umi, index) of the headline's records and the per-barcode
         # aggregation of the result — outside the headline's timed region, never part of `value`
         leg.free()
@@ -960,7 +1017,7 @@ def main():
             sort_leg["contexts_rehearsal"] = {"error": f"{type(e).__name__}: {e}"}
 
     e2e = None
-    if world == 1 and not args.no_e2e_leg:
+    if args.full and world == 1 and not args.no_e2e_leg:
         # BASELINE.md §3 / configs[4]: file -> result with PCIe and the host in the path; outside the timed region, never `value`
         leg.free()
         torch.cuda.empty_cache()
@@ -986,10 +1043,6 @@ def main():
         out = {
             "metric": "records/s, fused 2-bit decode+encode of 24-byte IBU records (HBM-resident)",
             "value": n_global * args.steps / elapsed,
-            # what a caller that takes plain allocations gets (one decode + one encode on the first set of arrays, this rank, before
-            # any probing: placement.first_placement_*), scaled to the job like `value`; `value` itself is measured on arrays from
-            # ibu_device_alloc_probed unless --placement-tries 1.  Compare THIS number with round 1 / BENCH_r01.
-            "value_first_placement": placement["first_placement_records_per_s"] * (n_global / max(n, 1)),
             # the same on arrays from plain ibu_device_alloc calls under the library's default option (auto probing): what a caller
             # that does nothing about placement gets since round 5
             "value_library_default_placement": (placement["library_default_records_per_s"] * (n_global / max(n, 1))
@@ -1016,26 +1069,34 @@ def main():
                                 "wall_ms_per_step": {"min": min(p[3] for p in per_rank) / args.steps * 1e3,
                                                      "max": max(p[3] for p in per_rank) / args.steps * 1e3}},
             "launch_gap_ms_per_step": elapsed / args.steps * 1e3 - (dec_ms + enc_ms),
-            "allreduce_ms": allreduce_ms,
             "kernel_GBps": {"decode": achieved, "encode": dec_bytes / (enc_ms * 1e-3) / 1e9},
             "roofline": {
                 "bound": "hbm", "kernel": f"ibu_k_decode<{bc_len},{umi_len}>", "achieved": achieved, "peak": HBM_PEAK_GBPS, "unit": "GB/s",
                 "frac": achieved / HBM_PEAK_GBPS, "traffic": traffic, "traffic_source": traffic_src,
                 "bytes_per_record": bpr, "records_per_launch": n,
-                "copy_ceiling": copy_GBps, "frac_of_copy_ceiling": achieved / copy_GBps,
             },
             "gpu": {"name": torch.cuda.get_device_name(dev), "uuid": str(getattr(torch.cuda.get_device_properties(dev), "uuid", ""))},
-            "verified_roundtrip": verified,
             "placement": placement,
-            "global_count": tot[0],
+            "full": args.full,
         }
+        if dumped:
+            out["outputs"] = {"dir": args.dump_outputs, "files": [f"{a}.npy" for a in dumped]}
+        if args.full:
+            # what a caller that takes plain allocations gets (one decode + one encode on the first set of arrays, this rank, before
+            # any probing: placement.first_placement_*), scaled to the job like `value`; `value` itself is measured on arrays from
+            # ibu_device_alloc_probed unless --placement-tries 1.  Compare THIS number with round 1 / BENCH_r01.
+            out["value_first_placement"] = placement["first_placement_records_per_s"] * (n_global / max(n, 1))
+            out["allreduce_ms"] = allreduce_ms
+            out["roofline"].update(copy_ceiling=copy_GBps, frac_of_copy_ceiling=achieved / copy_GBps)
+            out["verified_roundtrip"] = verified
+            out["global_count"] = tot[0]
         if wide:
             out["config2_32_32"] = wide
         if sort_leg:
             out["sort_leg"] = sort_leg
         if e2e:
             out["e2e"] = e2e
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(args)
         print(json.dumps(out), flush=True)
         failed = [k for k, leg_ in (("sort_leg", sort_leg), ("e2e", e2e)) if isinstance(leg_, dict) and

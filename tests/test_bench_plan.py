@@ -43,6 +43,16 @@ def test_default_mode_is_strong(monkeypatch):
     assert a.scaling == "strong" and a.records == 1e9 and (a.bc_len, a.umi_len) == (16, 12)
 
 
+def test_plain_run_is_lean_by_default():
+    """Without --full a run measures the headline only; --dump-outputs is off unless a directory is given."""
+    import bench
+
+    a = bench.parse(["--gpus", "1", "--steps", "7", "--warmup", "3"])
+    assert a.full is False and a.dump_outputs is None and (a.steps, a.warmup) == (7, 3)
+    a = bench.parse(["--full", "--dump-outputs", "out_dir"])
+    assert a.full is True and a.dump_outputs == "out_dir"
+
+
 def test_gpus_flag_means_n(monkeypatch):
     """`--gpus N` is honoured or refused, never ignored (VERDICT r03 weak 8): under a launcher it must equal WORLD_SIZE;
     run bare with N > 1 the ranks are started as a child torch.distributed.run on 127.0.0.1."""

@@ -31,7 +31,7 @@ def _torchrun(nproc, script, *args):
 def test_bench_two_ranks_on_one_gpu_strong():
     """Default for N > 1 = BASELINE configs[3]: --records is the WHOLE stream, range-sharded over the ranks."""
     out = _torchrun(2, "bench.py", "--gpus", "2", "--steps", "2", "--warmup", "1", "--records", "100000001", "--backend", "gloo",
-                    "--share-gpu", "--no-cpu-baseline")
+                    "--share-gpu", "--no-cpu-baseline", "--full")
     assert out["n_gpus"] == 2 and out["global_count"] == 100_000_001 and out["verified_roundtrip"] is True
     assert out["scaling"] == "strong" and out["config"]["records_total"] == 100_000_001
     assert out["config"]["records_per_rank"] == [50_000_000, 50_000_001]  # remainder to the last shard (mmap.rs:297-307)
@@ -46,7 +46,7 @@ def test_bench_two_ranks_on_one_gpu_strong():
 
 def test_bench_two_ranks_on_one_gpu_weak():
     out = _torchrun(2, "bench.py", "--gpus", "2", "--steps", "2", "--warmup", "1", "--records", "5e7", "--scaling", "weak",
-                    "--backend", "gloo", "--share-gpu", "--no-cpu-baseline")
+                    "--backend", "gloo", "--share-gpu", "--no-cpu-baseline", "--full")
     assert out["n_gpus"] == 2 and out["global_count"] == 100_000_000 and out["verified_roundtrip"] is True
     assert out["scaling"] == "weak" and out["config"]["records_total"] == 100_000_000
     assert out["config"]["records_per_rank"] == [50_000_000, 50_000_000]
@@ -57,7 +57,7 @@ def test_bench_bare_with_gpus_2_starts_its_own_ranks_or_fails_loudly():
     torch.distributed.run — on this one-GPU box the ranks share cuda:0 over gloo — and the line says n_gpus: 2.  Never a
     silent one-GPU run."""
     r = subprocess.run([sys.executable, "bench.py", "--gpus", "2", "--steps", "1", "--warmup", "1", "--records", "20000001", "--backend", "gloo",
-                        "--share-gpu", "--no-cpu-baseline", "--placement-tries", "1"], capture_output=True, text=True, timeout=900, cwd=ROOT,
+                        "--share-gpu", "--no-cpu-baseline", "--placement-tries", "1", "--full"], capture_output=True, text=True, timeout=900, cwd=ROOT,
                        env={k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")})
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
@@ -70,7 +70,7 @@ def test_bench_one_gpu_line_carries_the_e2e_leg(tmp_path):
     """The driver's N = 1 line: headline + an `e2e` object with the three file -> result rates, each checked against K4 of the
     resident copy inside bench.py (small sizes here: the rates are not asserted)."""
     r = subprocess.run([sys.executable, "bench.py", "--steps", "1", "--warmup", "1", "--records", "3000001", "--no-cpu-baseline", "--no-wide-leg",
-                        "--no-sort-leg", "--placement-tries", "1", "--e2e-records", "700003", "--e2e-dir", str(tmp_path)],
+                        "--no-sort-leg", "--placement-tries", "1", "--e2e-records", "700003", "--e2e-dir", str(tmp_path), "--full"],
                        capture_output=True, text=True, timeout=900, cwd=ROOT,
                        env={k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")})
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
@@ -87,7 +87,7 @@ def test_bench_sort_leg_carries_the_multi_context_rehearsal():
     """The sort leg of the driver's N = 1 line: the three single-GPU sorts, the per-barcode aggregation and the multi-GPU form of
     the sort rehearsed with 8 contexts on this GPU, each checked inside bench.py."""
     r = subprocess.run([sys.executable, "bench.py", "--steps", "1", "--warmup", "1", "--records", "3000001", "--no-cpu-baseline", "--no-wide-leg",
-                        "--no-e2e-leg", "--placement-tries", "1"], capture_output=True, text=True, timeout=900, cwd=ROOT,
+                        "--no-e2e-leg", "--placement-tries", "1", "--full"], capture_output=True, text=True, timeout=900, cwd=ROOT,
                        env={k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")})
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
     out = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][0])
@@ -96,6 +96,38 @@ def test_bench_sort_leg_carries_the_multi_context_rehearsal():
     cr = sl["contexts_rehearsal"]
     assert "error" not in cr and cr["contexts_on_this_gpu"] == 8 and cr["globally_sorted_and_multiset_preserved"] is True, cr
     assert sum(cr["records_per_shard_after"]) == cr["records"] == 3_000_000
+
+
+def test_bench_plain_run_is_the_headline_and_dumps_its_outputs(tmp_path, oracle):
+    """A run without --full: the headline line and nothing beside it; --dump-outputs writes what the last timed step computed at
+    a seeded sample of records, and the sample equals the oracle's decode (and the records themselves) at those indices."""
+    import numpy as np
+
+    n, steps = 3_000_001, 3
+    r = subprocess.run([sys.executable, "bench.py", "--gpus", "1", "--steps", str(steps), "--warmup", "1", "--records", str(n),
+                        "--placement-tries", "1", "--dump-outputs", str(tmp_path)], capture_output=True, text=True, timeout=900, cwd=ROOT,
+                       env={k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")})
+    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
+    lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
+    assert len(lines) == 1, r.stdout
+    out = json.loads(lines[0])
+    assert out["steps"] == steps and out["unit"] == "records/s" and out["higher_is_better"] is True and out["dtype"] == "u64"
+    assert abs(out["value"] - n * steps / (out["ms_per_step"] * steps * 1e-3)) < 1e-6 * out["value"]
+    assert out["full"] is False
+    assert not {"config2_32_32", "sort_leg", "e2e", "cpu_baseline", "value_first_placement", "global_count"} & set(out)
+    files = {p.name for p in tmp_path.iterdir()}
+    assert files == {"sample_index.npy", "barcode_ascii.npy", "umi_ascii.npy", "index.npy", "records_reencoded.npy"}
+    assert sum(p.stat().st_size for p in tmp_path.iterdir()) <= 64 << 20
+    got = {f[:-4]: np.load(tmp_path / f) for f in files}
+    assert all(a.dtype in (np.float32, np.float64) for a in got.values())
+    sel = got["sample_index"].astype(np.int64)
+    assert sel[0] == 0 and sel[-1] == n - 1 and np.all(np.diff(sel) > 0) and len(sel) > 100_000
+    recs = oracle.generate(0x1B00003, 0, n, 16, 12)
+    bc, umi, idx = oracle.decode_records(recs, 16, 12)
+    assert np.array_equal(got["barcode_ascii"], bc.reshape(n, 16)[sel].astype(np.float32))
+    assert np.array_equal(got["umi_ascii"], umi.reshape(n, 12)[sel].astype(np.float32))
+    assert np.array_equal(got["index"], idx[sel].astype(np.float64))
+    assert np.array_equal(got["records_reencoded"], recs.view(np.uint8).reshape(n, 24)[sel].astype(np.float32))
 
 
 @pytest.mark.parametrize("proc", ["reduce", "decode"])

@@ -1,6 +1,6 @@
 #!/bin/bash
 # Evidence run of a round, on the GPU box (gpurun -- 'bash tools/profile_round.sh r02_b'):
-#   1. python bench.py                                        -> <tag>_bench_1e9.json
+#   1. python bench.py --full                                 -> <tag>_bench_1e9.json
 #   2. rocprofv3 --kernel-trace --stats over the same command -> <tag>_bench_1e9_kernel_stats.csv (+ the line it printed)
 #   3. rocprofv3 --kernel-trace --stats over tools/sortbench.py at 1e9 (random index; whitelist barcodes in read order)
 #      -> <tag>_sort_1e9_kernel_stats.csv, <tag>_sort_whitelist_1e9_kernel_stats.csv
@@ -18,7 +18,7 @@ step() { echo "[profile_round] $(date +%T) $*"; }
 largest() { find "$1" -name "$2" -printf '%s %p\n' | sort -rn | head -1 | cut -d' ' -f2-; }
 
 step "bench (unprofiled)"
-python3 bench.py > "$OUT/${TAG}_bench_1e9.json" 2> "$OUT/bench.err" || exit 1
+python3 bench.py --full > "$OUT/${TAG}_bench_1e9.json" 2> "$OUT/bench.err" || exit 1
 
 step "bench under rocprofv3 --kernel-trace --stats"
 # (The default placement probing stays ON: since round 3 it is the library's and times the generator / reduce kernels, not decode,
@@ -27,7 +27,7 @@ step "bench under rocprofv3 --kernel-trace --stats"
 # process would time whatever first placement it drew: 10.17 ms twice in round 3 against 9.36 for the probed headline.)
 # (--no-e2e-leg: that leg launches the same decode / encode instantiations on ring slots and on a 1e8-record copy; in the stats file their
 # short launches would be averaged with the headline's — 89 decode launches of 1.9 ms on average instead of 17 of 9.45, r04_fin's first run)
-rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/prof_bench" -- python3 bench.py --no-cpu-baseline --no-e2e-leg \
+rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/prof_bench" -- python3 bench.py --full --no-cpu-baseline --no-e2e-leg \
   > "$OUT/${TAG}_bench_1e9_under_rocprof.json" 2> "$OUT/prof_bench.err" || exit 1
 cp "$(largest "$OUT/prof_bench" '*kernel_stats.csv')" "$OUT/${TAG}_bench_1e9_kernel_stats.csv"
 
