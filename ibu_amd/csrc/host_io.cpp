@@ -526,6 +526,46 @@ struct RawBytes {
   size_t size() const { return n; }
   void swap(RawBytes& o) { std::swap(p, o.p); std::swap(n, o.n); std::swap(cap, o.cap); }
 };
+// The header of the gzip member at hd (avail bytes from there on), read as a BGZF block: the one rule of both walks
+// (BgzfSource::refill, ibu_bgzf_scan).  RFC 1952 2.3: FEXTRA (which must carry the "BC" subfield, other subfields around it
+// allowed), then FNAME and FCOMMENT (zero-terminated) and FHCRC (the low 16 bits of the CRC-32 of the header in front of it) in
+// that order; BSIZE counts from the member's first byte.  Flag bits 5-7 are refused and FHCRC is checked, as zlib's inflate does.
+enum MemberKind { kMemberBgzf, kMemberNotBgzf, kMemberNeedMore, kMemberBad };
+MemberKind bgzf_member(const uint8_t* hd, size_t avail, size_t* hlen, size_t* bsize_out, const char** why) {
+  if (avail < 12) return kMemberNeedMore;
+  if (!(hd[0] == 0x1f && hd[1] == 0x8b && hd[2] == 8 && (hd[3] & 4))) { *why = "not a BGZF block (a gzip member without the BC extra field)"; return kMemberNotBgzf; }
+  if (hd[3] & 0xE0) { *why = "a gzip member header with reserved flag bits set"; return kMemberBad; }
+  const size_t xlen = (size_t)(hd[10] | (hd[11] << 8));
+  if (avail < 12 + xlen) return kMemberNeedMore;
+  size_t bsize = 0;
+  const uint8_t* extra = hd + 12;
+  for (size_t p = 0; p + 4 <= xlen;) {
+    const size_t slen = (size_t)(extra[p + 2] | (extra[p + 3] << 8));
+    if (extra[p] == 'B' && extra[p + 1] == 'C' && slen == 2 && p + 6 <= xlen) bsize = (size_t)(extra[p + 4] | (extra[p + 5] << 8)) + 1;
+    p += 4 + slen;
+  }
+  *why = "not a BGZF block (no usable BC extra field)";
+  if (bsize < 12 + 2 + xlen + 8) return kMemberNotBgzf;
+  if (avail < bsize) return kMemberNeedMore;
+  size_t p = 12 + xlen;
+  for (int f = 8; f <= 16; f <<= 1) {                  // FNAME, FCOMMENT: inside the block, in front of its trailer
+    if (!(hd[3] & f)) continue;
+    while (p < bsize - 8 && hd[p]) ++p;
+    if (p >= bsize - 8) return kMemberNotBgzf;
+    ++p;
+  }
+  if (hd[3] & 2) {                                     // FHCRC
+    if (p + 2 > bsize - 8) return kMemberNotBgzf;
+    const uint32_t h = (uint32_t)crc32(crc32(0L, Z_NULL, 0), hd, (uInt)p) & 0xFFFF;
+    if (h != (uint32_t)(hd[p] | (hd[p + 1] << 8))) { *why = "a gzip member header whose CRC-16 does not match"; return kMemberBad; }
+    p += 2;
+  }
+  if (p + 2 + 8 > bsize) return kMemberNotBgzf;
+  *hlen = p;
+  *bsize_out = bsize;
+  return kMemberBgzf;
+}
+
 struct BgzfSource : Source {
   std::unique_ptr<Source> inner;
   std::unique_ptr<Source> fallback;   // sequential inflate once a non-BGZF member shows up
@@ -605,20 +645,12 @@ struct BgzfSource : Source {
       const size_t avail = comp_len - comp_pos;
       if (avail == 0) { eof = true; break; }
       const uint8_t* hd = comp.data() + comp_pos;
-      if (avail < 12) { if (inner_eof) pending_err = EPROTO; break; }
-      const bool bgzf_like = hd[0] == 0x1f && hd[1] == 0x8b && hd[2] == 8 && (hd[3] & 4);
-      const size_t xlen = bgzf_like ? (size_t)(hd[10] | (hd[11] << 8)) : 0;
-      size_t bsize = 0;
-      if (bgzf_like) {
-        if (avail < 12 + xlen) { if (inner_eof) pending_err = EPROTO; break; }
-        const uint8_t* extra = hd + 12;
-        for (size_t p = 0; p + 4 <= xlen;) {
-          const size_t slen = (size_t)(extra[p + 2] | (extra[p + 3] << 8));
-          if (extra[p] == 'B' && extra[p + 1] == 'C' && slen == 2 && p + 6 <= xlen) bsize = (size_t)(extra[p + 4] | (extra[p + 5] << 8)) + 1;
-          p += 4 + slen;
-        }
-      }
-      if (!bgzf_like || bsize < 12 + 2 + xlen + 8) {
+      size_t hlen = 0, bsize = 0;
+      const char* why = nullptr;
+      const MemberKind kind = bgzf_member(hd, avail, &hlen, &bsize, &why);
+      if (kind == kMemberNeedMore) { if (inner_eof) pending_err = EPROTO; break; }  // the block is not whole yet / the stream ends inside it
+      if (kind == kMemberBad) { pending_err = EPROTO; break; }
+      if (kind == kMemberNotBgzf) {
         // not a BGZF block: everything not yet parsed goes back in front of the inner source and the sequential
         // decoder takes over from here
         std::unique_ptr<PrefixSource> ps(new PrefixSource);
@@ -628,11 +660,10 @@ struct BgzfSource : Source {
         comp_pos = comp_len;
         break;
       }
-      if (avail < bsize) { if (inner_eof) pending_err = EPROTO; break; }  // the block is not whole yet / the stream ends inside it
       const uint8_t* tr = hd + bsize - 8;
       Block b;
-      b.coff = comp_pos + 12 + xlen;
-      b.clen = bsize - 12 - xlen - 8;
+      b.coff = comp_pos + hlen;
+      b.clen = bsize - hlen - 8;
       b.crc = (uint32_t)tr[0] | ((uint32_t)tr[1] << 8) | ((uint32_t)tr[2] << 16) | ((uint32_t)tr[3] << 24);
       b.isize = (size_t)tr[4] | ((size_t)tr[5] << 8) | ((size_t)tr[6] << 16) | ((size_t)tr[7] << 24);
       if (b.isize > 65536) { pending_err = EPROTO; break; }
@@ -657,12 +688,15 @@ struct BgzfSource : Source {
       pgz::RawInflater& raw = *raws[t];
       for (size_t i = t; i < blocks.size(); i += nt) {
         const Block& b = blocks[i];
-        if (b.isize == 0 && b.clen <= 2) continue;  // empty block (the EOF marker)
+        // every block is inflated, the empty ones too (the EOF marker is "03 00"; "01 00" is refused as zlib refuses it); an
+        // empty block's output pointer must not be NULL even when the whole batch is empty (zlib refuses next_out == NULL)
+        uint8_t none = 0;
+        uint8_t* o = b.isize ? dst.data() + b.ooff : &none;
         int rc;
-        if (use_zlib) rc = inflate_block(&zs, comp.data() + b.coff, b.clen, dst.data() + b.ooff, b.isize, b.crc);
+        if (use_zlib) rc = inflate_block(&zs, comp.data() + b.coff, b.clen, o, b.isize, b.crc);
         else {
           uint32_t crc = 0;
-          rc = raw.inflate(comp.data() + b.coff, b.clen, dst.data() + b.ooff, b.isize, &crc);
+          rc = raw.inflate(comp.data() + b.coff, b.clen, o, b.isize, &crc);
           if (rc == 0 && crc != b.crc) rc = EPROTO;
         }
         if (rc) { rcs[t] = rc; bad_at[t] = i; break; }
@@ -911,24 +945,15 @@ extern "C" int32_t ibu_bgzf_scan(const uint8_t* buf, size_t len, int32_t final, 
   while (pos < len && nb < cap) {
     const size_t avail = len - pos;
     const uint8_t* hd = buf + pos;
-    if (avail < 12) { if (final) rc = err_niffler("the stream ends inside a BGZF block header"); break; }
-    const bool bgzf_like = hd[0] == 0x1f && hd[1] == 0x8b && hd[2] == 8 && (hd[3] & 4);
-    if (!bgzf_like) { rc = err_niffler("not a BGZF block (a gzip member without the BC extra field)"); break; }
-    const size_t xlen = (size_t)(hd[10] | (hd[11] << 8));
-    if (avail < 12 + xlen) { if (final) rc = err_niffler("the stream ends inside a BGZF block header"); break; }
-    size_t bsize = 0;
-    for (size_t p = 0; p + 4 <= xlen;) {
-      const uint8_t* extra = hd + 12;
-      const size_t slen = (size_t)(extra[p + 2] | (extra[p + 3] << 8));
-      if (extra[p] == 'B' && extra[p + 1] == 'C' && slen == 2 && p + 6 <= xlen) bsize = (size_t)(extra[p + 4] | (extra[p + 5] << 8)) + 1;
-      p += 4 + slen;
-    }
-    if (bsize < 12 + 2 + xlen + 8) { rc = err_niffler("not a BGZF block (no usable BC extra field)"); break; }
-    if (avail < bsize) { if (final) rc = err_niffler("the stream ends inside a BGZF block"); break; }
+    size_t hlen = 0, bsize = 0;
+    const char* why = nullptr;
+    const MemberKind kind = bgzf_member(hd, avail, &hlen, &bsize, &why);
+    if (kind == kMemberNeedMore) { if (final) rc = err_niffler("the stream ends inside a BGZF block"); break; }
+    if (kind != kMemberBgzf) { rc = err_niffler(why); break; }
     const uint8_t* tr = hd + bsize - 8;
     ibu_inflate_block_t b;
-    b.comp_offset = pos + 12 + xlen;
-    b.comp_len = (uint32_t)(bsize - 12 - xlen - 8);
+    b.comp_offset = pos + hlen;
+    b.comp_len = (uint32_t)(bsize - hlen - 8);
     b.crc32 = (uint32_t)tr[0] | ((uint32_t)tr[1] << 8) | ((uint32_t)tr[2] << 16) | ((uint32_t)tr[3] << 24);
     b.out_len = (uint32_t)tr[4] | ((uint32_t)tr[5] << 8) | ((uint32_t)tr[6] << 16) | ((uint32_t)tr[7] << 24);
     b.reserved = 0;

@@ -409,15 +409,13 @@ extern "C" int32_t ibu_load_bgzf_shard_to_device(ibu_ctx_t* ctx, const char* pat
       pgz::RawInflater raw;                                // 2. the header: the leading blocks, inflated here
       std::vector<uint8_t> in;
       while (lead_bytes < IBU_HEADER_SIZE && lead < B.size()) {
-        const ibu_inflate_block_t& b = B[lead];
-        if (b.out_len) {
-          in.assign(map + b.comp_offset, map + b.comp_offset + b.comp_len);
-          in.resize(b.comp_len + 512, 0);                  // the decoder may read (not use) a few bytes behind the stream
-          uint32_t crc = 0;
-          const int e = raw.inflate(in.data(), b.comp_len, head + lead_bytes, b.out_len, &crc);
-          if (e == ENOMEM) return err_io(ENOMEM, "inflate");
-          if (e || crc != b.crc32) return err_niffler("a BGZF block does not inflate to its announced length and CRC-32");
-        }
+        const ibu_inflate_block_t& b = B[lead];            // (an empty block, too: "01 00" is refused as the Reader refuses it)
+        in.assign(map + b.comp_offset, map + b.comp_offset + b.comp_len);
+        in.resize(b.comp_len + 512, 0);                    // the decoder may read (not use) a few bytes behind the stream
+        uint32_t crc = 0;
+        const int e = raw.inflate(in.data(), b.comp_len, head + lead_bytes, b.out_len, &crc);
+        if (e == ENOMEM) return err_io(ENOMEM, "inflate");
+        if (e || crc != b.crc32) return err_niffler("a BGZF block does not inflate to its announced length and CRC-32");
         lead_bytes += b.out_len;
         ++lead;
       }

@@ -491,7 +491,9 @@ int32_t ibu_barcode_counts(ibu_ctx_t* ctx, const void* d_sorted_records, size_t 
  * headers and trailers: the blocks can be found without inflating them, their COMPRESSED bytes can cross the PCIe link (half the
  * bytes of a records file) and every block can go to a wave of its own.
  * ibu_bgzf_scan (host): walks the block headers in buf[0, len) and describes up to `cap` whole blocks: comp_offset / comp_len = the
- * raw deflate bytes inside the member, out_len and crc32 from its trailer, out_offset = the sum of the out_len before it.
+ * raw deflate bytes inside the member (behind FEXTRA and, when their flags are set, FNAME, FCOMMENT and FHCRC), out_len and crc32
+ * from its trailer, out_offset = the sum of the out_len before it.  Reserved flag bits and a wrong header CRC-16 are refused as
+ * zlib refuses them.
  * *consumed = bytes of buf the described blocks cover (the next call starts there), *out_bytes = their uncompressed size.  A
  * member that is not a BGZF block, or one that is cut off with final != 0: IBU_ERR_NIFFLER (the blocks in front of it are
  * described, *n_blocks says how many); a block that is not whole yet with final == 0 ends the walk quietly.
