@@ -10,6 +10,7 @@
 #include <chrono>
 
 #include <cstddef>
+#include "bgzf_plan.hpp"
 #include "ctx.hpp"
 
 using namespace ibu;
@@ -155,7 +156,7 @@ extern "C" int32_t ibu_ctx_set_option(ibu_ctx_t* ctx, const char* key, int64_t v
     return IBU_OK;
   }
   if (strcmp(key, "inflate_one_launch") == 0) {          // a test knob: the block count from which a BGZF load launches its decoder ahead of the copies
-    if (value < 0 || value > (int64_t)ctx->cfg.cus * 3 * 64) return err_arg("inflate_one_launch must be 0 (default) .. one round of the decoder's short form");
+    if (value < 0 || value > (int64_t)inflate_one_round(ctx->cfg.cus)) return err_arg("inflate_one_launch must be 0 (default) .. one round of the decoder's short form");
     ctx->inflate_one_launch = (size_t)value;
     return IBU_OK;
   }

@@ -20,6 +20,7 @@
 #include <sys/stat.h>
 #include <unistd.h>
 
+#include <algorithm>
 #include <atomic>
 #include <chrono>
 #include <condition_variable>
@@ -28,10 +29,10 @@
 #include <thread>
 #include <vector>
 
+#include "bgzf_plan.hpp"
 #include "ctx.hpp"
 #include "host_io.hpp"
 #include "kernels.h"
-#include "pgzip.hpp"
 
 using namespace ibu;
 
@@ -266,13 +267,285 @@ extern "C" int32_t ibu_load_to_device(ibu_ctx_t* ctx, const char* path, const ib
 // ------------------------------------------------------------------------------------------
 // load_to_vec of a BGZF file, inflated on the device (k_inflate.hip): the COMPRESSED bytes cross the link
 // ------------------------------------------------------------------------------------------
-// The result is what ibu_load_to_device gives for the gunzipped file (load_to_vec, reader.rs:510-535: header read and validated,
-// (length - 32) % 24 != 0 -> InvalidMapSize).  The file is mapped; a thread walks its block headers (ibu_bgzf_scan: no inflating; large
-// files in eight pieces side by side) and inflates the blocks that hold the 32 header bytes on the host, while the calling thread
-// already sends the file through the pinned ring into a device buffer; the device then inflates every block straight to its place in
-// the records (the launch policy: further down).  A block is accepted exactly as the host
-// decoder accepts it; anything else — a member that is not a BGZF block, a file that ends inside one, a block that does not inflate
-// to its announced length and CRC — is IBU_ERR_NIFFLER, as from the Reader.
+// The result is what ibu_load_to_device gives for the gunzipped file (load_to_vec, reader.rs:510-535).  A block is accepted exactly as the
+// host decoder accepts it; anything else — a member that is not a BGZF block, a file that ends inside one, a block that does not inflate
+// to its announced length and CRC — is IBU_ERR_NIFFLER, as from the Reader (the index: bgzf_plan.cpp).
+namespace {
+
+struct Mapping {
+  const uint8_t* p = nullptr;
+  size_t n = 0;
+  ~Mapping() { if (p) munmap(const_cast<uint8_t*>(p), n); }
+};
+int32_t map_file(const char* path, Mapping* m) {
+  int fd = ::open(path, O_RDONLY | O_CLOEXEC);
+  if (fd < 0) return err_io(errno, path);
+  struct stat sb;
+  if (fstat(fd, &sb)) { const int e = errno; close(fd); return err_io(e, "metadata"); }
+  if (sb.st_size == 0) { close(fd); return err_io(0, "read header"); }
+  void* mp = mmap(nullptr, (size_t)sb.st_size, PROT_READ, MAP_PRIVATE, fd, 0);
+  const int map_errno = errno;
+  close(fd);
+  if (mp == MAP_FAILED) return err_io(map_errno, "mmap");
+  (void)madvise(mp, (size_t)sb.st_size, MADV_SEQUENTIAL);
+  m->p = static_cast<const uint8_t*>(mp);                 // (fields, not a temporary Mapping: its destructor would unmap)
+  m->n = (size_t)sb.st_size;
+  return IBU_OK;
+}
+
+// The staging on the device — the compressed file; the descriptors and status words behind it once their number is known — is the
+// context's and grows only (freeing 1.2 GB and allocating it again cost a call of 1e8 records 12 of its 104 ms).
+int32_t grow_stage(ibu_ctx* ctx, size_t need) {
+  if (need <= ctx->inflate_stage_bytes) return IBU_OK;
+  void* p = nullptr;
+  hipError_t e = ctx_malloc(ctx, &p, need);
+  if (e != hipSuccess) return hip_fail(e, "hipMalloc");
+  if (ctx->d_inflate_stage) {                              // (the bytes copied so far move along)
+    e = hipMemcpyAsync(p, ctx->d_inflate_stage, ctx->inflate_stage_bytes, hipMemcpyDeviceToDevice, ctx->copy_stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(ctx->copy_stream);
+    (void)hipFree(ctx->d_inflate_stage);
+    if (e != hipSuccess) { (void)hipFree(p); ctx->d_inflate_stage = nullptr; ctx->inflate_stage_bytes = 0; return hip_fail(e, "hipMemcpy"); }
+  }
+  ctx->d_inflate_stage = p;
+  ctx->inflate_stage_bytes = need;
+  return IBU_OK;
+}
+
+// One load of one shard.  At most one round of the decoder's short form (inflate_one_round: 49 152 blocks, 3 GB of records): ONE launch
+// behind the last copy — a wave takes its ~45 ms whatever the launch's size, so the call ends that long after its last byte has arrived
+// either way.  More: ONE launch as well, but AHEAD of the copies, in the decoder's other form (tables in scratch, eight waves per CU): its
+// waves take the blocks in file order and each waits until the copy stream has said that its blocks are there (`d_ready`, written
+// behind every piece; k_inflate.hip), so the device inflates at the rate the bytes come in.
+struct BgzfLoad {
+  static constexpr uint32_t kNone = 0xFFFFFFFFu;
+  ibu_ctx* ctx;
+  const ibu_ring_config_t* cfg;
+  const Mapping& file;
+  ibu_stream_stats_t* stats;
+  ibu_header_t* header;
+  void** d_records;                                        // nullptr: allocated here
+  size_t cap_records, shard, n_shards;
+  size_t range_records = 0;                                // > 0: d_records is the context's range buffer, grown to this many records
+  const BgzfIndex* idx = nullptr;                          // the index, or the walk beside the copies makes it
+  ShardPlan plan{};
+  BgzfIndex walked{};
+  std::thread walker{};
+  std::atomic<bool> walk_done{false};
+  int32_t walk_rc = IBU_OK;
+  ibu_error_detail_t walk_detail{};
+  bool prepared = false, owned = false, ahead = false;     // ahead: the launch that runs ahead of the copies is out
+  uint8_t *d_out = nullptr, *d_tables = nullptr;           // d_tables: the lanes' tables of a launch in the decoder's scratch form
+  InflateBlockDesc* d_desc = nullptr;
+  uint32_t *d_status = nullptr, *d_first_bad = nullptr, last_slot = 0;
+  size_t tables_room = 0, launches = 0;
+  std::vector<size_t> piece_end{};                         // piece k of the copies ends at this file byte
+  double t0 = now_s(), t_mark = t0, t_ph[4] = {0, 0, 0, 0};   // (IBU_TRACE_SORT=1: where the call's time went)
+  ~BgzfLoad() { if (walker.joinable()) walker.join(); }
+  void lap(int k) { const double t = now_s(); t_ph[k] += t - t_mark; t_mark = t; }
+  size_t ahead_from() const { return ctx->inflate_one_launch ? ctx->inflate_one_launch : inflate_one_round(ctx->cfg.cus); }
+  uint64_t* d_ready() const { return ctx->h_inflate_marks; }   // (pinned host memory: the device reads it over the link)
+  hipStream_t q() const { return ctx->inflate_streams[0]; }
+  // The walk on a thread of its own while this one already copies the file to the device: the copies need nothing but the file's size.
+  // (In line, the walk's 12.5 ms of page faults stood in front of a call of 1e8 records that takes 88.)
+  void walk_beside() {
+    plan.cend = file.n;                                    // (one shard of one: the whole file, before the walk is done)
+    auto run = [this] {
+      if ((walk_rc = bgzf_index(file.p, file.n, &walked))) walk_detail = tls_error();   // (the detail lives in the walker's thread)
+      walk_done.store(true, std::memory_order_release);
+    };
+    try { walker = std::thread(run); } catch (...) { run(); }   // no thread to be had: in line
+  }
+  int32_t run(size_t* n, uint64_t* first_record) {
+    int32_t rc = IBU_OK;
+    try { rc = load(); } catch (...) { rc = caught_io("ibu_load_bgzf_to_device"); }
+    if (rc) {                                              // every failure: nothing left running, nothing kept that this call allocated
+      if (walker.joinable()) walker.join();
+      if (ahead) __atomic_store_n(d_ready(), ~0ull, __ATOMIC_RELEASE);   // its waves must not wait for bytes that will not come
+      (void)hipStreamSynchronize(ctx->copy_stream);
+      for (hipStream_t s : ctx->inflate_streams)
+        if (s) (void)hipStreamSynchronize(s);
+      if (owned) { (void)hipFree(*d_records); *d_records = nullptr; }
+      if (owned && range_records) ctx->bgzf_range_bytes = 0;
+      return rc;
+    }
+    *n = plan.num;
+    if (first_record) *first_record = plan.rec_first;
+    if (stats) { stats->records = plan.num; stats->seconds_total = now_s() - t0; stats->numa_node = feed_place(ctx).node; stats->ring_node = ctx->ring.node; }
+    return IBU_OK;
+  }
+  int32_t load() {
+    // (one shard of one: room for the whole file and the descriptors of 64 KiB blocks: the copies start at once, nothing is allocated twice)
+    int32_t rc = n_shards == 1 ? grow_stage(ctx, ((file.n + kInflatePad + 255) & ~(size_t)255) + 40 * (file.n / 8192 + 64)) : IBU_OK;
+    if (!rc) rc = ring_ensure(ctx, cfg, false);
+    hipError_t e = hipSuccess;
+    for (hipStream_t& s : ctx->inflate_streams)
+      if (!s && !rc && e == hipSuccess) e = hipStreamCreateWithFlags(&s, hipStreamNonBlocking);
+    if (rc || e != hipSuccess) return rc ? rc : hip_fail(e, "hipStreamCreate");
+    lap(0);
+    if ((n_shards > 1 || idx) && (rc = prepare())) return rc;   // (a shard's bytes are known only after the walk)
+    if ((rc = copy())) return rc;
+    lap(1);
+    if ((!prepared && (rc = prepare())) || (rc = launch(true))) return rc;
+    lap(2);
+    if ((rc = finish())) return rc;
+    lap(3);
+    if (trace_sort())
+      fprintf(stderr, "ibu load_bgzf: %zu blocks (walked %s), %zu launches; ms: staging %.2f, copies (the walk beside them) and early launches %.2f, walk's results to the "
+              "device + last launches %.2f, waiting for them %.2f\n", idx->blocks.size(), idx->in_pieces ? "in 8 pieces side by side" : "in one go", launches,
+              1e3 * t_ph[0], 1e3 * t_ph[1], 1e3 * t_ph[2], 1e3 * t_ph[3]);
+    return IBU_OK;
+  }
+  // What the index allows, once it is there: the plan, the destination, the host-inflated bytes, the descriptors on the device
+  int32_t prepare() {
+    if (!idx) {
+      if (walker.joinable()) walker.join();
+      idx = &walked;
+      if (walked.head.size() >= IBU_HEADER_SIZE) *header = walked.header;
+      if (walk_rc) { tls_error() = walk_detail; return walk_rc; }
+    }
+    if (int32_t rc = plan_shard(*idx, shard, n_shards, &plan)) return rc;
+    const size_t nrest = plan.dev_blocks(), need = std::max({plan.num, range_records, (size_t)1}) * IBU_RECORD_SIZE;
+    if (range_records && need > ctx->bgzf_range_bytes) {   // the range buffer: the context keeps it and it grows only (freeing and
+      (void)hipFree(ctx->d_bgzf_range);                    // allocating 2.4 GB around every call cost a call of 1e8 records 80 of its
+      const hipError_t e = ctx_malloc(ctx, &ctx->d_bgzf_range, need);   // 155 ms; no placement probing: the records only pass through)
+      ctx->bgzf_range_bytes = e == hipSuccess ? need : 0;
+      if (e != hipSuccess) { ctx->d_bgzf_range = nullptr; return hip_fail(e, "hipMalloc"); }
+      owned = true;
+    } else if (!range_records && *d_records == nullptr) {
+      if (int32_t rc = ctx_alloc(ctx, plan.num * IBU_RECORD_SIZE, d_records)) return rc;
+      owned = true;
+    } else if (!range_records && plan.num > cap_records) {
+      return set_error(IBU_ERR_INVALID_ARG, plan.num, cap_records, 0, "Invalid argument: device buffer too small for the shard (%zu records, room for %zu)",
+                       plan.num, cap_records);
+    }
+    d_out = static_cast<uint8_t*>(*d_records);
+    hipError_t e = hipSuccess;
+    auto put = [&](const uint8_t* bytes, uint64_t at, uint64_t len) {   // bytes [at, at + len) of the stream, as far as they are the shard's
+      const uint64_t a = std::max(at, plan.lo), z = std::min(at + len, plan.hi);
+      if (a < z && e == hipSuccess) e = hipMemcpy(d_out + (a - plan.lo), bytes + (a - at), z - a, hipMemcpyHostToDevice);
+    };
+    put(idx->head.data(), 0, idx->head.size());            // the records behind the header in the blocks inflated for it
+    pgz::RawInflater raw;
+    std::vector<uint8_t> edge(65536);
+    for (size_t k = 0; k < plan.n_edges; ++k) {            // the blocks that straddle the shard's ends
+      const ibu_inflate_block_t& b = idx->blocks[plan.edge[k]];
+      if (int32_t rc = inflate_block_on_host(raw, file.p, b, edge.data())) return rc;
+      put(edge.data(), (uint64_t)b.out_offset, b.out_len);
+    }
+    if (e != hipSuccess) return hip_fail(e, "hipMemcpy");
+    const size_t comp_room = (plan.cend - plan.cbeg + kInflatePad + 255) & ~(size_t)255;
+    const size_t desc_room = (nrest * sizeof(InflateBlockDesc) + 255) & ~(size_t)255;
+    const size_t status_room = (4 * nrest + 16 + 255) & ~(size_t)255;
+    tables_room = nrest > ahead_from() ? inflate_scratch_bytes(ctx->cfg, nrest, 2) : 256;   // (the short form needs none)
+    if (int32_t rc = grow_stage(ctx, comp_room + desc_room + status_room + 256 + tables_room)) return rc;
+    d_desc = reinterpret_cast<InflateBlockDesc*>(static_cast<uint8_t*>(ctx->d_inflate_stage) + comp_room);
+    d_status = reinterpret_cast<uint32_t*>(reinterpret_cast<uint8_t*>(d_desc) + desc_room);
+    d_first_bad = d_status + nrest;
+    d_tables = reinterpret_cast<uint8_t*>(d_status) + status_room + 256;
+    if (!ctx->h_inflate_marks) {                           // (coherent whatever HIP_HOST_COHERENT says: the device must see the host's stores)
+      e = hipHostMalloc(reinterpret_cast<void**>(&ctx->h_inflate_marks), 8 * sizeof(uint64_t), hipHostMallocMapped | hipHostMallocCoherent);
+      if (e != hipSuccess) { ctx->h_inflate_marks = nullptr; return hip_fail(e, "hipHostMalloc"); }
+    }
+    std::vector<ibu_inflate_block_t> desc(idx->blocks.begin() + (ptrdiff_t)plan.dev_first, idx->blocks.begin() + (ptrdiff_t)plan.dev_end);
+    for (ibu_inflate_block_t& b : desc) {                  // relative to the shard's records / to the bytes on the device
+      b.out_offset -= (int64_t)plan.lo;
+      b.comp_offset -= plan.cbeg;
+    }
+    if (nrest) e = hipMemcpy(d_desc, desc.data(), nrest * sizeof(InflateBlockDesc), hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(d_first_bad, &kNone, 4, hipMemcpyHostToDevice);
+    __atomic_store_n(d_ready(), 0ull, __ATOMIC_RELEASE);
+    if (e != hipSuccess) return hip_fail(e, "hipMemcpy");
+    prepared = true;
+    return IBU_OK;
+  }
+  void publish(size_t done_upto) {                         // the host has SEEN the copies up to this file byte complete: the launch may use them
+    if (ahead) __atomic_store_n(d_ready(), (uint64_t)(done_upto - plan.cbeg), __ATOMIC_RELEASE);
+  }
+  int32_t copy() {
+    Ring& r = ctx->ring;
+    for (size_t k = 0, up = plan.cbeg; up < plan.cend; ++k) {   // up: file bytes [cbeg, up) are on their way
+      const uint32_t sl = (uint32_t)(k % r.slots);
+      const size_t len = std::min(plan.cend - up, r.slot_bytes);
+      if (ctx->load_piece_delay_ms) std::this_thread::sleep_for(std::chrono::milliseconds(ctx->load_piece_delay_ms));
+      hipError_t e = hipEventSynchronize(r.copied[sl]);
+      if (e != hipSuccess) return hip_fail(e, "hipEventSynchronize");
+      if (k >= r.slots) publish(piece_end[k - r.slots]);   // (this slot's previous piece has landed: so has everything in front of it)
+      uint8_t* dst = r.pinned[sl];
+      const uint8_t* src = file.p + up;
+      parallel_bytes(len, feeder_threads(cfg), [&](size_t off, size_t l) { memcpy(dst + off, src + off, l); return 0; });
+      e = hipMemcpyAsync(static_cast<uint8_t*>(ctx->d_inflate_stage) + (up - plan.cbeg), dst, len, hipMemcpyHostToDevice, ctx->copy_stream);
+      if (e == hipSuccess) e = hipEventRecord(r.copied[sl], ctx->copy_stream);
+      if (e != hipSuccess) return hip_fail(e, "H2D");
+      up += len;
+      last_slot = sl;
+      if (stats) { stats->bytes_h2d += len; stats->batches += 1; }
+      piece_end.push_back(up);
+      int32_t rc = IBU_OK;
+      if (!prepared && walk_done.load(std::memory_order_acquire) && (rc = prepare())) return rc;
+      if (prepared && (rc = launch(false))) return rc;
+    }
+    return IBU_OK;
+  }
+  int32_t launch(bool all) {
+    const size_t nrest = plan.dev_blocks();
+    const bool streamed = nrest > ahead_from();
+    if (launches || nrest == 0 || (!streamed && !all)) return IBU_OK;
+    ahead = streamed;
+    hipError_t e = hipSuccess;
+    if (streamed)
+      e = launch_inflate_blocks(ctx->cfg, ctx->d_inflate_stage, d_desc, nrest, d_out, d_status, d_first_bad, d_tables, tables_room, q(), 2, d_ready(),
+                                plan.cend - plan.cbeg);
+    else if ((e = hipStreamWaitEvent(q(), ctx->ring.copied[last_slot], 0)) == hipSuccess)   // (at most one round: the short form, behind the last copy)
+      e = launch_inflate_blocks(ctx->cfg, ctx->d_inflate_stage, d_desc, nrest, d_out, d_status, d_first_bad, d_tables, tables_room, q(), 0);
+    if (e != hipSuccess) return hip_fail(e, "inflate");
+    ++launches;
+    return IBU_OK;
+  }
+  int32_t finish() {
+    uint32_t first_bad = kNone;
+    hipError_t e = hipStreamSynchronize(ctx->copy_stream);
+    if (e == hipSuccess) publish(plan.cend);               // every byte is there
+    for (hipStream_t s : ctx->inflate_streams)
+      if (e == hipSuccess) e = hipStreamSynchronize(s);
+    if (e == hipSuccess) e = hipMemcpy(&first_bad, d_first_bad, 4, hipMemcpyDeviceToHost);
+    if (e != hipSuccess) return hip_fail(e, "ibu_load_bgzf_to_device");
+    if (first_bad != kNone && ahead)
+      if (int32_t rc = inflate_late(&first_bad)) return rc;
+    if (first_bad == kNone) return IBU_OK;
+    if (trace_sort()) {
+      uint32_t st1 = 0;
+      (void)hipMemcpy(&st1, d_status + first_bad, 4, hipMemcpyDeviceToHost);
+      fprintf(stderr, "ibu load_bgzf: block %u of the device's %zu refused (status %u: 1 not a deflate stream of these sizes, 2 CRC-32, 3 its bytes never arrived)\n",
+              first_bad, plan.dev_blocks(), st1);
+    }
+    return err_niffler("a BGZF block does not inflate to its announced length and CRC-32");
+  }
+  // Waves of the launch that ran ahead give up after ~4 s without their blocks (status 3): a slow source, not a bad file.  Everything
+  // is on the device now: those blocks — from the first of them on — go through a plain launch.  A block that was REFUSED stays refused.
+  int32_t inflate_late(uint32_t* first_bad) {
+    const size_t nrest = plan.dev_blocks();
+    std::vector<uint32_t> stv(nrest);
+    hipError_t e = hipMemcpy(stv.data(), d_status, 4 * nrest, hipMemcpyDeviceToHost);
+    if (e != hipSuccess) return hip_fail(e, "hipMemcpy");
+    if (std::any_of(stv.begin(), stv.end(), [](uint32_t st) { return st && st != 3; })) return IBU_OK;   // (refused stays refused)
+    const size_t late = (size_t)(std::find(stv.begin(), stv.end(), 3u) - stv.begin());
+    if (late == nrest) return IBU_OK;
+    if (trace_sort()) fprintf(stderr, "ibu load_bgzf: the bytes of blocks %zu ... came later than the waves waited: inflating them now\n", late);
+    e = hipMemcpy(d_first_bad, &kNone, 4, hipMemcpyHostToDevice);
+    ahead = false;                                         // (nothing to release any more on a failure)
+    for (size_t at = late, cnt = 0; at < nrest && e == hipSuccess; at += cnt, ++launches) {
+      cnt = std::min(nrest - at, (size_t)ctx->cfg.cus * 8 * 64);   // (eight waves of 64 blocks per CU a launch)
+      e = launch_inflate_blocks(ctx->cfg, ctx->d_inflate_stage, d_desc + at, cnt, d_out, d_status + at, d_first_bad, d_tables, tables_room, q(),
+                                cnt > inflate_one_round(ctx->cfg.cus) ? 2 : 0);
+    }
+    if (e == hipSuccess) e = hipStreamSynchronize(q());
+    if (e == hipSuccess) e = hipMemcpy(first_bad, d_first_bad, 4, hipMemcpyDeviceToHost);
+    return e == hipSuccess ? IBU_OK : hip_fail(e, "ibu_load_bgzf_to_device");
+  }
+};
+
+}  // namespace
+
 extern "C" int32_t ibu_load_bgzf_to_device(ibu_ctx_t* ctx, const char* path, const ibu_ring_config_t* cfg, ibu_header_t* header,
                                            void** d_records, size_t cap_records, size_t* n, ibu_stream_stats_t* stats) {
   return ibu_load_bgzf_shard_to_device(ctx, path, cfg, 0, 1, header, d_records, cap_records, n, nullptr, stats);
@@ -287,422 +560,12 @@ extern "C" int32_t ibu_load_bgzf_shard_to_device(ibu_ctx_t* ctx, const char* pat
   if (n_shards == 0 || shard >= n_shards) return err_arg("shard out of range");
   IBU_HIP(hipSetDevice(ctx->device));
   RunOnNode on_node(feed_place(ctx));
-  const double t0 = now_s();
   if (stats) memset(stats, 0, sizeof *stats);
-  int fd = ::open(path, O_RDONLY | O_CLOEXEC);
-  if (fd < 0) return err_io(errno, path);
-  struct stat sb;
-  if (fstat(fd, &sb)) { const int e = errno; close(fd); return err_io(e, "metadata"); }
-  const size_t size = (size_t)sb.st_size;
-  if (size == 0) { close(fd); return err_io(0, "read header"); }
-  void* mp = mmap(nullptr, size, PROT_READ, MAP_PRIVATE, fd, 0);
-  const int map_errno = errno;
-  close(fd);
-  if (mp == MAP_FAILED) return err_io(map_errno, "mmap");
-  struct Unmap { void* p; size_t n; ~Unmap() { munmap(p, n); } } unmap{mp, size};
-  (void)madvise(mp, size, MADV_SEQUENTIAL);
-  const uint8_t* map = static_cast<const uint8_t*>(mp);
-  double t_mark = now_s(), t_ph[4] = {0, 0, 0, 0};        // (IBU_TRACE_SORT=1: where the call's time went)
-  auto lap = [&](int k) { const double t = now_s(); t_ph[k] += t - t_mark; t_mark = t; };
-
-  // The WALK over the block headers (and the blocks that hold the 32 header bytes, inflated on the host) runs on a thread of its own
-  // while this one already copies the file to the device: the copies need nothing but the file's size.  (In line, the walk's 12.5 ms
-  // of page faults stood in front of a call of 1e8 records that takes 88.)
-  std::vector<ibu_inflate_block_t> B;
-  uint64_t total = 0;
-  uint8_t head[IBU_HEADER_SIZE + 65536];
-  size_t lead = 0, lead_bytes = 0;
-  int32_t walk_rc = IBU_OK;
-  bool walked_in_pieces = false;
-  ibu_error_detail_t walk_detail{};
-  std::atomic<bool> walked{false};
-  // The walk, in pieces side by side.  A block's start cannot be computed without the blocks in front of it, but it can be GUESSED: every
-  // piece but the first looks for the 16 bytes a bgzip header begins with (1f 8b 08 04 .. 06 00 'B' 'C' 02 00) at or behind its first
-  // byte and walks the chain from there to the end of its piece.  The guesses are then checked: piece i's chain must END exactly where
-  // piece i + 1's began — where it does not (the signature inside compressed data, an unusual extra field), or anything at all is off,
-  // the plain walk from byte 0 below decides, errors included.  (184 k blocks of a 6 GB file: 60 ms of page faults in one thread.)
-  auto walk_pieces = [&]() -> bool {
-    const size_t T = 8;
-    if (size < (T << 22)) return false;                    // (small files: the plain walk)
-    struct Piece { size_t begin = 0, end = 0; bool ok = false; uint64_t out = 0; std::vector<ibu_inflate_block_t> blocks; };
-    std::vector<Piece> pc(T);
-    auto run = [&](size_t i) {
-      Piece& P = pc[i];
-      try {
-        const size_t lo = size / T * i, hi = i + 1 == T ? size : size / T * (i + 1);
-        size_t pos = lo;
-        if (i) {                                           // the first header-like spot at or behind lo
-          const uint8_t sig_a[4] = {0x1f, 0x8b, 0x08, 0x04}, sig_b[6] = {0x06, 0x00, 'B', 'C', 0x02, 0x00};
-          for (;; ++pos) {
-            if (pos + 18 > size || pos >= hi) return;      // none in this piece: give up (the plain walk decides)
-            if (memcmp(map + pos, sig_a, 4) == 0 && memcmp(map + pos + 10, sig_b, 6) == 0) break;
-          }
-        }
-        P.begin = pos;
-        std::vector<ibu_inflate_block_t> part(1 << 14);
-        while (pos < hi) {
-          size_t nb = 0, consumed = 0, cap = part.size();
-          uint64_t ob = 0;
-          if (ibu_bgzf_scan(map + pos, size - pos, 1, part.data(), cap, &nb, &consumed, &ob) != IBU_OK || consumed == 0) return;
-          size_t keep = 0, bytes = 0;                      // only the blocks that START inside the piece
-          uint64_t outb = 0;
-          for (; keep < nb; ++keep) {
-            const size_t start = pos + (size_t)part[keep].comp_offset - 18;   // (bgzip's header: 18 bytes; checked again when the pieces are joined)
-            if (start >= hi) break;
-            bytes = (size_t)part[keep].comp_offset + part[keep].comp_len + 8;
-            part[keep].comp_offset += pos;
-            part[keep].out_offset += (int64_t)P.out;
-            outb = (uint64_t)(part[keep].out_offset - (int64_t)P.out) + part[keep].out_len;
-          }
-          P.blocks.insert(P.blocks.end(), part.begin(), part.begin() + (ptrdiff_t)keep);
-          P.out += outb;
-          pos += bytes;
-          if (keep < nb || keep == 0) break;
-        }
-        P.end = pos;
-        P.ok = true;
-      } catch (...) {}
-    };
-    {
-      std::vector<std::thread> th;
-      try { for (size_t i = 1; i < T; ++i) th.emplace_back(run, i); } catch (...) {}
-      const size_t started = th.size();
-      run(0);
-      for (auto& t : th) t.join();
-      if (started != T - 1) return false;
-    }
-    size_t nblocks = 0;
-    for (size_t i = 0; i < T; ++i) {
-      if (!pc[i].ok || (i == 0 && pc[i].begin != 0) || (i && pc[i].begin != pc[i - 1].end)) return false;
-      nblocks += pc[i].blocks.size();
-    }
-    if (pc[T - 1].end != size) return false;
-    B.reserve(nblocks);
-    for (size_t i = 0; i < T; ++i) {
-      for (ibu_inflate_block_t& b : pc[i].blocks) b.out_offset += (int64_t)total;
-      B.insert(B.end(), pc[i].blocks.begin(), pc[i].blocks.end());
-      total += pc[i].out;
-    }
-    return true;
-  };
-  auto walk = [&]() -> int32_t {
-    try {
-      bool have = false;
-      try { have = walk_pieces(); } catch (...) { have = false; }
-      if (!have) { B.clear(); total = 0; }
-      walked_in_pieces = have;
-      std::vector<ibu_inflate_block_t> part(have ? 1 : 1 << 16);
-      for (size_t pos = have ? size : 0; pos < size;) {    // 1. the blocks (a cut-off or foreign member: IBU_ERR_NIFFLER from the walk)
-        size_t nb = 0, consumed = 0;
-        uint64_t ob = 0;
-        const int32_t rc = ibu_bgzf_scan(map + pos, size - pos, 1, part.data(), part.size(), &nb, &consumed, &ob);
-        for (size_t i = 0; i < nb; ++i) {
-          part[i].comp_offset += pos;
-          part[i].out_offset += (int64_t)total;
-        }
-        B.insert(B.end(), part.begin(), part.begin() + (ptrdiff_t)nb);
-        if (rc) return rc;
-        if (consumed == 0) return err_niffler("the stream ends inside a BGZF block");
-        pos += consumed;
-        total += ob;
-      }
-      pgz::RawInflater raw;                                // 2. the header: the leading blocks, inflated here
-      std::vector<uint8_t> in;
-      while (lead_bytes < IBU_HEADER_SIZE && lead < B.size()) {
-        const ibu_inflate_block_t& b = B[lead];            // (an empty block, too: "01 00" is refused as the Reader refuses it)
-        in.assign(map + b.comp_offset, map + b.comp_offset + b.comp_len);
-        in.resize(b.comp_len + 512, 0);                    // the decoder may read (not use) a few bytes behind the stream
-        uint32_t crc = 0;
-        const int e = raw.inflate(in.data(), b.comp_len, head + lead_bytes, b.out_len, &crc);
-        if (e == ENOMEM) return err_io(ENOMEM, "inflate");
-        if (e || crc != b.crc32) return err_niffler("a BGZF block does not inflate to its announced length and CRC-32");
-        lead_bytes += b.out_len;
-        ++lead;
-      }
-    } catch (...) { return caught_io("ibu_load_bgzf_to_device"); }
-    if (lead_bytes < IBU_HEADER_SIZE) return err_io(0, "read header");
-    memcpy(header, head, IBU_HEADER_SIZE);
-    const int32_t rc = ibu_header_validate(header);
-    if (rc) return rc;
-    if ((total - IBU_HEADER_SIZE) % IBU_RECORD_SIZE != 0) return err_map_size();
-    return IBU_OK;
-  };
-  std::thread walker;
-  auto run_walk = [&] {
-    walk_rc = walk();
-    if (walk_rc) walk_detail = tls_error();                // (the detail lives in the walker's thread: the caller gets a copy)
-    walked.store(true, std::memory_order_release);
-  };
-  try { walker = std::thread(run_walk); } catch (...) { run_walk(); }   // no thread to be had: in line
-  struct Join { std::thread& t; ~Join() { if (t.joinable()) t.join(); } } join_walker{walker};
-
-  bool owned = false;
-  constexpr int kStreams = 3;
-  hipStream_t* ks = ctx->inflate_streams;
-  uint64_t* d_ready = nullptr;                             // (a launch that runs ahead of its input: see below)
-  bool ahead = false;
-  constexpr size_t kInflateMarks = 8;
-  auto fail = [&](int32_t code) {
-    if (walker.joinable()) walker.join();
-    if (ahead && d_ready)                                  // its waves must not wait for bytes that will not come
-      __atomic_store_n(d_ready, ~0ull, __ATOMIC_RELEASE);
-    (void)hipStreamSynchronize(ctx->copy_stream);
-    for (int k = 0; k < kStreams; ++k)
-      if (ks[k]) (void)hipStreamSynchronize(ks[k]);
-    if (owned) { (void)hipFree(*d_records); *d_records = nullptr; }
-    return code;
-  };
-  // the staging on the device — the compressed file; the descriptors and status words behind it once their number is known — is the
-  // context's and grows only (freeing 1.2 GB and allocating it again cost a call of 1e8 records 12 of its 104 ms)
-  auto stage = [&](size_t need) -> int32_t {
-    if (need <= ctx->inflate_stage_bytes) return IBU_OK;
-    void* p = nullptr;
-    hipError_t e = ctx_malloc(ctx, &p, need);
-    if (e != hipSuccess) return hip_fail(e, "hipMalloc");
-    if (ctx->d_inflate_stage) {                            // (the bytes copied so far move along)
-      e = hipMemcpyAsync(p, ctx->d_inflate_stage, ctx->inflate_stage_bytes, hipMemcpyDeviceToDevice, ctx->copy_stream);
-      if (e == hipSuccess) e = hipStreamSynchronize(ctx->copy_stream);
-      (void)hipFree(ctx->d_inflate_stage);
-      if (e != hipSuccess) { (void)hipFree(p); ctx->d_inflate_stage = nullptr; ctx->inflate_stage_bytes = 0; return hip_fail(e, "hipMemcpy"); }
-    }
-    ctx->d_inflate_stage = p;
-    ctx->inflate_stage_bytes = need;
-    return IBU_OK;
-  };
-  // (one shard of one: room for the whole file and the descriptors of a file of ordinary 64 KiB blocks right away, so that the copies
-  // can start at once and nothing is allocated a second time in the usual case)
-  int32_t rc = n_shards == 1 ? stage(((size + kInflatePad + 255) & ~(size_t)255) + 40 * (size / 8192 + 64)) : IBU_OK;
-  if (!rc) rc = ensure_sort_scratch(ctx, 16);
-  if (!rc) rc = ring_ensure(ctx, cfg, false);
-  hipError_t e = hipSuccess;
-  for (int k = 0; k < kStreams && e == hipSuccess && !rc; ++k)
-    if (!ks[k]) e = hipStreamCreateWithFlags(&ks[k], hipStreamNonBlocking);
-  if (!rc && e != hipSuccess) rc = hip_fail(e, "hipStreamCreate");
-  if (rc) return fail(rc);
-  Ring& r = ctx->ring;
-  lap(0);
-
-  // What the walk's result allows, once it is there: the shard's range, the destination, the descriptors on the device
-  size_t num = 0, nrest = 0, dev_first = 0;                // device blocks: B[dev_first, dev_first + nrest)
-  size_t cbeg = 0, cend = size;                            // the file bytes that go to the device (one shard of one: all, so that the copies
-  uint64_t rec_first = 0;                                  // can start before the walk is done)
-  uint8_t* d_out = nullptr;
-  InflateBlockDesc* d_desc = nullptr;
-  uint32_t *d_status = nullptr, *d_first_bad = nullptr;
-  uint8_t* d_tables = nullptr;                             // the lanes' tables of a launch in the decoder's scratch form, behind the status words
-  size_t tables_room = 0;
-  const uint32_t none = 0xFFFFFFFFu;
-  bool prepared = false;
-  auto prepare = [&]() -> int32_t {
-    if (walker.joinable()) walker.join();
-    if (walk_rc) { tls_error() = walk_detail; return walk_rc; }
-    const size_t num_all = (size_t)((total - IBU_HEADER_SIZE) / IBU_RECORD_SIZE);
-    size_t rs = 0, re = 0;
-    int32_t prc = ibu_shard_range(num_all, n_shards, shard, &rs, &re);
-    if (prc) return prc;
-    num = re - rs;
-    rec_first = rs;
-    const uint64_t lo = IBU_HEADER_SIZE + (uint64_t)IBU_RECORD_SIZE * rs, hi = IBU_HEADER_SIZE + (uint64_t)IBU_RECORD_SIZE * re;   // the shard's bytes
-    if (*d_records == nullptr) {
-      const int32_t arc = ctx_alloc(ctx, num * IBU_RECORD_SIZE, d_records);
-      if (arc) return arc;
-      owned = true;
-    } else if (num > cap_records) {
-      return set_error(IBU_ERR_INVALID_ARG, num, cap_records, 0, "Invalid argument: device buffer too small for the shard (%zu records, room for %zu)", num, cap_records);
-    }
-    d_out = static_cast<uint8_t*>(*d_records);
-    // the blocks wholly inside [lo, hi): the device's; what straddles an end (and the header's blocks): inflated here
-    size_t dev_end = lead;
-    dev_first = lead;
-    while (dev_first < B.size() && (uint64_t)B[dev_first].out_offset < lo) ++dev_first;
-    dev_end = dev_first;
-    while (dev_end < B.size() && (uint64_t)B[dev_end].out_offset + B[dev_end].out_len <= hi) ++dev_end;
-    nrest = dev_end - dev_first;
-    hipError_t pe = hipSuccess;
-    auto put = [&](const uint8_t* bytes, uint64_t at, uint64_t len) {   // bytes [at, at + len) of the stream, as far as they are the shard's
-      const uint64_t a = at < lo ? lo : at, z = at + len > hi ? hi : at + len;
-      if (a < z && pe == hipSuccess) pe = hipMemcpy(d_out + (a - lo), bytes + (a - at), z - a, hipMemcpyHostToDevice);
-    };
-    put(head, 0, lead_bytes);                              // the records behind the header in the blocks inflated for it
-    {
-      pgz::RawInflater raw;
-      std::vector<uint8_t> in, outb(65536);
-      const size_t edge[2] = {dev_first > lead ? dev_first - 1 : (size_t)-1, dev_end < B.size() ? dev_end : (size_t)-1};
-      for (int k = 0; k < 2 && num; ++k) {
-        const size_t i = edge[k];
-        if (i == (size_t)-1 || i < lead || (k == 1 && edge[0] == i)) continue;
-        const ibu_inflate_block_t& b = B[i];
-        if (!b.out_len || (uint64_t)b.out_offset >= hi || (uint64_t)b.out_offset + b.out_len <= lo) continue;
-        in.assign(map + b.comp_offset, map + b.comp_offset + b.comp_len);
-        in.resize(b.comp_len + 512, 0);
-        uint32_t crc = 0;
-        const int ie = raw.inflate(in.data(), b.comp_len, outb.data(), b.out_len, &crc);
-        if (ie == ENOMEM) return err_io(ENOMEM, "inflate");
-        if (ie || crc != b.crc32) return err_niffler("a BGZF block does not inflate to its announced length and CRC-32");
-        put(outb.data(), (uint64_t)b.out_offset, b.out_len);
-      }
-    }
-    if (pe != hipSuccess) return hip_fail(pe, "hipMemcpy");
-    if (n_shards > 1) {                                    // only the device blocks' bytes cross the link
-      cbeg = nrest ? (size_t)B[dev_first].comp_offset : 0;
-      cend = nrest ? (size_t)(B[dev_end - 1].comp_offset + B[dev_end - 1].comp_len) : 0;
-    }
-    const size_t comp_room = (cend - cbeg + kInflatePad + 255) & ~(size_t)255;
-    const size_t desc_room = (nrest * sizeof(InflateBlockDesc) + 255) & ~(size_t)255;
-    const size_t status_room = (4 * nrest + 16 + 255) & ~(size_t)255;
-    tables_room = nrest > (ctx->inflate_one_launch ? ctx->inflate_one_launch : (size_t)ctx->cfg.cus * 3 * 64)
-                      ? inflate_scratch_bytes(ctx->cfg, nrest, 2) : 256;   // (the short form needs none)
-    const int32_t src = stage(comp_room + desc_room + status_room + 256 + tables_room);
-    if (src) return src;
-    d_desc = reinterpret_cast<InflateBlockDesc*>(static_cast<uint8_t*>(ctx->d_inflate_stage) + comp_room);
-    d_status = reinterpret_cast<uint32_t*>(reinterpret_cast<uint8_t*>(d_desc) + desc_room);
-    d_first_bad = d_status + nrest;
-    d_tables = reinterpret_cast<uint8_t*>(d_status) + status_room + 256;
-    if (!ctx->h_inflate_marks) {
-      // (coherent whatever HIP_HOST_COHERENT says: the device must see the host's stores while its kernel runs)
-      hipError_t he = hipHostMalloc(reinterpret_cast<void**>(&ctx->h_inflate_marks), kInflateMarks * sizeof(uint64_t), hipHostMallocMapped | hipHostMallocCoherent);
-      if (he != hipSuccess) { ctx->h_inflate_marks = nullptr; return hip_fail(he, "hipHostMalloc"); }
-    }
-    d_ready = ctx->h_inflate_marks;                        // (pinned host memory: the device reads it over the link)
-    for (size_t i = dev_first; i < dev_end; ++i) {         // relative to the shard's records / to the bytes on the device
-      B[i].out_offset -= (int64_t)lo;
-      B[i].comp_offset -= cbeg;
-    }
-    if (nrest) pe = hipMemcpy(d_desc, B.data() + dev_first, nrest * sizeof(InflateBlockDesc), hipMemcpyHostToDevice);
-    if (pe == hipSuccess) pe = hipMemcpy(d_first_bad, &none, 4, hipMemcpyHostToDevice);
-    __atomic_store_n(d_ready, 0ull, __ATOMIC_RELEASE);
-    if (pe != hipSuccess) return hip_fail(pe, "hipMemcpy");
-    prepared = true;
-    return IBU_OK;
-  };
-
-  // The file's bytes to the device through the pinned ring; the blocks inflated where their records belong.  At most one round of the
-  // decoder's short form (three waves of 64 blocks per CU: 49 152 blocks, 3 GB of records): ONE launch behind the last copy — a wave
-  // takes its ~45 ms whatever the launch's size, so the call ends that long after its last byte has arrived either way.  More: ONE launch
-  // as well, but AHEAD of the copies — as soon as the walk's results are on the device — in the decoder's other form (tables in scratch,
-  // eight waves per CU): its waves take the blocks in file order and each waits until the copy stream has said that its blocks are there
-  // (`d_ready`, written behind every piece; k_inflate.hip), so the device inflates at the rate the bytes come in.  (Launches behind the
-  // copies instead — of 16 Ki or 32 Ki blocks on three streams, or of everything that had arrived once the one before was done — ran one
-  // after the other, each for its waves' 45-75 ms: 5e8 records 0.343 / 0.306 / 0.228 s.)
-  const size_t kOneLaunch = ctx->inflate_one_launch ? ctx->inflate_one_launch : (size_t)ctx->cfg.cus * 3 * 64;
-  size_t up = 0, launches = 0;                             // up: file bytes [cbeg, up) are on their way
-  uint32_t last_slot = 0;
-  std::vector<size_t> piece_end;                           // piece k of the copies ends at this file byte
-  auto publish = [&](size_t done_upto) {                   // the host has SEEN the copies up to this file byte complete: the launch may use them
-    if (ahead) __atomic_store_n(d_ready, (uint64_t)(done_upto - cbeg), __ATOMIC_RELEASE);
-  };
-  auto launch_ready = [&](bool all) -> int32_t {
-    if (launches || nrest == 0) return IBU_OK;
-    const bool streamed = nrest > kOneLaunch && d_ready;
-    if (!streamed && !all) return IBU_OK;
-    hipStream_t q = ks[0];
-    hipError_t le = hipSuccess;
-    if (streamed) {
-      ahead = true;
-      le = launch_inflate_blocks(ctx->cfg, ctx->d_inflate_stage, d_desc, nrest, d_out, d_status, d_first_bad, d_tables, tables_room, q, 2, d_ready,
-                                   cend - cbeg);
-    } else {
-      le = hipStreamWaitEvent(q, r.copied[last_slot], 0);
-      if (le == hipSuccess)
-        le = launch_inflate_blocks(ctx->cfg, ctx->d_inflate_stage, d_desc, nrest, d_out, d_status, d_first_bad, d_tables, tables_room, q,
-                                   nrest > (size_t)ctx->cfg.cus * 3 * 64 ? 2 : 0);
-    }
-    if (le != hipSuccess) return hip_fail(le, "inflate");
-    ++launches;
-    return IBU_OK;
-  };
-  if (n_shards > 1) {                                      // a shard's bytes are known only after the walk
-    rc = prepare();
-    if (rc) return fail(rc);
-  }
-  up = cbeg;
-  for (size_t k = 0; up < cend; ++k) {
-    const uint32_t sl = (uint32_t)(k % r.slots);
-    const size_t len = cend - up < r.slot_bytes ? cend - up : r.slot_bytes;
-    if (ctx->load_piece_delay_ms) std::this_thread::sleep_for(std::chrono::milliseconds(ctx->load_piece_delay_ms));
-    e = hipEventSynchronize(r.copied[sl]);
-    if (e != hipSuccess) return fail(hip_fail(e, "hipEventSynchronize"));
-    if (k >= r.slots) publish(piece_end[k - r.slots]);     // (this slot's previous piece has landed: so has everything in front of it)
-    uint8_t* dst = r.pinned[sl];
-    const uint8_t* src = map + up;
-    parallel_bytes(len, feeder_threads(cfg), [&](size_t off, size_t l) { memcpy(dst + off, src + off, l); return 0; });
-    e = hipMemcpyAsync(static_cast<uint8_t*>(ctx->d_inflate_stage) + (up - cbeg), dst, len, hipMemcpyHostToDevice, ctx->copy_stream);
-    if (e == hipSuccess) e = hipEventRecord(r.copied[sl], ctx->copy_stream);
-    if (e != hipSuccess) return fail(hip_fail(e, "H2D"));
-    up += len;
-    last_slot = sl;
-    if (stats) { stats->bytes_h2d += len; stats->batches += 1; }
-    try { piece_end.push_back(up); } catch (...) { return fail(caught_io("ibu_load_bgzf_to_device")); }
-    if (!prepared && walked.load(std::memory_order_acquire)) {
-      rc = prepare();
-      if (rc) return fail(rc);
-    }
-    if (prepared) {
-      rc = launch_ready(false);
-      if (rc) return fail(rc);
-    }
-  }
-  lap(1);
-  if (!prepared) {
-    rc = prepare();
-    if (rc) return fail(rc);
-  }
-  rc = launch_ready(true);
-  if (rc) return fail(rc);
-  lap(2);
-  uint32_t first_bad = none;
-  e = hipStreamSynchronize(ctx->copy_stream);
-  if (e == hipSuccess) publish(cend);                      // every byte is there
-  for (int k = 0; k < kStreams && e == hipSuccess; ++k) e = hipStreamSynchronize(ks[k]);
-  if (e == hipSuccess) e = hipMemcpy(&first_bad, d_first_bad, 4, hipMemcpyDeviceToHost);
-  if (e != hipSuccess) return fail(hip_fail(e, "ibu_load_bgzf_to_device"));
-  if (first_bad != none && ahead) {
-    // Waves of the launch that ran ahead give up after ~4 s without their blocks (status 3): a slow source, not a bad file.  Everything
-    // is on the device now: those blocks — from the first of them on — go through a plain launch.  A block that was REFUSED stays refused.
-    try {
-      std::vector<uint32_t> stv(nrest);
-      e = hipMemcpy(stv.data(), d_status, 4 * nrest, hipMemcpyDeviceToHost);
-      if (e != hipSuccess) return fail(hip_fail(e, "hipMemcpy"));
-      size_t late = nrest;
-      bool refused = false;
-      for (size_t i = 0; i < nrest; ++i) {
-        if (stv[i] == 3) { if (late == nrest) late = i; }
-        else if (stv[i]) refused = true;
-      }
-      if (!refused && late < nrest) {
-        if (trace_sort()) fprintf(stderr, "ibu load_bgzf: the bytes of blocks %zu ... came later than the waves waited: inflating them now\n", late);
-        e = hipMemcpy(d_first_bad, &none, 4, hipMemcpyHostToDevice);
-        ahead = false;                                      // (fail() has nothing to release any more)
-        for (size_t at = late; at < nrest && e == hipSuccess;) {
-          const size_t cnt = nrest - at < (size_t)ctx->cfg.cus * 8 * 64 ? nrest - at : (size_t)ctx->cfg.cus * 8 * 64;
-          e = launch_inflate_blocks(ctx->cfg, ctx->d_inflate_stage, d_desc + at, cnt, d_out, d_status + at, d_first_bad, d_tables, tables_room, ks[0],
-                                    cnt > (size_t)ctx->cfg.cus * 3 * 64 ? 2 : 0);
-          at += cnt;
-          ++launches;
-        }
-        if (e == hipSuccess) e = hipStreamSynchronize(ks[0]);
-        if (e == hipSuccess) e = hipMemcpy(&first_bad, d_first_bad, 4, hipMemcpyDeviceToHost);
-        if (e != hipSuccess) return fail(hip_fail(e, "ibu_load_bgzf_to_device"));
-      }
-    } catch (...) { return fail(caught_io("ibu_load_bgzf_to_device")); }
-  }
-  if (first_bad != none) {
-    if (trace_sort()) {
-      uint32_t st1 = 0;
-      (void)hipMemcpy(&st1, d_status + first_bad, 4, hipMemcpyDeviceToHost);
-      fprintf(stderr, "ibu load_bgzf: block %u of the device's %zu refused (status %u: 1 not a deflate stream of these sizes, 2 CRC-32, 3 its bytes never arrived)\n",
-              first_bad, nrest, st1);
-    }
-    return fail(err_niffler("a BGZF block does not inflate to its announced length and CRC-32"));
-  }
-  lap(3);
-  if (trace_sort())
-    fprintf(stderr, "ibu load_bgzf: %zu blocks (walked %s), %zu launches; ms: staging %.2f, copies (the walk beside them) and early launches %.2f, walk's results to the "
-            "device + last launches %.2f, waiting for them %.2f\n", B.size(), walked_in_pieces ? "in 8 pieces side by side" : "in one go", launches, 1e3 * t_ph[0], 1e3 * t_ph[1], 1e3 * t_ph[2], 1e3 * t_ph[3]);
-  *n = num;
-  if (first_record) *first_record = rec_first;
-  if (stats) { stats->records = num; stats->seconds_total = now_s() - t0; stats->numa_node = feed_place(ctx).node; stats->ring_node = ctx->ring.node; }
-  return IBU_OK;
+  Mapping file;
+  if (int32_t rc = map_file(path, &file)) return rc;
+  BgzfLoad L{ctx, cfg, file, stats, header, d_records, cap_records, shard, n_shards};
+  L.walk_beside();
+  return L.run(n, first_record);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -1315,92 +1178,59 @@ extern "C" int32_t ibu_mmap_process_devices(const ibu_mmap_t* m, const int32_t* 
 namespace {
 // A Reader over a BGZF FILE nothing has been read from: the processors need not pull it through the Reader's host inflate (0.4 G records/s
 // on 16 CPUs) — the file is loaded range by range with its compressed bytes crossing the link and its blocks inflated on the device
-// (ibu_load_bgzf_shard_to_device: ranges of about 6 GB of records, so that any file fits), and the processor runs over each range.
+// (BgzfLoad: ranges of about 6 GB of records, so that any file fits), and the processor runs over each range.  The file is mapped and
+// indexed once; the ranges land in the context's range buffer, sized by the first load for the largest range.
 // *handled = false: the file is not what that load takes (a foreign member, a cut, a length that is no whole number of records ...) —
 // nothing has been touched, and the Reader's own path delivers what it delivers for such a file, error and all.
 int32_t process_bgzf_file(ibu_ctx* ctx, const char* path, const ibu_ring_config_t* cfg, const ibu_header_t& want, DeviceProc& dp, int32_t proc, void* sink,
                           ibu_stream_stats_t* stats, uint64_t* records, bool* handled) {
   *handled = false;
-  struct stat sb;
-  if (stat(path, &sb) != 0) return IBU_OK;
+  const ibu_error_detail_t keep = tls_error();
+  Mapping file;
+  int32_t rc = map_file(path, &file);
   // ranges of ~6.4 GB of records where the file compresses to half (BGZF of 16/12 records: 0.50) — every range costs its launch's
   // waves' 45-75 ms once more, and a file that compresses better just gets larger ranges
-  const size_t K = (size_t)((double)sb.st_size / (ctx->bgzf_range_bytes_opt ? (double)ctx->bgzf_range_bytes_opt : 3.2e9)) + 1;
-  ibu_header_t h;
-  size_t n0 = 0;
-  uint64_t first = 0;
-  ibu_stream_stats_t st{};
-  const ibu_error_detail_t keep = tls_error();
-  // The ranges land in a buffer the CONTEXT keeps (it grows only; option "release_staging" frees it): allocating and freeing 2.4 GB
-  // around every call cost a call of 1e8 records 80 of its 155 ms.  First use, or a larger range than ever: the load allocates, and
-  // the context adopts what it allocated.
-  auto cap = [&] { return ctx->bgzf_range_bytes / IBU_RECORD_SIZE; };
-  int32_t rc = IBU_ERR_INVALID_ARG;
-  if (cap()) {
-    void* p = ctx->d_bgzf_range;
-    rc = ibu_load_bgzf_shard_to_device(ctx, path, cfg, 0, K, &h, &p, cap(), &n0, &first, &st);
-    if (rc == IBU_ERR_INVALID_ARG && tls_error().b == cap() && tls_error().a > cap()) {   // too small for this file's ranges
-      (void)hipFree(ctx->d_bgzf_range);
-      ctx->d_bgzf_range = nullptr;
-      ctx->bgzf_range_bytes = 0;
-    }
+  const size_t K = (size_t)((double)file.n / (ctx->bgzf_range_bytes_opt ? (double)ctx->bgzf_range_bytes_opt : 3.2e9)) + 1;
+  BgzfIndex idx;
+  ShardPlan last;                                          // (the largest range: the first load sizes the buffer for it)
+  ibu_header_t h{};
+  if (!rc && K > 1) {                                      // (one range: the load walks the file beside its copies)
+    RunOnNode on_node(feed_place(ctx));
+    if (!(rc = bgzf_index(file.p, file.n, &idx))) rc = plan_shard(idx, K - 1, K, &last);
+    h = idx.header;
   }
-  if (!cap()) {
-    const int probe = ctx->cfg.alloc_probe_tries;        // (no placement probing for it: the records only pass through)
-    ctx->cfg.alloc_probe_tries = 1;
-    void* p = nullptr;
-    rc = ibu_load_bgzf_shard_to_device(ctx, path, cfg, 0, K, &h, &p, 0, &n0, &first, &st);
-    ctx->cfg.alloc_probe_tries = probe;
-    if (rc == IBU_OK) { ctx->d_bgzf_range = p; ctx->bgzf_range_bytes = (n0 ? n0 : 1) * IBU_RECORD_SIZE; }
-  }
-  if (rc || memcmp(&h, &want, sizeof h) != 0) {          // not for this path: as if it had not been tried
-    tls_error() = keep;
-    return IBU_OK;
-  }
-  *handled = true;
-  auto done = [&](int32_t code) {
-    (void)hipStreamSynchronize(ctx->stream);
-    return code;
-  };
-  if (K > 1 && cap() < n0 + K) {                         // (a later range has at most K - 1 records more than the first)
-    void* big = nullptr;
-    hipError_t e = ctx_malloc(ctx, &big, (n0 + K) * IBU_RECORD_SIZE);
-    if (e == hipSuccess) e = hipMemcpy(big, ctx->d_bgzf_range, n0 * IBU_RECORD_SIZE, hipMemcpyDeviceToDevice);
-    if (e != hipSuccess) { if (big) (void)hipFree(big); return done(hip_fail(e, "hipMalloc")); }
-    (void)hipFree(ctx->d_bgzf_range);
-    ctx->d_bgzf_range = big;
-    ctx->bgzf_range_bytes = (n0 + K) * IBU_RECORD_SIZE;
-  }
+  struct Drain { hipStream_t s; ~Drain() { (void)hipStreamSynchronize(s); } } drain{ctx->stream};   // (no launch left over the buffer)
   uint64_t total = 0;
-  if (proc == IBU_PROC_REDUCE) {
-    hipError_t e = hipMemsetAsync(ctx->d_acc, 0, kReduceAccBytes, ctx->stream);
-    if (e != hipSuccess) return done(hip_fail(e, "hipMemsetAsync"));
-  }
   for (size_t i = 0; i < K; ++i) {
-    size_t n = n0;
-    if (i) {
-      void* p = ctx->d_bgzf_range;
-      rc = ibu_load_bgzf_shard_to_device(ctx, path, cfg, i, K, &h, &p, cap(), &n, &first, &st);
-      if (rc) return done(rc);
+    size_t n = 0;
+    uint64_t first = 0;
+    ibu_stream_stats_t st{};
+    if (!rc) {
+      RunOnNode on_node(feed_place(ctx));                  // (the load's host threads on the device's node, option "numa")
+      BgzfLoad L{ctx, cfg, file, &st, &h, &ctx->d_bgzf_range, 0, i, K, std::max(last.num, (size_t)1), K > 1 ? &idx : nullptr};
+      if (K == 1) L.walk_beside();
+      rc = L.run(&n, &first);
     }
-    if (stats) { stats->bytes_h2d += st.bytes_h2d; stats->batches += st.batches; }
-    rc = dp.fits(n, (size_t)first);
-    if (rc) return done(rc);
-    if (n) {
-      rc = dp.launch(static_cast<const uint8_t*>(ctx->d_bgzf_range), n, (size_t)first);
-      if (rc) return done(rc);
+    if (i == 0 && (rc || memcmp(&h, &want, sizeof h) != 0)) {   // not for this path: as if it had not been tried
+      tls_error() = keep;
+      return IBU_OK;
     }
+    if (i == 0) {
+      *handled = true;
+      const hipError_t e = proc == IBU_PROC_REDUCE ? hipMemsetAsync(ctx->d_acc, 0, kReduceAccBytes, ctx->stream) : hipSuccess;
+      if (e != hipSuccess) return hip_fail(e, "hipMemsetAsync");
+    }
+    if (rc) return rc;
+    if (stats) { stats->bytes_h2d += st.bytes_h2d; stats->batches += st.batches; stats->numa_node = st.numa_node; stats->ring_node = st.ring_node; }
+    if ((rc = dp.fits(n, (size_t)first)) || (n && (rc = dp.launch(static_cast<const uint8_t*>(ctx->d_bgzf_range), n, (size_t)first)))) return rc;
     total += n;
     hipError_t e = hipStreamSynchronize(ctx->stream);      // (the next range is loaded over these records)
-    if (e != hipSuccess) return done(hip_fail(e, "hipStreamSynchronize"));
+    if (e != hipSuccess) return hip_fail(e, "hipStreamSynchronize");
   }
-  if (proc == IBU_PROC_REDUCE) {
-    rc = ibu_reduce_fetch(ctx, ctx->stream, static_cast<ibu_reduce_result_t*>(sink));
-    if (rc) return done(rc);
-  }
+  if (proc == IBU_PROC_REDUCE && (rc = ibu_reduce_fetch(ctx, ctx->stream, static_cast<ibu_reduce_result_t*>(sink)))) return rc;
   *records = total;
-  if (stats) { stats->records = total; stats->numa_node = st.numa_node; stats->ring_node = st.ring_node; }
-  return done(IBU_OK);
+  if (stats) stats->records = total;
+  return IBU_OK;
 }
 }  // namespace
 

@@ -76,6 +76,22 @@ def test_cpp_mirror_under_asan_ubsan(tmp_path, oracle):
            "ASAN_OPTIONS": "detect_leaks=1:halt_on_error=1", "UBSAN_OPTIONS": "print_stacktrace=1:halt_on_error=1"}
     r = _run([os.path.join(BIN, "asan", "test_host")], env=env)
     assert r.returncode == 0 and "0 failed" in r.stdout, r.stdout[-2000:] + r.stderr[-4000:]
+    _plan_driver_runs_clean(os.path.join(BIN, "asan", "test_bgzf_plan"), tmp_path, oracle, env)
+
+
+def _plan_driver_runs_clean(exe, tmp_path, oracle, env):
+    """tests/cpp/test_bgzf_plan.cpp under a sanitizer: the BGZF index (walk in pieces and plain walk) and every shard's plan."""
+    import struct
+
+    from tests.bgzf import bgzf_compress
+
+    plain = struct.pack("<IIIIQ8s", 0x21554249, 2, 16, 12, 0, b"\0" * 8) + oracle.generate(13, 0, 30_000, 16, 12).tobytes()
+    p = tmp_path / "plan.bgz"
+    p.write_bytes(bgzf_compress(plain, block=4093))
+    for pieces_min in ("0", str(1 << 62)):
+        r = _run([exe, str(p), pieces_min], env=env)
+        assert r.returncode == 0 and '"rc": 0' in r.stdout and "WARNING: ThreadSanitizer" not in r.stderr, r.stderr[-4000:]
+        assert ('"in_pieces": 1' if pieces_min == "0" else '"in_pieces": 0') in r.stdout
 
 
 def test_plain_c_client_of_the_abi(built):
@@ -96,6 +112,7 @@ def test_cpp_mirror_under_tsan(tmp_path, oracle):
            "TSAN_OPTIONS": "halt_on_error=1"}
     r = _run([os.path.join(BIN, "tsan", "test_host")], env=env)
     assert r.returncode == 0 and "0 failed" in r.stdout and "WARNING: ThreadSanitizer" not in r.stderr, r.stdout[-2000:] + r.stderr[-4000:]
+    _plan_driver_runs_clean(os.path.join(BIN, "tsan", "test_bgzf_plan"), tmp_path, oracle, env)
 
 
 def test_roundtrip_example_1e6(built, tmp_path, kat):
