@@ -8,7 +8,6 @@
 // Three HIP streams per context (H2D, compute, D2H) chained per slot with events; the host threads copy batch
 // k+1 in and batch k-1 out while batch k is on the device.  PCIe is the bound (24 B/record one way, 36 B the
 // other at 16/12), not the kernels.
-#include <chrono>
 #include <condition_variable>
 #include <mutex>
 #include <thread>
@@ -23,28 +22,8 @@ namespace {
 
 constexpr uint32_t kMaxCols = IBU_MAX_SEQ_LEN + IBU_MAX_SEQ_LEN + 8;  // bytes per record on the column side
 
-double now_s() {
-  return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count();
-}
-
 // memcpy split over a few threads (page-cache / page-fault side of the host work)
-void par_memcpy(uint8_t* dst, const uint8_t* src, size_t bytes, uint32_t threads) {
-  const size_t min_chunk = (size_t)4 << 20;
-  size_t parts = bytes / min_chunk;
-  if (parts > threads) parts = threads;
-  if (parts <= 1) {
-    if (bytes) memcpy(dst, src, bytes);
-    return;
-  }
-  const size_t per = ((bytes / parts) + 4095) & ~(size_t)4095;
-  run_pieces((unsigned)parts, [=](unsigned i) {  // never throws (common.hpp)
-    const size_t off = (size_t)i * per;
-    if (off >= bytes) return;
-    memcpy(dst + off, src + off, off + per < bytes ? per : bytes - off);
-  });
-}
-
-uint32_t feeders(const ibu_ring_config_t* cfg) { return cfg && cfg->feeder_threads ? cfg->feeder_threads : 4; }
+void par_memcpy(uint8_t* dst, const uint8_t* src, size_t bytes, uint32_t threads) { parallel_memcpy(dst, src, bytes, threads, (size_t)4 << 20); }
 
 int32_t codec_ring_ensure(ibu_ctx* ctx, const ibu_ring_config_t* cfg) {
   uint32_t slots = cfg && cfg->slots ? cfg->slots : 4;
@@ -118,6 +97,41 @@ struct Handoff {
   void done(int32_t rc) { { std::lock_guard<std::mutex> g(m); if (rc && !err) err = rc; else if (!rc) ++delivered; } cv.notify_all(); }
 };
 
+// The frame of both pipelines: submit(k) fills slot k % slots and queues batch k's copies and kernel on this thread, collect(k) delivers
+// batch k on the collector thread; each returns IBU_OK or a status.  Nothing is in flight over ring memory when an error is returned.
+template <class Submit, class Collect>
+int32_t run_codec_pipeline(ibu_ctx* ctx, size_t nb, size_t slots, Submit&& submit, Collect&& collect) {
+  Handoff ho;
+  ibu_error_detail_t collector_detail;
+  memset(&collector_detail, 0, sizeof collector_detail);
+  std::thread collector;
+  try {
+    collector = std::thread([&]() {
+      (void)hipSetDevice(ctx->device);
+      size_t k;
+      while (ho.next(&k)) {
+        const int32_t e = collect(k);
+        if (e) ibu_last_error(&collector_detail);  // the error record is per thread: carry it over
+        ho.done(e);
+      }
+    });
+  } catch (...) {  // std::system_error (EAGAIN under a pids cgroup) / bad_alloc: nothing is in flight yet
+    return caught_io("cannot start the collector thread");
+  }
+  int32_t rc = IBU_OK;
+  for (size_t k = 0; k < nb && rc == IBU_OK; ++k) {
+    rc = ho.wait_slot(k, slots);  // slot k % slots is free: batch k - slots has been delivered
+    if (rc == IBU_OK && (rc = submit(k)) == IBU_OK) ho.publish();
+  }
+  ho.finish_producing(rc);
+  collector.join();
+  if (collector_detail.code)  // the collector failed first (the producer only saw its flag): report ITS error from this thread
+    rc = set_error(collector_detail.code, collector_detail.a, collector_detail.b, collector_detail.os_errno, "%s", collector_detail.message);
+  else if (rc == IBU_OK && ho.err)
+    rc = ho.err;
+  return rc ? drain3(ctx, rc) : IBU_OK;
+}
+
 struct ColLayout {  // where the three columns of a slot live inside its column buffer
   size_t bc, umi, idx, bytes;
   ColLayout(size_t slot_records, uint32_t bc_len, uint32_t umi_len)
@@ -163,7 +177,7 @@ extern "C" int32_t ibu_mmap_decode_to_host(const ibu_mmap_t* m, ibu_ctx_t* ctx, 
   CodecRing& r = ctx->cring;
   const ColLayout L(r.slot_records, h.bc_len, h.umi_len);
   const uint8_t* base = static_cast<const uint8_t*>(ibu_mmap_base(m)) + IBU_HEADER_SIZE;
-  const uint32_t nf = feeders(cfg);
+  const uint32_t nf = feeder_threads(cfg);
   const size_t total = end - start;
   const size_t nb = (total + r.slot_records - 1) / r.slot_records;
 
@@ -178,27 +192,8 @@ extern "C" int32_t ibu_mmap_decode_to_host(const ibu_mmap_t* m, ibu_ctx_t* ctx, 
     return IBU_OK;
   };
 
-  Handoff ho;
-  ibu_error_detail_t collector_detail;
-  memset(&collector_detail, 0, sizeof collector_detail);
-  std::thread collector;
-  try {
-  collector = std::thread([&]() {
-    (void)hipSetDevice(ctx->device);
-    size_t k;
-    while (ho.next(&k)) {
-      const int32_t e = collect(k);
-      if (e) ibu_last_error(&collector_detail);  // the error record is per thread: carry it over
-      ho.done(e);
-    }
-  });
-  } catch (...) {  // std::system_error (EAGAIN under a pids cgroup) / bad_alloc: nothing is in flight yet
-    return caught_io("cannot start the collector thread");
-  }
-  for (size_t k = 0; k < nb && rc == IBU_OK; ++k) {
+  auto submit = [&](size_t k) -> int32_t {  // batch k: mapped file -> pinned -> device -> decode -> pinned columns
     const uint32_t s = (uint32_t)(k % r.slots);
-    rc = ho.wait_slot(k, r.slots);  // slot s is free: batch k - slots has been delivered
-    if (rc) break;
     const size_t rows = rows_of(k);
     par_memcpy(r.h_aos[s], base + (start + k * r.slot_records) * IBU_RECORD_SIZE, rows * IBU_RECORD_SIZE, nf);
     hipError_t e = hipMemcpyAsync(r.d_aos[s], r.h_aos[s], rows * IBU_RECORD_SIZE, hipMemcpyHostToDevice, ctx->copy_stream);
@@ -218,21 +213,16 @@ extern "C" int32_t ibu_mmap_decode_to_host(const ibu_mmap_t* m, ibu_ctx_t* ctx, 
     if (e == hipSuccess && h_index)
       e = hipMemcpyAsync(r.h_col[s] + L.idx, r.d_col[s] + L.idx, rows * 8, hipMemcpyDeviceToHost, ctx->d2h_stream);
     if (e == hipSuccess) e = hipEventRecord(r.down[s], ctx->d2h_stream);
-    if (e != hipSuccess) { rc = hip_fail(e, "decode pipeline"); break; }
+    if (e != hipSuccess) return hip_fail(e, "decode pipeline");
     if (stats) {
       stats->bytes_h2d += rows * IBU_RECORD_SIZE;
       stats->bytes_d2h += rows * ((h_bc_ascii ? h.bc_len : 0) + (h_umi_ascii ? h.umi_len : 0) + (h_index ? 8 : 0));
       stats->batches += 1;
     }
-    ho.publish();
-  }
-  ho.finish_producing(rc);
-  collector.join();
-  if (collector_detail.code)  // the collector failed first (the producer only saw its flag): report ITS error from this thread
-    rc = set_error(collector_detail.code, collector_detail.a, collector_detail.b, collector_detail.os_errno, "%s", collector_detail.message);
-  else if (rc == IBU_OK && ho.err)
-    rc = ho.err;
-  if (rc) return drain3(ctx, rc);
+    return IBU_OK;
+  };
+  rc = run_codec_pipeline(ctx, nb, r.slots, submit, collect);
+  if (rc) return rc;
   if (stats) { stats->records = total; stats->seconds_total = now_s() - t0; }
   return IBU_OK;
 }
@@ -256,7 +246,7 @@ extern "C" int32_t ibu_writer_write_ascii_batch(ibu_writer_t* w, ibu_ctx_t* ctx,
   if (rc) return rc;
   CodecRing& r = ctx->cring;
   const ColLayout L(r.slot_records, bc_len, umi_len);
-  const uint32_t nf = feeders(cfg);
+  const uint32_t nf = feeder_threads(cfg);
   const size_t nb = (n + r.slot_records - 1) / r.slot_records;
   auto rows_of = [&](size_t k) { return k + 1 < nb ? r.slot_records : n - k * r.slot_records; };
   uint64_t first_bad = ~0ull, n_bad = 0;
@@ -273,27 +263,8 @@ extern "C" int32_t ibu_writer_write_ascii_batch(ibu_writer_t* w, ibu_ctx_t* ctx,
     return writer_write_bytes(w, r.h_aos[s], rows * IBU_RECORD_SIZE);  // buffered / direct rule of writer.rs:321-351
   };
 
-  Handoff ho;
-  ibu_error_detail_t collector_detail;
-  memset(&collector_detail, 0, sizeof collector_detail);
-  std::thread collector;
-  try {
-  collector = std::thread([&]() {  // delivers batches to the writer while the caller's thread stages the next ones
-    (void)hipSetDevice(ctx->device);
-    size_t k;
-    while (ho.next(&k)) {
-      const int32_t e = collect(k);
-      if (e) ibu_last_error(&collector_detail);
-      ho.done(e);
-    }
-  });
-  } catch (...) {  // std::system_error (EAGAIN under a pids cgroup) / bad_alloc: nothing is in flight yet
-    return caught_io("cannot start the collector thread");
-  }
-  for (size_t k = 0; k < nb && rc == IBU_OK; ++k) {
+  auto submit = [&](size_t k) -> int32_t {  // batch k: caller columns -> pinned -> device -> encode -> pinned records
     const uint32_t s = (uint32_t)(k % r.slots);
-    rc = ho.wait_slot(k, r.slots);
-    if (rc) break;
     const size_t rows = rows_of(k), row0 = k * r.slot_records;
     par_memcpy(r.h_col[s] + L.bc, h_bc_ascii + row0 * bc_len, rows * bc_len, nf);
     par_memcpy(r.h_col[s] + L.umi, h_umi_ascii + row0 * umi_len, rows * umi_len, nf);
@@ -315,21 +286,16 @@ extern "C" int32_t ibu_writer_write_ascii_batch(ibu_writer_t* w, ibu_ctx_t* ctx,
     if (e == hipSuccess) e = hipMemcpyAsync(r.h_aos[s], r.d_aos[s], rows * IBU_RECORD_SIZE, hipMemcpyDeviceToHost, ctx->d2h_stream);
     if (e == hipSuccess) e = hipMemcpyAsync(r.h_status[s], r.d_status[s], 2 * sizeof(uint64_t), hipMemcpyDeviceToHost, ctx->d2h_stream);
     if (e == hipSuccess) e = hipEventRecord(r.down[s], ctx->d2h_stream);
-    if (e != hipSuccess) { rc = hip_fail(e, "encode pipeline"); break; }
+    if (e != hipSuccess) return hip_fail(e, "encode pipeline");
     if (stats) {
       stats->bytes_h2d += rows * (bc_len + umi_len + (h_index ? 8 : 0));
       stats->bytes_d2h += rows * IBU_RECORD_SIZE;
       stats->batches += 1;
     }
-    ho.publish();
-  }
-  ho.finish_producing(rc);
-  collector.join();
-  if (collector_detail.code)  // the collector failed first (the producer only saw its flag): report ITS error from this thread
-    rc = set_error(collector_detail.code, collector_detail.a, collector_detail.b, collector_detail.os_errno, "%s", collector_detail.message);
-  else if (rc == IBU_OK && ho.err)
-    rc = ho.err;
-  if (rc) return drain3(ctx, rc);
+    return IBU_OK;
+  };
+  rc = run_codec_pipeline(ctx, nb, r.slots, submit, collect);
+  if (rc) return rc;
   if (stats) { stats->records = n; stats->seconds_total = now_s() - t0; }
   if (n_bad)
     return set_error(IBU_ERR_INVALID_BASE, first_bad, n_bad, 0,

@@ -6,6 +6,7 @@
 #include <stdio.h>
 #include <string.h>
 
+#include <chrono>
 #include <new>
 #include <system_error>
 #include <thread>
@@ -95,6 +96,34 @@ inline void run_pieces(unsigned n, F&& fn) noexcept {
   for (unsigned i = started; i < n; ++i) fn(i);
   for (auto& t : th) t.join();
 }
+// Split [0, total) over up to `threads` threads (run_pieces) in page-aligned pieces: one piece per `min_chunk` bytes begun, at most
+// `threads` and 64 of them.  fn(offset, len) returns 0 or errno and must not throw; the error of the first piece that failed wins.
+template <class F>
+inline int parallel_bytes(size_t total, unsigned threads, size_t min_chunk, F&& fn) noexcept {
+  size_t parts = (total + min_chunk - 1) / min_chunk;
+  if (parts > threads) parts = threads;
+  if (parts > 64) parts = 64;
+  if (parts <= 1) return total ? fn((size_t)0, total) : 0;
+  int rc[64] = {};
+  const size_t per = (total / parts + 4095) & ~(size_t)4095;
+  run_pieces((unsigned)parts, [&](unsigned i) {
+    const size_t off = (size_t)i * per;
+    if (off < total) rc[i] = fn(off, off + per < total ? per : total - off);
+  });
+  for (size_t i = 0; i < parts; ++i)
+    if (rc[i]) return rc[i];
+  return 0;
+}
+inline void parallel_memcpy(void* dst, const void* src, size_t bytes, unsigned threads, size_t min_chunk) noexcept {
+  uint8_t* d = static_cast<uint8_t*>(dst);
+  const uint8_t* s = static_cast<const uint8_t*>(src);
+  parallel_bytes(bytes, threads, min_chunk, [=](size_t off, size_t len) { memcpy(d + off, s + off, len); return 0; });
+}
+
+inline double now_s() {
+  return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count();
+}
+
 // Map whatever a C++ library call threw to a status; used as `catch (...) { return caught_io("what"); }` at the ABI.
 inline int32_t caught_io(const char* what) {
   try { throw; }

@@ -90,6 +90,8 @@ struct ibu_ctx {
 
 namespace ibu {
 int32_t ring_ensure(ibu_ctx* ctx, const ibu_ring_config_t* cfg, bool need_dev);
+// Host threads that copy into a staging slot (both rings).
+inline uint32_t feeder_threads(const ibu_ring_config_t* cfg) { return cfg && cfg->feeder_threads ? cfg->feeder_threads : 4; }
 void ring_release(ibu_ctx* ctx);
 void stream_orphan(ibu_ctx* ctx);   // stream.cpp: shut down the open ibu_stream_t that holds the ring (ibu_ctx_destroy)
 void codec_ring_release(ibu_ctx* ctx);

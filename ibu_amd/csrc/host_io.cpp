@@ -17,6 +17,7 @@
 #include <cstdlib>
 
 #include <atomic>
+#include <functional>
 #include <future>
 #include <memory>
 #include <new>
@@ -217,14 +218,7 @@ struct FdSource : Source {
       const int f = fd;
       run_pieces(kPieces, [&, base, f](unsigned i) {    // never throws
         const size_t off = (size_t)i * per;
-        if (off >= cap) return;
-        const size_t len = off + per < cap ? per : cap - off;
-        while (done[i] < len) {
-          const ssize_t k = pread(f, dst + off + done[i], len - done[i], base + (off_t)(off + done[i]));
-          if (k < 0) { if (errno == EINTR) continue; err[i] = errno; return; }
-          if (k == 0) return;                           // end of file inside this piece
-          done[i] += (size_t)k;
-        }
+        if (off < cap) err[i] = pread_upto(f, dst + off, off + per < cap ? per : cap - off, base + (off_t)off, &done[i]);
       });
       size_t total = 0;
       for (unsigned i = 0; i < kPieces; ++i) {           // the contiguous prefix that was read
@@ -497,6 +491,29 @@ struct ZstdSource : InflatingSource {
   }
 };
 
+// The next batch of a source, made on a thread of its own while the current one is handed out (at most one at a time).  Nothing
+// throws out of it, as it runs under extern "C" entry points: a job that throws is ENOMEM (bad_alloc) or EIO, and start() is false
+// when no thread can be had (std::system_error EAGAIN, bad_alloc) — the caller then runs the job inline with run().
+struct Background {
+  std::function<int()> job;                          // 0 or errno
+  std::future<int> next;
+  int run() noexcept {
+    try { return job(); }
+    catch (const std::bad_alloc&) { return ENOMEM; }
+    catch (...) { return EIO; }
+  }
+  bool start() noexcept {
+    try { next = std::async(std::launch::async, [this] { return run(); }); return true; }
+    catch (...) { return false; }
+  }
+  bool pending() const { return next.valid(); }
+  int get() noexcept {                               // synchronises with everything the job wrote
+    try { return next.get(); }
+    catch (const std::bad_alloc&) { return ENOMEM; }
+    catch (...) { return EIO; }
+  }
+};
+
 // BGZF (bgzip) input: a gzip file whose members are <= 64 KiB blocks that carry their own compressed size in a
 // "BC" extra subfield.  To niffler / flate2's MultiGzDecoder it is just a multi-member gzip stream, inflated by
 // one thread; because the block boundaries are known WITHOUT inflating, this source reads a batch of blocks and
@@ -526,12 +543,13 @@ struct RawBytes {
   size_t size() const { return n; }
   void swap(RawBytes& o) { std::swap(p, o.p); std::swap(n, o.n); std::swap(cap, o.cap); }
 };
-// The header of the gzip member at hd (avail bytes from there on), read as a BGZF block: the one rule of both walks
-// (BgzfSource::refill, ibu_bgzf_scan).  RFC 1952 2.3: FEXTRA (which must carry the "BC" subfield, other subfields around it
-// allowed), then FNAME and FCOMMENT (zero-terminated) and FHCRC (the low 16 bits of the CRC-32 of the header in front of it) in
-// that order; BSIZE counts from the member's first byte.  Flag bits 5-7 are refused and FHCRC is checked, as zlib's inflate does.
+// The gzip member at hd (avail bytes from there on), read as a BGZF block: the one rule of both walks (BgzfSource::refill,
+// ibu_bgzf_scan).  RFC 1952 2.3: FEXTRA (which must carry the "BC" subfield, other subfields around it allowed), then FNAME and
+// FCOMMENT (zero-terminated) and FHCRC (the low 16 bits of the CRC-32 of the header in front of it) in that order; BSIZE counts from
+// the member's first byte.  Flag bits 5-7 are refused and FHCRC is checked, as zlib's inflate does; so is an ISIZE above 64 KiB.
+// A block fills *b from its trailer, comp_offset counted from hd (out_offset is the caller's), and *bsize_out = BSIZE.
 enum MemberKind { kMemberBgzf, kMemberNotBgzf, kMemberNeedMore, kMemberBad };
-MemberKind bgzf_member(const uint8_t* hd, size_t avail, size_t* hlen, size_t* bsize_out, const char** why) {
+MemberKind bgzf_member(const uint8_t* hd, size_t avail, ibu_inflate_block_t* b, size_t* bsize_out, const char** why) {
   if (avail < 12) return kMemberNeedMore;
   if (!(hd[0] == 0x1f && hd[1] == 0x8b && hd[2] == 8 && (hd[3] & 4))) { *why = "not a BGZF block (a gzip member without the BC extra field)"; return kMemberNotBgzf; }
   if (hd[3] & 0xE0) { *why = "a gzip member header with reserved flag bits set"; return kMemberBad; }
@@ -561,7 +579,13 @@ MemberKind bgzf_member(const uint8_t* hd, size_t avail, size_t* hlen, size_t* bs
     p += 2;
   }
   if (p + 2 + 8 > bsize) return kMemberNotBgzf;
-  *hlen = p;
+  const uint8_t* tr = hd + bsize - 8;
+  b->out_len = (uint32_t)tr[4] | ((uint32_t)tr[5] << 8) | ((uint32_t)tr[6] << 16) | ((uint32_t)tr[7] << 24);
+  if (b->out_len > 65536) { *why = "a BGZF block announces more than 64 KiB"; return kMemberBad; }
+  b->comp_offset = p;
+  b->comp_len = (uint32_t)(bsize - p - 8);
+  b->crc32 = (uint32_t)tr[0] | ((uint32_t)tr[1] << 8) | ((uint32_t)tr[2] << 16) | ((uint32_t)tr[3] << 24);
+  b->reserved = 0;
   *bsize_out = bsize;
   return kMemberBgzf;
 }
@@ -572,15 +596,15 @@ struct BgzfSource : Source {
   std::vector<uint8_t> comp;
   RawBytes out;                       // the batch being handed out by read()
   RawBytes next_out;                  // the batch being inflated in the background while `out` is consumed
-  std::future<int> next;              // pending background refill (at most one; it alone touches inner/comp/eof/fallback)
+  Background bg;                      // the refill of next_out (while pending, it alone touches inner/comp/eof/fallback)
   size_t out_pos = 0;
   bool eof = false;
   int pending_err = 0;                // a bad spot was met: reported once what lies in front of it has been handed out
   unsigned threads;
-  struct Block { size_t coff, clen, ooff, isize; uint32_t crc; };
   std::unique_ptr<pgz::WorkerPool> pool;                       // threads - 1 workers, started with the first batch
   std::vector<std::unique_ptr<pgz::RawInflater>> raws;         // one decoder (tables, 64 KiB buffer) per thread, kept
   explicit BgzfSource(std::unique_ptr<Source> s) : inner(std::move(s)) {
+    bg.job = [this] { return refill(next_out); };
     const char* e = getenv("IBU_BGZF_THREADS");
     size_t c = e ? (size_t)atol(e) : ibu::inflate_threads();
     threads = (unsigned)(c < 1 ? 1 : (c > 64 ? 64 : c));
@@ -612,7 +636,7 @@ struct BgzfSource : Source {
     if ((uint32_t)crc32(crc32(0L, Z_NULL, 0), o, (uInt)isize) != crc) return EPROTO;
     return 0;
   }
-  ~BgzfSource() override { if (next.valid()) (void)next.get(); }  // never leave the worker running over freed members
+  ~BgzfSource() override { if (bg.pending()) (void)bg.get(); }  // never leave the worker running over freed members
   // Input is read in large pieces and the block headers are parsed from memory (one read(2) per 16 MiB instead of three
   // per block: at 1e9 records that was 1.4 M system calls on the thread every batch waits for); blocks are inflated
   // straight out of `comp`, a block that is not whole yet stays for the next batch.
@@ -620,7 +644,7 @@ struct BgzfSource : Source {
   bool inner_eof = false;
   int refill(RawBytes& dst) {
     dst.n = 0;
-    std::vector<Block> blocks;
+    std::vector<ibu_inflate_block_t> blocks;
     size_t total_out = 0;
     const size_t kBatchComp = batch_comp;
     const size_t kPadBytes = 512;
@@ -645,9 +669,10 @@ struct BgzfSource : Source {
       const size_t avail = comp_len - comp_pos;
       if (avail == 0) { eof = true; break; }
       const uint8_t* hd = comp.data() + comp_pos;
-      size_t hlen = 0, bsize = 0;
+      ibu_inflate_block_t b;
+      size_t bsize = 0;
       const char* why = nullptr;
-      const MemberKind kind = bgzf_member(hd, avail, &hlen, &bsize, &why);
+      const MemberKind kind = bgzf_member(hd, avail, &b, &bsize, &why);
       if (kind == kMemberNeedMore) { if (inner_eof) pending_err = EPROTO; break; }  // the block is not whole yet / the stream ends inside it
       if (kind == kMemberBad) { pending_err = EPROTO; break; }
       if (kind == kMemberNotBgzf) {
@@ -660,15 +685,9 @@ struct BgzfSource : Source {
         comp_pos = comp_len;
         break;
       }
-      const uint8_t* tr = hd + bsize - 8;
-      Block b;
-      b.coff = comp_pos + hlen;
-      b.clen = bsize - hlen - 8;
-      b.crc = (uint32_t)tr[0] | ((uint32_t)tr[1] << 8) | ((uint32_t)tr[2] << 16) | ((uint32_t)tr[3] << 24);
-      b.isize = (size_t)tr[4] | ((size_t)tr[5] << 8) | ((size_t)tr[6] << 16) | ((size_t)tr[7] << 24);
-      if (b.isize > 65536) { pending_err = EPROTO; break; }
-      b.ooff = total_out;
-      total_out += b.isize;
+      b.comp_offset += comp_pos;
+      b.out_offset = (int64_t)total_out;
+      total_out += b.out_len;
       blocks.push_back(b);
       comp_pos += bsize;
     }
@@ -687,17 +706,18 @@ struct BgzfSource : Source {
       if (!raws[t]) raws[t].reset(new pgz::RawInflater);
       pgz::RawInflater& raw = *raws[t];
       for (size_t i = t; i < blocks.size(); i += nt) {
-        const Block& b = blocks[i];
+        const ibu_inflate_block_t& b = blocks[i];
         // every block is inflated, the empty ones too (the EOF marker is "03 00"; "01 00" is refused as zlib refuses it); an
         // empty block's output pointer must not be NULL even when the whole batch is empty (zlib refuses next_out == NULL)
         uint8_t none = 0;
-        uint8_t* o = b.isize ? dst.data() + b.ooff : &none;
+        uint8_t* o = b.out_len ? dst.data() + b.out_offset : &none;
+        const uint8_t* c = comp.data() + b.comp_offset;
         int rc;
-        if (use_zlib) rc = inflate_block(&zs, comp.data() + b.coff, b.clen, o, b.isize, b.crc);
+        if (use_zlib) rc = inflate_block(&zs, c, b.comp_len, o, b.out_len, b.crc32);
         else {
           uint32_t crc = 0;
-          rc = raw.inflate(comp.data() + b.coff, b.clen, o, b.isize, &crc);
-          if (rc == 0 && crc != b.crc) rc = EPROTO;
+          rc = raw.inflate(c, b.comp_len, o, b.out_len, &crc);
+          if (rc == 0 && crc != b.crc32) rc = EPROTO;
         }
         if (rc) { rcs[t] = rc; bad_at[t] = i; break; }
       }
@@ -715,25 +735,11 @@ struct BgzfSource : Source {
       if (bad_at[t] < first_bad) first_bad = bad_at[t];
     }
     if (first_bad != ~(size_t)0) {                       // blocks in front of the first bad one are good and go out
-      dst.n = blocks[first_bad].ooff;
+      dst.n = (size_t)blocks[first_bad].out_offset;
       pending_err = EPROTO;
       eof = true;                                      // nothing is read behind the bad spot
     }
     return 0;
-  }
-  // refill() grows vectors: bad_alloc must not leave as an exception (this is called under extern "C" entry points)
-  int refill_noexcept() {
-    try { return refill(next_out); }
-    catch (const std::bad_alloc&) { return ENOMEM; }
-    catch (...) { return EIO; }
-  }
-  bool start_refill() {
-    try {
-      next = std::async(std::launch::async, [this] { return refill_noexcept(); });
-      return true;
-    } catch (...) {  // std::system_error (EAGAIN) / bad_alloc from the thread start
-      return false;
-    }
   }
   int read(uint8_t* dst, size_t cap, size_t* got) override {
     *got = 0;
@@ -747,26 +753,23 @@ struct BgzfSource : Source {
       }
       // current batch drained: take the one inflated in the background (or start the first), then immediately start
       // the next so that reading + inflating batch k+1 overlaps the caller's consumption of batch k
-      if (!next.valid()) {
+      if (!bg.pending()) {
         if (pending_err) return pending_err;   // everything in front of the bad spot has been handed out
         if (fallback) return fallback->read(dst, cap, got);
         if (eof) return 0;
-        if (!start_refill()) {   // no thread to be had: inflate the batch on this one
-          const int rc = refill_noexcept();
+        if (!bg.start()) {   // no thread to be had: inflate the batch on this one
+          const int rc = bg.run();
           if (rc) return rc;
           out.swap(next_out);
           out_pos = 0;
           continue;
         }
       }
-      int rc;
-      try { rc = next.get(); }  // synchronises with everything the worker wrote (eof, fallback, next_out)
-      catch (const std::bad_alloc&) { rc = ENOMEM; }
-      catch (...) { rc = EIO; }
+      const int rc = bg.get();  // (eof, fallback, next_out as the refill left them)
       if (rc) return rc;
       out.swap(next_out);
       out_pos = 0;
-      if (!eof && !fallback) (void)start_refill();  // failure: the next round inflates inline
+      if (!eof && !fallback) (void)bg.start();  // failure: the next round inflates inline
     }
   }
 };
@@ -780,7 +783,7 @@ struct ParGzSource : Source {
   std::unique_ptr<Source> inner;
   std::unique_ptr<pgz::ParallelGunzip> dec;
   std::vector<pgz::Span> out, next_out;              // pieces of the decoder's chunk buffers (valid while the NEXT batch decodes)
-  std::future<int> next;
+  Background bg;                                     // decodes next_out
   size_t span_i = 0, span_off = 0;
   bool eof = false, next_eof = false;
   static unsigned env_threads() {
@@ -795,9 +798,10 @@ struct ParGzSource : Source {
   explicit ParGzSource(std::unique_ptr<Source> s) : inner(std::move(s)) {
     Source* in = inner.get();
     dec.reset(new pgz::ParallelGunzip([in](uint8_t* d, size_t cap, size_t* got) { return in->read(d, cap, got); }, env_threads(), env_chunk()));
+    bg.job = [this] { return dec->next_batch(next_out, &next_eof); };
   }
   ~ParGzSource() override {
-    if (next.valid()) (void)next.get();
+    if (bg.pending()) (void)bg.get();
     if (getenv("IBU_PGZ_TRACE")) {                     // where the time of the parallel inflate went (wall seconds per phase)
       const pgz::Stats& t = dec->stats();
       fprintf(stderr, "[pgzip] in %llu B out %llu B batches %llu chunks accepted %llu discarded %llu no-candidate %llu markers %llu | "
@@ -805,19 +809,6 @@ struct ParGzSource : Source {
               (unsigned long long)t.bytes_in, (unsigned long long)t.bytes_out, (unsigned long long)t.batches,
               (unsigned long long)t.chunks_accepted, (unsigned long long)t.chunks_discarded, (unsigned long long)t.candidates_missing,
               (unsigned long long)t.marker_symbols, t.s_read, t.s_join_wait, t.s_helper_read, t.s_find, t.s_decode, t.s_windows, t.s_patch_crc, t.s_carry);
-    }
-  }
-  int refill_noexcept() {
-    try { return dec->next_batch(next_out, &next_eof); }
-    catch (const std::bad_alloc&) { return ENOMEM; }
-    catch (...) { return EIO; }
-  }
-  bool start_refill() {
-    try {
-      next = std::async(std::launch::async, [this] { return refill_noexcept(); });
-      return true;
-    } catch (...) {
-      return false;
     }
   }
   int read(uint8_t* dst, size_t cap, size_t* got) override {
@@ -831,11 +822,7 @@ struct ParGzSource : Source {
           const uint8_t* src = sp.p + span_off;
           uint8_t* d = dst + done;
           if (k >= ((size_t)4 << 20)) {                // one thread copies ~8 GB/s, the inflate delivers 5-6
-            const size_t per = ((k / 4) + 4095) & ~(size_t)4095;
-            run_pieces(4, [=](unsigned i) {
-              const size_t off = (size_t)i * per;
-              if (off < k) memcpy(d + off, src + off, off + per < k ? per : k - off);
-            });
+            parallel_memcpy(d, src, k, 4, (size_t)1 << 20);
           } else if (k) {
             memcpy(d, src, k);
           }
@@ -847,19 +834,12 @@ struct ParGzSource : Source {
         return 0;
       }
       if (eof) return 0;
-      int rc;
-      if (next.valid()) {
-        try { rc = next.get(); }
-        catch (const std::bad_alloc&) { rc = ENOMEM; }
-        catch (...) { rc = EIO; }
-      } else {
-        rc = refill_noexcept();                        // the first batch (or no thread to be had): decode it here
-      }
+      const int rc = bg.pending() ? bg.get() : bg.run();   // (run: the first batch, or no thread to be had: decode it here)
       if (rc) return rc;
       out.swap(next_out);                              // the batch just consumed is dead: its buffers are the ones the refill
       span_i = span_off = 0;                           // started below decodes into
       eof = next_eof;
-      if (!eof) (void)start_refill();                  // failure: the next round decodes inline
+      if (!eof) (void)bg.start();                      // failure: the next round decodes inline
     }
   }
 };
@@ -944,20 +924,13 @@ extern "C" int32_t ibu_bgzf_scan(const uint8_t* buf, size_t len, int32_t final, 
   int32_t rc = IBU_OK;
   while (pos < len && nb < cap) {
     const size_t avail = len - pos;
-    const uint8_t* hd = buf + pos;
-    size_t hlen = 0, bsize = 0;
+    ibu_inflate_block_t b;
+    size_t bsize = 0;
     const char* why = nullptr;
-    const MemberKind kind = bgzf_member(hd, avail, &hlen, &bsize, &why);
+    const MemberKind kind = bgzf_member(buf + pos, avail, &b, &bsize, &why);
     if (kind == kMemberNeedMore) { if (final) rc = err_niffler("the stream ends inside a BGZF block"); break; }
     if (kind != kMemberBgzf) { rc = err_niffler(why); break; }
-    const uint8_t* tr = hd + bsize - 8;
-    ibu_inflate_block_t b;
-    b.comp_offset = pos + hlen;
-    b.comp_len = (uint32_t)(bsize - hlen - 8);
-    b.crc32 = (uint32_t)tr[0] | ((uint32_t)tr[1] << 8) | ((uint32_t)tr[2] << 16) | ((uint32_t)tr[3] << 24);
-    b.out_len = (uint32_t)tr[4] | ((uint32_t)tr[5] << 8) | ((uint32_t)tr[6] << 16) | ((uint32_t)tr[7] << 24);
-    b.reserved = 0;
-    if (b.out_len > 65536) { rc = err_niffler("a BGZF block announces more than 64 KiB"); break; }
+    b.comp_offset += pos;
     b.out_offset = (int64_t)total;
     total += b.out_len;
     blocks[nb++] = b;
@@ -1259,6 +1232,20 @@ extern "C" void ibu_reader_close(ibu_reader_t* r) { delete r; }
 // ------------------------------------------------------------------------------------------
 // load_to_vec (src/io/reader.rs:510-535)
 // ------------------------------------------------------------------------------------------
+int ibu::pread_upto(int fd, uint8_t* dst, size_t len, off_t off, size_t* got) {
+  size_t done = 0;
+  int e = 0;
+  while (done < len) {
+    const ssize_t k = ::pread(fd, dst + done, len - done, off + (off_t)done);
+    if (k < 0 && errno == EINTR) continue;
+    if (k < 0) { e = errno; break; }
+    if (k == 0) break;  // end of file
+    done += (size_t)k;
+  }
+  *got = done;
+  return e;
+}
+
 int32_t ibu::open_plain_file(const char* path, int* fd_out, ibu_header_t* header, size_t* n_records) {
   int fd = ::open(path, O_RDONLY | O_CLOEXEC);
   if (fd < 0) return err_io(errno, path);
@@ -1324,35 +1311,11 @@ extern "C" int32_t ibu_load_to_vec(const char* path, ibu_header_t* header, ibu_r
   // a few threads with pread so the page faults of the fresh allocation and the kernel copies overlap.
   uint8_t* p = reinterpret_cast<uint8_t*>(v);
   const size_t total = num * IBU_RECORD_SIZE;
-  auto read_range = [&](size_t off, size_t len) -> int {
-    while (len) {
-      ssize_t k = ::pread(fd, p + off, len, (off_t)(IBU_HEADER_SIZE + off));
-      if (k < 0 && errno == EINTR) continue;
-      if (k < 0) return errno;
-      if (k == 0) return EIO;  // the file shrank underneath us
-      off += (size_t)k;
-      len -= (size_t)k;
-    }
-    return 0;
-  };
-  int err = 0;
-  const size_t kPar = (size_t)64 << 20;
-  if (total <= kPar) {
-    err = read_range(0, total);
-  } else {
-    unsigned hw = std::thread::hardware_concurrency();
-    size_t nt = hw ? (hw < 8 ? hw : 8) : 4;
-    if (nt > total / kPar + 1) nt = total / kPar + 1;
-    const size_t per = ((total / nt) + 4095) & ~(size_t)4095;
-    int rcs[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-    run_pieces((unsigned)nt, [&](unsigned i) {   // never throws; nt <= 8
-      const size_t off = (size_t)i * per;
-      if (off >= total) return;
-      rcs[i] = read_range(off, off + per < total ? per : total - off);
-    });
-    for (int r : rcs)
-      if (r && !err) err = r;
-  }
+  const size_t cores = host_cores();
+  const unsigned nt = cores < 8 ? (unsigned)cores : 8;   // one thread per 64 MiB begun, up to 8
+  const int err = parallel_bytes(total, nt, (size_t)64 << 20, [&](size_t off, size_t len) {
+    return pread_all(fd, p + off, len, (off_t)(IBU_HEADER_SIZE + off));
+  });
   if (err) {
     free(v);
     close(fd);
@@ -1367,10 +1330,35 @@ extern "C" int32_t ibu_load_to_vec(const char* path, ibu_header_t* header, ibu_r
 // ------------------------------------------------------------------------------------------
 // MmapReader (src/io/mmap.rs)
 // ------------------------------------------------------------------------------------------
+FileMap::~FileMap() {
+  if (p) munmap(const_cast<uint8_t*>(p), n);
+}
+int32_t ibu::map_file(const char* path, FileMap* m, int32_t (*check)(size_t size)) {
+  int fd = ::open(path, O_RDONLY | O_CLOEXEC);
+  if (fd < 0) return err_io(errno, path);
+  struct stat st;
+  if (fstat(fd, &st)) {
+    const int e = errno;
+    close(fd);
+    return err_io(e, "metadata");
+  }
+  const size_t size = (size_t)st.st_size;
+  if (const int32_t rc = check(size)) {
+    close(fd);
+    return rc;
+  }
+  void* p = mmap(nullptr, size, PROT_READ, MAP_PRIVATE, fd, 0);
+  const int e = errno;
+  close(fd);
+  if (p == MAP_FAILED) return err_io(e, "mmap");
+  m->p = static_cast<const uint8_t*>(p);
+  m->n = size;
+  return IBU_OK;
+}
+
 namespace {
 struct Mapping {  // Arc<Mmap>
-  uint8_t* base = nullptr;
-  size_t len = 0;
+  FileMap file;
   std::atomic<int> refs{1};
 };
 }  // namespace
@@ -1382,36 +1370,19 @@ struct ibu_mmap {
 
 extern "C" int32_t ibu_mmap_open(const char* path, ibu_mmap_t** out) {  // mmap.rs:143-161
   if (!path || !out) return err_arg("NULL argument");
-  int fd = ::open(path, O_RDONLY | O_CLOEXEC);
-  if (fd < 0) return err_io(errno, path);
-  struct stat st;
-  if (fstat(fd, &st)) {
-    int e = errno;
-    close(fd);
-    return err_io(e, "metadata");
-  }
-  const size_t flen = (size_t)st.st_size;
-  if (flen < IBU_HEADER_SIZE) {  // the reference panics slicing map[0..32]; an error here
-    close(fd);
-    return err_arg("file shorter than the 32-byte header (the reference panics here)");
-  }
-  void* p = mmap(nullptr, flen, PROT_READ, MAP_PRIVATE, fd, 0);
-  int e = errno;
-  close(fd);
-  if (p == MAP_FAILED) return err_io(e, "mmap");
+  std::unique_ptr<Mapping> mp(new Mapping);
+  int32_t rc = map_file(path, &mp->file, [](size_t size) -> int32_t {   // the reference panics slicing map[0..32]; an error here
+    return size < IBU_HEADER_SIZE ? err_arg("file shorter than the 32-byte header (the reference panics here)") : IBU_OK;
+  });
+  if (rc) return rc;
+  const size_t flen = mp->file.n;
   ibu_header_t h;
-  memcpy(&h, p, IBU_HEADER_SIZE);
-  int32_t rc = ibu_header_validate(&h);
+  memcpy(&h, mp->file.p, IBU_HEADER_SIZE);
+  rc = ibu_header_validate(&h);
   if (!rc && (flen - IBU_HEADER_SIZE) % IBU_RECORD_SIZE != 0) rc = err_map_size();
-  if (rc) {
-    munmap(p, flen);
-    return rc;
-  }
-  Mapping* mp = new Mapping;
-  mp->base = static_cast<uint8_t*>(p);
-  mp->len = flen;
+  if (rc) return rc;
   ibu_mmap* m = new ibu_mmap;
-  m->map = mp;
+  m->map = mp.release();
   m->header = h;
   m->len = (flen - IBU_HEADER_SIZE) / IBU_RECORD_SIZE;
   *out = m;
@@ -1434,17 +1405,14 @@ extern "C" int32_t ibu_mmap_slice(const ibu_mmap_t* m, size_t start, size_t end,
   if (!m || !recs || !n) return err_arg("NULL argument");
   if (start >= m->len || end > m->len) return err_index(end, m->len);  // Q7: idx is always `end`
   if (end <= start) return err_index(end, m->len);
-  *recs = reinterpret_cast<const ibu_record_t*>(m->map->base + IBU_HEADER_SIZE + start * IBU_RECORD_SIZE);
+  *recs = reinterpret_cast<const ibu_record_t*>(m->map->file.p + IBU_HEADER_SIZE + start * IBU_RECORD_SIZE);
   *n = end - start;
   return IBU_OK;
 }
-extern "C" const void* ibu_mmap_base(const ibu_mmap_t* m) { return m ? m->map->base : nullptr; }
+extern "C" const void* ibu_mmap_base(const ibu_mmap_t* m) { return m ? m->map->file.p : nullptr; }
 extern "C" void ibu_mmap_close(ibu_mmap_t* m) {
   if (!m) return;
-  if (m->map->refs.fetch_sub(1, std::memory_order_acq_rel) == 1) {
-    munmap(m->map->base, m->map->len);
-    delete m->map;
-  }
+  if (m->map->refs.fetch_sub(1, std::memory_order_acq_rel) == 1) delete m->map;
   delete m;
 }
 
@@ -1471,7 +1439,8 @@ static size_t cgroup_cpu_quota() {
   if (quota > 0 && period > 0) return (size_t)((quota + period - 1) / period);
   return 0;
 }
-size_t ibu::host_cores() {
+// The affinity count, at most `quota_factor` times the cgroup CPU quota; at least 1.
+static size_t cpus_within_quota(size_t quota_factor) {
   size_t n = 0;
   cpu_set_t set;
   if (sched_getaffinity(0, sizeof set, &set) == 0) {
@@ -1483,23 +1452,13 @@ size_t ibu::host_cores() {
     n = h ? h : 1;
   }
   const size_t q = cgroup_cpu_quota();
-  if (q && q < n) n = q;
+  if (q && quota_factor * q < n) n = quota_factor * q;
   return n;
 }
+size_t ibu::host_cores() { return cpus_within_quota(1); }
 size_t ibu::inflate_threads() {
-  size_t n = 0;
-  cpu_set_t set;
-  if (sched_getaffinity(0, sizeof set, &set) == 0) {
-    int c = CPU_COUNT(&set);
-    if (c > 0) n = (size_t)c;
-  }
-  if (!n) {
-    unsigned h = std::thread::hardware_concurrency();
-    n = h ? h : 1;
-  }
-  const size_t q = cgroup_cpu_quota();
-  if (q && 2 * q < n) n = 2 * q;
-  return n < 1 ? 1 : (n > 64 ? 64 : n);
+  const size_t n = cpus_within_quota(2);
+  return n > 64 ? 64 : n;
 }
 
 extern "C" int32_t ibu_mmap_process_parallel(const ibu_mmap_t* m, const ibu_processor_vtable_t* vt, void* user,

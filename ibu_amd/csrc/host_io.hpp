@@ -1,7 +1,9 @@
 // host_io.hpp — internal hooks the streaming layer (stream.cpp) needs from host_io.cpp.
 #pragma once
+#include <errno.h>
 #include <stddef.h>
 #include <stdint.h>
+#include <sys/types.h>
 
 #include "../../include/ibu_hip.h"
 
@@ -19,6 +21,26 @@ int32_t open_plain_file(const char* path, int* fd_out, ibu_header_t* header, siz
 int32_t reader_read_direct(ibu_reader_t* r, uint8_t* dst, size_t cap_bytes, size_t* got_bytes, bool* eof);
 const char* reader_bgzf_path_if_untouched(const ibu_reader_t* r);   // host_io.cpp
 void reader_set_drained(ibu_reader_t* r, uint64_t records);
+// pread until `len` bytes are in, the file ends or an error other than EINTR comes: 0 or errno, *got = the bytes read either way.
+int pread_upto(int fd, uint8_t* dst, size_t len, off_t off, size_t* got);
+// The same where a short read is an error: EIO (the file shrank underneath us).
+inline int pread_all(int fd, uint8_t* dst, size_t len, off_t off) {
+  size_t got = 0;
+  const int e = pread_upto(fd, dst, len, off, &got);
+  return e ? e : (got < len ? EIO : 0);
+}
+// A whole file mapped read-only (MAP_PRIVATE); unmapped when its owner goes.
+struct FileMap {
+  const uint8_t* p = nullptr;
+  size_t n = 0;
+  FileMap() {}
+  FileMap(const FileMap&) = delete;
+  FileMap& operator=(const FileMap&) = delete;
+  ~FileMap();
+};
+// Opens `path`, hands its size to `check` (a status other than IBU_OK is returned as it is, nothing mapped), maps it whole and closes
+// the descriptor.  Its own errors: err_io(errno, path), err_io(errno, "metadata"), err_io(errno, "mmap").
+int32_t map_file(const char* path, FileMap* m, int32_t (*check)(size_t size));
 // num_cpus::get()
 size_t host_cores();
 // Threads for the inflate workers (BGZF blocks, pgzip chunks): the CPUs this process may run on, but at most twice its

@@ -18,7 +18,6 @@
 #include <string.h>
 #include <zlib.h>
 
-#include <chrono>
 #include <condition_variable>
 #include <functional>
 #include <future>
@@ -717,8 +716,6 @@ class Pool {
   uint64_t gen_ = 0;
   bool stop_ = false;
 };
-
-inline double now_s() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
 
 // CRC-32 (the gzip polynomial) by carry-less multiplication: four 128-bit lanes folded over 64 bytes per step, then
 // folded together and Barrett-reduced (Gopal et al., "Fast CRC Computation for Generic Polynomials Using PCLMULQDQ",

@@ -14,10 +14,8 @@
 // split per call = per GPU) and the streaming Reader (reader.rs:279-306, incl. the gzip path
 // of reader.rs:345-352).
 #include <errno.h>
-#include <fcntl.h>
 #include <pthread.h>
 #include <sys/mman.h>
-#include <sys/stat.h>
 #include <unistd.h>
 
 #include <algorithm>
@@ -37,47 +35,6 @@
 using namespace ibu;
 
 namespace {
-
-double now_s() {
-  return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count();
-}
-
-// Split [0,total) over up to `threads` host threads; fn(offset, len) returns 0 or errno.
-template <class F>
-int parallel_bytes(size_t total, uint32_t threads, F fn) {
-  if (threads < 1) threads = 1;
-  const size_t min_chunk = 1u << 20;
-  size_t parts = (total + min_chunk - 1) / min_chunk;
-  if (parts > threads) parts = threads;
-  if (parts <= 1) return total ? fn((size_t)0, total) : 0;
-  if (parts > 64) parts = 64;
-  int rc[64];
-  for (size_t i = 0; i < parts; ++i) rc[i] = 0;
-  const size_t per = (total / parts + 4095) & ~(size_t)4095;
-  run_pieces((unsigned)parts, [&](unsigned i) {  // never throws (common.hpp): no exception crosses the C ABI
-    const size_t off = (size_t)i * per;
-    if (off >= total) return;
-    rc[i] = fn(off, off + per < total ? per : total - off);
-  });
-  for (size_t i = 0; i < parts; ++i)
-    if (rc[i]) return rc[i];
-  return 0;
-}
-
-int pread_all(int fd, uint8_t* dst, size_t len, off_t off) {
-  while (len) {
-    ssize_t k = ::pread(fd, dst, len, off);
-    if (k < 0) {
-      if (errno == EINTR) continue;
-      return errno;
-    }
-    if (k == 0) return EIO;  // file shrank underneath us
-    dst += k;
-    off += k;
-    len -= (size_t)k;
-  }
-  return 0;
-}
 
 struct KernelClock {  // sums hipEvent spans of the per-slot kernels
   std::vector<hipEvent_t> a, b;
@@ -110,8 +67,6 @@ int32_t drain(ibu_ctx* ctx, int32_t rc) {  // leave no copy or kernel in flight 
   (void)hipStreamSynchronize(ctx->stream);
   return rc;
 }
-
-uint32_t feeder_threads(const ibu_ring_config_t* cfg) { return cfg && cfg->feeder_threads ? cfg->feeder_threads : 4; }
 
 struct DeviceProc {  // the device-side ParallelProcessor applied to each staged slot
   ibu_ctx* ctx;
@@ -241,7 +196,7 @@ extern "C" int32_t ibu_load_to_device(ibu_ctx_t* ctx, const char* path, const ib
     if (e != hipSuccess) { rc = hip_fail(e, "hipEventSynchronize"); break; }
     const off_t base = (off_t)(IBU_HEADER_SIZE + done * IBU_RECORD_SIZE);
     uint8_t* dst = r.pinned[s];
-    int err = parallel_bytes(bytes, feeder_threads(cfg), [&](size_t off, size_t len) {
+    int err = parallel_bytes(bytes, feeder_threads(cfg), (size_t)1 << 20, [&](size_t off, size_t len) {
       return pread_all(fd, dst + off, len, base + (off_t)off);
     });
     if (err) { rc = err_io(err, "read records"); break; }
@@ -272,25 +227,11 @@ extern "C" int32_t ibu_load_to_device(ibu_ctx_t* ctx, const char* path, const ib
 // to its announced length and CRC — is IBU_ERR_NIFFLER, as from the Reader (the index: bgzf_plan.cpp).
 namespace {
 
-struct Mapping {
-  const uint8_t* p = nullptr;
-  size_t n = 0;
-  ~Mapping() { if (p) munmap(const_cast<uint8_t*>(p), n); }
-};
-int32_t map_file(const char* path, Mapping* m) {
-  int fd = ::open(path, O_RDONLY | O_CLOEXEC);
-  if (fd < 0) return err_io(errno, path);
-  struct stat sb;
-  if (fstat(fd, &sb)) { const int e = errno; close(fd); return err_io(e, "metadata"); }
-  if (sb.st_size == 0) { close(fd); return err_io(0, "read header"); }
-  void* mp = mmap(nullptr, (size_t)sb.st_size, PROT_READ, MAP_PRIVATE, fd, 0);
-  const int map_errno = errno;
-  close(fd);
-  if (mp == MAP_FAILED) return err_io(map_errno, "mmap");
-  (void)madvise(mp, (size_t)sb.st_size, MADV_SEQUENTIAL);
-  m->p = static_cast<const uint8_t*>(mp);                 // (fields, not a temporary Mapping: its destructor would unmap)
-  m->n = (size_t)sb.st_size;
-  return IBU_OK;
+// The file, mapped: an empty one is a cut-off header, and it is read front to back.
+int32_t map_bgzf(const char* path, FileMap* m) {
+  const int32_t rc = map_file(path, m, [](size_t size) -> int32_t { return size ? IBU_OK : err_io(0, "read header"); });
+  if (rc == IBU_OK) (void)madvise(const_cast<uint8_t*>(m->p), m->n, MADV_SEQUENTIAL);
+  return rc;
 }
 
 // The staging on the device — the compressed file; the descriptors and status words behind it once their number is known — is the
@@ -320,7 +261,7 @@ struct BgzfLoad {
   static constexpr uint32_t kNone = 0xFFFFFFFFu;
   ibu_ctx* ctx;
   const ibu_ring_config_t* cfg;
-  const Mapping& file;
+  const FileMap& file;
   ibu_stream_stats_t* stats;
   ibu_header_t* header;
   void** d_records;                                        // nullptr: allocated here
@@ -472,7 +413,7 @@ struct BgzfLoad {
       if (k >= r.slots) publish(piece_end[k - r.slots]);   // (this slot's previous piece has landed: so has everything in front of it)
       uint8_t* dst = r.pinned[sl];
       const uint8_t* src = file.p + up;
-      parallel_bytes(len, feeder_threads(cfg), [&](size_t off, size_t l) { memcpy(dst + off, src + off, l); return 0; });
+      parallel_memcpy(dst, src, len, feeder_threads(cfg), (size_t)1 << 20);
       e = hipMemcpyAsync(static_cast<uint8_t*>(ctx->d_inflate_stage) + (up - plan.cbeg), dst, len, hipMemcpyHostToDevice, ctx->copy_stream);
       if (e == hipSuccess) e = hipEventRecord(r.copied[sl], ctx->copy_stream);
       if (e != hipSuccess) return hip_fail(e, "H2D");
@@ -561,8 +502,8 @@ extern "C" int32_t ibu_load_bgzf_shard_to_device(ibu_ctx_t* ctx, const char* pat
   IBU_HIP(hipSetDevice(ctx->device));
   RunOnNode on_node(feed_place(ctx));
   if (stats) memset(stats, 0, sizeof *stats);
-  Mapping file;
-  if (int32_t rc = map_file(path, &file)) return rc;
+  FileMap file;
+  if (int32_t rc = map_bgzf(path, &file)) return rc;
   BgzfLoad L{ctx, cfg, file, stats, header, d_records, cap_records, shard, n_shards};
   L.walk_beside();
   return L.run(n, first_record);
@@ -774,10 +715,7 @@ void stream_produce(ibu_stream* s) {
       n = s->end - row < s->slot_records ? s->end - row : s->slot_records;
       const uint8_t* srcp = map + row * IBU_RECORD_SIZE;
       uint8_t* dst = r.pinned[si];
-      parallel_bytes(n * IBU_RECORD_SIZE, s->feeders, [&](size_t off, size_t len) {
-        memcpy(dst + off, srcp + off, len);  // page-cache / page-fault side of the reference's hot loop
-        return 0;
-      });
+      parallel_memcpy(dst, srcp, n * IBU_RECORD_SIZE, s->feeders, (size_t)1 << 20);  // page-cache / page-fault side of the reference's hot loop
       row += n;
       eof = row >= s->end;
     } else {
@@ -1186,8 +1124,8 @@ int32_t process_bgzf_file(ibu_ctx* ctx, const char* path, const ibu_ring_config_
                           ibu_stream_stats_t* stats, uint64_t* records, bool* handled) {
   *handled = false;
   const ibu_error_detail_t keep = tls_error();
-  Mapping file;
-  int32_t rc = map_file(path, &file);
+  FileMap file;
+  int32_t rc = map_bgzf(path, &file);
   // ranges of ~6.4 GB of records where the file compresses to half (BGZF of 16/12 records: 0.50) — every range costs its launch's
   // waves' 45-75 ms once more, and a file that compresses better just gets larger ranges
   const size_t K = (size_t)((double)file.n / (ctx->bgzf_range_bytes_opt ? (double)ctx->bgzf_range_bytes_opt : 3.2e9)) + 1;
