@@ -1,4 +1,4 @@
-//! Raw `extern "C"` declarations — one-to-one with include/ibu_hip.h (ABI revision 4).
+//! Raw `extern "C"` declarations — one-to-one with include/ibu_hip.h (ABI revision 5).
 #![allow(non_camel_case_types)]
 use std::os::raw::{c_char, c_int, c_void};
 
@@ -281,6 +281,7 @@ extern "C" {
                                   out: *mut *mut ibu_stream_t) -> i32;
     pub fn ibu_stream_open_mmap(m: *const ibu_mmap_t, ctx: *mut ibu_ctx_t, cfg: *const ibu_ring_config_t, shard: usize,
                                 n_shards: usize, out: *mut *mut ibu_stream_t) -> i32;
+    pub fn ibu_stream_open_path(path: *const c_char, ctx: *mut ibu_ctx_t, cfg: *const ibu_ring_config_t, out: *mut *mut ibu_stream_t) -> i32;
     pub fn ibu_stream_header(s: *const ibu_stream_t, out: *mut ibu_header_t) -> i32;
     pub fn ibu_stream_next(s: *mut ibu_stream_t, stream: *mut c_void, d_records: *mut *const c_void, n: *mut usize,
                            first_index: *mut u64) -> i32;

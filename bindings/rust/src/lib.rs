@@ -647,6 +647,14 @@ pub mod device {
         _p: PhantomData<&'s ()>,
     }
     impl<'a> DeviceStream<'a> {
+        /// `Reader::from_path` + the stream (`ibu_stream_open_path`): a BGZF file the device load takes is read in ranges whose blocks are
+        /// inflated on the device; anything else goes through the Reader of the same descriptor.  The stream owns its source.
+        pub fn from_path<P: AsRef<Path>>(path: P, ctx: &'a Context) -> Result<Self> {
+            let c = CString::new(path.as_ref().to_string_lossy().as_bytes()).unwrap();
+            let mut raw = std::ptr::null_mut();
+            check(unsafe { ffi::ibu_stream_open_path(c.as_ptr(), ctx.raw, std::ptr::null(), &mut raw) })?;
+            Ok(DeviceStream { raw, _p: PhantomData })
+        }
         pub fn header(&self) -> Result<Header> {
             let mut h: Header = bytemuck::Zeroable::zeroed();
             check(unsafe { ffi::ibu_stream_header(self.raw, &mut h) })?;

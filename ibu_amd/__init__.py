@@ -688,6 +688,17 @@ class DeviceStream:
         source._streams.add(s)
         return s
 
+    @classmethod
+    def from_path(cls, path, ctx, ring=None):
+        """`Reader::from_path` + the stream (ibu_stream_open_path), as a context manager that owns its source: a BGZF file the device
+        load takes is read in ranges whose blocks are inflated on the device, anything else goes through the Reader of the same
+        descriptor.  The same iteration and DeviceBatch as Reader.device_stream."""
+        out = C.c_void_p()
+        _check(lib.ibu_stream_open_path(str(path).encode(), ctx._c, _ring(ring), C.byref(out)))
+        s = cls.__new__(cls)
+        s._s, s.ctx, s._source = out, ctx, None
+        return s
+
     def header(self):
         h = CHeader()
         _check(lib.ibu_stream_header(self._s, C.byref(h)))

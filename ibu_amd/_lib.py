@@ -182,6 +182,7 @@ SIGNATURES = {
     "ibu_numa_of_pci": (i32, [C.c_char_p, C.c_char_p, P(i32), C.c_char_p, sz, P(i32)]),
     "ibu_stream_open_reader": (i32, [vp, vp, P(CRingConfig), P(vp)]),
     "ibu_stream_open_mmap": (i32, [vp, vp, P(CRingConfig), sz, sz, P(vp)]),
+    "ibu_stream_open_path": (i32, [C.c_char_p, vp, P(CRingConfig), P(vp)]),
     "ibu_stream_header": (i32, [vp, P(CHeader)]),
     "ibu_stream_next": (i32, [vp, vp, P(vp), P(sz), P(u64)]),
     "ibu_stream_release": (i32, [vp, vp, vp]),

@@ -1,6 +1,8 @@
 // bgzf_plan.cpp — the walk over a BGZF file's block headers, the host inflate of single blocks, and the plan of one shard.
 #include "bgzf_plan.hpp"
 
+#include <algorithm>
+
 #include "common.hpp"
 
 namespace ibu {
@@ -121,14 +123,24 @@ int32_t bgzf_index(const uint8_t* map, size_t size, BgzfIndex* idx, size_t piece
 }
 
 int32_t plan_shard(const BgzfIndex& idx, size_t shard, size_t n_shards, ShardPlan* plan) {
-  ShardPlan& p = *plan = ShardPlan();
-  const std::vector<ibu_inflate_block_t>& B = idx.blocks;
   size_t rs = 0, re = 0;
   if (int32_t rc = ibu_shard_range((size_t)((idx.total - IBU_HEADER_SIZE) / IBU_RECORD_SIZE), n_shards, shard, &rs, &re)) return rc;
-  p.rec_first = rs;
-  p.num = re - rs;
-  p.lo = IBU_HEADER_SIZE + (uint64_t)IBU_RECORD_SIZE * rs;
-  p.hi = IBU_HEADER_SIZE + (uint64_t)IBU_RECORD_SIZE * re;
+  const int32_t rc = plan_records(idx, rs, re - rs, plan);
+  if (rc == IBU_OK && n_shards == 1) {                     // all of the file: the copies can start before the walk is done
+    plan->cbeg = 0;
+    plan->cend = idx.file_bytes;
+  }
+  return rc;
+}
+
+int32_t plan_records(const BgzfIndex& idx, size_t rec_first, size_t num, ShardPlan* plan) {
+  ShardPlan& p = *plan = ShardPlan();
+  const std::vector<ibu_inflate_block_t>& B = idx.blocks;
+  if (rec_first + num < rec_first || rec_first + num > (size_t)((idx.total - IBU_HEADER_SIZE) / IBU_RECORD_SIZE)) return err_arg("records out of range");
+  p.rec_first = rec_first;
+  p.num = num;
+  p.lo = IBU_HEADER_SIZE + (uint64_t)IBU_RECORD_SIZE * rec_first;
+  p.hi = IBU_HEADER_SIZE + (uint64_t)IBU_RECORD_SIZE * (rec_first + num);
   p.dev_first = idx.lead;
   while (p.dev_first < B.size() && (uint64_t)B[p.dev_first].out_offset < p.lo) ++p.dev_first;
   p.dev_end = p.dev_first;
@@ -138,13 +150,26 @@ int32_t plan_shard(const BgzfIndex& idx, size_t shard, size_t n_shards, ShardPla
     if (p.num && i < B.size() && B[i].out_len && (uint64_t)B[i].out_offset < p.hi && (uint64_t)B[i].out_offset + B[i].out_len > p.lo)
       p.edge[p.n_edges++] = i;
   }
-  if (n_shards == 1) {                                   // all of the file: the copies can start before the walk is done
-    p.cend = idx.file_bytes;
-  } else if (p.dev_blocks()) {                           // only the device blocks' bytes cross the link
+  if (p.dev_blocks()) {                                    // only the device blocks' bytes cross the link
     p.cbeg = (size_t)B[p.dev_first].comp_offset;
     p.cend = (size_t)(B[p.dev_end - 1].comp_offset + B[p.dev_end - 1].comp_len);
   }
   return IBU_OK;
+}
+
+size_t plan_range_records(const BgzfIndex& idx, size_t target_bytes, size_t slot_records) {
+  const size_t refill = IBU_DEFAULT_BUFFER_SIZE / IBU_RECORD_SIZE;
+  const size_t n = (size_t)((idx.total - IBU_HEADER_SIZE) / IBU_RECORD_SIZE);
+  const size_t per = target_bytes >= idx.file_bytes ? n : (size_t)((double)n * (double)target_bytes / (double)(idx.file_bytes ? idx.file_bytes : 1));
+  size_t unit = refill;
+  if (slot_records) {
+    size_t a = slot_records, b = refill;                   // gcd
+    while (b) { const size_t t = a % b; a = b; b = t; }
+    const size_t lcm = slot_records / a * refill;
+    if (lcm <= per) unit = lcm;
+  }
+  if (per >= n) return std::max((n + unit - 1) / unit, (size_t)1) * unit;   // one range
+  return std::max((per + unit / 2) / unit, (size_t)1) * unit;
 }
 
 }  // namespace ibu

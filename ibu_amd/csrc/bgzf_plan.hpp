@@ -31,5 +31,13 @@ struct ShardPlan {
   size_t dev_blocks() const { return dev_end - dev_first; }
 };
 int32_t plan_shard(const BgzfIndex& idx, size_t shard, size_t n_shards, ShardPlan* plan);
+// The same plan for records [rec_first, rec_first + num) (plan_shard is this over ibu_shard_range, with the whole file crossing the link
+// when there is one shard): only the device blocks' bytes cross the link.
+int32_t plan_records(const BgzfIndex& idx, size_t rec_first, size_t num, ShardPlan* plan);
+// The records of every range but the last of the pull stream over the file (ibu_stream_open_path): about `target_bytes` compressed bytes
+// at the file's ratio, a multiple of the reference's refill (IBU_DEFAULT_BUFFER_SIZE: 49 152 records), and of lcm(slot_records, 49 152)
+// where that is no larger — every batch but the last is then a whole slot: the multiple nearest the target, at least one; a target of the
+// whole file or more is one range.  The ranges: ceil(records / this).
+size_t plan_range_records(const BgzfIndex& idx, size_t target_bytes, size_t slot_records);
 
 }  // namespace ibu

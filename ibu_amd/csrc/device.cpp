@@ -170,6 +170,11 @@ extern "C" int32_t ibu_ctx_set_option(ibu_ctx_t* ctx, const char* key, int64_t v
     ctx->bgzf_device = (int)value;
     return IBU_OK;
   }
+  if (strcmp(key, "bgzf_stream_ahead") == 0) {           // the launch form of a path stream's ranges after the first
+    if (value != 0 && value != 1) return err_arg("bgzf_stream_ahead must be 0 or 1");
+    ctx->bgzf_stream_ahead = (int)value;
+    return IBU_OK;
+  }
   if (strcmp(key, "load_piece_delay_ms") == 0) {         // a test knob: a slow source for the BGZF loads
     if (value < 0 || value > 10000) return err_arg("load_piece_delay_ms must be 0 .. 10000");
     ctx->load_piece_delay_ms = (uint32_t)value;
@@ -177,6 +182,7 @@ extern "C" int32_t ibu_ctx_set_option(ibu_ctx_t* ctx, const char* key, int64_t v
   }
   if (strcmp(key, "release_staging") == 0) {             // one-shot: the device staging ibu_load_bgzf_*_to_device keeps (the compressed file's size) goes back now
     if (value != 1) return err_arg("release_staging must be 1");
+    if (ctx->stage_lent) return err_arg("an open ibu_stream_open_path stream loads through the staging: close it first");
     IBU_HIP(hipSetDevice(ctx->device));
     for (hipStream_t q : ctx->inflate_streams)
       if (q) IBU_HIP(hipStreamSynchronize(q));

@@ -69,7 +69,7 @@ extern "C" const char* ibu_version(void) { return "ibu_hip 0.5.0 (format v2, ref
 // 3: ibu_decode_sink_t.cap_records (layout change), + lower_bound_records, "base_order" / "sort_variant" options
 // 4: ibu_stream_stats_t + numa_node / ring_node (layout change), + ibu_stream_* (pull stream), ibu_ctx_numa, ibu_numa_of_pci, options "numa",
 //    "peer_access", "alloc_probe_tries" = 0 (auto, the new default)
-extern "C" uint32_t ibu_abi_revision(void) { return 4; }
+extern "C" uint32_t ibu_abi_revision(void) { return 5; }
 extern "C" void ibu_free(void* p) { free(p); }
 
 // ------------------------------------------------------------------------------------------
@@ -1147,6 +1147,30 @@ void ibu::reader_set_drained(ibu_reader_t* r, uint64_t records) {
   r->pos = r->cap = 0;
   r->bytes_read = IBU_HEADER_SIZE + IBU_RECORD_SIZE * records;
   r->inner.reset(new MemSource(nullptr, 0));             // (the inflate threads of the host path are not needed any more)
+}
+int32_t ibu::reader_open_bgzf_at(int fd, uint64_t member_offset, size_t skip, const ibu_header_t& h, uint64_t records_before, ibu_reader_t** out) {
+  *out = nullptr;
+  if (lseek(fd, (off_t)member_offset, SEEK_SET) < 0) return err_io(errno, "seek");
+  std::unique_ptr<ibu_reader> r(new (std::nothrow) ibu_reader);
+  if (!r) return err_io(ENOMEM, "alloc");
+  try {
+    r->inner.reset(new BgzfSource(std::unique_ptr<Source>(new FdSource(fd, false))));
+    r->buffer.resize(IBU_DEFAULT_BUFFER_SIZE);
+  } catch (...) {
+    return caught_io("ibu_stream: host inflate");
+  }
+  r->compressed = true;
+  r->header = h;
+  r->bytes_read = IBU_HEADER_SIZE + IBU_RECORD_SIZE * records_before;
+  for (size_t left = skip; left;) {                      // (into the reader's own buffer: it is handed out empty)
+    size_t got = 0;
+    const int e = r->inner->read(r->buffer.data(), std::min(left, r->buffer.size()), &got);
+    if (e) return src_error(r.get(), e, "read");
+    if (got == 0) return err_niffler("corrupt or truncated compressed stream");
+    left -= got;
+  }
+  *out = r.release();
+  return IBU_OK;
 }
 extern "C" int32_t ibu_reader_open_fd(int fd, ibu_reader_t** out) {  // reader.rs:389-396
   if (fd < 0) return err_arg("fd < 0");

@@ -21,6 +21,10 @@ int32_t open_plain_file(const char* path, int* fd_out, ibu_header_t* header, siz
 int32_t reader_read_direct(ibu_reader_t* r, uint8_t* dst, size_t cap_bytes, size_t* got_bytes, bool* eof);
 const char* reader_bgzf_path_if_untouched(const ibu_reader_t* r);   // host_io.cpp
 void reader_set_drained(ibu_reader_t* r, uint64_t records);
+// A Reader over the BGZF file open on `fd` that takes over at record `records_before`: the host inflate from the member at file byte
+// `member_offset` on, its first `skip` bytes dropped (the member holds that record's first byte), header `h`.  It reads as the Reader
+// of the whole file reads from there: the same errors, positions counted from the file's start.  `fd` stays the caller's.
+int32_t reader_open_bgzf_at(int fd, uint64_t member_offset, size_t skip, const ibu_header_t& h, uint64_t records_before, ibu_reader_t** out);
 // pread until `len` bytes are in, the file ends or an error other than EINTR comes: 0 or errno, *got = the bytes read either way.
 int pread_upto(int fd, uint8_t* dst, size_t len, off_t off, size_t* got);
 // The same where a short read is an error: EIO (the file shrank underneath us).

@@ -14,8 +14,10 @@
 // split per call = per GPU) and the streaming Reader (reader.rs:279-306, incl. the gzip path
 // of reader.rs:345-352).
 #include <errno.h>
+#include <fcntl.h>
 #include <pthread.h>
 #include <sys/mman.h>
+#include <sys/stat.h>
 #include <unistd.h>
 
 #include <algorithm>
@@ -23,6 +25,7 @@
 #include <chrono>
 #include <condition_variable>
 #include <deque>
+#include <memory>
 #include <mutex>
 #include <thread>
 #include <vector>
@@ -252,6 +255,18 @@ int32_t grow_stage(ibu_ctx* ctx, size_t need) {
   return IBU_OK;
 }
 
+// The device staging one load of `plan` needs: its compressed bytes, the descriptors, the status words and the lanes' tables of the
+// decoder's scratch form (a load of more blocks than one round of the short form, or than option "inflate_one_launch")
+size_t stage_bytes(const ibu_ctx* ctx, const ShardPlan& plan, size_t* comp_room, size_t* desc_room, size_t* status_room, size_t* tables_room) {
+  const size_t nrest = plan.dev_blocks();
+  *comp_room = (plan.cend - plan.cbeg + kInflatePad + 255) & ~(size_t)255;
+  *desc_room = (nrest * sizeof(InflateBlockDesc) + 255) & ~(size_t)255;
+  *status_room = (4 * nrest + 16 + 255) & ~(size_t)255;
+  const size_t ahead_from = ctx->inflate_one_launch ? ctx->inflate_one_launch : inflate_one_round(ctx->cfg.cus);
+  *tables_room = nrest > ahead_from ? inflate_scratch_bytes(ctx->cfg, nrest, 2) : 256;   // (the short form needs none)
+  return *comp_room + *desc_room + *status_room + 256 + *tables_room;
+}
+
 // One load of one shard.  At most one round of the decoder's short form (inflate_one_round: 49 152 blocks, 3 GB of records): ONE launch
 // behind the last copy — a wave takes its ~45 ms whatever the launch's size, so the call ends that long after its last byte has arrived
 // either way.  More: ONE launch as well, but AHEAD of the copies, in the decoder's other form (tables in scratch, eight waves per CU): its
@@ -269,6 +284,13 @@ struct BgzfLoad {
   size_t range_records = 0;                                // > 0: d_records is the context's range buffer, grown to this many records
   const BgzfIndex* idx = nullptr;                          // the index, or the walk beside the copies makes it
   ShardPlan plan{};
+  const ShardPlan* fixed = nullptr;                        // a plan made by the caller (the pull stream's ranges: plan_records)
+  bool ring_lent = false;                                  // the caller holds the context's ring (the pull stream): no ring_ensure
+  bool behind = false;                                     // launch behind the last copy in chunks (inflate_late's), never ahead of the copies
+  uint64_t host_bytes = 0;                                 // record bytes inflated on the host and copied (header blocks, edges)
+  std::vector<uint8_t> edge_bytes{};                       // (the host side of the asynchronous copies lives as long as the load)
+  std::vector<ibu_inflate_block_t> desc_host{};
+  uint32_t none_word = kNone;
   BgzfIndex walked{};
   std::thread walker{};
   std::atomic<bool> walk_done{false};
@@ -316,8 +338,8 @@ struct BgzfLoad {
   }
   int32_t load() {
     // (one shard of one: room for the whole file and the descriptors of 64 KiB blocks: the copies start at once, nothing is allocated twice)
-    int32_t rc = n_shards == 1 ? grow_stage(ctx, ((file.n + kInflatePad + 255) & ~(size_t)255) + 40 * (file.n / 8192 + 64)) : IBU_OK;
-    if (!rc) rc = ring_ensure(ctx, cfg, false);
+    int32_t rc = ring_lent ? IBU_OK : ring_ensure(ctx, cfg, false);   // (first: a context whose ring is lent keeps its staging untouched)
+    if (!rc && n_shards == 1 && !fixed) rc = grow_stage(ctx, ((file.n + kInflatePad + 255) & ~(size_t)255) + 40 * (file.n / 8192 + 64));
     hipError_t e = hipSuccess;
     for (hipStream_t& s : ctx->inflate_streams)
       if (!s && !rc && e == hipSuccess) e = hipStreamCreateWithFlags(&s, hipStreamNonBlocking);
@@ -344,7 +366,8 @@ struct BgzfLoad {
       if (walked.head.size() >= IBU_HEADER_SIZE) *header = walked.header;
       if (walk_rc) { tls_error() = walk_detail; return walk_rc; }
     }
-    if (int32_t rc = plan_shard(*idx, shard, n_shards, &plan)) return rc;
+    if (fixed) plan = *fixed;
+    else if (int32_t rc = plan_shard(*idx, shard, n_shards, &plan)) return rc;
     const size_t nrest = plan.dev_blocks(), need = std::max({plan.num, range_records, (size_t)1}) * IBU_RECORD_SIZE;
     if (range_records && need > ctx->bgzf_range_bytes) {   // the range buffer: the context keeps it and it grows only (freeing and
       (void)hipFree(ctx->d_bgzf_range);                    // allocating 2.4 GB around every call cost a call of 1e8 records 80 of its
@@ -361,24 +384,25 @@ struct BgzfLoad {
     }
     d_out = static_cast<uint8_t*>(*d_records);
     hipError_t e = hipSuccess;
+    // Every copy of the load goes out on its own non-blocking streams: a synchronous copy would wait for the work of every blocking stream
+    // (the pull stream loads the next range while the caller's kernels run on its batches)
     auto put = [&](const uint8_t* bytes, uint64_t at, uint64_t len) {   // bytes [at, at + len) of the stream, as far as they are the shard's
       const uint64_t a = std::max(at, plan.lo), z = std::min(at + len, plan.hi);
-      if (a < z && e == hipSuccess) e = hipMemcpy(d_out + (a - plan.lo), bytes + (a - at), z - a, hipMemcpyHostToDevice);
+      if (a < z && e == hipSuccess) e = hipMemcpyAsync(d_out + (a - plan.lo), bytes + (a - at), z - a, hipMemcpyHostToDevice, q());
+      if (a < z) host_bytes += z - a;
     };
     put(idx->head.data(), 0, idx->head.size());            // the records behind the header in the blocks inflated for it
     pgz::RawInflater raw;
-    std::vector<uint8_t> edge(65536);
+    edge_bytes.resize(2 * 65536);
     for (size_t k = 0; k < plan.n_edges; ++k) {            // the blocks that straddle the shard's ends
       const ibu_inflate_block_t& b = idx->blocks[plan.edge[k]];
-      if (int32_t rc = inflate_block_on_host(raw, file.p, b, edge.data())) return rc;
-      put(edge.data(), (uint64_t)b.out_offset, b.out_len);
+      uint8_t* edge = edge_bytes.data() + k * 65536;
+      if (int32_t rc = inflate_block_on_host(raw, file.p, b, edge)) return rc;
+      put(edge, (uint64_t)b.out_offset, b.out_len);
     }
     if (e != hipSuccess) return hip_fail(e, "hipMemcpy");
-    const size_t comp_room = (plan.cend - plan.cbeg + kInflatePad + 255) & ~(size_t)255;
-    const size_t desc_room = (nrest * sizeof(InflateBlockDesc) + 255) & ~(size_t)255;
-    const size_t status_room = (4 * nrest + 16 + 255) & ~(size_t)255;
-    tables_room = nrest > ahead_from() ? inflate_scratch_bytes(ctx->cfg, nrest, 2) : 256;   // (the short form needs none)
-    if (int32_t rc = grow_stage(ctx, comp_room + desc_room + status_room + 256 + tables_room)) return rc;
+    size_t comp_room = 0, desc_room = 0, status_room = 0;
+    if (int32_t rc = grow_stage(ctx, stage_bytes(ctx, plan, &comp_room, &desc_room, &status_room, &tables_room))) return rc;
     d_desc = reinterpret_cast<InflateBlockDesc*>(static_cast<uint8_t*>(ctx->d_inflate_stage) + comp_room);
     d_status = reinterpret_cast<uint32_t*>(reinterpret_cast<uint8_t*>(d_desc) + desc_room);
     d_first_bad = d_status + nrest;
@@ -387,13 +411,13 @@ struct BgzfLoad {
       e = hipHostMalloc(reinterpret_cast<void**>(&ctx->h_inflate_marks), 8 * sizeof(uint64_t), hipHostMallocMapped | hipHostMallocCoherent);
       if (e != hipSuccess) { ctx->h_inflate_marks = nullptr; return hip_fail(e, "hipHostMalloc"); }
     }
-    std::vector<ibu_inflate_block_t> desc(idx->blocks.begin() + (ptrdiff_t)plan.dev_first, idx->blocks.begin() + (ptrdiff_t)plan.dev_end);
-    for (ibu_inflate_block_t& b : desc) {                  // relative to the shard's records / to the bytes on the device
+    desc_host.assign(idx->blocks.begin() + (ptrdiff_t)plan.dev_first, idx->blocks.begin() + (ptrdiff_t)plan.dev_end);
+    for (ibu_inflate_block_t& b : desc_host) {             // relative to the shard's records / to the bytes on the device
       b.out_offset -= (int64_t)plan.lo;
       b.comp_offset -= plan.cbeg;
     }
-    if (nrest) e = hipMemcpy(d_desc, desc.data(), nrest * sizeof(InflateBlockDesc), hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(d_first_bad, &kNone, 4, hipMemcpyHostToDevice);
+    if (nrest && e == hipSuccess) e = hipMemcpyAsync(d_desc, desc_host.data(), nrest * sizeof(InflateBlockDesc), hipMemcpyHostToDevice, q());
+    if (e == hipSuccess) e = hipMemcpyAsync(d_first_bad, &none_word, 4, hipMemcpyHostToDevice, q());
     __atomic_store_n(d_ready(), 0ull, __ATOMIC_RELEASE);
     if (e != hipSuccess) return hip_fail(e, "hipMemcpy");
     prepared = true;
@@ -429,6 +453,7 @@ struct BgzfLoad {
   }
   int32_t launch(bool all) {
     const size_t nrest = plan.dev_blocks();
+    if (behind) return all && !launches && nrest ? launch_behind(0) : IBU_OK;
     const bool streamed = nrest > ahead_from();
     if (launches || nrest == 0 || (!streamed && !all)) return IBU_OK;
     ahead = streamed;
@@ -442,13 +467,25 @@ struct BgzfLoad {
     ++launches;
     return IBU_OK;
   }
+  // Blocks [at, nrest) in launches of at most eight waves of 64 blocks per CU, behind the last copy (everything is on the device by then)
+  int32_t launch_behind(size_t at) {
+    const size_t nrest = plan.dev_blocks();
+    hipError_t e = hipStreamWaitEvent(q(), ctx->ring.copied[last_slot], 0);
+    for (size_t cnt = 0; at < nrest && e == hipSuccess; at += cnt, ++launches) {
+      cnt = std::min(nrest - at, (size_t)ctx->cfg.cus * 8 * 64);
+      e = launch_inflate_blocks(ctx->cfg, ctx->d_inflate_stage, d_desc + at, cnt, d_out, d_status + at, d_first_bad, d_tables, tables_room, q(),
+                                cnt > inflate_one_round(ctx->cfg.cus) ? 2 : 0);
+    }
+    return e == hipSuccess ? IBU_OK : hip_fail(e, "inflate");
+  }
   int32_t finish() {
     uint32_t first_bad = kNone;
     hipError_t e = hipStreamSynchronize(ctx->copy_stream);
     if (e == hipSuccess) publish(plan.cend);               // every byte is there
     for (hipStream_t s : ctx->inflate_streams)
       if (e == hipSuccess) e = hipStreamSynchronize(s);
-    if (e == hipSuccess) e = hipMemcpy(&first_bad, d_first_bad, 4, hipMemcpyDeviceToHost);
+    if (e == hipSuccess) e = hipMemcpyAsync(&first_bad, d_first_bad, 4, hipMemcpyDeviceToHost, q());
+    if (e == hipSuccess) e = hipStreamSynchronize(q());
     if (e != hipSuccess) return hip_fail(e, "ibu_load_bgzf_to_device");
     if (first_bad != kNone && ahead)
       if (int32_t rc = inflate_late(&first_bad)) return rc;
@@ -466,21 +503,19 @@ struct BgzfLoad {
   int32_t inflate_late(uint32_t* first_bad) {
     const size_t nrest = plan.dev_blocks();
     std::vector<uint32_t> stv(nrest);
-    hipError_t e = hipMemcpy(stv.data(), d_status, 4 * nrest, hipMemcpyDeviceToHost);
+    hipError_t e = hipMemcpyAsync(stv.data(), d_status, 4 * nrest, hipMemcpyDeviceToHost, q());
+    if (e == hipSuccess) e = hipStreamSynchronize(q());
     if (e != hipSuccess) return hip_fail(e, "hipMemcpy");
     if (std::any_of(stv.begin(), stv.end(), [](uint32_t st) { return st && st != 3; })) return IBU_OK;   // (refused stays refused)
     const size_t late = (size_t)(std::find(stv.begin(), stv.end(), 3u) - stv.begin());
     if (late == nrest) return IBU_OK;
     if (trace_sort()) fprintf(stderr, "ibu load_bgzf: the bytes of blocks %zu ... came later than the waves waited: inflating them now\n", late);
-    e = hipMemcpy(d_first_bad, &kNone, 4, hipMemcpyHostToDevice);
+    e = hipMemcpyAsync(d_first_bad, &none_word, 4, hipMemcpyHostToDevice, q());
     ahead = false;                                         // (nothing to release any more on a failure)
-    for (size_t at = late, cnt = 0; at < nrest && e == hipSuccess; at += cnt, ++launches) {
-      cnt = std::min(nrest - at, (size_t)ctx->cfg.cus * 8 * 64);   // (eight waves of 64 blocks per CU a launch)
-      e = launch_inflate_blocks(ctx->cfg, ctx->d_inflate_stage, d_desc + at, cnt, d_out, d_status + at, d_first_bad, d_tables, tables_room, q(),
-                                cnt > inflate_one_round(ctx->cfg.cus) ? 2 : 0);
-    }
+    if (e != hipSuccess) return hip_fail(e, "hipMemcpy");
+    if (int32_t rc = launch_behind(late)) return rc;
+    e = hipMemcpyAsync(first_bad, d_first_bad, 4, hipMemcpyDeviceToHost, q());
     if (e == hipSuccess) e = hipStreamSynchronize(q());
-    if (e == hipSuccess) e = hipMemcpy(first_bad, d_first_bad, 4, hipMemcpyDeviceToHost);
     return e == hipSuccess ? IBU_OK : hip_fail(e, "ibu_load_bgzf_to_device");
   }
 };
@@ -593,6 +628,23 @@ struct ibu_stream {
   size_t stage_pos = 0, stage_len = 0;   // records
   bool src_eof = false;              // the Reader source reported its end
   std::thread producer;
+  // ibu_stream_open_path: the stream owns its source — the file's descriptor and the Reader of the host path (the whole file, or the
+  // rest of it from a range the device refused) ...
+  int own_fd = -1;
+  ibu_reader_t* own_rd = nullptr;
+  ibu_ring_config_t cfg{};
+  // ... and, in the device form, the file mapped and indexed once and read in ranges of range_records into two range buffers
+  bool ranges = false;
+  std::unique_ptr<FileMap> file;
+  BgzfIndex idx;
+  size_t range_records = 0, n_ranges = 0;
+  struct RangeBuf { uint8_t* d = nullptr; size_t cap = 0; uint32_t out = 0; std::vector<hipEvent_t> released; };   // out: batches queued or held
+  RangeBuf rbuf[2];
+  std::vector<hipEvent_t> spare_events;
+  int waiting = -1;                  // the producer waits for this range buffer's batches to come back
+  struct RangeBatch { uint8_t* p; size_t n; uint64_t first; int buf; };
+  std::deque<RangeBatch> rready;     // in stream order, in front of any slot batch
+  std::vector<RangeBatch> rheld;
 };
 
 namespace {
@@ -665,6 +717,115 @@ int32_t fill_from_reader(ibu_stream* s, uint8_t* dst, size_t* filled, bool* eof)
   return IBU_OK;
 }
 
+// The ring's device slots, for a path stream that goes over to the host path (the device form lends only the pinned side)
+int32_t ring_add_dev(ibu_ctx* ctx) {
+  Ring& r = ctx->ring;
+  if (!r.dev.empty()) return IBU_OK;
+  r.dev.assign(r.slots, nullptr);
+  for (uint32_t i = 0; i < r.slots; ++i) {
+    const hipError_t e = hipMalloc(reinterpret_cast<void**>(&r.dev[i]), r.slot_bytes);
+    if (e != hipSuccess) {
+      for (uint8_t* p : r.dev)
+        if (p) (void)hipFree(p);
+      r.dev.clear();
+      return hip_fail(e, "hipMalloc");
+    }
+  }
+  return IBU_OK;
+}
+
+// The host path of a path stream from record `from` on: the whole file through the Reader of the same descriptor (from == 0), or the
+// member holding that record's first byte on (a range boundary, so a refill boundary: the refills are counted on unchanged)
+int32_t host_take_over(ibu_stream* s, uint64_t from) {
+  if (int32_t rc = ring_add_dev(s->ctx)) return rc;
+  if (from == 0) {
+    if (lseek(s->own_fd, 0, SEEK_SET) < 0) return err_io(errno, "seek");
+    const int32_t rc = ibu_reader_open_fd(s->own_fd, &s->own_rd);
+    if (rc == IBU_OK) s->rd = s->own_rd;
+    return rc;
+  }
+  const std::vector<ibu_inflate_block_t>& B = s->idx.blocks;
+  const uint64_t lo = IBU_HEADER_SIZE + (uint64_t)IBU_RECORD_SIZE * from;
+  size_t j = s->idx.lead;
+  while (j < B.size() && (uint64_t)B[j].out_offset + B[j].out_len <= lo) ++j;
+  if (j == B.size()) return err_niffler("corrupt or truncated compressed stream");
+  const uint64_t member = j ? B[j - 1].comp_offset + B[j - 1].comp_len + 8 : 0;   // (every member is a BGZF block: they follow each other)
+  const int32_t rc = reader_open_bgzf_at(s->own_fd, member, (size_t)(lo - (uint64_t)B[j].out_offset), s->header, from, &s->own_rd);
+  if (rc == IBU_OK) s->rd = s->own_rd;
+  return rc;
+}
+
+// The device form of a path stream: range k goes to range buffer k % 2 once every batch of the range before it there has been released
+// and the work queued on the release streams has run; its compressed bytes cross the link through the ring's pinned slots and its blocks
+// are inflated on the device (BgzfLoad), and its batches — views into the buffer — go out.  A load that fails hands over to the host path:
+// *host = true, *from = the range's first record (the first range: anything; later ones: a block the device refused).
+int32_t produce_ranges(ibu_stream* s, bool* host, uint64_t* from) {
+  ibu_ctx* ctx = s->ctx;
+  const size_t total = (size_t)((s->idx.total - IBU_HEADER_SIZE) / IBU_RECORD_SIZE);
+  for (size_t k = 0; k < s->n_ranges; ++k) {
+    const int b = (int)(k & 1);
+    ibu_stream::RangeBuf& rb = s->rbuf[b];
+    const size_t first = k * s->range_records, num = std::min(s->range_records, total - first);
+    std::vector<hipEvent_t> released;
+    {
+      std::unique_lock<std::mutex> lk(s->mu);
+      s->waiting = b;
+      s->cv.notify_all();
+      s->cv.wait(lk, [&] { return s->stop || rb.out == 0; });
+      s->waiting = -1;
+      if (s->stop) return IBU_OK;
+      released.swap(rb.released);
+    }
+    hipError_t e = hipSuccess;
+    for (hipEvent_t ev : released)
+      if (e == hipSuccess) e = hipEventSynchronize(ev);
+    {
+      std::lock_guard<std::mutex> g(s->mu);
+      s->spare_events.insert(s->spare_events.end(), released.begin(), released.end());
+    }
+    if (e != hipSuccess) return hip_fail(e, "hipEventSynchronize");
+    if (rb.cap < num) {                                    // (allocated when first needed: a file of one range has one buffer)
+      if (rb.d) (void)hipFree(rb.d);
+      rb.d = nullptr;
+      rb.cap = 0;
+      if ((e = hipMalloc(reinterpret_cast<void**>(&rb.d), num * IBU_RECORD_SIZE)) != hipSuccess) { rb.d = nullptr; return hip_fail(e, "hipMalloc"); }
+      rb.cap = num;
+    }
+    ShardPlan plan;
+    if (int32_t rc = plan_records(s->idx, first, num, &plan)) return rc;
+    ibu_stream_stats_t st{};
+    ibu_header_t h = s->header;
+    void* dst = rb.d;
+    size_t n = 0;
+    const ibu_error_detail_t keep = tls_error();
+    BgzfLoad L{ctx, &s->cfg, *s->file, &st, &h, &dst, rb.cap, 0, 1, 0, &s->idx};
+    L.fixed = &plan;
+    L.ring_lent = true;
+    L.behind = k > 0 && !ctx->bgzf_stream_ahead;           // (the first range, with nothing held, always launches ahead of its copies, as the load does)
+    const int32_t rc = L.run(&n, nullptr);
+    if (rc && (k == 0 || rc == IBU_ERR_NIFFLER)) {         // the host path decides: the same records, the same error
+      tls_error() = keep;
+      *host = true;
+      *from = first;
+      std::lock_guard<std::mutex> g(s->mu);
+      if (k) s->stats.bytes_h2d += st.bytes_h2d + L.host_bytes;   // (the first range: the stats are the Reader stream's alone)
+      return IBU_OK;
+    }
+    if (rc) return rc;
+    std::lock_guard<std::mutex> g(s->mu);
+    for (size_t at = 0; at < n; at += s->slot_records) {
+      const size_t nb = std::min(s->slot_records, n - at);
+      s->rready.push_back(ibu_stream::RangeBatch{rb.d + at * IBU_RECORD_SIZE, nb, (uint64_t)(first + at), b});
+      ++rb.out;
+      s->stats.batches += 1;
+    }
+    s->stats.records += n;
+    s->stats.bytes_h2d += st.bytes_h2d + L.host_bytes;
+    s->cv.notify_all();
+  }
+  return IBU_OK;
+}
+
 void stream_produce(ibu_stream* s) {
   ibu_ctx* ctx = s->ctx;
   Ring& r = ctx->ring;
@@ -682,6 +843,12 @@ void stream_produce(ibu_stream* s) {
   uint64_t delivered = 0;
   size_t row = s->start;
   bool eof = s->m ? s->start >= s->end : false;
+  if (rc == IBU_OK && s->ranges) {   // the device form: the ranges, and the host path only from where the device refused a block
+    bool host = false;
+    rc = produce_ranges(s, &host, &delivered);
+    if (rc == IBU_OK) eof = !host;
+    if (rc == IBU_OK && host) rc = host_take_over(s, delivered);
+  }
   while (rc == IBU_OK && !eof) {
     // any slot the consumer does not hold will do (never-used ones first, then the one released longest ago): with slots - 1 batches
     // held the one slot left keeps the stream moving — filling in ring order would wait for a HELD slot while a free one sat idle
@@ -751,7 +918,7 @@ void stream_produce(ibu_stream* s) {
 
 int32_t stream_open(ibu_ctx* ctx, const ibu_ring_config_t* cfg, ibu_stream* s) {
   IBU_HIP(hipSetDevice(ctx->device));
-  int32_t rc = ring_ensure(ctx, cfg, true);
+  int32_t rc = ring_ensure(ctx, cfg, !s->ranges);      // (the device form of a path stream copies through the pinned side only)
   if (rc) return rc;
   Ring& r = ctx->ring;
   s->ctx = ctx;
@@ -773,6 +940,8 @@ int32_t stream_open(ibu_ctx* ctx, const ibu_ring_config_t* cfg, ibu_stream* s) {
   return IBU_OK;
 }
 
+constexpr uint32_t kRangeBatch = 0xFFFFFFFFu;   // stream_take's slot for a batch of a range: the newest of ibu_stream::rheld
+
 // The consumer side of next(): the oldest READY slot, the caller's stream ordered behind its copy.  *n == 0: end of stream.
 int32_t stream_take(ibu_stream* s, hipStream_t st, uint32_t* slot_out, size_t* n, uint64_t* first) {
   Ring& r = s->ctx->ring;
@@ -780,6 +949,15 @@ int32_t stream_take(ibu_stream* s, hipStream_t st, uint32_t* slot_out, size_t* n
   {
     std::unique_lock<std::mutex> lk(s->mu);
     for (;;) {
+      if (!s->rready.empty()) {      // a batch of a range (a path stream): inflated before it was queued, nothing for `st` to wait for
+        const ibu_stream::RangeBatch b = s->rready.front();
+        s->rready.pop_front();
+        s->rheld.push_back(b);
+        *slot_out = kRangeBatch;
+        *n = b.n;
+        *first = b.first;
+        return IBU_OK;
+      }
       if (!s->ready.empty()) break;
       if (s->done) {
         *n = 0;
@@ -787,6 +965,8 @@ int32_t stream_take(ibu_stream* s, hipStream_t st, uint32_t* slot_out, size_t* n
         return IBU_OK;
       }
       if (s->held >= r.slots) return err_arg("every ring slot is held: release a batch before asking for the next");
+      if (s->waiting >= 0 && s->rbuf[s->waiting].out)
+        return err_arg("the next range goes to the range buffer whose batches are held: release them before asking for the next");
       s->cv.wait(lk);
     }
     si = s->ready.front();
@@ -828,6 +1008,25 @@ void stream_shutdown(ibu_stream* s) {
   (void)hipStreamSynchronize(ctx->stream);
   for (uint32_t i = 0; i < s->slot.size(); ++i)   // work the caller queued on its own streams before releasing
     if (s->slot[i].state == ibu_stream::RELEASED) (void)hipEventSynchronize(ctx->ring.consumed[i]);
+  for (ibu_stream::RangeBuf& rb : s->rbuf) {      // a path stream's own: the range buffers, its events, its Reader and descriptor
+    for (hipEvent_t ev : rb.released) {
+      (void)hipEventSynchronize(ev);
+      (void)hipEventDestroy(ev);
+    }
+    rb.released.clear();
+    if (rb.d) (void)hipFree(rb.d);
+    rb = ibu_stream::RangeBuf();
+  }
+  for (hipEvent_t ev : s->spare_events) (void)hipEventDestroy(ev);
+  s->spare_events.clear();
+  s->rready.clear();
+  s->rheld.clear();
+  if (s->ranges) ctx->stage_lent = false;
+  if (s->own_rd) ibu_reader_close(s->own_rd);
+  s->own_rd = nullptr;
+  s->rd = nullptr;
+  if (s->own_fd >= 0) close(s->own_fd);
+  s->own_fd = -1;
   ctx->ring_lent = nullptr;
 }
 
@@ -866,6 +1065,87 @@ extern "C" int32_t ibu_stream_open_mmap(const ibu_mmap_t* m, ibu_ctx_t* ctx, con
   return IBU_OK;
 }
 
+// Reader::from_path + the pull stream (reader.rs:345-352): one descriptor, sniffed once.  A BGZF file the device load takes is read in ranges
+// inflated on the device (produce_ranges); anything else is ibu_stream_open_reader over ibu_reader_open_fd of that descriptor.
+namespace {
+int32_t open_path_device_form(ibu_stream* s, ibu_ctx* ctx) {
+  struct stat st;
+  if (fstat(s->own_fd, &st) || !S_ISREG(st.st_mode) || st.st_size < 18 || getenv("IBU_NO_PARALLEL_BGZF")) return IBU_ERR_NIFFLER;
+  void* p = mmap(nullptr, (size_t)st.st_size, PROT_READ, MAP_PRIVATE, s->own_fd, 0);
+  if (p == MAP_FAILED) return IBU_ERR_IO;
+  s->file.reset(new FileMap);
+  s->file->p = static_cast<const uint8_t*>(p);
+  s->file->n = (size_t)st.st_size;
+  const uint8_t* m = s->file->p;                           // the Reader's sniff: a BGZF block first
+  if (!(m[0] == 0x1f && m[1] == 0x8b && m[2] == 8 && (m[3] & 4) && m[12] == 'B' && m[13] == 'C' && m[14] == 2 && m[15] == 0)) return IBU_ERR_NIFFLER;
+  (void)madvise(const_cast<uint8_t*>(m), s->file->n, MADV_SEQUENTIAL);
+  RunOnNode on_node(feed_place(ctx));
+  if (int32_t rc = bgzf_index(m, s->file->n, &s->idx)) return rc;
+  s->header = s->idx.header;
+  const size_t total = (size_t)((s->idx.total - IBU_HEADER_SIZE) / IBU_RECORD_SIZE);
+  const size_t target = ctx->bgzf_range_bytes_opt ? ctx->bgzf_range_bytes_opt : (size_t)3200000000ull;
+  s->range_records = plan_range_records(s->idx, target, ctx->ring.slot_bytes / IBU_RECORD_SIZE);
+  s->n_ranges = (total + s->range_records - 1) / s->range_records;
+  size_t need = 0;                                         // the staging for the largest range, now: a load never grows it under the caller
+  for (size_t k = 0; k < s->n_ranges; ++k) {
+    ShardPlan plan;
+    if (int32_t rc = plan_records(s->idx, k * s->range_records, std::min(s->range_records, total - k * s->range_records), &plan)) return rc;
+    size_t a, b, c, d;
+    need = std::max(need, stage_bytes(ctx, plan, &a, &b, &c, &d));
+  }
+  if (s->n_ranges && need > ctx->inflate_stage_bytes) {
+    (void)hipFree(ctx->d_inflate_stage);
+    ctx->d_inflate_stage = nullptr;
+    ctx->inflate_stage_bytes = 0;
+    if (hipError_t e = ctx_malloc(ctx, &ctx->d_inflate_stage, need); e != hipSuccess) { ctx->d_inflate_stage = nullptr; return hip_fail(e, "hipMalloc"); }
+    ctx->inflate_stage_bytes = need;
+  }
+  s->ranges = true;
+  return IBU_OK;
+}
+}  // namespace
+
+extern "C" int32_t ibu_stream_open_path(const char* path, ibu_ctx_t* ctx, const ibu_ring_config_t* cfg, ibu_stream_t** out) {
+  if (!path || !ctx || !out) return err_arg("NULL argument");
+  *out = nullptr;
+  IBU_HIP(hipSetDevice(ctx->device));
+  if (int32_t rc = ring_ensure(ctx, cfg, false)) return rc;   // (a ring lent to another stream: refused before the file is touched)
+  std::unique_ptr<ibu_stream> s(new (std::nothrow) ibu_stream);
+  if (!s) return err_io(ENOMEM, "ibu_stream_open_path");
+  if (cfg) s->cfg = *cfg;
+  s->own_fd = ::open(path, O_RDONLY | O_CLOEXEC);
+  if (s->own_fd < 0) return err_io(errno, path);
+  struct Fd { ibu_stream* s; ~Fd() { if (s && s->own_fd >= 0) close(s->own_fd); } } fd_guard{s.get()};   // (until the stream owns it)
+  int32_t rc = IBU_ERR_NIFFLER;
+  if (ctx->bgzf_device) {
+    const ibu_error_detail_t keep = tls_error();
+    try {
+      rc = open_path_device_form(s.get(), ctx);
+    } catch (...) {
+      rc = caught_io("ibu_stream_open_path");
+    }
+    if (rc) {                                              // not for the device form: as if it had not been tried
+      tls_error() = keep;
+      s->file.reset();
+      s->idx = BgzfIndex();
+      s->ranges = false;
+    }
+  }
+  if (rc) {
+    if ((rc = ibu_reader_open_fd(s->own_fd, &s->own_rd))) return rc;
+    s->rd = s->own_rd;
+    ibu_reader_header(s->rd, &s->header);
+  }
+  if ((rc = stream_open(ctx, cfg, s.get()))) {
+    if (s->own_rd) ibu_reader_close(s->own_rd);
+    return rc;
+  }
+  if (s->ranges) ctx->stage_lent = true;
+  fd_guard.s = nullptr;                                    // the stream owns the descriptor now
+  *out = s.release();
+  return IBU_OK;
+}
+
 extern "C" int32_t ibu_stream_header(const ibu_stream_t* s, ibu_header_t* out) {
   if (!s || !out) return err_arg("NULL argument");
   *out = s->header;
@@ -882,7 +1162,12 @@ extern "C" int32_t ibu_stream_next(ibu_stream_t* s, void* stream, const void** d
   uint64_t first = 0;
   const int32_t rc = stream_take(s, pick_stream(s->ctx, stream), &si, n, &first);
   if (rc || *n == 0) return rc;
-  *d_records = s->ctx->ring.dev[si];
+  if (si == kRangeBatch) {
+    std::lock_guard<std::mutex> g(s->mu);
+    *d_records = s->rheld.back().p;
+  } else {
+    *d_records = s->ctx->ring.dev[si];
+  }
   if (first_index) *first_index = first;
   return IBU_OK;
 }
@@ -895,7 +1180,27 @@ extern "C" int32_t ibu_stream_release(ibu_stream_t* s, const void* d_records, vo
   uint32_t si = r.slots;
   {
     std::lock_guard<std::mutex> g(s->mu);
-    for (uint32_t i = 0; i < r.slots; ++i)
+    for (size_t i = 0; i < s->rheld.size(); ++i) {
+      if (s->rheld[i].p != d_records) continue;
+      // a batch of a range: its buffer is loaded again once every batch of it has come back and the work queued on the release
+      // streams has run (the producer waits for these events)
+      hipEvent_t ev = nullptr;
+      if (!s->spare_events.empty()) {
+        ev = s->spare_events.back();
+        s->spare_events.pop_back();
+      } else {
+        IBU_HIP(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
+      }
+      ibu_stream::RangeBuf& rb = s->rbuf[s->rheld[i].buf];
+      const hipError_t e = hipEventRecord(ev, pick_stream(s->ctx, stream));
+      if (e == hipSuccess) rb.released.push_back(ev);
+      else s->spare_events.push_back(ev);
+      s->rheld.erase(s->rheld.begin() + (ptrdiff_t)i);
+      --rb.out;                      // (even when the record failed: the stream must be able to end)
+      s->cv.notify_all();
+      return e == hipSuccess ? IBU_OK : hip_fail(e, "hipEventRecord");
+    }
+    for (uint32_t i = 0; i < r.dev.size(); ++i)
       if (r.dev[i] == d_records && s->slot[i].state == ibu_stream::HELD) si = i;
   }
   if (si == r.slots) return err_arg("not a batch this stream handed out and still holds");

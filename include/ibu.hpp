@@ -548,9 +548,17 @@ class DeviceStream {
   }
   StreamStats stats() const { StreamStats st{}; check(ibu_stream_stats(s_, &st)); return st; }
   ibu_stream_t* raw() const { return s_; }
+  // Reader::from_path + the stream (ibu_stream_open_path): a BGZF file the device load takes is read in ranges inflated on the device,
+  // anything else through the Reader of the same descriptor.  The stream owns its source.
+  static inline DeviceStream from_path(const char* path, device::Context& ctx, const RingConfig* ring = nullptr);
  private:
   ibu_stream_t* s_;
 };
+inline DeviceStream DeviceStream::from_path(const char* path, device::Context& ctx, const RingConfig* ring) {
+  ibu_stream_t* s = nullptr;
+  check(ibu_stream_open_path(path, ctx.raw(), ring, &s));
+  return DeviceStream(s);
+}
 inline DeviceStream Reader::device_stream(device::Context& ctx, const RingConfig* ring) {
   ibu_stream_t* s = nullptr;
   check(ibu_stream_open_reader(r_, ctx.raw(), ring, &s));

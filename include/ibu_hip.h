@@ -302,7 +302,9 @@ int32_t ibu_device_count(int32_t* n);
  *                           their blocks to arrive) for files of more blocks than this; 0 (default) = one round of the decoder's short
  *                           form, 49 152 blocks: smaller files get one launch behind the last copy.
  *   "bgzf_device"    0 | 1  1 (default): ibu_reader_process_device on an untouched BGZF file inflates on the device (see there).
- *   "bgzf_range_bytes"  >= 0  a test knob: the compressed bytes per range of that path (0 = default: 3.2 GB).
+ *   "bgzf_range_bytes"  >= 0  a test knob: the compressed bytes per range of that path and of ibu_stream_open_path (0 = default: 3.2 GB).
+ *   "bgzf_stream_ahead" 0 | 1  the decoder's launch form for the ranges after the first of ibu_stream_open_path: 1 (default) ahead of
+ *                           the copies (the waves wait for their bytes), 0 behind the range's last copy.
  *   "load_piece_delay_ms" 0..10000  a test knob: the BGZF loads sleep that long before every piece they copy (a slow source: the waves
  *                           of a launch that runs ahead give up after ~4 s, and what they left is inflated once everything has arrived).
  *   "release_staging"    1  one-shot: frees the device staging ibu_load_bgzf_to_device / _shard_ keep between calls (the size of the
@@ -506,7 +508,8 @@ int32_t ibu_barcode_counts(ibu_ctx_t* ctx, const void* d_sorted_records, size_t 
  * blocks per wave; BGZF level 1 of 16/12 records: 53 GB/s of output for 1e8 records, 100 GB/s for 3e8 (the 16 host inflate threads
  * of the same box: 9.6).
  * A wave takes ~46 ms for its 64 blocks whatever the call's size, so a call wants tens of thousands of blocks:
- * ibu_load_bgzf_to_device (above) is the library's own use of it; the streams keep the host inflate (a ring slot holds too few). */
+ * ibu_load_bgzf_to_device (above) and the range loads of ibu_stream_open_path (below) are the library's own uses of it; the streams over
+ * a Reader or a map keep the host inflate (a ring slot holds too few blocks). */
 #define IBU_INFLATE_PAD 2048
 typedef struct ibu_inflate_block {
   uint64_t comp_offset;
@@ -657,6 +660,35 @@ typedef struct ibu_stream ibu_stream_t;
 int32_t ibu_stream_open_reader(ibu_reader_t* r, ibu_ctx_t* ctx, const ibu_ring_config_t* cfg, ibu_stream_t** out);
 int32_t ibu_stream_open_mmap(const ibu_mmap_t* m, ibu_ctx_t* ctx, const ibu_ring_config_t* cfg, size_t shard, size_t n_shards,
                              ibu_stream_t** out);
+/* Reader::from_path + the stream (reader.rs:345-352; ABI revision 5): opens `path` once (one descriptor) and sniffs it.  The stream owns
+ * its source and closes it.
+ * A BGZF file the device load takes (every member a BGZF block, whole records, a valid header; context option "bgzf_device" = 1, the
+ *   default) is read in RANGES: only a range's compressed bytes cross the link (through the ring's pinned slots), its blocks are
+ *   inflated on the device (ibu_inflate_blocks_device's decoder; the blocks straddling the range's ends on the host), and next() hands
+ *   out views into the range's device buffer.  Open builds the block index (one walk) and sizes the inflate staging for the largest range.
+ *   Ranges: about option "bgzf_range_bytes" compressed bytes (default 3.2 GB, ~6.4 GB of 16/12 records); every range but the last holds a
+ *     multiple of IBU_DEFAULT_BUFFER_SIZE's 49 152 records, and of lcm(slot_records, 49 152) where that is no larger than the range —
+ *     with the default ring every batch but the last is then a whole slot.  A batch holds at most slot_records records, is 16-byte
+ *     aligned and never spans two ranges.
+ *   Two range buffers: range k + 1 is copied and inflated while the caller works on the batches of range k.  A buffer is loaded again
+ *     only once every batch of it has been released AND the work queued on the release streams has run.  next() that would need a
+ *     buffer whose batches the caller still holds returns IBU_ERR_INVALID_ARG at once (as with every slot held); after a release the
+ *     same call succeeds.
+ *   Device memory: the two range buffers (2 x range records x 24 B; the second is allocated only when a second range is loaded,
+ *     both are freed at close) plus the context's inflate staging (the largest range's compressed bytes, descriptors and tables; the
+ *     context keeps it, as after ibu_load_bgzf_to_device; option "release_staging" is refused while such a stream is open).
+ *   Launch form: every range launches the decoder ahead of its copies (its waves wait for their bytes), as the load does, also while
+ *     the caller's kernels run on the range before: measured against launching behind the last copy in launches of eight waves per CU
+ *     (context option "bgzf_stream_ahead" = 0), it was as fast at 1e8 records and 3 % faster at 1e9.
+ *   The caller may run the library's kernels (decode, sort, barcode counts, reduce) on a held batch on the same context while the
+ *     next range loads: the loader's tables live in the inflate staging and its copies and launches go out on its own streams only.
+ *   Errors: a block the device refuses in the first range sends the whole file through the host path below.  In a later range the
+ *     host inflate takes over at the range's first record (a refill boundary): the stream ends with exactly the records and the
+ *     error ibu_stream_open_reader gives on the same file.
+ *   Stats: bytes_h2d = the compressed bytes sent plus the host-inflated header and edge bytes; batches / records = what was queued.
+ * Anything else (a plain file, one gzip member, zstd / xz / bz2, a BGZF file with a foreign member, a cut, a bad header, "bgzf_device"
+ *   = 0): exactly ibu_stream_open_reader over ibu_reader_open_fd of the same descriptor — the same batches, errors and stats. */
+int32_t ibu_stream_open_path(const char* path, ibu_ctx_t* ctx, const ibu_ring_config_t* cfg, ibu_stream_t** out);
 int32_t ibu_stream_header(const ibu_stream_t* s, ibu_header_t* out);
 int32_t ibu_stream_next(ibu_stream_t* s, void* stream, const void** d_records, size_t* n, uint64_t* first_index);
 int32_t ibu_stream_release(ibu_stream_t* s, const void* d_records, void* stream);

@@ -37,6 +37,7 @@ def main():
     ap.add_argument("--slots", type=int, default=4)
     ap.add_argument("--slot-records", type=int, default=4 << 20)
     ap.add_argument("--feeders", type=int, default=8)
+    ap.add_argument("--stream-forms", action="store_true", help="with --gzip: the BGZF path stream leg in both launch forms (option bgzf_stream_ahead 0 and 1)")
     ap.add_argument("--skip-host-codec", action="store_true", help="leave out the host<->host codec stages (they hold 36 B/record in host arrays)")
     a = ap.parse_args()
     import ibu_amd as ia
@@ -244,6 +245,33 @@ def main():
             emit("BGZF Reader process_device DECODE (parallel inflate)", dt, st, gz_bytes=bgz_bytes,
                  gz_ratio=round(bgz_bytes / file_bytes, 3), compress_seconds=round(tc, 2), equals_plain_path=same)
             assert same
+
+            def pull_leg(label, open_stream, **extra):
+                # the pull stream over the same file and ring: the caller launches the decode on every batch
+                ctx.copy(d_idx, d_bc, min(d_idx.nbytes, d_bc.nbytes))   # (the last leg's index column spoilt: a leg that writes nothing fails)
+                ctx.synchronize()
+                t0 = time.perf_counter()
+                with open_stream() as s_:
+                    for b in s_:
+                        ctx.decode_ascii(b.ptr, b.n, bc_len, umi_len, d_bc.ptr + b.first_index * bc_len, d_umi.ptr + b.first_index * umi_len,
+                                         d_idx.ptr + b.first_index * 8)
+                        b.release()
+                    ctx.synchronize()
+                    st = s_.stats()
+                dt = time.perf_counter() - t0
+                same = [d_bc.download().tobytes(), d_umi.download().tobytes(), d_idx.download().tobytes()] == plain
+                emit(label, dt, st, gz_bytes=bgz_bytes, equals_plain_path=same, **extra)
+                assert same
+
+            for ahead in ((0, 1) if a.stream_forms else (None,)):
+                if ahead is not None:
+                    ctx.set_option("bgzf_stream_ahead", ahead)
+                pull_leg("BGZF path stream pull -> caller-launched DECODE (device inflate)", lambda: ia.DeviceStream.from_path(bgz, ctx, ring=ring),
+                         **({} if ahead is None else {"bgzf_stream_ahead": ahead}))
+            ctx.set_option("bgzf_stream_ahead", 1)
+            r = ia.Reader.from_path(bgz)
+            pull_leg("BGZF Reader device_stream pull -> caller-launched DECODE (host inflate)", lambda: r.device_stream(ctx, ring=ring))
+            r.close()
             os.unlink(bgz)
     finally:
         if os.path.exists(path):
