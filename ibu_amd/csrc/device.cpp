@@ -110,7 +110,8 @@ extern "C" void ibu_ctx_destroy(ibu_ctx_t* ctx) {
   for (hipStream_t q : ctx->inflate_streams)
     if (q) (void)hipStreamDestroy(q);
   if (ctx->d_inflate_stage) (void)hipFree(ctx->d_inflate_stage);
-  if (ctx->d_bgzf_range) (void)hipFree(ctx->d_bgzf_range);
+  for (void* p : ctx->d_range_buf)
+    if (p) (void)hipFree(p);
   if (ctx->h_inflate_marks) (void)hipHostFree(ctx->h_inflate_marks);
   if (ctx->stream) (void)hipStreamDestroy(ctx->stream);
   if (ctx->copy_stream) (void)hipStreamDestroy(ctx->copy_stream);
@@ -160,7 +161,7 @@ extern "C" int32_t ibu_ctx_set_option(ibu_ctx_t* ctx, const char* key, int64_t v
     ctx->inflate_one_launch = (size_t)value;
     return IBU_OK;
   }
-  if (strcmp(key, "bgzf_range_bytes") == 0) {            // a test knob: the ranges of ibu_reader_process_device's BGZF path
+  if (strcmp(key, "bgzf_range_bytes") == 0) {            // a test knob: the ranges of a path stream's device form (also under ibu_reader_process_device)
     if (value < 0) return err_arg("bgzf_range_bytes must be >= 0");
     ctx->bgzf_range_bytes_opt = (size_t)value;
     return IBU_OK;
@@ -180,7 +181,7 @@ extern "C" int32_t ibu_ctx_set_option(ibu_ctx_t* ctx, const char* key, int64_t v
     ctx->load_piece_delay_ms = (uint32_t)value;
     return IBU_OK;
   }
-  if (strcmp(key, "release_staging") == 0) {             // one-shot: the device staging ibu_load_bgzf_*_to_device keeps (the compressed file's size) goes back now
+  if (strcmp(key, "release_staging") == 0) {             // one-shot: the device staging the BGZF loads keep (the compressed file's size, the range buffers) goes back now
     if (value != 1) return err_arg("release_staging must be 1");
     if (ctx->stage_lent) return err_arg("an open ibu_stream_open_path stream loads through the staging: close it first");
     IBU_HIP(hipSetDevice(ctx->device));
@@ -189,9 +190,11 @@ extern "C" int32_t ibu_ctx_set_option(ibu_ctx_t* ctx, const char* key, int64_t v
     if (ctx->d_inflate_stage) IBU_HIP(hipFree(ctx->d_inflate_stage));
     ctx->d_inflate_stage = nullptr;
     ctx->inflate_stage_bytes = 0;
-    if (ctx->d_bgzf_range) IBU_HIP(hipFree(ctx->d_bgzf_range));
-    ctx->d_bgzf_range = nullptr;
-    ctx->bgzf_range_bytes = 0;
+    for (int b = 0; b < 2; ++b) {
+      if (ctx->d_range_buf[b]) IBU_HIP(hipFree(ctx->d_range_buf[b]));
+      ctx->d_range_buf[b] = nullptr;
+      ctx->range_buf_bytes[b] = 0;
+    }
     return IBU_OK;
   }
   if (strcmp(key, "sort_pull_streams") == 0) {

@@ -19,7 +19,7 @@ int32_t open_plain_file(const char* path, int* fd_out, ibu_header_t* header, siz
 // r->bytes_read unchanged; a source error likewise leaves in *got_bytes the complete record bytes read in front of it.
 // *eof: the stream ended (possibly with *got_bytes > 0).
 int32_t reader_read_direct(ibu_reader_t* r, uint8_t* dst, size_t cap_bytes, size_t* got_bytes, bool* eof);
-const char* reader_bgzf_path_if_untouched(const ibu_reader_t* r);   // host_io.cpp
+int reader_bgzf_fd_if_untouched(const ibu_reader_t* r);   // host_io.cpp
 void reader_set_drained(ibu_reader_t* r, uint64_t records);
 // A Reader over the BGZF file open on `fd` that takes over at record `records_before`: the host inflate from the member at file byte
 // `member_offset` on, its first `skip` bytes dropped (the member holds that record's first byte), header `h`.  It reads as the Reader

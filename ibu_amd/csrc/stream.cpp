@@ -7,7 +7,9 @@
 //
 // ONE pipeline feeds the device: the pull stream (ibu_stream_*, below) — a producer thread that fills pinned slots and queues
 // their H2D copies, and a consumer that takes device-resident batches in order.  ibu_mmap_process_device and
-// ibu_reader_process_device are that consumer with one of the two built-in processors as the loop body.
+// ibu_reader_process_device are that consumer with one of the two built-in processors as the loop body.  A BGZF file goes through
+// the same stream in its device form (ibu_stream_open_path; ibu_reader_process_device of an untouched BGZF Reader): the producer
+// loads ranges of records inflated on the device (BgzfLoad) and the batches are views into the range buffers.
 //
 // These are the device-backed forms of load_to_vec (reader.rs:510-535), Writer::write_batch
 // (writer.rs:315-351), MmapReader::process_parallel (mmap.rs:286-332, ONE shard of its static
@@ -281,13 +283,10 @@ struct BgzfLoad {
   ibu_header_t* header;
   void** d_records;                                        // nullptr: allocated here
   size_t cap_records, shard, n_shards;
-  size_t range_records = 0;                                // > 0: d_records is the context's range buffer, grown to this many records
-  const BgzfIndex* idx = nullptr;                          // the index, or the walk beside the copies makes it
-  ShardPlan plan{};
-  const ShardPlan* fixed = nullptr;                        // a plan made by the caller (the pull stream's ranges: plan_records)
+  const BgzfIndex* idx = nullptr;                          // the index and the plan the caller made (the pull stream's ranges), or the
+  ShardPlan plan{};                                        // walk beside the copies makes the index and plan_shard the plan
   bool ring_lent = false;                                  // the caller holds the context's ring (the pull stream): no ring_ensure
   bool behind = false;                                     // launch behind the last copy in chunks (inflate_late's), never ahead of the copies
-  uint64_t host_bytes = 0;                                 // record bytes inflated on the host and copied (header blocks, edges)
   std::vector<uint8_t> edge_bytes{};                       // (the host side of the asynchronous copies lives as long as the load)
   std::vector<ibu_inflate_block_t> desc_host{};
   uint32_t none_word = kNone;
@@ -328,7 +327,6 @@ struct BgzfLoad {
       for (hipStream_t s : ctx->inflate_streams)
         if (s) (void)hipStreamSynchronize(s);
       if (owned) { (void)hipFree(*d_records); *d_records = nullptr; }
-      if (owned && range_records) ctx->bgzf_range_bytes = 0;
       return rc;
     }
     *n = plan.num;
@@ -339,7 +337,7 @@ struct BgzfLoad {
   int32_t load() {
     // (one shard of one: room for the whole file and the descriptors of 64 KiB blocks: the copies start at once, nothing is allocated twice)
     int32_t rc = ring_lent ? IBU_OK : ring_ensure(ctx, cfg, false);   // (first: a context whose ring is lent keeps its staging untouched)
-    if (!rc && n_shards == 1 && !fixed) rc = grow_stage(ctx, ((file.n + kInflatePad + 255) & ~(size_t)255) + 40 * (file.n / 8192 + 64));
+    if (!rc && n_shards == 1 && !idx) rc = grow_stage(ctx, ((file.n + kInflatePad + 255) & ~(size_t)255) + 40 * (file.n / 8192 + 64));
     hipError_t e = hipSuccess;
     for (hipStream_t& s : ctx->inflate_streams)
       if (!s && !rc && e == hipSuccess) e = hipStreamCreateWithFlags(&s, hipStreamNonBlocking);
@@ -365,20 +363,13 @@ struct BgzfLoad {
       idx = &walked;
       if (walked.head.size() >= IBU_HEADER_SIZE) *header = walked.header;
       if (walk_rc) { tls_error() = walk_detail; return walk_rc; }
+      if (int32_t rc = plan_shard(*idx, shard, n_shards, &plan)) return rc;
     }
-    if (fixed) plan = *fixed;
-    else if (int32_t rc = plan_shard(*idx, shard, n_shards, &plan)) return rc;
-    const size_t nrest = plan.dev_blocks(), need = std::max({plan.num, range_records, (size_t)1}) * IBU_RECORD_SIZE;
-    if (range_records && need > ctx->bgzf_range_bytes) {   // the range buffer: the context keeps it and it grows only (freeing and
-      (void)hipFree(ctx->d_bgzf_range);                    // allocating 2.4 GB around every call cost a call of 1e8 records 80 of its
-      const hipError_t e = ctx_malloc(ctx, &ctx->d_bgzf_range, need);   // 155 ms; no placement probing: the records only pass through)
-      ctx->bgzf_range_bytes = e == hipSuccess ? need : 0;
-      if (e != hipSuccess) { ctx->d_bgzf_range = nullptr; return hip_fail(e, "hipMalloc"); }
-      owned = true;
-    } else if (!range_records && *d_records == nullptr) {
+    const size_t nrest = plan.dev_blocks();
+    if (*d_records == nullptr) {
       if (int32_t rc = ctx_alloc(ctx, plan.num * IBU_RECORD_SIZE, d_records)) return rc;
       owned = true;
-    } else if (!range_records && plan.num > cap_records) {
+    } else if (plan.num > cap_records) {
       return set_error(IBU_ERR_INVALID_ARG, plan.num, cap_records, 0, "Invalid argument: device buffer too small for the shard (%zu records, room for %zu)",
                        plan.num, cap_records);
     }
@@ -389,7 +380,6 @@ struct BgzfLoad {
     auto put = [&](const uint8_t* bytes, uint64_t at, uint64_t len) {   // bytes [at, at + len) of the stream, as far as they are the shard's
       const uint64_t a = std::max(at, plan.lo), z = std::min(at + len, plan.hi);
       if (a < z && e == hipSuccess) e = hipMemcpyAsync(d_out + (a - plan.lo), bytes + (a - at), z - a, hipMemcpyHostToDevice, q());
-      if (a < z) host_bytes += z - a;
     };
     put(idx->head.data(), 0, idx->head.size());            // the records behind the header in the blocks inflated for it
     pgz::RawInflater raw;
@@ -628,23 +618,25 @@ struct ibu_stream {
   size_t stage_pos = 0, stage_len = 0;   // records
   bool src_eof = false;              // the Reader source reported its end
   std::thread producer;
-  // ibu_stream_open_path: the stream owns its source — the file's descriptor and the Reader of the host path (the whole file, or the
-  // rest of it from a range the device refused) ...
+  // A path stream (ibu_stream_open_path; ibu_reader_process_device of a BGZF file) owns a descriptor of its file and the Reader of the
+  // host path where it opens one (the whole file when no Reader is borrowed, or the rest of it from a range the device refused) ...
   int own_fd = -1;
   ibu_reader_t* own_rd = nullptr;
   ibu_ring_config_t cfg{};
-  // ... and, in the device form, the file mapped and indexed once and read in ranges of range_records into two range buffers
+  // ... and, in the device form, the file mapped and indexed once and read in ranges of range_records into the context's two range
+  // buffers (ctx->d_range_buf)
   bool ranges = false;
   std::unique_ptr<FileMap> file;
   BgzfIndex idx;
   size_t range_records = 0, n_ranges = 0;
-  struct RangeBuf { uint8_t* d = nullptr; size_t cap = 0; uint32_t out = 0; std::vector<hipEvent_t> released; };   // out: batches queued or held
+  struct RangeBuf { uint32_t out = 0; std::vector<hipEvent_t> released; };   // out: batches queued or held
   RangeBuf rbuf[2];
   std::vector<hipEvent_t> spare_events;
   int waiting = -1;                  // the producer waits for this range buffer's batches to come back
-  struct RangeBatch { uint8_t* p; size_t n; uint64_t first; int buf; };
-  std::deque<RangeBatch> rready;     // in stream order, in front of any slot batch
-  std::vector<RangeBatch> rheld;
+  // What next() hands out: a ring slot's batch (slot >= 0) or a view into range buffer `buf`
+  struct Batch { uint8_t* p = nullptr; size_t n = 0; uint64_t first = 0; int slot = -1, buf = -1; };
+  std::deque<Batch> rready;          // a range's batches in stream order, in front of any slot batch
+  std::vector<Batch> rheld;
 };
 
 namespace {
@@ -734,10 +726,12 @@ int32_t ring_add_dev(ibu_ctx* ctx) {
   return IBU_OK;
 }
 
-// The host path of a path stream from record `from` on: the whole file through the Reader of the same descriptor (from == 0), or the
-// member holding that record's first byte on (a range boundary, so a refill boundary: the refills are counted on unchanged)
+// The host path of a path stream from record `from` on: the whole file through the borrowed Reader or one of the same descriptor
+// (from == 0), or the member holding that record's first byte on (a range boundary, so a refill boundary: the refills are counted on
+// unchanged)
 int32_t host_take_over(ibu_stream* s, uint64_t from) {
   if (int32_t rc = ring_add_dev(s->ctx)) return rc;
+  if (from == 0 && s->rd) return IBU_OK;                   // (the caller's Reader, untouched: it reads as it would have read)
   if (from == 0) {
     if (lseek(s->own_fd, 0, SEEK_SET) < 0) return err_io(errno, "seek");
     const int32_t rc = ibu_reader_open_fd(s->own_fd, &s->own_rd);
@@ -755,17 +749,23 @@ int32_t host_take_over(ibu_stream* s, uint64_t from) {
   return rc;
 }
 
+// Range k of a path stream's device form: records [k * range_records, ...) (plan_records); a file of one range is the load's whole-file
+// plan (plan_shard: every byte of the file crosses the link, as for ibu_load_bgzf_to_device)
+int32_t range_plan(const ibu_stream* s, size_t k, ShardPlan* plan) {
+  if (s->n_ranges == 1) return plan_shard(s->idx, 0, 1, plan);
+  const size_t total = (size_t)((s->idx.total - IBU_HEADER_SIZE) / IBU_RECORD_SIZE), first = k * s->range_records;
+  return plan_records(s->idx, first, std::min(s->range_records, total - first), plan);
+}
+
 // The device form of a path stream: range k goes to range buffer k % 2 once every batch of the range before it there has been released
 // and the work queued on the release streams has run; its compressed bytes cross the link through the ring's pinned slots and its blocks
 // are inflated on the device (BgzfLoad), and its batches — views into the buffer — go out.  A load that fails hands over to the host path:
 // *host = true, *from = the range's first record (the first range: anything; later ones: a block the device refused).
 int32_t produce_ranges(ibu_stream* s, bool* host, uint64_t* from) {
   ibu_ctx* ctx = s->ctx;
-  const size_t total = (size_t)((s->idx.total - IBU_HEADER_SIZE) / IBU_RECORD_SIZE);
   for (size_t k = 0; k < s->n_ranges; ++k) {
     const int b = (int)(k & 1);
     ibu_stream::RangeBuf& rb = s->rbuf[b];
-    const size_t first = k * s->range_records, num = std::min(s->range_records, total - first);
     std::vector<hipEvent_t> released;
     {
       std::unique_lock<std::mutex> lk(s->mu);
@@ -784,43 +784,51 @@ int32_t produce_ranges(ibu_stream* s, bool* host, uint64_t* from) {
       s->spare_events.insert(s->spare_events.end(), released.begin(), released.end());
     }
     if (e != hipSuccess) return hip_fail(e, "hipEventSynchronize");
-    if (rb.cap < num) {                                    // (allocated when first needed: a file of one range has one buffer)
-      if (rb.d) (void)hipFree(rb.d);
-      rb.d = nullptr;
-      rb.cap = 0;
-      if ((e = hipMalloc(reinterpret_cast<void**>(&rb.d), num * IBU_RECORD_SIZE)) != hipSuccess) { rb.d = nullptr; return hip_fail(e, "hipMalloc"); }
-      rb.cap = num;
-    }
     ShardPlan plan;
-    if (int32_t rc = plan_records(s->idx, first, num, &plan)) return rc;
+    if (int32_t rc = range_plan(s, k, &plan)) return rc;
+    // The range buffer: the context keeps it and it grows only (freeing and allocating 2.4 GB around every call cost a call of 1e8 records
+    // 80 of its 155 ms); allocated when first needed, so a file of one range has one buffer.  Plain hipMalloc: no placement probing (the
+    // records only pass through), and this thread must not touch the context's allocator state beside the caller's calls on the context.
+    void*& d = ctx->d_range_buf[b];
+    size_t& cap = ctx->range_buf_bytes[b];
+    if (cap < plan.num * IBU_RECORD_SIZE) {
+      (void)hipFree(d);
+      d = nullptr;
+      cap = 0;
+      if ((e = hipMalloc(&d, plan.num * IBU_RECORD_SIZE)) != hipSuccess) { d = nullptr; return hip_fail(e, "hipMalloc"); }
+      cap = plan.num * IBU_RECORD_SIZE;
+    }
     ibu_stream_stats_t st{};
     ibu_header_t h = s->header;
-    void* dst = rb.d;
+    void* dst = d;
     size_t n = 0;
     const ibu_error_detail_t keep = tls_error();
-    BgzfLoad L{ctx, &s->cfg, *s->file, &st, &h, &dst, rb.cap, 0, 1, 0, &s->idx};
-    L.fixed = &plan;
+    BgzfLoad L{ctx, &s->cfg, *s->file, &st, &h, &dst, cap / IBU_RECORD_SIZE, 0, 1, &s->idx, plan};
     L.ring_lent = true;
     L.behind = k > 0 && !ctx->bgzf_stream_ahead;           // (the first range, with nothing held, always launches ahead of its copies, as the load does)
     const int32_t rc = L.run(&n, nullptr);
     if (rc && (k == 0 || rc == IBU_ERR_NIFFLER)) {         // the host path decides: the same records, the same error
       tls_error() = keep;
       *host = true;
-      *from = first;
+      *from = plan.rec_first;
       std::lock_guard<std::mutex> g(s->mu);
-      if (k) s->stats.bytes_h2d += st.bytes_h2d + L.host_bytes;   // (the first range: the stats are the Reader stream's alone)
+      if (k) s->stats.bytes_h2d += st.bytes_h2d;           // (the first range: the stats are the Reader stream's alone)
       return IBU_OK;
     }
     if (rc) return rc;
     std::lock_guard<std::mutex> g(s->mu);
     for (size_t at = 0; at < n; at += s->slot_records) {
-      const size_t nb = std::min(s->slot_records, n - at);
-      s->rready.push_back(ibu_stream::RangeBatch{rb.d + at * IBU_RECORD_SIZE, nb, (uint64_t)(first + at), b});
+      ibu_stream::Batch bt;
+      bt.p = static_cast<uint8_t*>(d) + at * IBU_RECORD_SIZE;
+      bt.n = std::min(s->slot_records, n - at);
+      bt.first = plan.rec_first + at;
+      bt.buf = b;
+      s->rready.push_back(bt);
       ++rb.out;
       s->stats.batches += 1;
     }
     s->stats.records += n;
-    s->stats.bytes_h2d += st.bytes_h2d + L.host_bytes;
+    s->stats.bytes_h2d += st.bytes_h2d;
     s->cv.notify_all();
   }
   return IBU_OK;
@@ -940,27 +948,22 @@ int32_t stream_open(ibu_ctx* ctx, const ibu_ring_config_t* cfg, ibu_stream* s) {
   return IBU_OK;
 }
 
-constexpr uint32_t kRangeBatch = 0xFFFFFFFFu;   // stream_take's slot for a batch of a range: the newest of ibu_stream::rheld
-
-// The consumer side of next(): the oldest READY slot, the caller's stream ordered behind its copy.  *n == 0: end of stream.
-int32_t stream_take(ibu_stream* s, hipStream_t st, uint32_t* slot_out, size_t* n, uint64_t* first) {
+// The consumer side of next(): a range's next batch (inflated before it was queued: nothing for `st` to wait for), else the oldest READY
+// slot with `st` ordered behind its copy.  b->n == 0: end of stream.
+int32_t stream_take(ibu_stream* s, hipStream_t st, ibu_stream::Batch* b) {
   Ring& r = s->ctx->ring;
-  uint32_t si = 0;
   {
     std::unique_lock<std::mutex> lk(s->mu);
     for (;;) {
-      if (!s->rready.empty()) {      // a batch of a range (a path stream): inflated before it was queued, nothing for `st` to wait for
-        const ibu_stream::RangeBatch b = s->rready.front();
+      if (!s->rready.empty()) {
+        *b = s->rready.front();
         s->rready.pop_front();
-        s->rheld.push_back(b);
-        *slot_out = kRangeBatch;
-        *n = b.n;
-        *first = b.first;
+        s->rheld.push_back(*b);
         return IBU_OK;
       }
       if (!s->ready.empty()) break;
       if (s->done) {
-        *n = 0;
+        b->n = 0;
         if (s->rc) { tls_error() = s->detail; return s->rc; }
         return IBU_OK;
       }
@@ -969,30 +972,45 @@ int32_t stream_take(ibu_stream* s, hipStream_t st, uint32_t* slot_out, size_t* n
         return err_arg("the next range goes to the range buffer whose batches are held: release them before asking for the next");
       s->cv.wait(lk);
     }
-    si = s->ready.front();
+    const uint32_t si = s->ready.front();
     s->ready.pop_front();
     s->slot[si].state = ibu_stream::HELD;
     ++s->held;
-    *n = s->slot[si].n;
-    *first = s->slot[si].first;
+    b->p = r.dev[si];
+    b->n = s->slot[si].n;
+    b->first = s->slot[si].first;
+    b->slot = (int)si;
   }
-  IBU_HIP(hipStreamWaitEvent(st, r.copied[si], 0));
-  *slot_out = si;
+  IBU_HIP(hipStreamWaitEvent(st, r.copied[b->slot], 0));
   return IBU_OK;
 }
 
-int32_t stream_give_back(ibu_stream* s, uint32_t si, hipStream_t st) {
-  Ring& r = s->ctx->ring;
-  hipError_t e = hipEventRecord(r.consumed[si], st);
-  {
-    std::lock_guard<std::mutex> g(s->mu);
-    s->slot[si].state = ibu_stream::RELEASED;   // (even when the record failed: the stream must be able to end)
-    s->slot[si].seq = ++s->release_seq;
+// release: a ring slot is refilled once `st` has run up to here (`consumed`); a range buffer is loaded again once every batch of it has
+// come back and the work queued on the release streams has run (the producer waits for these events)
+int32_t stream_give_back(ibu_stream* s, const ibu_stream::Batch& b, hipStream_t st) {
+  hipError_t e = b.slot >= 0 ? hipEventRecord(s->ctx->ring.consumed[b.slot], st) : hipSuccess;
+  std::lock_guard<std::mutex> g(s->mu);
+  if (b.buf >= 0) {
+    hipEvent_t ev = nullptr;
+    if (!s->spare_events.empty()) {
+      ev = s->spare_events.back();
+      s->spare_events.pop_back();
+    } else {
+      e = hipEventCreateWithFlags(&ev, hipEventDisableTiming);
+    }
+    if (e == hipSuccess) e = hipEventRecord(ev, st);
+    if (e == hipSuccess) s->rbuf[b.buf].released.push_back(ev);
+    else if (ev) s->spare_events.push_back(ev);
+    for (size_t i = 0; i < s->rheld.size(); ++i)
+      if (s->rheld[i].p == b.p) { s->rheld.erase(s->rheld.begin() + (ptrdiff_t)i); break; }
+    --s->rbuf[b.buf].out;
+  } else {
+    s->slot[b.slot].state = ibu_stream::RELEASED;
+    s->slot[b.slot].seq = ++s->release_seq;
     --s->held;
-    s->cv.notify_all();
   }
-  if (e != hipSuccess) return hip_fail(e, "hipEventRecord");
-  return IBU_OK;
+  s->cv.notify_all();                // (even when the record failed: the stream must be able to end)
+  return e == hipSuccess ? IBU_OK : hip_fail(e, "hipEventRecord");
 }
 
 void stream_shutdown(ibu_stream* s) {
@@ -1008,13 +1026,11 @@ void stream_shutdown(ibu_stream* s) {
   (void)hipStreamSynchronize(ctx->stream);
   for (uint32_t i = 0; i < s->slot.size(); ++i)   // work the caller queued on its own streams before releasing
     if (s->slot[i].state == ibu_stream::RELEASED) (void)hipEventSynchronize(ctx->ring.consumed[i]);
-  for (ibu_stream::RangeBuf& rb : s->rbuf) {      // a path stream's own: the range buffers, its events, its Reader and descriptor
-    for (hipEvent_t ev : rb.released) {
+  for (ibu_stream::RangeBuf& rb : s->rbuf) {      // a path stream's own: its events, its Reader and descriptor (the range buffers are
+    for (hipEvent_t ev : rb.released) {            // the context's)
       (void)hipEventSynchronize(ev);
       (void)hipEventDestroy(ev);
     }
-    rb.released.clear();
-    if (rb.d) (void)hipFree(rb.d);
     rb = ibu_stream::RangeBuf();
   }
   for (hipEvent_t ev : s->spare_events) (void)hipEventDestroy(ev);
@@ -1066,9 +1082,12 @@ extern "C" int32_t ibu_stream_open_mmap(const ibu_mmap_t* m, ibu_ctx_t* ctx, con
 }
 
 // Reader::from_path + the pull stream (reader.rs:345-352): one descriptor, sniffed once.  A BGZF file the device load takes is read in ranges
-// inflated on the device (produce_ranges); anything else is ibu_stream_open_reader over ibu_reader_open_fd of that descriptor.
+// inflated on the device (produce_ranges); anything else goes through a Reader: ibu_stream_open_reader over ibu_reader_open_fd of that
+// descriptor, or over the caller's Reader of the same file (ibu_reader_process_device).
 namespace {
-int32_t open_path_device_form(ibu_stream* s, ibu_ctx* ctx) {
+// The device form over s->own_fd: sniffed, mapped, indexed once, the ranges planned for the context's ring (ring_ensure first) and the
+// inflate staging sized for the largest.  A header other than `want` (when given) is a refusal like any other.
+int32_t index_and_plan(ibu_stream* s, ibu_ctx* ctx, const ibu_header_t* want) {
   struct stat st;
   if (fstat(s->own_fd, &st) || !S_ISREG(st.st_mode) || st.st_size < 18 || getenv("IBU_NO_PARALLEL_BGZF")) return IBU_ERR_NIFFLER;
   void* p = mmap(nullptr, (size_t)st.st_size, PROT_READ, MAP_PRIVATE, s->own_fd, 0);
@@ -1081,6 +1100,7 @@ int32_t open_path_device_form(ibu_stream* s, ibu_ctx* ctx) {
   (void)madvise(const_cast<uint8_t*>(m), s->file->n, MADV_SEQUENTIAL);
   RunOnNode on_node(feed_place(ctx));
   if (int32_t rc = bgzf_index(m, s->file->n, &s->idx)) return rc;
+  if (want && memcmp(&s->idx.header, want, sizeof *want) != 0) return IBU_ERR_NIFFLER;
   s->header = s->idx.header;
   const size_t total = (size_t)((s->idx.total - IBU_HEADER_SIZE) / IBU_RECORD_SIZE);
   const size_t target = ctx->bgzf_range_bytes_opt ? ctx->bgzf_range_bytes_opt : (size_t)3200000000ull;
@@ -1089,7 +1109,7 @@ int32_t open_path_device_form(ibu_stream* s, ibu_ctx* ctx) {
   size_t need = 0;                                         // the staging for the largest range, now: a load never grows it under the caller
   for (size_t k = 0; k < s->n_ranges; ++k) {
     ShardPlan plan;
-    if (int32_t rc = plan_records(s->idx, k * s->range_records, std::min(s->range_records, total - k * s->range_records), &plan)) return rc;
+    if (int32_t rc = range_plan(s, k, &plan)) return rc;
     size_t a, b, c, d;
     need = std::max(need, stage_bytes(ctx, plan, &a, &b, &c, &d));
   }
@@ -1103,6 +1123,54 @@ int32_t open_path_device_form(ibu_stream* s, ibu_ctx* ctx) {
   s->ranges = true;
   return IBU_OK;
 }
+
+// The same, or false: not for the device form (option "bgzf_device" = 0, no descriptor, anything index_and_plan refuses), as if it had not
+// been tried: nothing kept, the error detail as it was
+bool open_device_form(ibu_stream* s, ibu_ctx* ctx, const ibu_header_t* want) {
+  if (!ctx->bgzf_device || s->own_fd < 0) return false;
+  const ibu_error_detail_t keep = tls_error();
+  int32_t rc = IBU_OK;
+  try {
+    rc = index_and_plan(s, ctx, want);
+  } catch (...) {
+    rc = caught_io("ibu_stream_open_path");
+  }
+  if (rc) {
+    tls_error() = keep;
+    s->file.reset();
+    s->idx = BgzfIndex();
+  }
+  return rc == IBU_OK;
+}
+
+// A path stream over descriptor `fd` (-1: none), which it owns from here on (closed on a failure too).  `rd`: the caller's Reader of the
+// same file, borrowed as the host path from record 0 and as the whole source where the device form does not take the file; NULL: a
+// Reader of `fd` where needed.  The context's ring is sized already (ring_ensure).
+int32_t open_path_stream(int fd, ibu_reader_t* rd, ibu_ctx* ctx, const ibu_ring_config_t* cfg, ibu_stream** out) {
+  std::unique_ptr<ibu_stream> s(new (std::nothrow) ibu_stream);
+  if (!s) {
+    if (fd >= 0) close(fd);
+    return err_io(ENOMEM, "ibu_stream_open_path");
+  }
+  s->own_fd = fd;
+  struct Own { ibu_stream* s; ~Own() { if (s && s->own_rd) ibu_reader_close(s->own_rd); if (s && s->own_fd >= 0) close(s->own_fd); } } own{s.get()};   // (until the stream runs)
+  if (cfg) s->cfg = *cfg;
+  ibu_header_t want{};
+  if (rd) ibu_reader_header(rd, &want);
+  if (!open_device_form(s.get(), ctx, rd ? &want : nullptr)) {
+    if (!rd) {
+      if (int32_t rc = ibu_reader_open_fd(fd, &s->own_rd)) return rc;
+      rd = s->own_rd;
+    }
+    ibu_reader_header(rd, &s->header);
+  }
+  s->rd = rd;
+  if (int32_t rc = stream_open(ctx, cfg, s.get())) return rc;
+  if (s->ranges) ctx->stage_lent = true;
+  own.s = nullptr;
+  *out = s.release();
+  return IBU_OK;
+}
 }  // namespace
 
 extern "C" int32_t ibu_stream_open_path(const char* path, ibu_ctx_t* ctx, const ibu_ring_config_t* cfg, ibu_stream_t** out) {
@@ -1110,40 +1178,9 @@ extern "C" int32_t ibu_stream_open_path(const char* path, ibu_ctx_t* ctx, const 
   *out = nullptr;
   IBU_HIP(hipSetDevice(ctx->device));
   if (int32_t rc = ring_ensure(ctx, cfg, false)) return rc;   // (a ring lent to another stream: refused before the file is touched)
-  std::unique_ptr<ibu_stream> s(new (std::nothrow) ibu_stream);
-  if (!s) return err_io(ENOMEM, "ibu_stream_open_path");
-  if (cfg) s->cfg = *cfg;
-  s->own_fd = ::open(path, O_RDONLY | O_CLOEXEC);
-  if (s->own_fd < 0) return err_io(errno, path);
-  struct Fd { ibu_stream* s; ~Fd() { if (s && s->own_fd >= 0) close(s->own_fd); } } fd_guard{s.get()};   // (until the stream owns it)
-  int32_t rc = IBU_ERR_NIFFLER;
-  if (ctx->bgzf_device) {
-    const ibu_error_detail_t keep = tls_error();
-    try {
-      rc = open_path_device_form(s.get(), ctx);
-    } catch (...) {
-      rc = caught_io("ibu_stream_open_path");
-    }
-    if (rc) {                                              // not for the device form: as if it had not been tried
-      tls_error() = keep;
-      s->file.reset();
-      s->idx = BgzfIndex();
-      s->ranges = false;
-    }
-  }
-  if (rc) {
-    if ((rc = ibu_reader_open_fd(s->own_fd, &s->own_rd))) return rc;
-    s->rd = s->own_rd;
-    ibu_reader_header(s->rd, &s->header);
-  }
-  if ((rc = stream_open(ctx, cfg, s.get()))) {
-    if (s->own_rd) ibu_reader_close(s->own_rd);
-    return rc;
-  }
-  if (s->ranges) ctx->stage_lent = true;
-  fd_guard.s = nullptr;                                    // the stream owns the descriptor now
-  *out = s.release();
-  return IBU_OK;
+  const int fd = ::open(path, O_RDONLY | O_CLOEXEC);
+  if (fd < 0) return err_io(errno, path);
+  return open_path_stream(fd, nullptr, ctx, cfg, out);
 }
 
 extern "C" int32_t ibu_stream_header(const ibu_stream_t* s, ibu_header_t* out) {
@@ -1158,17 +1195,12 @@ extern "C" int32_t ibu_stream_next(ibu_stream_t* s, void* stream, const void** d
   *n = 0;
   if (!s->ctx) return err_arg("the stream's context has been destroyed");
   IBU_HIP(hipSetDevice(s->ctx->device));
-  uint32_t si = 0;
-  uint64_t first = 0;
-  const int32_t rc = stream_take(s, pick_stream(s->ctx, stream), &si, n, &first);
-  if (rc || *n == 0) return rc;
-  if (si == kRangeBatch) {
-    std::lock_guard<std::mutex> g(s->mu);
-    *d_records = s->rheld.back().p;
-  } else {
-    *d_records = s->ctx->ring.dev[si];
-  }
-  if (first_index) *first_index = first;
+  ibu_stream::Batch b;
+  const int32_t rc = stream_take(s, pick_stream(s->ctx, stream), &b);
+  if (rc || b.n == 0) return rc;
+  *d_records = b.p;
+  *n = b.n;
+  if (first_index) *first_index = b.first;
   return IBU_OK;
 }
 
@@ -1177,34 +1209,19 @@ extern "C" int32_t ibu_stream_release(ibu_stream_t* s, const void* d_records, vo
   if (!s->ctx) return err_arg("the stream's context has been destroyed");
   IBU_HIP(hipSetDevice(s->ctx->device));
   Ring& r = s->ctx->ring;
-  uint32_t si = r.slots;
+  ibu_stream::Batch b;
   {
     std::lock_guard<std::mutex> g(s->mu);
-    for (size_t i = 0; i < s->rheld.size(); ++i) {
-      if (s->rheld[i].p != d_records) continue;
-      // a batch of a range: its buffer is loaded again once every batch of it has come back and the work queued on the release
-      // streams has run (the producer waits for these events)
-      hipEvent_t ev = nullptr;
-      if (!s->spare_events.empty()) {
-        ev = s->spare_events.back();
-        s->spare_events.pop_back();
-      } else {
-        IBU_HIP(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
+    for (const ibu_stream::Batch& h : s->rheld)
+      if (h.p == d_records) b = h;
+    for (uint32_t i = 0; i < r.dev.size() && !b.p; ++i)
+      if (r.dev[i] == d_records && s->slot[i].state == ibu_stream::HELD) {
+        b.p = r.dev[i];
+        b.slot = (int)i;
       }
-      ibu_stream::RangeBuf& rb = s->rbuf[s->rheld[i].buf];
-      const hipError_t e = hipEventRecord(ev, pick_stream(s->ctx, stream));
-      if (e == hipSuccess) rb.released.push_back(ev);
-      else s->spare_events.push_back(ev);
-      s->rheld.erase(s->rheld.begin() + (ptrdiff_t)i);
-      --rb.out;                      // (even when the record failed: the stream must be able to end)
-      s->cv.notify_all();
-      return e == hipSuccess ? IBU_OK : hip_fail(e, "hipEventRecord");
-    }
-    for (uint32_t i = 0; i < r.dev.size(); ++i)
-      if (r.dev[i] == d_records && s->slot[i].state == ibu_stream::HELD) si = i;
   }
-  if (si == r.slots) return err_arg("not a batch this stream handed out and still holds");
-  return stream_give_back(s, si, pick_stream(s->ctx, stream));
+  if (!b.p) return err_arg("not a batch this stream handed out and still holds");
+  return stream_give_back(s, b, pick_stream(s->ctx, stream));
 }
 
 extern "C" int32_t ibu_stream_stats(const ibu_stream_t* s, ibu_stream_stats_t* out) {
@@ -1245,25 +1262,26 @@ int32_t run_processor(ibu_stream* s, int32_t proc, void* sink, ibu_stream_stats_
   rc = kc.init(r.slots);
   if (rc) return rc;
   if (proc == IBU_PROC_REDUCE) IBU_HIP(hipMemsetAsync(ctx->d_acc, 0, kReduceAccBytes, ctx->stream));
-  for (;;) {
-    uint32_t si = 0;
-    size_t n = 0;
-    uint64_t first = 0;
-    rc = stream_take(s, ctx->stream, &si, &n, &first);
-    if (rc || n == 0) break;
-    const size_t row0 = (size_t)(first - s->first0);
-    rc = dp.fits(n, row0);           // a gzip / BGZF / xz / zstd stream does not announce its length: every batch is checked
+  for (uint64_t seq = 0;; ++seq) {
+    ibu_stream::Batch b;
+    rc = stream_take(s, ctx->stream, &b);
+    if (rc || b.n == 0) break;
+    const size_t row0 = (size_t)(b.first - s->first0);
+    rc = dp.fits(b.n, row0);         // a gzip / BGZF / xz / zstd stream does not announce its length: every batch is checked
     if (rc == IBU_OK) {
-      kc.harvest(si);                // the slot's previous kernel finished before the producer refilled it: no wait
-      hipError_t e = hipEventRecord(kc.a[si], ctx->stream);
+      // the clock's pair of a ring batch is its slot's: the slot's previous kernel finished before the producer refilled it, no wait.
+      // A range's batches take the pairs in turn (harvesting one waits for the kernel slots batches back)
+      const uint32_t k = b.slot >= 0 ? (uint32_t)b.slot : (uint32_t)(seq % r.slots);
+      kc.harvest(k);
+      hipError_t e = hipEventRecord(kc.a[k], ctx->stream);
       if (e == hipSuccess) {
-        rc = dp.launch(r.dev[si], n, row0);
-        if (rc == IBU_OK) e = hipEventRecord(kc.b[si], ctx->stream);
+        rc = dp.launch(b.p, b.n, row0);
+        if (rc == IBU_OK) e = hipEventRecord(kc.b[k], ctx->stream);
       }
       if (rc == IBU_OK && e != hipSuccess) rc = hip_fail(e, "hipEventRecord");
-      if (rc == IBU_OK) kc.live[si] = 1;
+      if (rc == IBU_OK) kc.live[k] = 1;
     }
-    const int32_t rel = stream_give_back(s, si, ctx->stream);
+    const int32_t rel = stream_give_back(s, b, ctx->stream);
     if (rc == IBU_OK) rc = rel;
     if (rc) break;
   }
@@ -1279,10 +1297,15 @@ int32_t run_processor(ibu_stream* s, int32_t proc, void* sink, ibu_stream_stats_
   }
   return IBU_OK;
 }
-// open -> run -> close, with the error (and its detail) of the first failing step
-int32_t process_stream(ibu_stream* s, int32_t open_rc, int32_t proc, void* sink, ibu_stream_stats_t* stats, double t0) {
+// open -> run -> close, with the error (and its detail) of the first failing step; *records (nullable): the records delivered
+int32_t process_stream(ibu_stream* s, int32_t open_rc, int32_t proc, void* sink, ibu_stream_stats_t* stats, double t0,
+                       uint64_t* records = nullptr) {
   if (open_rc) return open_rc;
   const int32_t rc = run_processor(s, proc, sink, stats);
+  if (records) {
+    std::lock_guard<std::mutex> g(s->mu);
+    *records = s->stats.records;
+  }
   const ibu_error_detail_t keep = tls_error();
   ibu_stream_close(s);               // drains the copy stream and the context's stream: nothing is in flight over ring memory
   if (rc) { tls_error() = keep; return rc; }
@@ -1418,65 +1441,10 @@ extern "C" int32_t ibu_mmap_process_devices(const ibu_mmap_t* m, const int32_t* 
 // ------------------------------------------------------------------------------------------
 // streaming Reader (plain / gzip), device form
 // ------------------------------------------------------------------------------------------
-namespace {
 // A Reader over a BGZF FILE nothing has been read from: the processors need not pull it through the Reader's host inflate (0.4 G records/s
-// on 16 CPUs) — the file is loaded range by range with its compressed bytes crossing the link and its blocks inflated on the device
-// (BgzfLoad: ranges of about 6 GB of records, so that any file fits), and the processor runs over each range.  The file is mapped and
-// indexed once; the ranges land in the context's range buffer, sized by the first load for the largest range.
-// *handled = false: the file is not what that load takes (a foreign member, a cut, a length that is no whole number of records ...) —
-// nothing has been touched, and the Reader's own path delivers what it delivers for such a file, error and all.
-int32_t process_bgzf_file(ibu_ctx* ctx, const char* path, const ibu_ring_config_t* cfg, const ibu_header_t& want, DeviceProc& dp, int32_t proc, void* sink,
-                          ibu_stream_stats_t* stats, uint64_t* records, bool* handled) {
-  *handled = false;
-  const ibu_error_detail_t keep = tls_error();
-  FileMap file;
-  int32_t rc = map_bgzf(path, &file);
-  // ranges of ~6.4 GB of records where the file compresses to half (BGZF of 16/12 records: 0.50) — every range costs its launch's
-  // waves' 45-75 ms once more, and a file that compresses better just gets larger ranges
-  const size_t K = (size_t)((double)file.n / (ctx->bgzf_range_bytes_opt ? (double)ctx->bgzf_range_bytes_opt : 3.2e9)) + 1;
-  BgzfIndex idx;
-  ShardPlan last;                                          // (the largest range: the first load sizes the buffer for it)
-  ibu_header_t h{};
-  if (!rc && K > 1) {                                      // (one range: the load walks the file beside its copies)
-    RunOnNode on_node(feed_place(ctx));
-    if (!(rc = bgzf_index(file.p, file.n, &idx))) rc = plan_shard(idx, K - 1, K, &last);
-    h = idx.header;
-  }
-  struct Drain { hipStream_t s; ~Drain() { (void)hipStreamSynchronize(s); } } drain{ctx->stream};   // (no launch left over the buffer)
-  uint64_t total = 0;
-  for (size_t i = 0; i < K; ++i) {
-    size_t n = 0;
-    uint64_t first = 0;
-    ibu_stream_stats_t st{};
-    if (!rc) {
-      RunOnNode on_node(feed_place(ctx));                  // (the load's host threads on the device's node, option "numa")
-      BgzfLoad L{ctx, cfg, file, &st, &h, &ctx->d_bgzf_range, 0, i, K, std::max(last.num, (size_t)1), K > 1 ? &idx : nullptr};
-      if (K == 1) L.walk_beside();
-      rc = L.run(&n, &first);
-    }
-    if (i == 0 && (rc || memcmp(&h, &want, sizeof h) != 0)) {   // not for this path: as if it had not been tried
-      tls_error() = keep;
-      return IBU_OK;
-    }
-    if (i == 0) {
-      *handled = true;
-      const hipError_t e = proc == IBU_PROC_REDUCE ? hipMemsetAsync(ctx->d_acc, 0, kReduceAccBytes, ctx->stream) : hipSuccess;
-      if (e != hipSuccess) return hip_fail(e, "hipMemsetAsync");
-    }
-    if (rc) return rc;
-    if (stats) { stats->bytes_h2d += st.bytes_h2d; stats->batches += st.batches; stats->numa_node = st.numa_node; stats->ring_node = st.ring_node; }
-    if ((rc = dp.fits(n, (size_t)first)) || (n && (rc = dp.launch(static_cast<const uint8_t*>(ctx->d_bgzf_range), n, (size_t)first)))) return rc;
-    total += n;
-    hipError_t e = hipStreamSynchronize(ctx->stream);      // (the next range is loaded over these records)
-    if (e != hipSuccess) return hip_fail(e, "hipStreamSynchronize");
-  }
-  if (proc == IBU_PROC_REDUCE && (rc = ibu_reduce_fetch(ctx, ctx->stream, static_cast<ibu_reduce_result_t*>(sink)))) return rc;
-  *records = total;
-  if (stats) stats->records = total;
-  return IBU_OK;
-}
-}  // namespace
-
+// on 16 CPUs) — the path stream's device form reads the Reader's own file (a descriptor of its own, through /proc/self/fd: the Reader's
+// position never moves, and a name renamed or replaced since does not matter) with the Reader as its host path from record 0.  A file
+// that form does not take, or a descriptor that will not open, goes through the Reader's own path, error and all.
 extern "C" int32_t ibu_reader_process_device(ibu_reader_t* rd, ibu_ctx_t* ctx, const ibu_ring_config_t* cfg,
                                              int32_t proc, void* sink, ibu_stream_stats_t* stats) {
   if (!rd || !ctx) return err_arg("NULL argument");
@@ -1487,21 +1455,20 @@ extern "C" int32_t ibu_reader_process_device(ibu_reader_t* rd, ibu_ctx_t* ctx, c
   DeviceProc dp;
   int32_t rc = make_proc(ctx, proc, h, sink, &dp);   // argument errors before the producer thread exists
   if (rc) return rc;
-  if (const char* bp = ctx->bgzf_device ? reader_bgzf_path_if_untouched(rd) : nullptr) {
-    bool handled = false;
-    uint64_t records = 0;
-    IBU_HIP(hipSetDevice(ctx->device));
-    rc = process_bgzf_file(ctx, bp, cfg, h, dp, proc, sink, stats, &records, &handled);
-    if (handled) {
-      if (rc == IBU_OK) {
-        reader_set_drained(rd, records);
-        if (stats) stats->seconds_total = now_s() - t0;
-      }
-      return rc;
-    }
-    if (stats) memset(stats, 0, sizeof *stats);
-  }
   ibu_stream_t* s = nullptr;
-  rc = ibu_stream_open_reader(rd, ctx, cfg, &s);
-  return process_stream(s, rc, proc, sink, stats, t0);
+  const int bgzf_fd = ctx->bgzf_device ? reader_bgzf_fd_if_untouched(rd) : -1;
+  if (bgzf_fd < 0) {
+    rc = ibu_stream_open_reader(rd, ctx, cfg, &s);
+    return process_stream(s, rc, proc, sink, stats, t0);
+  }
+  IBU_HIP(hipSetDevice(ctx->device));
+  if ((rc = ring_ensure(ctx, cfg, false))) return rc;
+  char name[40];
+  snprintf(name, sizeof name, "/proc/self/fd/%d", bgzf_fd);
+  rc = open_path_stream(::open(name, O_RDONLY | O_CLOEXEC), rd, ctx, cfg, &s);
+  const bool device = rc == IBU_OK && s->ranges;
+  uint64_t records = 0;
+  rc = process_stream(s, rc, proc, sink, stats, t0, &records);
+  if (rc == IBU_OK && device) reader_set_drained(rd, records);   // (the host path may have been a Reader of its own from a later range on)
+  return rc;
 }

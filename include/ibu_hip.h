@@ -301,14 +301,17 @@ int32_t ibu_device_count(int32_t* n);
  *   "inflate_one_launch" 0..49152  a test knob: ibu_load_bgzf_*_to_device launches its decoder AHEAD of the copies (the waves wait for
  *                           their blocks to arrive) for files of more blocks than this; 0 (default) = one round of the decoder's short
  *                           form, 49 152 blocks: smaller files get one launch behind the last copy.
- *   "bgzf_device"    0 | 1  1 (default): ibu_reader_process_device on an untouched BGZF file inflates on the device (see there).
- *   "bgzf_range_bytes"  >= 0  a test knob: the compressed bytes per range of that path and of ibu_stream_open_path (0 = default: 3.2 GB).
+ *   "bgzf_device"    0 | 1  1 (default): ibu_stream_open_path and ibu_reader_process_device on an untouched BGZF file inflate on the
+ *                           device (see there); 0: through the Reader's host inflate.
+ *   "bgzf_range_bytes"  >= 0  a test knob: about the compressed bytes per range of that device form (0 = default: 3.2 GB); the ranges
+ *                           are whole refills, as ibu_stream_open_path says.
  *   "bgzf_stream_ahead" 0 | 1  the decoder's launch form for the ranges after the first of ibu_stream_open_path: 1 (default) ahead of
  *                           the copies (the waves wait for their bytes), 0 behind the range's last copy.
  *   "load_piece_delay_ms" 0..10000  a test knob: the BGZF loads sleep that long before every piece they copy (a slow source: the waves
  *                           of a launch that runs ahead give up after ~4 s, and what they left is inflated once everything has arrived).
- *   "release_staging"    1  one-shot: frees the device staging ibu_load_bgzf_to_device / _shard_ keep between calls (the size of the
- *                           compressed bytes of the largest load so far); the next load allocates it again.
+ *   "release_staging"    1  one-shot: frees the device staging the BGZF loads keep between calls (the size of the compressed bytes
+ *                           of the largest load so far) and the two range buffers of ibu_stream_open_path's device form; the next
+ *                           load allocates them again.  Refused while such a stream is open.
  *   "numa"           0 | 1  1 = auto (default): the context looks up the NUMA node its device hangs off (PCI bus id ->
  *                           /sys/bus/pci/devices/<bdf>/numa_node -> that node's cpulist) and keeps its host side there: the pinned
  *                           ring is allocated under a preferred-node policy, the threads that fill it (the stream producer and its
@@ -674,9 +677,10 @@ int32_t ibu_stream_open_mmap(const ibu_mmap_t* m, ibu_ctx_t* ctx, const ibu_ring
  *     only once every batch of it has been released AND the work queued on the release streams has run.  next() that would need a
  *     buffer whose batches the caller still holds returns IBU_ERR_INVALID_ARG at once (as with every slot held); after a release the
  *     same call succeeds.
- *   Device memory: the two range buffers (2 x range records x 24 B; the second is allocated only when a second range is loaded,
- *     both are freed at close) plus the context's inflate staging (the largest range's compressed bytes, descriptors and tables; the
- *     context keeps it, as after ibu_load_bgzf_to_device; option "release_staging" is refused while such a stream is open).
+ *   Device memory: the two range buffers (2 x range records x 24 B; the second is allocated only when a second range is loaded) plus
+ *     the inflate staging (the largest range's compressed bytes, descriptors and tables).  The context keeps all of them after close,
+ *     like the staging of ibu_load_bgzf_to_device, and they grow only: the next stream or call does not allocate them again.  Option
+ *     "release_staging" frees them; it is refused while such a stream is open.
  *   Launch form: every range launches the decoder ahead of its copies (its waves wait for their bytes), as the load does, also while
  *     the caller's kernels run on the range before: measured against launching behind the last copy in launches of eight waves per CU
  *     (context option "bgzf_stream_ahead" = 0), it was as fast at 1e8 records and 3 % faster at 1e9.
@@ -685,7 +689,8 @@ int32_t ibu_stream_open_mmap(const ibu_mmap_t* m, ibu_ctx_t* ctx, const ibu_ring
  *   Errors: a block the device refuses in the first range sends the whole file through the host path below.  In a later range the
  *     host inflate takes over at the range's first record (a refill boundary): the stream ends with exactly the records and the
  *     error ibu_stream_open_reader gives on the same file.
- *   Stats: bytes_h2d = the compressed bytes sent plus the host-inflated header and edge bytes; batches / records = what was queued.
+ *   Stats: bytes_h2d = the compressed file bytes the loads copied over the link (a file of one range: the whole file, as
+ *     ibu_load_bgzf_to_device), plus the record bytes of the host path after a takeover; batches / records = what was queued.
  * Anything else (a plain file, one gzip member, zstd / xz / bz2, a BGZF file with a foreign member, a cut, a bad header, "bgzf_device"
  *   = 0): exactly ibu_stream_open_reader over ibu_reader_open_fd of the same descriptor — the same batches, errors and stats. */
 int32_t ibu_stream_open_path(const char* path, ibu_ctx_t* ctx, const ibu_ring_config_t* cfg, ibu_stream_t** out);
@@ -738,12 +743,15 @@ int32_t ibu_mmap_process_contexts(const ibu_mmap_t* m, ibu_ctx_t* const* ctxs, s
 
 /* Streaming Reader (plain or gzip; reader.rs:345-352 path) -> device processor: host inflate
  * thread -> pinned ring -> H2D || kernel.  Consumes the reader to EOF.
- * A reader opened by ibu_reader_open_path on a BGZF file from which nothing has been read yet: the library reads the file itself —
- * ranges of about 6 GB of records through ibu_load_bgzf_shard_to_device, the compressed bytes over the link, the blocks inflated on
- * the device — and runs the processor over every range (context option "bgzf_device" = 1, the default; 0: through the Reader's host
- * inflate): 1e8 records REDUCE / DECODE 1.3 G records/s instead of 0.4.  Same results; the reader stands at its end afterwards; stats:
- * bytes_h2d = the compressed bytes.  A file that load does not take (a foreign member, a cut, a length that is no whole number of
- * records, a block that does not inflate) goes through the Reader's own path and fails as it fails there. */
+ * A reader opened by ibu_reader_open_path on a BGZF file from which nothing has been read yet: the loop runs over the device form of
+ * ibu_stream_open_path on the reader's own file (a descriptor of its own on the file the reader has open, so a name renamed or
+ * replaced since does not matter and the reader's position never moves), with the reader as its host path — the compressed bytes
+ * over the link, the blocks inflated on the device, range k + 1 loaded while the processor runs on range k (context option
+ * "bgzf_device" = 1, the default; 0: through the Reader's host inflate): 1e8 records REDUCE / DECODE 1.3 G records/s instead of 0.4.
+ * Same results; the reader stands at its end afterwards; stats as for that stream (bytes_h2d = the compressed bytes: the file's size
+ * for a file of one range).  A file that form does not take (a foreign member, a cut, a length that is no whole number of records,
+ * another header, a block the device refuses in the first range) goes through the Reader's own path and fails as it fails there; a
+ * block refused in a later range ends the call with the records and the error of the Reader's path, as the stream does. */
 int32_t ibu_reader_process_device(ibu_reader_t* r, ibu_ctx_t* ctx, const ibu_ring_config_t* cfg,
                                   int32_t proc, void* sink, ibu_stream_stats_t* stats);
 

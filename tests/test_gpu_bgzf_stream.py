@@ -232,6 +232,44 @@ def test_fallbacks_match_the_reader_stream(ia, ctx, oracle, tmp_path, case, ring
         assert len(pgot) == 24 * 2 * REFILL                       # ranges 1 and 2 from the device, nothing of the refill the block spoils
     if stats_too:
         assert (pb, pst.records, pst.batches, pst.bytes_h2d) == (rb, rst.records, rst.batches, rst.bytes_h2d)
+    # Reader.process_device on the same file, on the device form and through the Reader's host inflate: the same result or error
+    reduce_, decode = {}, {}
+    for dev in (1, 0):
+        with _opts(ctx, **{**opts, "bgzf_device": dev}):
+            reduce_[dev] = _process(ia, ctx, p, ring, ia.PROC_REDUCE)
+            decode[dev] = _process(ia, ctx, p, ring, ia.PROC_DECODE, n)
+    for got in (reduce_, decode):
+        (r1, e1), (r0, e0) = got[1], got[0]
+        assert _same_error(e1, e0) and r1 == r0, (case, e1, e0)
+    if reduce_[0][1] is None:
+        assert reduce_[0][0] == oracle.reduce_records(recs)
+    if case == "bad_crc_range_3_of_4":                              # the rows of ranges 1 and 2, decoded on the device before the error
+        bc, umi, idx = oracle.decode_records(recs[:2 * REFILL], 16, 12)
+        for dev in (1, 0):
+            cols = decode[dev][0]
+            assert (cols[0][:len(bc.tobytes())], cols[1][:len(umi.tobytes())], cols[2][:len(idx.tobytes())]) == \
+                   (bc.tobytes(), umi.tobytes(), idx.tobytes()), dev
+
+
+def _process(ia, ctx, path, ring, proc, n=0):
+    """Reader.from_path(path).process_device: (the reduce result / the decoded columns of a sink of n rows, the error or None)."""
+    r = ia.Reader.from_path(path)
+    cols = [ctx.alloc(max(n, 1) * w) for w in (16, 12, 8)] if proc == ia.PROC_DECODE else None
+    if cols:
+        for c in cols:
+            c.upload(np.zeros(c.nbytes, np.uint8))
+    res, err = None, None
+    try:
+        res, _ = r.process_device(ctx, proc, sink=tuple(cols) if cols else None, ring=ring)
+    except ia.IbuError as e:
+        err = e
+    finally:
+        r.close()
+    if cols:
+        res = tuple(c.download().tobytes()[:n * w] for c, w in zip(cols, (16, 12, 8)))
+        for c in cols:
+            c.free()
+    return res, err
 
 
 def _ranged(ia, ctx, oracle, tmp_path, n, refills_per_range):

@@ -462,6 +462,19 @@ def test_inflate_fuzz(ia, ctx, seed):
             assert got[b.out_offset:b.out_offset + b.out_len] == data[b.out_offset:b.out_offset + b.out_len], (seed, i)
 
 
+def _path_stream_stats(ia, c, p, ring, staging_refused=False):
+    """The stats of a path stream pulled to its end (staging_refused: option "release_staging" is refused while it is open)."""
+    with ia.DeviceStream.from_path(p, c, ring=ring) as s:
+        if staging_refused:
+            with pytest.raises(ia.IbuError) as e:
+                c.set_option("release_staging", 1)
+            assert e.value.kind == "InvalidArg"
+        for b in s:
+            with b:
+                pass
+        return s.stats()
+
+
 def test_reader_process_device_of_a_bgzf_file_inflates_on_the_device(ia, oracle, tmp_path):
     """`Reader::from_path(bgzf).process(...)` with the records on the device: the library reads the file itself, the compressed bytes cross
     the link, the blocks inflate on the device (option "bgzf_device" = 1, the default) — same results as through the Reader's host inflate
@@ -486,6 +499,8 @@ def test_reader_process_device_of_a_bgzf_file_inflates_on_the_device(ia, oracle,
             assert (st.bytes_h2d == len(good)) == bool(dev), (dev, st.bytes_h2d, len(good))   # the compressed file / the records crossed the link
             assert not r.read_batch()                                 # the reader stands at its end
             r.close()
+            pst = _path_stream_stats(ia, c, p, ring)                  # the same stats as a path stream over the file
+            assert (pst.records, pst.bytes_h2d) == (st.records, st.bytes_h2d), dev
             r = ia.Reader.from_path(p)
             d_bc, d_umi, d_idx = c.alloc(n * 16), c.alloc(n * 12), c.alloc(n * 8)
             r.process_device(c, ia.PROC_DECODE, sink=(d_bc, d_umi, d_idx), ring=ring)
@@ -499,12 +514,14 @@ def test_reader_process_device_of_a_bgzf_file_inflates_on_the_device(ia, oracle,
             for b in (d_bc, d_umi, d_idx):
                 b.free()
         c.set_option("bgzf_device", 1)
-        for rng_bytes in (len(good) // 2 + 1, len(good) // 5, 40_000):   # the file in 2, 6 and ~90 ranges: rows land where they belong
+        for rng_bytes in (len(good) // 2 + 1, len(good) // 5, 40_000):   # the file in 3, 7 and 7 ranges (whole refills): rows land where they belong
             c.set_option("bgzf_range_bytes", rng_bytes)
             r = ia.Reader.from_path(p)
             res, st = r.process_device(c, ia.PROC_REDUCE, ring=ring)
             assert res == want and st.records == n and st.bytes_h2d <= len(good)
             r.close()
+            pst = _path_stream_stats(ia, c, p, ring, staging_refused=True)   # between two calls on the context: its range buffers
+            assert (pst.records, pst.bytes_h2d) == (st.records, st.bytes_h2d)
             r = ia.Reader.from_path(p)
             d_bc, d_umi, d_idx = c.alloc(n * 16), c.alloc(n * 12), c.alloc(n * 8)
             r.process_device(c, ia.PROC_DECODE, sink=(d_bc, d_umi, d_idx), ring=ring)
@@ -514,6 +531,17 @@ def test_reader_process_device_of_a_bgzf_file_inflates_on_the_device(ia, oracle,
                 b.free()
             c.set_option("release_staging", 1)                        # (the next round starts without the buffers of this one)
         c.set_option("bgzf_range_bytes", 0)
+        moved = tmp_path / "moved.ibu.gz"
+        other = _bgzf(plain[:32] + oracle.generate(SEED + 405, 0, 1000, 16, 12).tobytes(), level=1)
+        for replaced in (False, True):                                # the Reader's own file, whatever became of its name since
+            r = ia.Reader.from_path(p)
+            p.rename(moved)
+            if replaced:
+                p.write_bytes(other)
+            res, st = r.process_device(c, ia.PROC_REDUCE, ring=ring)
+            assert res == want and st.records == n and st.bytes_h2d == len(good), replaced   # read on the device
+            r.close()
+            moved.replace(p)
         r = ia.Reader.from_path(p)                                    # three records taken on the host first: the host path goes on from there
         head = [next(r) for _ in range(3)]
         res, st = r.process_device(c, ia.PROC_REDUCE, ring=ring)
