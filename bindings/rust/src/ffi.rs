@@ -35,6 +35,14 @@ pub struct ibu_reduce_result_t {
     pub xor: [u64; 3],
 }
 #[repr(C)]
+#[derive(Default, Debug, Clone, Copy, PartialEq, Eq)]
+pub struct ibu_correct_counts_t {
+    pub exact: u64,
+    pub corrected: u64,
+    pub ambiguous: u64,
+    pub unmatched: u64,
+}
+#[repr(C)]
 #[derive(Default, Clone, Copy)]
 pub struct ibu_ring_config_t {
     pub slots: u32,
@@ -128,6 +136,7 @@ pub enum ibu_reader_t {}
 pub enum ibu_mmap_t {}
 pub enum ibu_ctx_t {}
 pub enum ibu_stream_t {}
+pub enum ibu_whitelist_t {}
 pub type ibu_write_fn = unsafe extern "C" fn(*mut c_void, *const u8, usize) -> i32;
 pub type ibu_flush_fn = unsafe extern "C" fn(*mut c_void) -> i32;
 pub type ibu_read_fn = unsafe extern "C" fn(*mut c_void, *mut u8, usize, *mut usize) -> i32;
@@ -196,6 +205,14 @@ extern "C" {
     pub fn ibu_barcode_counts(ctx: *mut ibu_ctx_t, d_sorted_records: *const c_void, n: usize, d_barcodes: *mut u64,
                               d_counts: *mut u64, d_unique_umis: *mut u64, cap: usize, n_barcodes: *mut usize,
                               n_barcode_umi_pairs: *mut usize, stream: *mut c_void) -> i32;
+    pub fn ibu_whitelist_create(ctx: *mut ibu_ctx_t, d_codes: *const u64, w: usize, bc_len: u32, stream: *mut c_void,
+                                out: *mut *mut ibu_whitelist_t) -> i32;
+    pub fn ibu_whitelist_info(wl: *const ibu_whitelist_t, bc_len: *mut u32, n_distinct: *mut usize, device_bytes: *mut usize) -> i32;
+    pub fn ibu_whitelist_destroy(wl: *mut ibu_whitelist_t);
+    pub fn ibu_correct_barcodes(ctx: *mut ibu_ctx_t, wl: *const ibu_whitelist_t, d_records: *mut c_void, n: usize, max_mismatches: u32,
+                                d_class: *mut u8, counts: *mut ibu_correct_counts_t, stream: *mut c_void) -> i32;
+    pub fn ibu_select_records(ctx: *mut ibu_ctx_t, d_records: *const c_void, d_class: *const u8, n: usize, keep_mask: u32,
+                              d_out: *mut c_void, cap: usize, n_out: *mut usize, stream: *mut c_void) -> i32;
     pub fn ibu_bgzf_scan(buf: *const u8, len: usize, is_final: i32, blocks: *mut ibu_inflate_block_t, cap: usize, n_blocks: *mut usize,
                          consumed: *mut usize, out_bytes: *mut u64) -> i32;
     pub fn ibu_inflate_blocks_device(ctx: *mut ibu_ctx_t, d_comp: *const c_void, d_blocks: *const ibu_inflate_block_t, n: usize,

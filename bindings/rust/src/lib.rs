@@ -607,6 +607,24 @@ pub mod device {
             check(unsafe { ffi::ibu_ctx_synchronize(self.raw, std::ptr::null_mut()) })?;
             Ok((0..nb).map(|k| (host[k], host[nb + k], host[2 * nb + k])).collect())
         }
+        /// Barcode correction against a whitelist, in place over `n` device records (`ibu_correct_barcodes`): exact hits stay, a
+        /// barcode with exactly one whitelist entry one substitution away moves onto it.  `class` (optional): `n` bytes, one
+        /// class per record (0 exact, 1 corrected, 2 ambiguous, 3 unmatched).  Synchronises and returns the four totals.
+        pub fn correct_barcodes(&self, wl: &Whitelist, recs: &DeviceBuf, n: usize, max_mismatches: u32, class: Option<&DeviceBuf>)
+                                -> Result<ffi::ibu_correct_counts_t> {
+            let mut c = ffi::ibu_correct_counts_t::default();
+            let cls = class.map_or(std::ptr::null_mut(), |b| b.ptr as *mut u8);
+            check(unsafe { ffi::ibu_correct_barcodes(self.raw, wl.raw, recs.ptr, n, max_mismatches, cls, &mut c, std::ptr::null_mut()) })?;
+            Ok(c)
+        }
+        /// Stable compaction by class (`ibu_select_records`): the records whose class has its bit set in `keep_mask`, in input
+        /// order, into `out` (which must hold them: ask with `out = None` first).  Returns how many.
+        pub fn select_records(&self, recs: &DeviceBuf, class: &DeviceBuf, n: usize, keep_mask: u32, out: Option<&DeviceBuf>) -> Result<usize> {
+            let mut k = 0usize;
+            let (p, cap) = out.map_or((std::ptr::null_mut(), 0usize), |b| (b.ptr, b.bytes / 24));
+            check(unsafe { ffi::ibu_select_records(self.raw, recs.ptr, class.ptr as *const u8, n, keep_mask, p, cap, &mut k, std::ptr::null_mut()) })?;
+            Ok(k)
+        }
         /// Device analogue of `load_to_vec`.
         pub fn load_to_device<P: AsRef<Path>>(&self, path: P) -> Result<(Header, *mut c_void, usize)> {
             let c = CString::new(path.as_ref().to_string_lossy().as_bytes()).unwrap();
@@ -629,6 +647,30 @@ pub mod device {
                 ffi::ibu_load_bgzf_shard_to_device(self.raw, c.as_ptr(), std::ptr::null(), shard, n_shards, &mut h, &mut p, 0, &mut n, &mut first, std::ptr::null_mut())
             })?;
             Ok((h, p, n, first))
+        }
+    }
+    /// `ibu_whitelist_t`: the device lookup table of a barcode whitelist, built from `w` 2-bit codes in device memory.  Borrows
+    /// its context, so it cannot outlive it.
+    pub struct Whitelist<'c> {
+        pub(crate) raw: *mut ffi::ibu_whitelist_t,
+        _p: PhantomData<&'c Context>,
+    }
+    impl<'c> Whitelist<'c> {
+        pub fn new(ctx: &'c Context, codes: &DeviceBuf, w: usize, bc_len: u32) -> Result<Self> {
+            let mut raw = std::ptr::null_mut();
+            check(unsafe { ffi::ibu_whitelist_create(ctx.raw, codes.ptr as *const u64, w, bc_len, std::ptr::null_mut(), &mut raw) })?;
+            Ok(Self { raw, _p: PhantomData })
+        }
+        /// (bases per barcode, distinct codes, bytes of device memory the table takes)
+        pub fn info(&self) -> Result<(u32, usize, usize)> {
+            let (mut b, mut n, mut bytes) = (0u32, 0usize, 0usize);
+            check(unsafe { ffi::ibu_whitelist_info(self.raw, &mut b, &mut n, &mut bytes) })?;
+            Ok((b, n, bytes))
+        }
+    }
+    impl Drop for Whitelist<'_> {
+        fn drop(&mut self) {
+            unsafe { ffi::ibu_whitelist_destroy(self.raw) }
         }
     }
     /// `ibu_stream_t`: iterate to pull one device-resident batch at a time.  An `Err` item is the source's error

@@ -14,7 +14,7 @@ from collections import namedtuple
 import numpy as np
 
 from . import _lib
-from ._lib import CAllocProbe, CDecodeSink, CErrorDetail, CKeyPlan, CHeader, CNumaInfo, CProcessorVTable, CRecord, CReduceResult, CRingConfig, CStreamStats
+from ._lib import CAllocProbe, CCorrectCounts, CDecodeSink, CErrorDetail, CKeyPlan, CHeader, CNumaInfo, CProcessorVTable, CRecord, CReduceResult, CRingConfig, CStreamStats
 
 lib = _lib.load()
 
@@ -789,6 +789,7 @@ class Context:
         _check(lib.ibu_ctx_create(device, C.byref(c)))
         self._c = c
         self._buffers = weakref.WeakSet()   # live DeviceBuffers allocated through this context
+        self._whitelists = weakref.WeakSet()   # live Whitelists built on it
 
     @property
     def stream(self):
@@ -904,6 +905,29 @@ class Context:
         self.synchronize(stream)
         return (d_b.download(np.uint64), d_c.download(np.uint64), d_u.download(np.uint64) if d_u else None)
 
+    # barcode correction against a whitelist
+    def correct_barcodes(self, wl, d_records, n, max_mismatches=1, d_class=None, counts=True, stream=None):
+        """ibu_correct_barcodes, in place over n device records: exact whitelist hits stay, a barcode with exactly one
+        whitelist entry one substitution away moves onto it.  d_class (optional): n bytes, one class per record (0 exact,
+        1 corrected, 2 ambiguous, 3 unmatched).  counts=True synchronises and returns the four totals as a dict;
+        counts=False leaves the call asynchronous and returns None."""
+        c = CCorrectCounts() if counts else None
+        _check(lib.ibu_correct_barcodes(self._c, wl._c, _dptr(d_records), n, max_mismatches, _dptr(d_class),
+                                        C.byref(c) if counts else None, stream))
+        if not counts:
+            return None
+        return {"exact": c.exact, "corrected": c.corrected, "ambiguous": c.ambiguous, "unmatched": c.unmatched}
+
+    def select_records(self, d_records, d_class, n, keep_mask=0b0011, stream=None):
+        """ibu_select_records: the records whose class has its bit set in keep_mask (default: exact and corrected), in
+        input order -> (DeviceBuffer, n_out).  One call, so one count pass and one synchronisation: the buffer has room for
+        all n records (what a whitelist step usually keeps nearly all of); the first n_out of them are valid once `stream` has
+        run (the scatter may still be queued on return)."""
+        k = C.c_size_t()
+        out = self.alloc(max(24 * n, 16))
+        _check(lib.ibu_select_records(self._c, _dptr(d_records), _dptr(d_class), n, keep_mask, _dptr(out), n, C.byref(k), stream))
+        return out, k.value
+
     def inflate_blocks(self, d_comp, blocks, d_out, stream=None):
         """ibu_inflate_blocks_device: the deflate blocks `blocks` (a ctypes array of ibu_inflate_block_t, or what bgzf_scan
         returned) of the compressed bytes at d_comp -> d_out.  Returns (status per block as numpy u32, first bad block or None);
@@ -1010,13 +1034,65 @@ class Context:
         if getattr(self, "_c", None):
             for b in list(getattr(self, "_buffers", ())):   # buffers that outlive the context would leak their HBM
                 b.free()
+            for w in list(getattr(self, "_whitelists", ())):   # a whitelist goes before its context
+                w.close()
             lib.ibu_ctx_destroy(self._c)
             self._c = None
 
     __del__ = close
 
 
-__all__ = ["Header", "Record", "HEADER_SIZE", "MAGIC", "RECORD_SIZE", "VERSION", "IbuError", "load_to_vec",
+class Whitelist:
+    """ibu_whitelist_t: the device lookup table of a barcode whitelist, built from `w` 2-bit codes in device memory
+    (what Context.pack_2bit writes).  Belongs to `ctx`; close it before the context."""
+
+    def __init__(self, ctx, d_codes, w, bc_len, stream=None):
+        h = C.c_void_p()
+        _check(lib.ibu_whitelist_create(getattr(ctx, "_c", None), _dptr(d_codes), w, bc_len, stream, C.byref(h)))
+        self._c, self.ctx = h, ctx
+        ctx._whitelists.add(self)   # a context that closes first destroys what was built on it (Context.close)
+        b, nd, db = C.c_uint32(), C.c_size_t(), C.c_size_t()
+        _check(lib.ibu_whitelist_info(self._c, C.byref(b), C.byref(nd), C.byref(db)))
+        self.bc_len, self.n_distinct, self.device_bytes = b.value, nd.value, db.value
+
+    @classmethod
+    def from_ascii(cls, ctx, barcodes):
+        """From barcodes as text: a list of equally long str / bytes, or a 2-D uint8 array (one row per barcode).
+        Uploads them and packs them on the device (Context.pack_2bit; a byte outside ACGTacgt raises InvalidBase)."""
+        if isinstance(barcodes, np.ndarray):
+            a = np.ascontiguousarray(barcodes, dtype=np.uint8)
+        else:
+            rows = [b.encode() if isinstance(b, str) else bytes(b) for b in barcodes]
+            if not rows or any(len(r) != len(rows[0]) for r in rows):
+                raise ValueError("a whitelist needs at least one barcode, all of one length")
+            a = np.frombuffer(b"".join(rows), dtype=np.uint8).reshape(len(rows), len(rows[0]))
+        if a.ndim != 2 or a.shape[0] == 0:
+            raise ValueError("barcodes must be a non-empty list or a 2-D uint8 array")
+        w, bc_len = a.shape
+        d_ascii, d_codes = ctx.upload(a), ctx.alloc(8 * w)
+        try:
+            ctx.pack_2bit(d_ascii, w, bc_len, d_codes)
+            ctx.codec_status()
+            return cls(ctx, d_codes, w, bc_len)
+        finally:
+            d_ascii.free()
+            d_codes.free()
+
+    def close(self):
+        if getattr(self, "_c", None):
+            lib.ibu_whitelist_destroy(self._c)
+            self._c = None
+
+    __del__ = close
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
+
+
+__all__ = ["Whitelist", "Header", "Record", "HEADER_SIZE", "MAGIC", "RECORD_SIZE", "VERSION", "IbuError", "load_to_vec",
            "MmapReader", "Reader", "Writer", "ParallelProcessor", "ProcessError", "shard_range", "Context",
            "DeviceBuffer", "DeviceStream", "DeviceBatch", "numa_of_pci", "records_array", "key_plan", "REC_DTYPE", "device_count", "PROC_REDUCE", "PROC_DECODE",
            "DEFAULT_BUFFER_SIZE", "BATCH_SIZE"]

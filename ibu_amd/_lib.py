@@ -30,6 +30,10 @@ class CReduceResult(C.Structure):  # ibu_reduce_result_t
     _fields_ = [("count", u64), ("sum", u64 * 3), ("xor_", u64 * 3)]
 
 
+class CCorrectCounts(C.Structure):  # ibu_correct_counts_t
+    _fields_ = [("exact", u64), ("corrected", u64), ("ambiguous", u64), ("unmatched", u64)]
+
+
 class CRingConfig(C.Structure):  # ibu_ring_config_t
     _fields_ = [("slots", u32), ("slot_records", u32), ("feeder_threads", u32), ("reserved", u32)]
 
@@ -142,6 +146,11 @@ SIGNATURES = {
     "ibu_mmap_decode_to_host": (i32, [vp, vp, vp, sz, sz, vp, vp, vp, vp]),
     "ibu_writer_write_ascii_batch": (i32, [vp, vp, vp, vp, vp, vp, u64, sz, u32, u32, vp]),
     "ibu_barcode_counts": (i32, [vp, vp, sz, vp, vp, vp, sz, P(sz), P(sz), vp]),
+    "ibu_whitelist_create": (i32, [vp, vp, sz, u32, vp, P(vp)]),
+    "ibu_whitelist_info": (i32, [vp, P(u32), P(sz), P(sz)]),
+    "ibu_whitelist_destroy": (None, [vp]),
+    "ibu_correct_barcodes": (i32, [vp, vp, vp, sz, u32, vp, P(CCorrectCounts), vp]),
+    "ibu_select_records": (i32, [vp, vp, vp, sz, u32, vp, sz, P(sz), vp]),
     "ibu_bgzf_scan": (i32, [vp, sz, i32, P(CInflateBlock), sz, P(sz), P(sz), P(C.c_uint64)]),
     "ibu_inflate_blocks_device": (i32, [vp, vp, vp, sz, vp, vp, vp, vp]),
     "ibu_device_alloc": (i32, [vp, sz, P(vp)]),

@@ -104,6 +104,7 @@ extern "C" void ibu_ctx_destroy(ibu_ctx_t* ctx) {
   if (ctx->d_status) (void)hipFree(ctx->d_status);
   if (ctx->d_acc) (void)hipFree(ctx->d_acc);
   if (ctx->d_flag) (void)hipFree(ctx->d_flag);
+  if (ctx->d_correct_acc) (void)hipFree(ctx->d_correct_acc);
   if (ctx->h_pinned) (void)hipHostFree(ctx->h_pinned);
   if (ctx->h_part) (void)hipHostFree(ctx->h_part);
   if (ctx->side_stream) (void)hipStreamDestroy(ctx->side_stream);
@@ -720,6 +721,136 @@ extern "C" int32_t ibu_barcode_counts(ibu_ctx_t* ctx, const void* d_sorted_recor
   }
   IBU_HIP(launch_runs_emit(ctx->cfg, d_sorted_records, n, ctx->d_sort_scratch, true, ctx->d_runs_scratch, runs, pairs, d_barcodes,
                            d_counts, d_unique_umis, st));
+  return IBU_OK;
+}
+// ---- barcode correction against a whitelist (k_whitelist.hip) --------------------------------------------------------
+struct ibu_whitelist {
+  ibu_ctx* ctx = nullptr;
+  void* d_mem = nullptr;       // the table's slots, then the build's four status words
+  size_t slots = 0, n_distinct = 0, device_bytes = 0;
+  uint32_t bc_len = 0;
+  bool has_ones = false;       // the all-ones key (a legal code at 32 bases only) is in the whitelist
+};
+extern "C" int32_t ibu_whitelist_create(ibu_ctx_t* ctx, const uint64_t* d_codes, size_t w, uint32_t bc_len, void* stream,
+                                        ibu_whitelist_t** out) {
+  if (!ctx) {   // without a context there is nothing to build on: say whether a device is missing altogether
+    int count = 0;
+    hipError_t e = hipGetDeviceCount(&count);
+    if (e != hipSuccess) return hip_fail(e, "hipGetDeviceCount");
+    if (count == 0) return set_error(IBU_ERR_NO_DEVICE, 0, 0, 0, "no HIP device: a whitelist lives on a device context");
+    return err_arg("ctx is NULL");
+  }
+  int32_t rc = check_ctx(ctx);
+  if (rc) return rc;
+  if (!out) return err_arg("out is NULL");
+  *out = nullptr;
+  if (w == 0) return err_arg("a whitelist needs at least one code");
+  if (bc_len == 0 || bc_len > 32) return err_arg("bc_len must be 1..32");
+  if (!d_codes || !aligned8(d_codes)) return err_arg("d_codes must be non-NULL and 8-byte aligned");
+  if (w > (1ull << 31)) return err_arg("a whitelist holds at most 2^31 codes");
+  hipStream_t st = pick_stream(ctx, stream);
+  ibu_whitelist* wl = new ibu_whitelist;
+  wl->ctx = ctx;
+  wl->bc_len = bc_len;
+  wl->slots = whitelist_slots(w);
+  wl->device_bytes = wl->slots * sizeof(uint64_t) + 4 * sizeof(uint64_t);
+  hipError_t e = ctx_malloc(ctx, &wl->d_mem, wl->device_bytes);
+  uint64_t* table = static_cast<uint64_t*>(wl->d_mem);
+  uint64_t* status = table ? table + wl->slots : nullptr;
+  if (e == hipSuccess) e = hipMemsetAsync(table, 0xFF, (wl->slots + 1) * sizeof(uint64_t), st);   // free slots, status[0] = no bad code
+  if (e == hipSuccess) e = hipMemsetAsync(status + 1, 0, 3 * sizeof(uint64_t), st);
+  if (e == hipSuccess) e = launch_whitelist_build(ctx->cfg, d_codes, w, bc_len, table, wl->slots, status, st);
+  if (e == hipSuccess) e = hipMemcpyAsync(ctx->h_pinned, status, 4 * sizeof(uint64_t), hipMemcpyDeviceToHost, st);
+  if (e == hipSuccess) e = hipStreamSynchronize(st);
+  if (e != hipSuccess) {
+    ibu_whitelist_destroy(wl);
+    return hip_fail(e, "ibu_whitelist_create");
+  }
+  const uint64_t first_bad = ctx->h_pinned[0];
+  wl->n_distinct = ctx->h_pinned[1];
+  wl->has_ones = ctx->h_pinned[2] != 0;
+  if (first_bad != ~0ull) {
+    ibu_whitelist_destroy(wl);
+    return set_error(IBU_ERR_INVALID_ARG, first_bad, bc_len, 0, "Invalid argument: whitelist code %llu has bits at or above 2*bc_len (bc_len %u)",
+                     (unsigned long long)first_bad, bc_len);
+  }
+  *out = wl;
+  return IBU_OK;
+}
+extern "C" int32_t ibu_whitelist_info(const ibu_whitelist_t* wl, uint32_t* bc_len, size_t* n_distinct, size_t* device_bytes) {
+  if (!wl) return err_arg("wl is NULL");
+  if (bc_len) *bc_len = wl->bc_len;
+  if (n_distinct) *n_distinct = wl->n_distinct;
+  if (device_bytes) *device_bytes = wl->device_bytes;
+  return IBU_OK;
+}
+extern "C" void ibu_whitelist_destroy(ibu_whitelist_t* wl) {
+  if (!wl) return;
+  if (wl->d_mem) {
+    (void)hipSetDevice(wl->ctx->device);
+    (void)hipFree(wl->d_mem);   // (waits for launches that still probe the table)
+  }
+  delete wl;
+}
+extern "C" int32_t ibu_correct_barcodes(ibu_ctx_t* ctx, const ibu_whitelist_t* wl, void* d_records, size_t n, uint32_t max_mismatches,
+                                        uint8_t* d_class, ibu_correct_counts_t* counts, void* stream) {
+  int32_t rc = check_ctx(ctx);
+  if (rc) return rc;
+  if (!wl) return err_arg("wl is NULL");
+  if (wl->ctx != ctx) return err_arg("the whitelist was created on another context");
+  if (max_mismatches > 1) return err_arg("max_mismatches must be 0 or 1");
+  if (counts) *counts = ibu_correct_counts_t{0, 0, 0, 0};
+  if (n == 0) return IBU_OK;
+  if (!d_records || !aligned8(d_records)) return err_arg("d_records must be non-NULL and 8-byte aligned");
+  if (n >= (1ull << 40)) return err_arg("correct_barcodes handles fewer than 2^40 records per call");
+  hipStream_t st = pick_stream(ctx, stream);
+  const WhitelistTable t{static_cast<const uint64_t*>(wl->d_mem), wl->slots, wl->bc_len, wl->has_ones};
+  if (!counts) {   // nothing to bring back: the launch stays asynchronous and touches no per-call state
+    IBU_HIP(launch_correct(ctx->cfg, t, d_records, n, max_mismatches, d_class, nullptr, st));
+    return IBU_OK;
+  }
+  if (!ctx->d_correct_acc) IBU_HIP(ctx_malloc(ctx, reinterpret_cast<void**>(&ctx->d_correct_acc), kCorrectAccBytes));
+  IBU_HIP(hipMemsetAsync(ctx->d_correct_acc, 0, kCorrectAccBytes, st));
+  IBU_HIP(launch_correct(ctx->cfg, t, d_records, n, max_mismatches, d_class, ctx->d_correct_acc, st));
+  IBU_HIP(launch_correct_fold(ctx->d_correct_acc, st));
+  IBU_HIP(hipMemcpyAsync(ctx->h_pinned, ctx->d_correct_acc, 4 * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
+  IBU_HIP(hipStreamSynchronize(st));
+  counts->exact = ctx->h_pinned[0];
+  counts->corrected = ctx->h_pinned[1];
+  counts->ambiguous = ctx->h_pinned[2];
+  counts->unmatched = ctx->h_pinned[3];
+  return IBU_OK;
+}
+extern "C" int32_t ibu_select_records(ibu_ctx_t* ctx, const void* d_records, const uint8_t* d_class, size_t n, uint32_t keep_mask,
+                                      void* d_out, size_t cap, size_t* n_out, void* stream) {
+  int32_t rc = check_ctx(ctx);
+  if (rc) return rc;
+  if (!n_out) return err_arg("n_out is NULL");
+  *n_out = 0;
+  if (n == 0) return IBU_OK;
+  if (!d_records || !aligned8(d_records)) return err_arg("d_records must be non-NULL and 8-byte aligned");
+  if (!d_class) return err_arg("d_class is NULL");
+  if (n >= (1ull << 40)) return err_arg("select_records handles fewer than 2^40 records per call");
+  const bool size_query = !d_out && cap == 0;
+  if (!size_query) {
+    if (!d_out || !aligned8(d_out)) return err_arg("d_out must be non-NULL and 8-byte aligned");
+    const uintptr_t a = reinterpret_cast<uintptr_t>(d_out), b = reinterpret_cast<uintptr_t>(d_records);
+    const size_t cap_in = cap < n ? cap : n;   // no more than n records are ever written
+    if (a < b + 24 * n && b < a + 24 * cap_in) return err_arg("d_out overlaps d_records");
+  }
+  hipStream_t st = pick_stream(ctx, stream);
+  rc = ensure_sort_scratch(ctx, select_scratch_bytes(n));
+  if (rc) return rc;
+  IBU_HIP(launch_select_count(ctx->cfg, d_class, n, keep_mask & 0xFFu, ctx->d_sort_scratch, ctx->sort_scratch_bytes, st));
+  IBU_HIP(hipMemcpyAsync(ctx->h_pinned, ctx->d_sort_scratch, sizeof(uint64_t), hipMemcpyDeviceToHost, st));
+  IBU_HIP(hipStreamSynchronize(st));
+  const uint64_t kept = ctx->h_pinned[0];
+  *n_out = kept;
+  if (size_query) return IBU_OK;
+  if (kept > cap)
+    return set_error(IBU_ERR_INVALID_ARG, kept, cap, 0, "Invalid argument: output capacity %llu is smaller than the %llu records kept (see *n_out)",
+                     (unsigned long long)cap, (unsigned long long)kept);
+  IBU_HIP(launch_select_scatter(ctx->cfg, d_records, d_class, n, keep_mask & 0xFFu, ctx->d_sort_scratch, d_out, st));
   return IBU_OK;
 }
 extern "C" int32_t ibu_sort_records(ibu_ctx_t* ctx, void* d_records, void* d_tmp, size_t n, void* stream) {

@@ -1,0 +1,410 @@
+// k_whitelist.hip — barcode correction against a whitelist: table build, correct, select (include/ibu_hip.h:
+// ibu_whitelist_create, ibu_correct_barcodes, ibu_select_records).  Design notes: kcommon.hpp, DESIGN.md "Whitelist".
+//
+// The table: open addressing with linear probing over 64-bit keys, a power of two of slots, at most half of them
+// taken, so a successful search looks at 1.5 slots on average and an unsuccessful one at 2.5 (linear probing at load
+// 1/2: (1 + 1/(1-a))/2 and (1 + 1/(1-a)^2)/2); a slot's 128-byte line usually holds the whole probe sequence.  kEmpty
+// (all ones) marks a free slot.  With 32 bases every 64-bit value is a legal code, all ones
+// included: that one key never enters the table, the build reports it in a status word and every lookup gets it as a
+// kernel argument (`has_ones`).  With fewer bases all ones has bits above 2*bc_len and is refused as a code anyway.
+// Read-only after the build: any number of correct launches, on any streams, may probe it at once.
+#include "kcommon.hpp"
+#include "kernels.h"
+
+namespace ibu {
+
+static constexpr u64 kEmpty = ~0ull;
+
+__device__ __forceinline__ u32 wl_slot(u64 key, u32 shift) {   // Fibonacci hashing: the top log2(slots) bits of key * phi
+  return (u32)((key * 0x9E3779B97F4A7C15ull) >> shift);
+}
+__device__ __forceinline__ bool wl_lookup(const u64* __restrict__ table, u32 mask, u32 shift, u32 has_ones, u64 key) {
+  if (key == kEmpty) return has_ones != 0;
+  u32 s = wl_slot(key, shift) & mask;
+  for (;;) {
+    const u64 k = table[s];
+    if (k == key) return true;
+    if (k == kEmpty) return false;       // at most half the slots are taken: every probe sequence meets a free one
+    s = (s + 1) & mask;
+  }
+}
+
+// =============================================================================================
+// build: one thread per code.  status[0] = lowest position of a code with bits at or above 2*bc_len (the caller sets
+// it to all ones), status[1] = distinct codes, status[2] = 1 when the all-ones key is among them.
+// =============================================================================================
+extern "C" __global__ void __launch_bounds__(kBlock)
+ibu_k_whitelist_build(const u64* __restrict__ codes, u64 w, u64 high /*~mask2(bc_len)*/, u64* __restrict__ table, u32 mask, u32 shift,
+                      u64* __restrict__ status) {
+  const u64 stride = (u64)gridDim.x * kBlock;
+  u64 first_bad = kEmpty;
+  u32 fresh = 0;
+  for (u64 i = (u64)blockIdx.x * kBlock + threadIdx.x; i < w; i += stride) {
+    const u64 key = codes[i];
+    if (key & high) { first_bad = i < first_bad ? i : first_bad; continue; }
+    if (key == kEmpty) {
+      if (atomicCAS(&status[2], 0ull, 1ull) == 0ull) ++fresh;
+      continue;
+    }
+    u32 s = wl_slot(key, shift) & mask;
+    for (;;) {
+      const u64 old = atomicCAS(&table[s], kEmpty, key);
+      if (old == kEmpty) { ++fresh; break; }
+      if (old == key) break;             // a duplicate counts once
+      s = (s + 1) & mask;
+    }
+  }
+#pragma unroll
+  for (int m = 32; m >= 1; m >>= 1) {
+    const u32 lo = __shfl_xor((u32)first_bad, m), hi = __shfl_xor((u32)(first_bad >> 32), m);
+    const u64 o = ((u64)hi << 32) | lo;
+    first_bad = o < first_bad ? o : first_bad;
+    fresh += __shfl_xor(fresh, m);
+  }
+  if ((threadIdx.x & (kWave - 1)) == 0) {
+    if (first_bad != kEmpty) atomicMin(&status[0], first_bad);
+    if (fresh) atomicAdd(&status[1], (u64)fresh);
+  }
+}
+
+// =============================================================================================
+// correct.  Classes: 0 exact, 1 corrected, 2 ambiguous, 3 unmatched (ibu_hip.h).
+// =============================================================================================
+struct WlArgs {
+  const u64* table;
+  u32 mask, shift, has_ones, bc_len;
+  u32 search;      // max_mismatches
+};
+
+// Neighbour j of `low` (j in [0, 3*bc_len)): base j / 3 substituted by one of the three other bases.
+__device__ __forceinline__ u64 wl_neighbour(u64 low, u32 j) {
+  const u32 i = (j * 0xAAABu) >> 17;     // j / 3 for j < 2^15
+  return low ^ ((u64)(j - 3 * i + 1) << (2 * i));
+}
+
+// One lane, one record: all 3*bc_len neighbours in turn (the tail kernel).
+__device__ __forceinline__ u32 wl_search_lane(const WlArgs& a, u64 low, u64* fix) {
+  u32 hits = 0;
+  u64 cand = 0;
+  for (u32 j = 0; j < 3 * a.bc_len; ++j) {
+    const u64 nb = wl_neighbour(low, j);
+    if (wl_lookup(a.table, a.mask, a.shift, a.has_ones, nb)) { if (hits++ == 0) cand = nb; }
+  }
+  *fix = cand;
+  return hits == 1 ? 1u : hits ? 2u : 3u;
+}
+
+// The wave takes the barcodes of its missing lanes one after the other: lane L tests neighbours L and L + 64 (3*bc_len
+// is at most 96), the ballots give the number of whitelisted neighbours and, where it is one, which.  A miss costs the
+// wave two probe rounds instead of a lane 96 of them with the other 63 lanes waiting.  `miss` is the lane's own flag;
+// returns the lane's class (3 where it did not miss is never read) and its corrected barcode.
+__device__ __forceinline__ u32 wl_search_wave(const WlArgs& a, bool miss, u64 low, u64* fix, u32 lane) {
+  u64 todo = __ballot(miss);
+  u32 cls = 3;
+  u64 cand = 0;
+  const u32 nn = 3 * a.bc_len;
+  while (todo) {                                   // wave-uniform
+    const u32 src = (u32)__builtin_ctzll(todo);
+    todo &= todo - 1;
+    const u64 bc = ((u64)(u32)__builtin_amdgcn_readlane((u32)(low >> 32), src) << 32) | (u64)(u32)__builtin_amdgcn_readlane((u32)low, src);
+    const bool h0 = lane < nn && wl_lookup(a.table, a.mask, a.shift, a.has_ones, wl_neighbour(bc, lane));
+    const u64 b0 = __ballot(h0);
+    u64 b1 = 0;
+    if (nn > 64) {                                 // wave-uniform
+      const bool h1 = lane + 64 < nn && wl_lookup(a.table, a.mask, a.shift, a.has_ones, wl_neighbour(bc, lane + 64));
+      b1 = __ballot(h1);
+    }
+    const u32 hits = (u32)__builtin_popcountll(b0) + (u32)__builtin_popcountll(b1);
+    const u32 j = b0 ? (u32)__builtin_ctzll(b0) : 64u + (u32)__builtin_ctzll(b1 | (1ull << 63));
+    if (lane == src) {
+      cls = hits == 1 ? 1u : hits ? 2u : 3u;
+      cand = wl_neighbour(bc, j);
+    }
+  }
+  *fix = cand;
+  return cls;
+}
+
+// Totals of a workgroup: lane counters -> wave (shuffles) -> workgroup (LDS) -> one atomic per class and workgroup
+// into slot blockIdx % kReduceSlots of `acc` (kReduceSlots x 4 u64, folded by ibu_k_correct_fold).
+__device__ __forceinline__ void wl_flush_totals(u32 cnt[4], u64* acc, u32 (*part)[4]) {
+  const u32 lane = threadIdx.x & (kWave - 1), wib = threadIdx.x >> 6;
+#pragma unroll
+  for (int m = 32; m >= 1; m >>= 1)
+#pragma unroll
+    for (int c = 0; c < 4; ++c) cnt[c] += __shfl_xor(cnt[c], m);
+  if (lane == 0)
+#pragma unroll
+    for (int c = 0; c < 4; ++c) part[wib][c] = cnt[c];
+  __syncthreads();
+  if (threadIdx.x < 4) {
+    u64 v = 0;
+    for (u32 k = 0; k < blockDim.x / kWave; ++k) v += part[k][threadIdx.x];
+    if (v) atomicAdd(&acc[4 * (blockIdx.x & (kReduceSlots - 1)) + threadIdx.x], v);
+  }
+}
+
+struct CorRegs { u32x4 v[3]; };
+
+// Tiled: the records arrive as three coalesced 16-byte loads per lane (next tile in flight), are re-tiled through the
+// wave's LDS slice, lane L owns records 2L and 2L+1.  Nothing of a record is stored but the 8 barcode bytes of a
+// corrected one; the class bytes of a tile leave as one 128-byte row.  Misses: the wave-cooperative neighbour search (the form
+// in which every lane searched its own record measured 2-4.7x slower: profiles/README.md r06_a).
+extern "C" __global__ void __launch_bounds__(kBlock, 8)
+ibu_k_correct(uint8_t* __restrict__ recs, u32 ntiles, const WlArgs a, uint8_t* __restrict__ cls_out, u64* __restrict__ acc) {
+  __shared__ __attribute__((aligned(16))) uint8_t lds[kWavesPerBlock * kTileBytes];
+  __shared__ u32 part[kWavesPerBlock][4];
+  const u32 lane = threadIdx.x & (kWave - 1), wib = threadIdx.x >> 6;
+  uint8_t* tile = lds + wib * kTileBytes;
+  const u64 m = mask2(a.bc_len);
+  const bool cls16 = (reinterpret_cast<uintptr_t>(cls_out) & 1u) == 0;   // wave-uniform: two class bytes as one 16-bit store
+  u32 cnt[4] = {0, 0, 0, 0};
+  sweep_tiles<CorRegs>(
+      tile_range(ntiles, wib),
+      [&](CorRegs& g, u32 t) {
+        const uint8_t* src = recs + (size_t)t * kTileBytes + 16 * lane;
+#pragma unroll
+        for (int k = 0; k < 3; ++k) g.v[k] = ld16(src + 1024 * k);
+      },
+      [&](const CorRegs& g, u32 t) {
+        wave_lds_fence();
+#pragma unroll
+        for (int k = 0; k < 3; ++k) *reinterpret_cast<u32x4*>(tile + 1024 * k + 16 * lane) = g.v[k];
+        wave_lds_fence();
+        u64 bc[2], fix[2];
+        u32 c[2];
+#pragma unroll
+        for (int h = 0; h < 2; ++h) {
+          bc[h] = *reinterpret_cast<const u64*>(tile + (2 * lane + h) * 24);
+          c[h] = wl_lookup(a.table, a.mask, a.shift, a.has_ones, bc[h] & m) ? 0u : 3u;
+          fix[h] = 0;
+        }
+        if (a.search) {                              // wave-uniform
+#pragma unroll
+          for (int h = 0; h < 2; ++h) {
+            const u32 s = wl_search_wave(a, c[h] != 0, bc[h] & m, &fix[h], lane);
+            if (c[h] != 0) c[h] = s;
+          }
+        }
+        u64* r = reinterpret_cast<u64*>(recs + (size_t)t * kTileBytes) + 6 * lane;   // records 2L, 2L+1: words 6L and 6L+3
+#pragma unroll
+        for (int h = 0; h < 2; ++h) {
+          if (c[h] == 1) r[3 * h] = (bc[h] & ~m) | fix[h];
+          cnt[0] += c[h] == 0; cnt[1] += c[h] == 1; cnt[2] += c[h] == 2; cnt[3] += c[h] == 3;
+        }
+        if (cls_out) {                               // wave-uniform
+          uint8_t* q = cls_out + (size_t)t * kTileRecs + 2 * lane;
+          if (cls16) *reinterpret_cast<uint16_t*>(q) = (uint16_t)(c[0] | (c[1] << 8));
+          else { q[0] = (uint8_t)c[0]; q[1] = (uint8_t)c[1]; }
+        }
+      });
+  if (acc) wl_flush_totals(cnt, acc, part);          // uniform over the grid
+}
+
+// One thread per record: the rows peeled off the front of an 8- but not 16-byte aligned array and the n % 128 rest.
+extern "C" __global__ void __launch_bounds__(kBlock)
+ibu_k_correct_tail(u64* __restrict__ recs, u64 row0, u64 n, const WlArgs a, uint8_t* __restrict__ cls_out, u64* __restrict__ acc) {
+  __shared__ u32 part[kWavesPerBlock][4];
+  const u64 i = row0 + (u64)blockIdx.x * kBlock + threadIdx.x;
+  u32 cnt[4] = {0, 0, 0, 0};
+  if (i < n) {
+    const u64 m = mask2(a.bc_len), bc = recs[3 * i];
+    u32 c = wl_lookup(a.table, a.mask, a.shift, a.has_ones, bc & m) ? 0u : 3u;
+    if (c && a.search) {
+      u64 fix;
+      c = wl_search_lane(a, bc & m, &fix);
+      if (c == 1) recs[3 * i] = (bc & ~m) | fix;
+    }
+    if (cls_out) cls_out[i] = (uint8_t)c;
+    cnt[0] = c == 0; cnt[1] = c == 1; cnt[2] = c == 2; cnt[3] = c == 3;
+  }
+  if (acc) wl_flush_totals(cnt, acc, part);
+}
+
+// slots -> slot 0: one wave, lane = slot
+extern "C" __global__ void ibu_k_correct_fold(u64* acc) {
+  const u32 lane = threadIdx.x;
+  u64 v[4];
+#pragma unroll
+  for (int c = 0; c < 4; ++c) v[c] = acc[4 * lane + c];
+#pragma unroll
+  for (int m = 32; m >= 1; m >>= 1)
+#pragma unroll
+    for (int c = 0; c < 4; ++c) {
+      const u32 lo = __shfl_xor((u32)v[c], m), hi = __shfl_xor((u32)(v[c] >> 32), m);
+      v[c] += ((u64)hi << 32) | lo;
+    }
+  if (lane == 0)
+#pragma unroll
+    for (int c = 0; c < 4; ++c) acc[c] = v[c];
+}
+
+// =============================================================================================
+// select: stable compaction by class.  A UNIT is 2048 consecutive records and belongs to one wave, so nothing here
+// needs a workgroup barrier: count (kept records per unit) -> scan (exclusive, in place, total in front) -> scatter
+// (a unit's kept records, in input order, from its offset on).
+// =============================================================================================
+static constexpr u32 kSelUnit = 2048, kSelRounds = kSelUnit / kWave;
+
+__device__ __forceinline__ bool sel_keep(const uint8_t* __restrict__ cls, u64 i, u64 n, u32 keep_mask) {
+  const u32 c = i < n ? cls[i] : 255u;
+  return c < 8u && ((keep_mask >> c) & 1u);
+}
+
+// units[0] = total (after the scan); units[1 + u] = kept records of unit u, then their exclusive prefix sum
+extern "C" __global__ void __launch_bounds__(kBlock, 8)
+ibu_k_select_count(const uint8_t* __restrict__ cls, u64 n, u32 nunits, u32 keep_mask, u64* __restrict__ units) {
+  const u32 lane = threadIdx.x & (kWave - 1);
+  const u32 nwaves = gridDim.x * kWavesPerBlock;
+  for (u32 u = blockIdx.x * kWavesPerBlock + (threadIdx.x >> 6); u < nunits; u += nwaves) {
+    u32 k = 0;
+#pragma unroll 8
+    for (u32 r = 0; r < kSelRounds; ++r) k += sel_keep(cls, (u64)u * kSelUnit + r * kWave + lane, n, keep_mask);
+#pragma unroll
+    for (int m = 32; m >= 1; m >>= 1) k += __shfl_xor(k, m);
+    if (lane == 0) units[1 + u] = k;
+  }
+}
+
+// One workgroup of 1024 threads, 16 units per thread and iteration.
+static constexpr u32 kScanBlock = 1024, kScanPer = 16;
+extern "C" __global__ void __launch_bounds__(kScanBlock)
+ibu_k_select_scan(u64* __restrict__ units, u32 nunits) {
+  __shared__ u64 wsum[kScanBlock / kWave];
+  const u32 lane = threadIdx.x & (kWave - 1), wib = threadIdx.x >> 6;
+  u64 carry = 0;
+  for (u32 base = 0; base < nunits; base += kScanBlock * kScanPer) {   // uniform over the workgroup
+    const u32 first = base + threadIdx.x * kScanPer;
+    u64 sum = 0;
+    for (u32 k = 0; k < kScanPer; ++k)
+      if (first + k < nunits) sum += units[1 + first + k];
+    u64 inc = sum;
+#pragma unroll
+    for (int d = 1; d < kWave; d <<= 1) {
+      const u32 lo = __shfl_up((u32)inc, d), hi = __shfl_up((u32)(inc >> 32), d);
+      if (lane >= (u32)d) inc += ((u64)hi << 32) | lo;
+    }
+    if (lane == kWave - 1) wsum[wib] = inc;
+    __syncthreads();
+    u64 off = carry, tot = 0;
+    for (u32 k = 0; k < kScanBlock / kWave; ++k) {
+      const u64 s = wsum[k];
+      if (k < wib) off += s;
+      tot += s;
+    }
+    __syncthreads();
+    u64 run = off + inc - sum;
+    for (u32 k = 0; k < kScanPer; ++k)
+      if (first + k < nunits) {
+        const u64 v = units[1 + first + k];
+        units[1 + first + k] = run;
+        run += v;
+      }
+    carry += tot;
+  }
+  if (threadIdx.x == 0) units[0] = carry;
+}
+
+extern "C" __global__ void __launch_bounds__(kBlock, 8)
+ibu_k_select_scatter(const u64* __restrict__ recs, const uint8_t* __restrict__ cls, u64 n, u32 nunits, u32 keep_mask,
+                     const u64* __restrict__ units, u64* __restrict__ out) {
+  const u32 lane = threadIdx.x & (kWave - 1);
+  const u32 nwaves = gridDim.x * kWavesPerBlock;
+  const u64 below = lane ? (~0ull >> (64 - lane)) : 0ull;
+  for (u32 u = blockIdx.x * kWavesPerBlock + (threadIdx.x >> 6); u < nunits; u += nwaves) {
+    u64 pos = units[1 + u];
+#pragma unroll 4
+    for (u32 r = 0; r < kSelRounds; ++r) {
+      const u64 i = (u64)u * kSelUnit + r * kWave + lane;
+      const bool keep = sel_keep(cls, i, n, keep_mask);
+      const u64 b = __ballot(keep);
+      if (keep) {
+        const u64* s = recs + 3 * i;
+        u64* d = out + 3 * (pos + (u32)__builtin_popcountll(b & below));
+        const u64 x = __builtin_nontemporal_load(s), y = __builtin_nontemporal_load(s + 1), z = __builtin_nontemporal_load(s + 2);
+        __builtin_nontemporal_store(x, d); __builtin_nontemporal_store(y, d + 1); __builtin_nontemporal_store(z, d + 2);
+      }
+      pos += (u32)__builtin_popcountll(b);
+    }
+  }
+}
+
+// =============================================================================================
+// Launchers
+// =============================================================================================
+size_t whitelist_slots(size_t w) {   // a power of two, at least 2 w (load factor at most 1/2) and at least 1024
+  size_t s = 1024;
+  while (s < 2 * w) s <<= 1;
+  return s;
+}
+static inline u32 log2_of(size_t pow2) { u32 l = 0; while (((size_t)1 << l) < pow2) ++l; return l; }
+
+hipError_t launch_whitelist_build(const LaunchCfg& cfg, const uint64_t* codes, size_t w, uint32_t bc_len, uint64_t* table, size_t slots,
+                                  uint64_t* status, hipStream_t st) {
+  (void)hipGetLastError();
+  if (w == 0) return hipSuccess;
+  if (slots < 2 * w || (slots & (slots - 1)) || slots > (1ull << 32)) return hipErrorInvalidValue;
+  u64 blocks = (w + kBlock - 1) / kBlock;
+  static std::atomic<int> occ;
+  const u64 cap = (u64)cfg.cus * resident_blocks<kBlock>(cfg, ibu_k_whitelist_build, 0, &occ);
+  if (blocks > cap) blocks = cap;
+  const u64 high = bc_len >= 32 ? 0ull : ~((1ull << (2 * bc_len)) - 1);   // the bits no code may have
+  hipLaunchKernelGGL(ibu_k_whitelist_build, dim3((u32)blocks), dim3(kBlock), 0, st, (const u64*)codes, (u64)w, high,
+                     (u64*)table, (u32)(slots - 1), 64u - log2_of(slots), (u64*)status);
+  return hipGetLastError();
+}
+
+hipError_t launch_correct(const LaunchCfg& cfg, const WhitelistTable& wl, void* recs, size_t n, uint32_t max_mismatches, uint8_t* d_class,
+                          uint64_t* acc, hipStream_t st) {
+  (void)hipGetLastError();
+  if (n == 0) return hipSuccess;
+  if (n / kTileRecs > 0xFFFFFFFFull) return hipErrorInvalidValue;
+  WlArgs a;
+  a.table = (const u64*)wl.table; a.mask = (u32)(wl.slots - 1); a.shift = 64u - log2_of(wl.slots); a.has_ones = wl.has_ones ? 1u : 0u;
+  a.bc_len = wl.bc_len; a.search = max_mismatches;
+  const Span sp[1] = {{recs, 24}};
+  const RowSplit rs = split_rows(cfg, sp, 1, n, kTileRecs);   // an 8-B aligned base peels exactly one record
+  if (rs.head)
+    hipLaunchKernelGGL(ibu_k_correct_tail, dim3(tail_grid(rs.head)), dim3(kBlock), 0, st, (u64*)recs, (u64)0, (u64)rs.head, a, d_class, (u64*)acc);
+  if (rs.main) {
+    const u32 ntiles = (u32)(rs.main / kTileRecs);
+    static std::atomic<int> occ;
+    hipLaunchKernelGGL(ibu_k_correct, dim3(grid_for(ntiles, cfg.cus, resident_blocks<kBlock>(cfg, ibu_k_correct, 0, &occ))),
+                       dim3(kBlock), 0, st, adv((uint8_t*)recs, 24 * rs.head), ntiles, a, adv(d_class, rs.head), (u64*)acc);
+  }
+  if (rs.head + rs.main < n)
+    hipLaunchKernelGGL(ibu_k_correct_tail, dim3(tail_grid(n - rs.head - rs.main)), dim3(kBlock), 0, st, (u64*)recs, (u64)(rs.head + rs.main),
+                       (u64)n, a, d_class, (u64*)acc);
+  return hipGetLastError();
+}
+hipError_t launch_correct_fold(uint64_t* acc, hipStream_t st) {
+  (void)hipGetLastError();
+  hipLaunchKernelGGL(ibu_k_correct_fold, dim3(1), dim3(kReduceSlots), 0, st, (u64*)acc);
+  return hipGetLastError();
+}
+
+size_t select_scratch_bytes(size_t n) { return 8 * (1 + (n + kSelUnit - 1) / kSelUnit); }
+hipError_t launch_select_count(const LaunchCfg& cfg, const uint8_t* d_class, size_t n, uint32_t keep_mask, void* scratch, size_t scratch_bytes,
+                               hipStream_t st) {
+  (void)hipGetLastError();
+  if (n == 0) return hipSuccess;
+  const u64 nunits = (n + kSelUnit - 1) / kSelUnit;
+  if (nunits > 0xFFFFFFFFull || scratch_bytes < select_scratch_bytes(n)) return hipErrorInvalidValue;
+  static std::atomic<int> occ;
+  hipLaunchKernelGGL(ibu_k_select_count, dim3(grid_for((u32)nunits, cfg.cus, resident_blocks<kBlock>(cfg, ibu_k_select_count, 0, &occ))),
+                     dim3(kBlock), 0, st, d_class, (u64)n, (u32)nunits, keep_mask, (u64*)scratch);
+  hipLaunchKernelGGL(ibu_k_select_scan, dim3(1), dim3(kScanBlock), 0, st, (u64*)scratch, (u32)nunits);
+  return hipGetLastError();
+}
+hipError_t launch_select_scatter(const LaunchCfg& cfg, const void* recs, const uint8_t* d_class, size_t n, uint32_t keep_mask,
+                                 const void* scratch, void* out, hipStream_t st) {
+  (void)hipGetLastError();
+  if (n == 0) return hipSuccess;
+  const u64 nunits = (n + kSelUnit - 1) / kSelUnit;
+  static std::atomic<int> occ;
+  hipLaunchKernelGGL(ibu_k_select_scatter, dim3(grid_for((u32)nunits, cfg.cus, resident_blocks<kBlock>(cfg, ibu_k_select_scatter, 0, &occ))),
+                     dim3(kBlock), 0, st, (const u64*)recs, d_class, (u64)n, (u32)nunits, keep_mask, (const u64*)scratch, (u64*)out);
+  return hipGetLastError();
+}
+
+}  // namespace ibu

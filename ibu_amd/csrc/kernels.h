@@ -121,6 +121,25 @@ hipError_t launch_runs_count(const LaunchCfg&, const void* recs, size_t n, void*
 size_t runs_emit_scratch_bytes(uint64_t n_runs);
 hipError_t launch_runs_emit(const LaunchCfg&, const void* recs, size_t n, const void* scratch, bool from_stash, void* run_scratch, uint64_t n_runs,
                             uint64_t n_pairs, uint64_t* barcodes, uint64_t* counts, uint64_t* uniq, hipStream_t st);
+// barcode correction against a whitelist (k_whitelist.hip).  The table: `slots` 64-bit keys (a power of two, at least 2 w), all ones =
+// free; the all-ones key itself (a legal code at 32 bases) travels beside it as `has_ones`.
+struct WhitelistTable { const uint64_t* table; size_t slots; uint32_t bc_len; bool has_ones; };
+size_t whitelist_slots(size_t w);
+// status: u64[4]; the caller sets [0] to all ones and the rest to 0: [0] lowest position of a code with bits at or above 2*bc_len,
+// [1] distinct codes, [2] 1 = the all-ones key is among them.  `table` must be filled with 0xFF bytes.
+hipError_t launch_whitelist_build(const LaunchCfg&, const uint64_t* codes, size_t w, uint32_t bc_len, uint64_t* table, size_t slots,
+                                  uint64_t* status, hipStream_t st);
+// acc (nullable): kReduceSlots x 4 u64, zeroed by the caller; launch_correct_fold leaves the four totals in its first four words.
+static constexpr size_t kCorrectAccBytes = (size_t)kReduceSlots * 4 * sizeof(uint64_t);
+hipError_t launch_correct(const LaunchCfg&, const WhitelistTable& wl, void* recs, size_t n, uint32_t max_mismatches, uint8_t* d_class,
+                          uint64_t* acc, hipStream_t st);
+hipError_t launch_correct_fold(uint64_t* acc, hipStream_t st);
+// select: count + scan leave the number of kept records in scratch[0] (u64) and every unit's offset behind it; scatter writes them.
+size_t select_scratch_bytes(size_t n);
+hipError_t launch_select_count(const LaunchCfg&, const uint8_t* d_class, size_t n, uint32_t keep_mask, void* scratch, size_t scratch_bytes,
+                               hipStream_t st);
+hipError_t launch_select_scatter(const LaunchCfg&, const void* recs, const uint8_t* d_class, size_t n, uint32_t keep_mask,
+                                 const void* scratch, void* out, hipStream_t st);
 
 // DEFLATE blocks inflated on the device, one wave per block (k_inflate.hip).  The compressed bytes must be readable 2 KiB past the
 // last block (kInflatePad); block i's output goes to d_out_base + ooff (signed: a block that begins in front of the window a batch

@@ -360,6 +360,8 @@ class MmapReader {
 
 // ---- device path (no reference equivalent: the MI355X side of the boundary) --------------------------------
 namespace device {
+class Whitelist;
+using CorrectCounts = ibu_correct_counts_t;
 inline int device_count() { int32_t n = 0; return ibu_device_count(&n) == IBU_OK ? n : 0; }
 
 class Context {
@@ -424,6 +426,19 @@ class Context {
   void expand(const ibu_key_plan_t& plan, const void* d_elems, size_t n, void* d_recs, void* st = nullptr) { check(ibu_records_expand(c_, &plan, d_elems, n, d_recs, st)); }
   // BarcodeAnalyzer (parallel.rs:72-98) on sorted device records: (barcode, records, distinct UMIs), ascending barcode
   inline std::vector<std::tuple<uint64_t, uint64_t, uint64_t>> barcode_counts(const void* d_sorted, size_t n);
+  // barcode correction against a whitelist, in place (ibu_correct_barcodes): d_class (nullable) receives one class byte per record;
+  // returns the four totals (synchronises).  correct_barcodes_async: no totals, nothing synchronised.
+  inline CorrectCounts correct_barcodes(const Whitelist& wl, void* d_recs, size_t n, uint32_t max_mismatches = 1, uint8_t* d_class = nullptr,
+                                        void* st = nullptr);
+  inline void correct_barcodes_async(const Whitelist& wl, void* d_recs, size_t n, uint32_t max_mismatches = 1, uint8_t* d_class = nullptr,
+                                     void* st = nullptr);
+  // stable compaction by class (ibu_select_records) -> how many records went to d_out (capacity `cap` records); d_out == nullptr
+  // and cap == 0: only count
+  size_t select_records(const void* d_recs, const uint8_t* d_class, size_t n, uint32_t keep_mask, void* d_out, size_t cap, void* st = nullptr) {
+    size_t k = 0;
+    check(ibu_select_records(c_, d_recs, d_class, n, keep_mask, d_out, cap, &k, st));
+    return k;
+  }
   // load_to_vec, device form -> (header, device pointer owned by the caller: release with free(), n)
   std::tuple<Header, void*, size_t> load_to_device(const std::string& path, const RingConfig* ring = nullptr, StreamStats* stats = nullptr) {
     Header h; void* p = nullptr; size_t n = 0;
@@ -475,6 +490,34 @@ class DeviceBuffer {  // RAII hipMalloc through the context
   size_t bytes_;
   void* p_;
 };
+
+// The device lookup table of a barcode whitelist (ibu_whitelist_t), built from w 2-bit codes in device memory.  Destroy it before
+// its context.
+class Whitelist {
+ public:
+  Whitelist(Context& ctx, const uint64_t* d_codes, size_t w, uint32_t bc_len, void* st = nullptr) {
+    check(ibu_whitelist_create(ctx.raw(), d_codes, w, bc_len, st, &w_));
+  }
+  Whitelist(Whitelist&& o) noexcept : w_(o.w_) { o.w_ = nullptr; }
+  Whitelist(const Whitelist&) = delete;
+  Whitelist& operator=(const Whitelist&) = delete;
+  ~Whitelist() { if (w_) ibu_whitelist_destroy(w_); }
+  const ibu_whitelist_t* raw() const { return w_; }
+  uint32_t bc_len() const { uint32_t b = 0; check(ibu_whitelist_info(w_, &b, nullptr, nullptr)); return b; }
+  size_t n_distinct() const { size_t n = 0; check(ibu_whitelist_info(w_, nullptr, &n, nullptr)); return n; }
+  size_t device_bytes() const { size_t n = 0; check(ibu_whitelist_info(w_, nullptr, nullptr, &n)); return n; }
+
+ private:
+  ibu_whitelist_t* w_ = nullptr;
+};
+inline CorrectCounts Context::correct_barcodes(const Whitelist& wl, void* d_recs, size_t n, uint32_t max_mismatches, uint8_t* d_class, void* st) {
+  CorrectCounts c{};
+  check(ibu_correct_barcodes(c_, wl.raw(), d_recs, n, max_mismatches, d_class, &c, st));
+  return c;
+}
+inline void Context::correct_barcodes_async(const Whitelist& wl, void* d_recs, size_t n, uint32_t max_mismatches, uint8_t* d_class, void* st) {
+  check(ibu_correct_barcodes(c_, wl.raw(), d_recs, n, max_mismatches, d_class, nullptr, st));
+}
 
 inline std::vector<std::tuple<uint64_t, uint64_t, uint64_t>> Context::barcode_counts(const void* d_sorted, size_t n) {
   size_t nb = 0, np = 0;

@@ -491,6 +491,46 @@ int32_t ibu_sort_records_contexts(ibu_ctx_t* const* ctxs, size_t n_ctxs, ibu_sor
 int32_t ibu_barcode_counts(ibu_ctx_t* ctx, const void* d_sorted_records, size_t n, uint64_t* d_barcodes,
                            uint64_t* d_counts, uint64_t* d_unique_umis, size_t cap, size_t* n_barcodes,
                            size_t* n_barcode_umi_pairs, void* stream);
+/* Barcode correction against a whitelist, on the device (k_whitelist.hip) — the step between a load and ibu_sort_records /
+ * ibu_barcode_counts that makes the latter's "a caller that knows a bound (its whitelist)" true of real input.  The reference has
+ * no such function (as it has no sort and no aggregation); the semantics are this library's and are stated in full here.
+ * A whitelist is a set of w >= 1 codes, each a bc_len-base barcode in the 2-bit form the records hold (1 <= bc_len <= 32, every bit
+ * at or above 2*bc_len zero); duplicates count once.  For a record, low = barcode & mask(2*bc_len); the bits above are carried
+ * along untouched (the decoder ignores them).  A neighbour of low is low ^ (x << 2i), i in [0, bc_len), x in {1, 2, 3}: one base
+ * substituted — the same set under either base order, so the option "base_order" does not enter.  Every record gets one class:
+ *   0 exact      low is in the whitelist                                   the record is untouched
+ *   1 corrected  not exact, exactly one neighbour is in the whitelist      the low 2*bc_len bits of barcode become that neighbour
+ *   2 ambiguous  not exact, two or more neighbours are in the whitelist    untouched
+ *   3 unmatched  neither                                                   untouched
+ * With max_mismatches == 0 only classes 0 and 3 occur.  umi, index and the barcode bits above 2*bc_len are never written.
+ * The device table: open addressing over 64-bit keys, a power of two of slots (at least 1024, at least 2 w), 8 bytes each. */
+typedef struct ibu_whitelist ibu_whitelist_t;
+typedef struct ibu_correct_counts { uint64_t exact, corrected, ambiguous, unmatched; } ibu_correct_counts_t;
+/* Builds the device lookup table from w codes in DEVICE memory (what ibu_pack_2bit writes; 8-byte aligned).  Synchronous.
+ * IBU_ERR_INVALID_ARG: w == 0, w > 2^31, bc_len outside 1..32, a code with bits at or above 2*bc_len (detail.a = the lowest
+ * position of such a code).  A NULL ctx on a host without a device: IBU_ERR_NO_DEVICE.  The whitelist belongs to `ctx` (and its
+ * device); it is read-only once built and may serve any number of ibu_correct_barcodes calls, on different streams at once (see there for
+ * `counts`). */
+int32_t ibu_whitelist_create(ibu_ctx_t* ctx, const uint64_t* d_codes, size_t w, uint32_t bc_len, void* stream, ibu_whitelist_t** out);
+/* Any of the three outputs may be NULL.  n_distinct: the codes after duplicates are dropped; device_bytes: what the table takes. */
+int32_t ibu_whitelist_info(const ibu_whitelist_t* wl, uint32_t* bc_len, size_t* n_distinct, size_t* device_bytes);
+void ibu_whitelist_destroy(ibu_whitelist_t* wl); /* before its context is destroyed */
+/* In place over n device records (8-byte aligned).  d_class (nullable): n bytes, one class per record.  counts (nullable): this
+ * call's four totals; non-NULL synchronises `stream`, NULL leaves the call asynchronous.  max_mismatches: 0 or 1 (anything else
+ * IBU_ERR_INVALID_ARG).  A whitelist of another context: IBU_ERR_INVALID_ARG.  n < 2^40.  n == 0 is OK and touches nothing.
+ * Reads 24 B per record and a table line for its barcode; writes 1 B of class and, for corrected records only, 8 B.  Only records
+ * that miss look at their 3*bc_len neighbours (a wave searches its missing records one after the other, 64 neighbours at a time).
+ * The totals of a call with counts != NULL pass through the context (as every small read-back does): of the calls in flight on ONE
+ * context at the same time — other streams, other host threads — at most one may ask for counts; the others pass counts == NULL. */
+int32_t ibu_correct_barcodes(ibu_ctx_t* ctx, const ibu_whitelist_t* wl, void* d_records, size_t n, uint32_t max_mismatches,
+                             uint8_t* d_class, ibu_correct_counts_t* counts, void* stream);
+/* Stable compaction: the records whose class c has bit c of keep_mask set, in their input order, to d_out (8-byte aligned; must
+ * not overlap d_records).  *n_out = how many.  Size query: d_out == NULL and cap == 0.  cap too small: IBU_ERR_INVALID_ARG with
+ * *n_out set and nothing written (detail.a = records kept, detail.b = cap).  Class bytes above 7 are never kept.  Synchronises
+ * `stream` once (the count comes back before anything is written); the writes may still be queued on return.  n < 2^40.  Uses the
+ * context's sort scratch (8 bytes per 2048 records). */
+int32_t ibu_select_records(ibu_ctx_t* ctx, const void* d_records, const uint8_t* d_class, size_t n, uint32_t keep_mask,
+                           void* d_out, size_t cap, size_t* n_out, void* stream);
 /* BGZF / DEFLATE on the device (k_inflate.hip).  A bgzip file — to niffler (src/io/reader.rs:345-352) a gzip stream of many
  * members — is a chain of independent deflate blocks of at most 64 KiB whose compressed and uncompressed sizes stand in their
  * headers and trailers: the blocks can be found without inflating them, their COMPRESSED bytes can cross the PCIe link (half the

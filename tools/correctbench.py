@@ -1,0 +1,109 @@
+#!/usr/bin/env python3
+"""Barcode correction against a whitelist on device-resident records: ibu_correct_barcodes (with class bytes) timed against
+ibu_reduce — the library's plain 24-bytes-read-per-record kernel — in the same process, on the same array, interleaved; and
+ibu_select_records (classes 0 | 1) against ibu_device_copy of the bytes it keeps.  One JSON line per configuration.
+  python tools/correctbench.py [--records 1e9] [--whitelists 1e5,1e6,6.9e6] [--errors 0,0.02,0.1] [--random 0.01] [--rounds 5]
+Barcodes of 16 bases drawn uniformly from the whitelist; `errors` of them get one substituted base, `random` of them (1 % unless
+told otherwise; 0 leaves the hit path alone) are uniform random.
+Times are HIP events on the stream the calls run on (the select call synchronises once inside: its time includes that)."""
+import argparse
+import ctypes as C
+import json
+import os
+import statistics
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--records", default="1e9")
+    ap.add_argument("--whitelists", default="1e5,1e6,6.9e6")
+    ap.add_argument("--errors", default="0,0.02,0.1")
+    ap.add_argument("--rounds", type=int, default=5)
+    ap.add_argument("--random", type=float, default=0.01, help="share of uniform random barcodes (they always take the miss path)")
+    a = ap.parse_args()
+    import torch                                             # before the library, as bench.py does
+    torch.cuda.init()
+    import ibu_amd as ia
+
+    bc_len, umi_len = 16, 12
+    ctx = ia.Context(0)
+    side = torch.cuda.Stream()
+    st = side.cuda_stream
+    n = int(float(a.records))
+    asked = n
+    while True:                                              # fall back to half the records if memory is short, and say so
+        try:
+            d, orig, out, d_cls = ctx.alloc(24 * n), ctx.alloc(24 * n), ctx.alloc(24 * n), ctx.alloc(n)
+            cols = [ctx.alloc(8 * n) for _ in range(3)]
+            break
+        except ia.IbuError:
+            for b in list(ctx._buffers):
+                b.free()
+            n //= 2
+            if n < 1000:
+                raise
+    g = torch.Generator(device="cuda").manual_seed(0x1B00008)
+    ctx.generate(0x1B00005, 0, n, bc_len, umi_len, orig)
+    ctx.deserialize(orig, n, cols[0], cols[1], cols[2])
+    ctx.synchronize()
+    bc = torch.as_tensor(cols[0], device="cuda").view(torch.int64)
+
+    def timed(fn):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record(side)
+        fn()
+        e1.record(side)
+        e1.synchronize()
+        return e0.elapsed_time(e1)
+
+    def stat(v):
+        v = v[1:]                                            # the first round is the warm-up
+        return {"median_ms": round(statistics.median(v), 3), "min_ms": round(min(v), 3), "max_ms": round(max(v), 3)}
+
+    for w in (int(float(x)) for x in a.whitelists.split(",")):
+        codes = torch.unique(torch.randint(0, 1 << (2 * bc_len), (w + w // 64 + 1024,), generator=g, device="cuda", dtype=torch.int64))
+        codes = codes[torch.randperm(len(codes), generator=g, device="cuda")][:w].contiguous()
+        torch.cuda.synchronize()
+        wl = ia.Whitelist(ctx, codes, len(codes), bc_len)
+        for err in (float(x) for x in a.errors.split(",")):
+            for lo in range(0, n, 1 << 26):
+                hi = min(n, lo + (1 << 26))
+                k = hi - lo
+                b = codes[torch.randint(0, len(codes), (k,), generator=g, device="cuda", dtype=torch.int64)]
+                u = torch.rand(k, generator=g, device="cuda")
+                flip = torch.randint(1, 4, (k,), generator=g, device="cuda", dtype=torch.int64) << (2 * torch.randint(0, bc_len, (k,), generator=g, device="cuda", dtype=torch.int64))
+                b = torch.where(u < err, b ^ flip, b)
+                b = torch.where(u >= 1.0 - a.random, torch.randint(0, 1 << (2 * bc_len), (k,), generator=g, device="cuda", dtype=torch.int64), b)
+                bc[lo:hi] = b
+            del b, u, flip
+            torch.cuda.synchronize()
+            ctx.serialize(cols[0], cols[1], cols[2], n, orig)
+            ctx.synchronize()
+            t_red, t_cor, t_sel, t_cpy = [], [], [], []
+            counts = kept = None
+            k_out = C.c_size_t()
+            for _ in range(a.rounds + 1):
+                ctx.copy(d, orig, 24 * n, stream=st)
+                t_red.append(timed(lambda: ctx.reduce(d, n, stream=st, reset=False, fetch=False)))
+                t_cor.append(timed(lambda: ctx.correct_barcodes(wl, d, n, 1, d_cls, counts=False, stream=st)))
+                t_sel.append(timed(lambda: ia._check(ia.lib.ibu_select_records(ctx._c, d.ptr, d_cls.ptr, n, 0b0011, out.ptr, n, C.byref(k_out), st))))
+                kept = k_out.value
+                t_cpy.append(timed(lambda: ctx.copy(out, d, 24 * kept, stream=st)))
+            ctx.copy(d, orig, 24 * n, stream=st)
+            counts = ctx.correct_barcodes(wl, d, n, 1, d_cls, stream=st)
+            red, cor, sel, cpy = stat(t_red), stat(t_cor), stat(t_sel), stat(t_cpy)
+            print(json.dumps({"n": n, "records_asked": asked, "bc_len": bc_len, "w": len(codes), "table_MiB": round(wl.device_bytes / 2**20, 1),
+                              "errors": err, "random": a.random, "counts": counts, "kept": kept,
+                              "reduce": red, "correct": cor, "correct_over_reduce": round(cor["median_ms"] / red["median_ms"], 3),
+                              "correct_GBps_of_25B": round(25 * n / cor["median_ms"] / 1e6),
+                              "select": sel, "copy_of_kept": cpy, "select_over_copy": round(sel["median_ms"] / cpy["median_ms"], 3)}), flush=True)
+        wl.close()
+    ctx.close()
+
+
+if __name__ == "__main__":
+    main()
