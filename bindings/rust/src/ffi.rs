@@ -1,4 +1,4 @@
-//! Raw `extern "C"` declarations — one-to-one with include/ibu_hip.h (ABI revision 5).
+//! Raw `extern "C"` declarations — one-to-one with include/ibu_hip.h (ABI revision 6).
 #![allow(non_camel_case_types)]
 use std::os::raw::{c_char, c_int, c_void};
 
@@ -205,6 +205,13 @@ extern "C" {
     pub fn ibu_barcode_counts(ctx: *mut ibu_ctx_t, d_sorted_records: *const c_void, n: usize, d_barcodes: *mut u64,
                               d_counts: *mut u64, d_unique_umis: *mut u64, cap: usize, n_barcodes: *mut usize,
                               n_barcode_umi_pairs: *mut usize, stream: *mut c_void) -> i32;
+    pub fn ibu_records_swap_umi_index(ctx: *mut ibu_ctx_t, d_src: *const c_void, d_dst: *mut c_void, n: usize, stream: *mut c_void) -> i32;
+    pub fn ibu_pair_counts(ctx: *mut ibu_ctx_t, d_sorted_records: *const c_void, n: usize, d_first: *mut u64, d_second: *mut u64,
+                           d_records_per_pair: *mut u64, d_distinct_third: *mut u64, cap: usize, n_pairs: *mut usize,
+                           n_triples: *mut usize, stream: *mut c_void) -> i32;
+    pub fn ibu_count_matrix(ctx: *mut ibu_ctx_t, d_records: *mut c_void, d_tmp: *mut c_void, n: usize, flags: u32, d_barcodes: *mut u64,
+                            d_indices: *mut u64, d_reads: *mut u64, d_umis: *mut u64, cap: usize, n_entries: *mut usize,
+                            n_molecules: *mut usize, stream: *mut c_void) -> i32;
     pub fn ibu_whitelist_create(ctx: *mut ibu_ctx_t, d_codes: *const u64, w: usize, bc_len: u32, stream: *mut c_void,
                                 out: *mut *mut ibu_whitelist_t) -> i32;
     pub fn ibu_whitelist_info(wl: *const ibu_whitelist_t, bc_len: *mut u32, n_distinct: *mut usize, device_bytes: *mut usize) -> i32;

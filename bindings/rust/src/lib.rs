@@ -20,6 +20,8 @@ pub const MAGIC: u32 = 0x21554249;
 pub const VERSION: u32 = 2;
 pub const HEADER_SIZE: usize = 32;
 pub const RECORD_SIZE: usize = 24;
+/// `ibu_count_matrix` flag: leave the records as {barcode, index, umi} (IBU_COUNT_LEAVE_SWAPPED).
+pub const COUNT_LEAVE_SWAPPED: u32 = 1;
 
 // ---- errors (reference src/error.rs:56-128) ---------------------------------------------
 #[derive(thiserror::Error, Debug)]
@@ -606,6 +608,58 @@ pub mod device {
             }
             check(unsafe { ffi::ibu_ctx_synchronize(self.raw, std::ptr::null_mut()) })?;
             Ok((0..nb).map(|k| (host[k], host[nb + k], host[2 * nb + k])).collect())
+        }
+        /// `ibu_records_swap_umi_index`: record i of `dst` = {barcode, index, umi} of record i of `src` (its own inverse).
+        /// `dst = None`: in place.
+        pub fn swap_umi_index(&self, src: &DeviceBuf, dst: Option<&DeviceBuf>, n: usize) -> Result<()> {
+            let d = dst.map_or(src.ptr, |b| b.ptr);
+            check(unsafe { ffi::ibu_records_swap_umi_index(self.raw, src.ptr, d, n, std::ptr::null_mut()) })
+        }
+        fn download_columns(&self, cols: &[&DeviceBuf], k: usize) -> Result<Vec<u64>> {
+            let mut host = vec![0u64; cols.len() * k];
+            for (j, d) in cols.iter().enumerate() {
+                check(unsafe { ffi::ibu_memcpy_d2h(self.raw, host[j * k..].as_mut_ptr() as *mut c_void, d.ptr, 8 * k, std::ptr::null_mut()) })?;
+            }
+            check(unsafe { ffi::ibu_ctx_synchronize(self.raw, std::ptr::null_mut()) })?;
+            Ok(host)
+        }
+        /// `ibu_pair_counts`: one (first word, second word, records, distinct third words) per maximal run of records with equal
+        /// first and second words, in input order.  On swapped-and-sorted records: the count matrix in COO form.
+        pub fn pair_counts(&self, sorted: &DeviceBuf, n: usize) -> Result<Vec<(u64, u64, u64, u64)>> {
+            let (mut np, mut nt) = (0usize, 0usize);
+            check(unsafe {
+                ffi::ibu_pair_counts(self.raw, sorted.ptr, n, std::ptr::null_mut(), std::ptr::null_mut(), std::ptr::null_mut(),
+                                     std::ptr::null_mut(), 0, &mut np, &mut nt, std::ptr::null_mut())
+            })?;
+            if np == 0 {
+                return Ok(Vec::new());
+            }
+            let (a, b, c, d) = (self.alloc(8 * np)?, self.alloc(8 * np)?, self.alloc(8 * np)?, self.alloc(8 * np)?);
+            check(unsafe {
+                ffi::ibu_pair_counts(self.raw, sorted.ptr, n, a.ptr as *mut u64, b.ptr as *mut u64, c.ptr as *mut u64, d.ptr as *mut u64,
+                                     np, &mut np, &mut nt, std::ptr::null_mut())
+            })?;
+            let host = self.download_columns(&[&a, &b, &c, &d], np)?;
+            Ok((0..np).map(|k| (host[k], host[np + k], host[2 * np + k], host[3 * np + k])).collect())
+        }
+        /// `ibu_count_matrix` over `n` records in any order (`tmp`: 24 n bytes): (barcode, index, reads, distinct UMIs) per
+        /// entry, ascending by (barcode, index).  The records come back ordered by (barcode, index, umi); `leave_swapped` leaves
+        /// their second and third words exchanged.  `cap`: a bound on the number of entries (`n` always fits).
+        pub fn count_matrix(&self, recs: &DeviceBuf, tmp: &DeviceBuf, n: usize, cap: usize, leave_swapped: bool)
+                            -> Result<Vec<(u64, u64, u64, u64)>> {
+            if n == 0 {
+                return Ok(Vec::new());
+            }
+            let cap = cap.max(1);
+            let (a, b, c, d) = (self.alloc(8 * cap)?, self.alloc(8 * cap)?, self.alloc(8 * cap)?, self.alloc(8 * cap)?);
+            let (mut ne, mut nm) = (0usize, 0usize);
+            let flags = if leave_swapped { COUNT_LEAVE_SWAPPED } else { 0 };
+            check(unsafe {
+                ffi::ibu_count_matrix(self.raw, recs.ptr, tmp.ptr, n, flags, a.ptr as *mut u64, b.ptr as *mut u64, c.ptr as *mut u64,
+                                      d.ptr as *mut u64, cap, &mut ne, &mut nm, std::ptr::null_mut())
+            })?;
+            let host = self.download_columns(&[&a, &b, &c, &d], ne)?;
+            Ok((0..ne).map(|k| (host[k], host[ne + k], host[2 * ne + k], host[3 * ne + k])).collect())
         }
         /// Barcode correction against a whitelist, in place over `n` device records (`ibu_correct_barcodes`): exact hits stay, a
         /// barcode with exactly one whitelist entry one substitution away moves onto it.  `class` (optional): `n` bytes, one

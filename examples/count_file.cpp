@@ -1,0 +1,79 @@
+// count_file — the count matrix of a single-cell records file: for every (barcode, index) pair — cell x feature, the index
+// word being where users of the format keep the feature number — the number of distinct UMIs (molecules) and of records
+// (reads).  Read an IBU file; with a whitelist, correct the barcodes against it (ibu_correct_barcodes) and keep the exact and
+// the corrected records (ibu_select_records); build the matrix on the GPU (ibu_count_matrix) and print it in COO form, one
+//   barcode<TAB>index<TAB>umis<TAB>reads
+// line per entry, ascending by (barcode code, index).  The row lengths of the CSR view — entries per barcode — need nothing
+// new: ibu_barcode_counts on the records as ibu_count_matrix leaves them with IBU_COUNT_LEAVE_SWAPPED ({barcode, index, umi})
+// returns each barcode and, as its "unique UMIs", its number of distinct indices; they are printed behind the matrix as
+//   #row<TAB>barcode<TAB>entries<TAB>reads
+//   count_file IN [WHITELIST.txt]
+// WHITELIST.txt: one barcode per line, as many bases as the file's header says.
+#include <cstdio>
+#include <fstream>
+#include <string>
+#include <vector>
+
+#include "ibu.hpp"
+
+static std::string decode(uint64_t code, uint32_t len) {        // base i at bits [2i, 2i+1] (the default base order)
+  std::string s(len, 'A');
+  for (uint32_t i = 0; i < len; ++i) s[i] = "ACGT"[(code >> (2 * i)) & 3];
+  return s;
+}
+
+int main(int argc, char** argv) {
+  if (argc < 2) { std::fprintf(stderr, "usage: count_file IN [WHITELIST.txt]\n"); return 2; }
+  try {
+    using namespace ibu;
+    device::Context ctx(0);
+    auto [h, d_recs, n] = ctx.load_to_device(argv[1]);          // load_to_vec, device form
+    device::DeviceBuffer tmp(ctx, (n ? n : 1) * RECORD_SIZE);
+    void* recs = d_recs;                                        // the records the matrix is built from, and its scratch
+    void* scratch = tmp.ptr();
+    size_t kept = n;
+    if (argc > 2 && n) {
+      std::vector<uint8_t> ascii;
+      size_t w = 0;
+      std::ifstream f(argv[2]);
+      if (!f) throw std::runtime_error(std::string("cannot open ") + argv[2]);
+      std::string line;
+      while (std::getline(f, line)) {
+        while (!line.empty() && (line.back() == '\r' || line.back() == ' ' || line.back() == '\t')) line.pop_back();
+        if (line.empty()) continue;
+        if (line.size() != h.bc_len) throw std::runtime_error("whitelist line " + std::to_string(w + 1) + " is not " + std::to_string(h.bc_len) + " bases long");
+        ascii.insert(ascii.end(), line.begin(), line.end());
+        ++w;
+      }
+      if (!w) throw std::runtime_error("the whitelist is empty");
+      device::DeviceBuffer d_ascii(ctx, ascii.size()), d_codes(ctx, 8 * w), d_class(ctx, n);
+      d_ascii.upload(ascii);
+      ctx.pack_2bit(d_ascii.as<uint8_t>(), w, h.bc_len, d_codes.as<uint64_t>());
+      ctx.codec_status();                                       // throws InvalidBase on a letter outside ACGTacgt
+      device::Whitelist wl(ctx, d_codes.as<uint64_t>(), w, h.bc_len);
+      const device::CorrectCounts c = ctx.correct_barcodes(wl, d_recs, n, 1, d_class.as<uint8_t>());
+      kept = ctx.select_records(d_recs, d_class.as<uint8_t>(), n, 0b0011, tmp.ptr(), n);
+      ctx.synchronize();
+      std::fprintf(stderr, "%zu records: exact %llu, corrected %llu, ambiguous %llu, unmatched %llu; kept %zu\n", n, (unsigned long long)c.exact,
+                   (unsigned long long)c.corrected, (unsigned long long)c.ambiguous, (unsigned long long)c.unmatched, kept);
+      recs = tmp.ptr();                                         // the kept records live in tmp; the input array is scratch from here on
+      scratch = d_recs;
+    }
+    // the matrix; the records stay {barcode, index, umi} so that the row lengths can be read off them
+    const auto entries = ctx.count_matrix(recs, scratch, kept, 0, /*leave_swapped=*/true);
+    for (const device::MatrixEntry& e : entries)
+      std::printf("%s\t%llu\t%llu\t%llu\n", decode(e.first, h.bc_len).c_str(), (unsigned long long)e.second, (unsigned long long)e.distinct,
+                  (unsigned long long)e.records);
+    size_t total = 0;
+    for (auto& [barcode, reads, n_entries] : ctx.barcode_counts(recs, kept)) {
+      std::printf("#row\t%s\t%llu\t%llu\n", decode(barcode, h.bc_len).c_str(), (unsigned long long)n_entries, (unsigned long long)reads);
+      total += n_entries;
+    }
+    if (total != entries.size()) throw std::runtime_error("the row lengths do not add up to the number of entries");
+    ctx.free(d_recs);
+  } catch (const std::exception& e) {
+    std::fprintf(stderr, "error: %s\n", e.what());
+    return 1;
+  }
+  return 0;
+}

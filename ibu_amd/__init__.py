@@ -26,6 +26,7 @@ DEFAULT_BUFFER_SIZE = 48 * 1024 * RECORD_SIZE  # reader.rs:14, writer.rs:10
 BATCH_SIZE = 1024 * 1024  # mmap.rs:284
 
 PROC_REDUCE, PROC_DECODE = 1, 2
+COUNT_LEAVE_SWAPPED = 1  # ibu_count_matrix flags (IBU_COUNT_LEAVE_SWAPPED)
 
 #: numpy view of a `&[Record]` (bytemuck::cast_slice)
 REC_DTYPE = np.dtype([("barcode", "<u8"), ("umi", "<u8"), ("index", "<u8")])
@@ -904,6 +905,46 @@ class Context:
                                       C.byref(nb), C.byref(npairs), stream))
         self.synchronize(stream)
         return (d_b.download(np.uint64), d_c.download(np.uint64), d_u.download(np.uint64) if d_u else None)
+
+    # count matrix: reads and distinct UMIs per (barcode, index) pair
+    def swap_umi_index(self, d_src, d_dst, n, stream=None):
+        """ibu_records_swap_umi_index: record i of d_dst = {barcode, index, umi} of record i of d_src (its own inverse).
+        d_dst may be d_src (in place); asynchronous on `stream`."""
+        _check(lib.ibu_records_swap_umi_index(self._c, _dptr(d_src), _dptr(d_dst), n, stream))
+
+    def pair_counts(self, d_sorted_records, n, distinct_third=True, stream=None):
+        """ibu_pair_counts: one entry per maximal run of records with equal first and second words ->
+        (first, second, records_per_pair, distinct_third | None) as numpy u64 arrays in input order.  On records that went
+        through swap_umi_index and sort_records: the count matrix in COO form (barcode, index, reads, distinct UMIs); on
+        ordinarily sorted records: the molecules (barcode, umi, reads, distinct indices)."""
+        npairs, ntriples = C.c_size_t(), C.c_size_t()
+        _check(lib.ibu_pair_counts(self._c, _dptr(d_sorted_records), n, None, None, None, None, 0, C.byref(npairs),
+                                   C.byref(ntriples), stream))
+        u = npairs.value
+        if u == 0:
+            e = np.empty(0, np.uint64)
+            return e, e.copy(), e.copy(), (e.copy() if distinct_third else None)
+        outs = [self.alloc(8 * u) for _ in range(3)] + [self.alloc(8 * u) if distinct_third else None]
+        _check(lib.ibu_pair_counts(self._c, _dptr(d_sorted_records), n, *[_dptr(o) for o in outs], u, C.byref(npairs),
+                                   C.byref(ntriples), stream))
+        self.synchronize(stream)
+        return tuple(o.download(np.uint64) if o else None for o in outs)
+
+    def count_matrix(self, d_records, d_tmp, n, cap=None, leave_swapped=False, stream=None):
+        """ibu_count_matrix over n device records in any order (d_tmp: 24 n bytes of scratch) ->
+        (barcodes, indices, reads, umis) as numpy u64 arrays, ascending by (barcode, index): the count matrix in COO form.
+        On return the records are ordered by (barcode, index, umi), with their fields in place unless leave_swapped.
+        cap: a bound on the number of entries (default n, which always fits)."""
+        if n == 0:
+            e = np.empty(0, np.uint64)
+            return e, e.copy(), e.copy(), e.copy()
+        cap = n if cap is None else cap
+        outs = [self.alloc(max(8 * cap, 16)) for _ in range(4)]
+        ne, nm = C.c_size_t(), C.c_size_t()
+        _check(lib.ibu_count_matrix(self._c, _dptr(d_records), _dptr(d_tmp), n, COUNT_LEAVE_SWAPPED if leave_swapped else 0,
+                                    *[_dptr(o) for o in outs], cap, C.byref(ne), C.byref(nm), stream))
+        self.synchronize(stream)
+        return tuple(o.download(np.uint64, count=ne.value) for o in outs)
 
     # barcode correction against a whitelist
     def correct_barcodes(self, wl, d_records, n, max_mismatches=1, d_class=None, counts=True, stream=None):

@@ -683,6 +683,16 @@ extern "C" int32_t ibu_records_expand(ibu_ctx_t* ctx, const ibu_key_plan_t* plan
   IBU_HIP(launch_expand(ctx->cfg, *reinterpret_cast<const CompactPlan*>(plan), d_elems, n, d_records, pick_stream(ctx, stream)));
   return IBU_OK;
 }
+// the emit scratch of the run-length aggregations (16 bytes per entry): grows only
+static int32_t ensure_runs_scratch(ibu_ctx* ctx, size_t need) {
+  if (need <= ctx->runs_scratch_bytes) return IBU_OK;
+  if (ctx->d_runs_scratch) IBU_HIP(hipFree(ctx->d_runs_scratch));
+  ctx->d_runs_scratch = nullptr;
+  ctx->runs_scratch_bytes = 0;
+  IBU_HIP(ctx_malloc(ctx, &ctx->d_runs_scratch, need));
+  ctx->runs_scratch_bytes = need;
+  return IBU_OK;
+}
 // BarcodeAnalyzer (parallel.rs:72-98) on sorted device records.
 extern "C" int32_t ibu_barcode_counts(ibu_ctx_t* ctx, const void* d_sorted_records, size_t n, uint64_t* d_barcodes,
                                       uint64_t* d_counts, uint64_t* d_unique_umis, size_t cap, size_t* n_barcodes,
@@ -711,14 +721,8 @@ extern "C" int32_t ibu_barcode_counts(ibu_ctx_t* ctx, const void* d_sorted_recor
   if (size_query) return IBU_OK;
   if (!d_barcodes || !d_counts) return err_arg("d_barcodes / d_counts are NULL");
   if (runs > cap) return err_arg("output capacity is smaller than the number of distinct barcodes (see *n_barcodes)");
-  const size_t need = runs_emit_scratch_bytes(runs);
-  if (need > ctx->runs_scratch_bytes) {
-    if (ctx->d_runs_scratch) IBU_HIP(hipFree(ctx->d_runs_scratch));
-    ctx->d_runs_scratch = nullptr;
-    ctx->runs_scratch_bytes = 0;
-    IBU_HIP(ctx_malloc(ctx, &ctx->d_runs_scratch, need));
-    ctx->runs_scratch_bytes = need;
-  }
+  rc = ensure_runs_scratch(ctx, runs_emit_scratch_bytes(runs));
+  if (rc) return rc;
   IBU_HIP(launch_runs_emit(ctx->cfg, d_sorted_records, n, ctx->d_sort_scratch, true, ctx->d_runs_scratch, runs, pairs, d_barcodes,
                            d_counts, d_unique_umis, st));
   return IBU_OK;
@@ -865,4 +869,75 @@ extern "C" int32_t ibu_sort_records(ibu_ctx_t* ctx, void* d_records, void* d_tmp
   IBU_HIP(launch_sort_records(ctx->cfg, d_records, d_tmp, n, ctx->d_sort_scratch, ctx->sort_scratch_bytes,
                               pick_stream(ctx, stream)));
   return IBU_OK;
+}
+// ---- count matrix: distinct UMIs and reads per (barcode, index) pair (k_records.hip: the field exchange; k_aggregate.hip: the
+// pair-level run walk).  The semantics are this library's: include/ibu_hip.h.
+extern "C" int32_t ibu_records_swap_umi_index(ibu_ctx_t* ctx, const void* d_src, void* d_dst, size_t n, void* stream) {
+  int32_t rc = check_ctx(ctx);
+  if (rc) return rc;
+  if (n == 0) return IBU_OK;
+  if (!d_src || !d_dst || !aligned8(d_src) || !aligned8(d_dst)) return err_arg("d_src / d_dst must be non-NULL and 8-byte aligned");
+  if (n >= (1ull << 40)) return err_arg("records_swap_umi_index handles fewer than 2^40 records per call");
+  const uintptr_t a = reinterpret_cast<uintptr_t>(d_dst), b = reinterpret_cast<uintptr_t>(d_src);
+  if (a != b && a < b + 24 * n && b < a + 24 * n) return err_arg("d_dst overlaps d_src (only d_dst == d_src, in place, is allowed)");
+  IBU_HIP(launch_swap_fields(ctx->cfg, d_src, d_dst, n, pick_stream(ctx, stream)));
+  return IBU_OK;
+}
+extern "C" int32_t ibu_pair_counts(ibu_ctx_t* ctx, const void* d_sorted_records, size_t n, uint64_t* d_first, uint64_t* d_second,
+                                   uint64_t* d_records_per_pair, uint64_t* d_distinct_third, size_t cap, size_t* n_pairs,
+                                   size_t* n_triples, void* stream) {
+  int32_t rc = check_ctx(ctx);
+  if (rc) return rc;
+  if (!n_pairs) return err_arg("n_pairs is NULL");
+  *n_pairs = 0;
+  if (n_triples) *n_triples = 0;
+  if (n == 0) return IBU_OK;
+  if (!d_sorted_records || !aligned8(d_sorted_records)) return err_arg("d_sorted_records must be non-NULL and 8-byte aligned");
+  if (n >= (1ull << 40)) return err_arg("pair_counts handles fewer than 2^40 records per call");
+  hipStream_t st = pick_stream(ctx, stream);
+  rc = ensure_sort_scratch(ctx, runs_scratch_bytes(n));
+  if (rc) return rc;
+  const bool size_query = !d_first && !d_second && !d_records_per_pair && cap == 0;
+  IBU_HIP(launch_runs_count(ctx->cfg, d_sorted_records, n, ctx->d_sort_scratch, ctx->sort_scratch_bytes, false, st, true));
+  IBU_HIP(hipMemcpyAsync(ctx->h_pinned, ctx->d_sort_scratch, 2 * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
+  IBU_HIP(hipStreamSynchronize(st));
+  const uint64_t pairs = ctx->h_pinned[0], triples = ctx->h_pinned[1];
+  *n_pairs = pairs;
+  if (n_triples) *n_triples = triples;
+  if (size_query) return IBU_OK;
+  if (!d_first || !d_second || !d_records_per_pair) return err_arg("d_first / d_second / d_records_per_pair are NULL");
+  if (!aligned8(d_first) || !aligned8(d_second) || !aligned8(d_records_per_pair) || !aligned8(d_distinct_third))
+    return err_arg("the output arrays must be 8-byte aligned");
+  if (pairs > cap)
+    return set_error(IBU_ERR_INVALID_ARG, pairs, cap, 0, "Invalid argument: output capacity %llu is smaller than the %llu entries (see *n_pairs)",
+                     (unsigned long long)cap, (unsigned long long)pairs);
+  rc = ensure_runs_scratch(ctx, runs_emit_scratch_bytes(pairs));
+  if (rc) return rc;
+  IBU_HIP(launch_pairs_emit(ctx->cfg, d_sorted_records, n, ctx->d_sort_scratch, ctx->d_runs_scratch, pairs, triples, d_first, d_second,
+                            d_records_per_pair, d_distinct_third, st));
+  return IBU_OK;
+}
+extern "C" int32_t ibu_count_matrix(ibu_ctx_t* ctx, void* d_records, void* d_tmp, size_t n, uint32_t flags, uint64_t* d_barcodes,
+                                    uint64_t* d_indices, uint64_t* d_reads, uint64_t* d_umis, size_t cap, size_t* n_entries,
+                                    size_t* n_molecules, void* stream) {
+  int32_t rc = check_ctx(ctx);
+  if (rc) return rc;
+  if (!n_entries) return err_arg("n_entries is NULL");
+  *n_entries = 0;
+  if (n_molecules) *n_molecules = 0;
+  if (flags & ~(uint32_t)IBU_COUNT_LEAVE_SWAPPED) return err_arg("unknown bit in flags");
+  if (n == 0) return IBU_OK;
+  if (!d_records || !d_tmp || !aligned8(d_records) || !aligned8(d_tmp))
+    return err_arg("d_records / d_tmp must be non-NULL and 8-byte aligned");
+  if (!d_barcodes || !d_indices || !d_reads) return err_arg("d_barcodes / d_indices / d_reads are NULL");
+  if (!aligned8(d_barcodes) || !aligned8(d_indices) || !aligned8(d_reads) || !aligned8(d_umis))
+    return err_arg("the output arrays must be 8-byte aligned");
+  if (n >= (1ull << 40)) return err_arg("count_matrix handles fewer than 2^40 records per call");
+  if ((rc = ibu_records_swap_umi_index(ctx, d_records, d_records, n, stream)) != 0) return rc;
+  if ((rc = ibu_sort_records(ctx, d_records, d_tmp, n, stream)) != 0) return rc;
+  // a capacity that is too small is reported once the records are back in the state the flags promise
+  const int32_t rc_counts = ibu_pair_counts(ctx, d_records, n, d_barcodes, d_indices, d_reads, d_umis, cap, n_entries, n_molecules, stream);
+  if (!(flags & IBU_COUNT_LEAVE_SWAPPED) && (rc_counts == IBU_OK || rc_counts == IBU_ERR_INVALID_ARG))
+    if ((rc = ibu_records_swap_umi_index(ctx, d_records, d_records, n, stream)) != 0) return rc;
+  return rc_counts;
 }

@@ -68,7 +68,9 @@ extern "C" const char* ibu_version(void) { return "ibu_hip 0.5.0 (format v2, ref
 // 3: ibu_decode_sink_t.cap_records (layout change), + lower_bound_records, "base_order" / "sort_variant" options
 // 4: ibu_stream_stats_t + numa_node / ring_node (layout change), + ibu_stream_* (pull stream), ibu_ctx_numa, ibu_numa_of_pci, options "numa",
 //    "peer_access", "alloc_probe_tries" = 0 (auto, the new default)
-extern "C" uint32_t ibu_abi_revision(void) { return 5; }
+// 5: + ibu_stream_open_path, the whitelist group (whitelist_create / _info / _destroy, correct_barcodes, select_records)
+// 6: + records_swap_umi_index, pair_counts, count_matrix (IBU_COUNT_LEAVE_SWAPPED)
+extern "C" uint32_t ibu_abi_revision(void) { return 6; }
 extern "C" void ibu_free(void* p) { free(p); }
 
 // ------------------------------------------------------------------------------------------

@@ -1,4 +1,4 @@
-// k_records.hip — K1/K1' (AoS <-> u64 columns), K4 reduce, synthetic generator, sortedness check.
+// k_records.hip — K1/K1' (AoS <-> u64 columns), the field exchange, K4 reduce, synthetic generator, sortedness check.
 // Design notes: kcommon.hpp.  Reference semantics are cited at the C-ABI entry points in device.cpp
 // and include/ibu_hip.h (cast_slice of &[Record]: reader.rs:301, writer.rs:317, mmap.rs:268; the
 // in-repo processors: lib.rs:117-129, examples/parallel.rs:21-36, examples/roundtrip.rs:84-87).
@@ -92,6 +92,44 @@ ibu_k_serialize(const u64* __restrict__ bc, const u64* __restrict__ umi, const u
       });
 }
 
+// =============================================================================================
+// Field exchange: record i of dst = {w0, w2, w1} of record i of src (ibu_records_swap_umi_index).  The sort compares the three
+// words of a record in storage order, so (barcode, index, umi) order — what a count matrix groups by — is the sort applied to
+// records that went through this kernel, and a second pass puts the fields back.  Same shape as K1 / K1': the tile is staged in
+// the wave's LDS slice, lane L exchanges the two words of records L and L + 64 there (stride-24 ds_read_b64 / ds_write_b64:
+// conflict-free) and the wave stores the slice as three coalesced dwordx4.  dst == src is safe: a wave owns whole tiles and a
+// tile is in LDS before any of it is written (the prefetch in flight is another tile, or this one's unused re-read).
+// =============================================================================================
+extern "C" __global__ void __launch_bounds__(kBlock, 8)
+ibu_k_swap_fields(const uint8_t* src, u32 ntiles, uint8_t* dst) {
+  __shared__ __attribute__((aligned(16))) uint8_t lds[kWavesPerBlock * kTileBytes];
+  const u32 lane = threadIdx.x & (kWave - 1);
+  const u32 wib = threadIdx.x >> 6;
+  uint8_t* tile = lds + wib * kTileBytes;
+  sweep_tiles<RecRegs>(
+      tile_range(ntiles, wib),
+      [&](RecRegs& g, u32 t) {
+        const uint8_t* p = src + (size_t)t * kTileBytes + 16 * lane;
+#pragma unroll
+        for (int k = 0; k < 3; ++k) g.v[k] = ld16(p + 1024 * k);
+      },
+      [&](const RecRegs& g, u32 t) {
+        wave_lds_fence();
+#pragma unroll
+        for (int k = 0; k < 3; ++k) *reinterpret_cast<u32x4*>(tile + 1024 * k + 16 * lane) = g.v[k];
+        wave_lds_fence();
+#pragma unroll
+        for (int h = 0; h < 2; ++h) {
+          u64* r = reinterpret_cast<u64*>(tile + (lane + 64 * h) * 24);
+          const u64 a = r[1], b = r[2];
+          r[1] = b; r[2] = a;
+        }
+        wave_lds_fence();
+        uint8_t* q = dst + (size_t)t * kTileBytes + 16 * lane;
+#pragma unroll
+        for (int k = 0; k < 3; ++k) st16(q + 1024 * k, *reinterpret_cast<const u32x4*>(tile + 1024 * k + 16 * lane));
+      });
+}
 
 // =============================================================================================
 // K4  reduce: wrapping sums and XORs of the three fields.  Pure streaming read, no LDS in the
@@ -303,6 +341,12 @@ extern "C" __global__ void ibu_k_serialize_tail(const u64* bc, const u64* umi, c
   if (i >= n) return;
   recs[3 * i] = bc[i]; recs[3 * i + 1] = umi[i]; recs[3 * i + 2] = idx[i];
 }
+extern "C" __global__ void ibu_k_swap_fields_tail(const u64* src, u64 row0, u64 n, u64* dst) {   // dst == src allowed: a thread reads its record first
+  const u64 i = row0 + (u64)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const u64 w0 = src[3 * i], w1 = src[3 * i + 1], w2 = src[3 * i + 2];
+  dst[3 * i] = w0; dst[3 * i + 1] = w2; dst[3 * i + 2] = w1;
+}
 extern "C" __global__ void ibu_k_reduce_tail(const u64* __restrict__ recs, u64 row0, u64 n, u64* acc) {
   // one thread per record (peeled head rows, the n % 128 rest, or a whole input no peel can align); each wave folds its
   // 64 records with shuffles first, so the atomics are six per WAVE whatever the size
@@ -391,6 +435,25 @@ hipError_t launch_serialize(const LaunchCfg& cfg, const uint64_t* bc, const uint
   if (rs.head + rs.main < n)
     hipLaunchKernelGGL(ibu_k_serialize_tail, dim3(tail_grid(n - rs.head - rs.main)), dim3(256), 0, st, (const u64*)bc,
                        (const u64*)umi, (const u64*)idx, (u64)(rs.head + rs.main), (u64)n, (u64*)recs);
+  return hipGetLastError();
+}
+
+hipError_t launch_swap_fields(const LaunchCfg& cfg, const void* src, void* dst, size_t n, hipStream_t st) {
+  (void)hipGetLastError();
+  if (n == 0) return hipSuccess;
+  const Span sp[2] = {{src, 24}, {dst, 24}};
+  const RowSplit rs = split_rows(cfg, sp, 2, n, kTileRecs);   // an 8-B aligned base peels one record; bases of different phase: all rows take the tail kernel
+  if (rs.head)
+    hipLaunchKernelGGL(ibu_k_swap_fields_tail, dim3(tail_grid(rs.head)), dim3(256), 0, st, (const u64*)src, (u64)0, (u64)rs.head, (u64*)dst);
+  if (rs.main) {
+    const u32 ntiles = (u32)(rs.main / kTileRecs);
+    static std::atomic<int> occ;
+    hipLaunchKernelGGL(ibu_k_swap_fields, dim3(grid_for(ntiles, cfg.cus, resident_blocks<kBlock>(cfg, ibu_k_swap_fields, 0, &occ))), dim3(kBlock),
+                       0, st, adv((const uint8_t*)src, 24 * rs.head), ntiles, adv((uint8_t*)dst, 24 * rs.head));
+  }
+  if (rs.head + rs.main < n)
+    hipLaunchKernelGGL(ibu_k_swap_fields_tail, dim3(tail_grid(n - rs.head - rs.main)), dim3(256), 0, st, (const u64*)src,
+                       (u64)(rs.head + rs.main), (u64)n, (u64*)dst);
   return hipGetLastError();
 }
 

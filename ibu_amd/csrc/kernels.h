@@ -117,10 +117,16 @@ hipError_t launch_sort_elems(const LaunchCfg&, const CompactPlan& pl, void* recs
                              size_t scratch_bytes, hipStream_t st);
 // per-barcode run-length aggregation of sorted records (k_aggregate.hip)
 size_t runs_scratch_bytes(size_t n);
-hipError_t launch_runs_count(const LaunchCfg&, const void* recs, size_t n, void* scratch, size_t scratch_bytes, bool keep_heads, hipStream_t st);
+// pair_level: runs of equal (w0, w1) with the distinct (w0, w1, w2) ranked inside them (ibu_pair_counts; keep_heads is not used there)
+hipError_t launch_runs_count(const LaunchCfg&, const void* recs, size_t n, void* scratch, size_t scratch_bytes, bool keep_heads, hipStream_t st,
+                             bool pair_level = false);
 size_t runs_emit_scratch_bytes(uint64_t n_runs);
 hipError_t launch_runs_emit(const LaunchCfg&, const void* recs, size_t n, const void* scratch, bool from_stash, void* run_scratch, uint64_t n_runs,
                             uint64_t n_pairs, uint64_t* barcodes, uint64_t* counts, uint64_t* uniq, hipStream_t st);
+hipError_t launch_pairs_emit(const LaunchCfg&, const void* recs, size_t n, const void* scratch, void* run_scratch, uint64_t n_pairs,
+                             uint64_t n_triples, uint64_t* first, uint64_t* second, uint64_t* counts, uint64_t* distinct, hipStream_t st);
+// record i of dst = {w0, w2, w1} of record i of src; dst == src (in place) or disjoint (k_records.hip)
+hipError_t launch_swap_fields(const LaunchCfg&, const void* src, void* dst, size_t n, hipStream_t st);
 // barcode correction against a whitelist (k_whitelist.hip).  The table: `slots` 64-bit keys (a power of two, at least 2 w), all ones =
 // free; the all-ones key itself (a legal code at 32 bases) travels beside it as `has_ones`.
 struct WhitelistTable { const uint64_t* table; size_t slots; uint32_t bc_len; bool has_ones; };

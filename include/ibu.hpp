@@ -362,6 +362,8 @@ class MmapReader {
 namespace device {
 class Whitelist;
 using CorrectCounts = ibu_correct_counts_t;
+// one entry of ibu_pair_counts / ibu_count_matrix: (barcode, index, reads, distinct UMIs) on the count-matrix path
+struct MatrixEntry { uint64_t first, second, records, distinct; };
 inline int device_count() { int32_t n = 0; return ibu_device_count(&n) == IBU_OK ? n : 0; }
 
 class Context {
@@ -426,6 +428,14 @@ class Context {
   void expand(const ibu_key_plan_t& plan, const void* d_elems, size_t n, void* d_recs, void* st = nullptr) { check(ibu_records_expand(c_, &plan, d_elems, n, d_recs, st)); }
   // BarcodeAnalyzer (parallel.rs:72-98) on sorted device records: (barcode, records, distinct UMIs), ascending barcode
   inline std::vector<std::tuple<uint64_t, uint64_t, uint64_t>> barcode_counts(const void* d_sorted, size_t n);
+  // count matrix.  swap_umi_index: record i of d_dst = {barcode, index, umi} of record i of d_src; d_dst == d_src is in place.
+  void swap_umi_index(const void* d_src, void* d_dst, size_t n, void* st = nullptr) { check(ibu_records_swap_umi_index(c_, d_src, d_dst, n, st)); }
+  // one entry per run of equal (first word, second word): (first, second, records, distinct third words), in input order (ibu_pair_counts)
+  inline std::vector<MatrixEntry> pair_counts(const void* d_sorted, size_t n);
+  // the count matrix of n records in any order: (barcode, index, reads, umis) ascending by (barcode, index); the records come back
+  // ordered by (barcode, index, umi), with the umi and index words exchanged if leave_swapped (ibu_count_matrix).  cap: a bound on
+  // the number of entries, 0 = n (always fits)
+  inline std::vector<MatrixEntry> count_matrix(void* d_recs, void* d_tmp, size_t n, size_t cap = 0, bool leave_swapped = false);
   // barcode correction against a whitelist, in place (ibu_correct_barcodes): d_class (nullable) receives one class byte per record;
   // returns the four totals (synchronises).  correct_barcodes_async: no totals, nothing synchronised.
   inline CorrectCounts correct_barcodes(const Whitelist& wl, void* d_recs, size_t n, uint32_t max_mismatches = 1, uint8_t* d_class = nullptr,
@@ -519,6 +529,31 @@ inline void Context::correct_barcodes_async(const Whitelist& wl, void* d_recs, s
   check(ibu_correct_barcodes(c_, wl.raw(), d_recs, n, max_mismatches, d_class, nullptr, st));
 }
 
+inline std::vector<MatrixEntry> Context::pair_counts(const void* d_sorted, size_t n) {
+  size_t np = 0, nt = 0;
+  check(ibu_pair_counts(c_, d_sorted, n, nullptr, nullptr, nullptr, nullptr, 0, &np, &nt, nullptr));
+  std::vector<MatrixEntry> out;
+  if (!np) return out;
+  DeviceBuffer a(*this, 8 * np), b(*this, 8 * np), c(*this, 8 * np), d(*this, 8 * np);
+  check(ibu_pair_counts(c_, d_sorted, n, a.as<uint64_t>(), b.as<uint64_t>(), c.as<uint64_t>(), d.as<uint64_t>(), np, &np, &nt, nullptr));
+  auto ha = a.download<uint64_t>(np), hb = b.download<uint64_t>(np), hc = c.download<uint64_t>(np), hd = d.download<uint64_t>(np);
+  out.reserve(np);
+  for (size_t k = 0; k < np; ++k) out.push_back({ha[k], hb[k], hc[k], hd[k]});
+  return out;
+}
+inline std::vector<MatrixEntry> Context::count_matrix(void* d_recs, void* d_tmp, size_t n, size_t cap, bool leave_swapped) {
+  std::vector<MatrixEntry> out;
+  if (!n) return out;
+  if (!cap) cap = n;
+  DeviceBuffer a(*this, 8 * cap), b(*this, 8 * cap), c(*this, 8 * cap), d(*this, 8 * cap);
+  size_t ne = 0, nm = 0;
+  check(ibu_count_matrix(c_, d_recs, d_tmp, n, leave_swapped ? IBU_COUNT_LEAVE_SWAPPED : 0u, a.as<uint64_t>(), b.as<uint64_t>(), c.as<uint64_t>(),
+                         d.as<uint64_t>(), cap, &ne, &nm, nullptr));
+  auto ha = a.download<uint64_t>(ne), hb = b.download<uint64_t>(ne), hc = c.download<uint64_t>(ne), hd = d.download<uint64_t>(ne);
+  out.reserve(ne);
+  for (size_t k = 0; k < ne; ++k) out.push_back({ha[k], hb[k], hc[k], hd[k]});
+  return out;
+}
 inline std::vector<std::tuple<uint64_t, uint64_t, uint64_t>> Context::barcode_counts(const void* d_sorted, size_t n) {
   size_t nb = 0, np = 0;
   check(ibu_barcode_counts(c_, d_sorted, n, nullptr, nullptr, nullptr, 0, &nb, &np, nullptr));

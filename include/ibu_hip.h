@@ -491,6 +491,54 @@ int32_t ibu_sort_records_contexts(ibu_ctx_t* const* ctxs, size_t n_ctxs, ibu_sor
 int32_t ibu_barcode_counts(ibu_ctx_t* ctx, const void* d_sorted_records, size_t n, uint64_t* d_barcodes,
                            uint64_t* d_counts, uint64_t* d_unique_umis, size_t cap, size_t* n_barcodes,
                            size_t* n_barcode_umi_pairs, void* stream);
+/* Count matrix on the device: reads and distinct UMIs per (barcode, index) pair — cell x feature, the `index` word being where
+ * users of the format keep the feature / gene number (reference README.md:40-47).  The reference has no such function (as it has no
+ * sort and no aggregation); the semantics are this library's and are stated in full here.  Write w0, w1, w2 for the three
+ * little-endian 64-bit words of a 24-byte record in storage order (normally barcode, umi, index).
+ *
+ * ibu_records_swap_umi_index: record i of d_dst = {w0, w2, w1} of record i of d_src.  Its own inverse.  d_dst == d_src (in place) is
+ * allowed; any other overlap of the two n-record ranges is IBU_ERR_INVALID_ARG.  8-byte aligned arrays, n < 2^40, n == 0 is OK and
+ * touches nothing, asynchronous on `stream`.  48 B per record (one read, one write): the tiled kernel when both bases have the same
+ * phase modulo 16 (an 8- but not 16-byte aligned pair peels one record), one thread per record otherwise.  Why it exists:
+ * ibu_sort_records compares the three words in storage order and nothing else, so (barcode, index, umi) order — which makes the
+ * records of one (barcode, index) pair adjacent — is the sort applied to records whose second and third words changed places. */
+int32_t ibu_records_swap_umi_index(ibu_ctx_t* ctx, const void* d_src, void* d_dst, size_t n, void* stream);
+/* Run-length aggregation at pair level (k_aggregate.hip).  An ENTRY is a maximal run of consecutive records with equal (w0, w1).
+ * For entry k, in input order: d_first[k] = w0, d_second[k] = w1, d_records_per_pair[k] = the length of the run, and, when
+ * d_distinct_third != NULL, d_distinct_third[k] = the number of positions in the run whose w2 differs from the record before it (the
+ * first record of a run counts) — on sorted input the number of distinct w2 of the pair.  *n_pairs = the number of entries,
+ * *n_triples (nullable) = the sum of d_distinct_third (computed whether or not that array is asked for).
+ * Two uses:
+ *   on records that went through ibu_records_swap_umi_index and ibu_sort_records, entries are (barcode, index) pairs,
+ *     records_per_pair = reads, distinct_third = distinct UMIs (molecules): the count matrix in COO form, rows ascending by
+ *     (barcode, index);
+ *   on ordinarily sorted records, entries are (barcode, umi) molecules with their reads and the number of distinct indices — the
+ *     molecules with more than one are the chimeric ones a caller may want to drop.
+ * Row pointers for a CSR view need nothing new: ibu_barcode_counts on the swapped-and-sorted records returns each barcode and, as
+ * unique_umis, its number of entries (examples/count_file.cpp).
+ * Unsorted input yields the run-length encoding described above, as ibu_barcode_counts documents for itself.  Size query: d_first =
+ * d_second = d_records_per_pair = NULL and cap = 0.  cap too small: IBU_ERR_INVALID_ARG with *n_pairs (and *n_triples) set and
+ * nothing written (detail.a = entries, detail.b = cap).  n == 0: OK, both totals 0.  n < 2^40; 8-byte aligned arrays.  Synchronises
+ * `stream` once (the totals come back to size the output); the writes may still be queued on return.  Reads the records twice (once
+ * for the size query): entries are typically a sizeable fraction of n, so the count pass keeps no heads.  Scratch: the context's
+ * sort scratch (per-segment tables) and 16 B per entry of its run scratch, grown on demand. */
+int32_t ibu_pair_counts(ibu_ctx_t* ctx, const void* d_sorted_records, size_t n, uint64_t* d_first, uint64_t* d_second,
+                        uint64_t* d_records_per_pair, uint64_t* d_distinct_third, size_t cap, size_t* n_pairs, size_t* n_triples,
+                        void* stream);
+/* The count matrix in one call: swap in place -> ibu_sort_records(d_records, d_tmp) -> ibu_pair_counts -> swap back in place.
+ * Input in any order (sorted or not); d_tmp: n*24 B of scratch.  Entry k, ascending by (barcode, index): d_barcodes[k], d_indices[k],
+ * d_reads[k] = records of the pair, d_umis[k] (nullable) = its distinct UMIs; *n_entries = entries, *n_molecules (nullable) = the sum
+ * of d_umis.  On return the records are the input multiset, every record with its fields in their normal places, ordered by
+ * (barcode, index, umi).  flags: IBU_COUNT_LEAVE_SWAPPED skips the last pass and leaves {barcode, index, umi} records (for a caller
+ * that goes on to ibu_barcode_counts for the row pointers); any other bit is IBU_ERR_INVALID_ARG (nothing touched).  No size query
+ * (it would cost the sort): d_barcodes, d_indices and d_reads must be non-NULL, and a cap that is too small fails AFTER the sort with
+ * IBU_ERR_INVALID_ARG, *n_entries set, nothing written to the outputs and the records in the state the flags promise.  The safe cap
+ * is n, or the caller's bound (whitelist size x features).  n == 0: OK.  n < 2^40.  Synchronises `stream` as ibu_sort_records and
+ * ibu_pair_counts do; the last kernels may still be queued on return. */
+#define IBU_COUNT_LEAVE_SWAPPED 1u
+int32_t ibu_count_matrix(ibu_ctx_t* ctx, void* d_records, void* d_tmp, size_t n, uint32_t flags, uint64_t* d_barcodes,
+                         uint64_t* d_indices, uint64_t* d_reads, uint64_t* d_umis, size_t cap, size_t* n_entries, size_t* n_molecules,
+                         void* stream);
 /* Barcode correction against a whitelist, on the device (k_whitelist.hip) — the step between a load and ibu_sort_records /
  * ibu_barcode_counts that makes the latter's "a caller that knows a bound (its whitelist)" true of real input.  The reference has
  * no such function (as it has no sort and no aggregation); the semantics are this library's and are stated in full here.

@@ -3,6 +3,7 @@
 timed by phase — the size query (count pass + scan + 16-byte read-back) and the emit call (count + scan + emit + finish)
 into preallocated device arrays, no download.
   python tools/aggbench.py [--records 1e9] [--lens 10,12] [--rounds 5]
+  python tools/aggbench.py --matrix 1e5x100,own_pair,one_pair [--records 1e9]     the count-matrix legs (matrix_legs below)
 bc_len 10 gives 2^20 distinct barcodes (a single-cell whitelist's order of magnitude); 16 gives ~n runs of length one."""
 import argparse
 import ctypes as C
@@ -24,13 +25,125 @@ def _rand_bits(torch, g, nbits, count):
     return (hi << 32) | torch.randint(0, 1 << 32, (count,), generator=g, device="cuda", dtype=torch.int64)
 
 
+def matrix_legs(a):
+    """--matrix: the count-matrix path on resident 16/12 records, timed with events on a side stream (the first round is the
+    warm-up).  Per input: ibu_records_swap_umi_index (out of place and in place) against ibu_device_copy of the same bytes on the
+    same arrays; ibu_pair_counts (size query, and with outputs) against ibu_reduce (one plain read) and against
+    ibu_barcode_counts with outputs on records that are each their own barcode (two reads and per-run outputs); ibu_count_matrix
+    in one call and as its four steps."""
+    import numpy as np
+    import torch                                             # before the library, as bench.py does
+    torch.cuda.init()
+    import ibu_amd as ia
+    from ibu_amd import _dptr, _check, lib
+
+    ctx = ia.Context(0)
+    side = torch.cuda.Stream()
+    st = side.cuda_stream
+    n = int(float(a.records.split(",")[0]))
+    bc_len, umi_len = 16, 12
+    orig, d, t = ctx.alloc(24 * n), ctx.alloc(24 * n), ctx.alloc(24 * n)
+    outs = [ctx.alloc(8 * n) for _ in range(4)]
+    g = torch.Generator(device="cuda").manual_seed(0x1B00009)
+
+    def timed(fn):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record(side)
+        fn()
+        e1.record(side)
+        e1.synchronize()
+        return e0.elapsed_time(e1)
+
+    def stat(v):
+        v = v[1:]
+        return {"median_ms": round(statistics.median(v), 3), "min_ms": round(min(v), 3), "max_ms": round(max(v), 3)}
+
+    def rounds(fn, before=None):
+        v = []
+        for _ in range(a.rounds + 1):
+            if before:
+                before()
+                torch.cuda.synchronize()
+            v.append(timed(fn))
+        return stat(v)
+
+    def restore():
+        _check(lib.ibu_device_copy(ctx._c, _dptr(d), _dptr(orig), 24 * n, st))
+
+    npairs, ntriples, nb, nbu = C.c_size_t(), C.c_size_t(), C.c_size_t(), C.c_size_t()
+    # the yardstick of the pair level: every record its own barcode, ibu_barcode_counts with outputs
+    ctx.generate(0x1B00005, 0, n, bc_len, umi_len, d)
+    ctx.sort_records(d, t, n)
+    ctx.synchronize()
+    own = rounds(lambda: _check(lib.ibu_barcode_counts(ctx._c, _dptr(d), n, _dptr(outs[0]), _dptr(outs[1]), _dptr(outs[2]), n, C.byref(nb), C.byref(nbu), st)))
+    print(json.dumps({"leg": "barcode_counts_every_record_its_own_barcode", "n": n, "distinct_barcodes": nb.value, **own}), flush=True)
+
+    for name in a.matrix.split(","):
+        ctx.generate(0x1B00005, 0, n, bc_len, umi_len, orig)
+        if name != "own_pair":                               # replace the columns (own_pair: random 16-base barcodes, index = i)
+            cols = [ctx.alloc(8 * n) for _ in range(3)]
+            ctx.deserialize(orig, n, cols[0], cols[1], cols[2])
+            ctx.synchronize()
+            bc, um, ix = (torch.as_tensor(c, device="cuda").view(torch.int64) for c in cols)
+            if name == "1e5x100":                            # 1e5 barcodes x 100 indices, a mean of 4 reads per molecule
+                n_umis = max(1, n // (4 * 100_000 * 100))
+                for lo in range(0, n, 1 << 26):
+                    hi = min(n, lo + (1 << 26))
+                    bc[lo:hi] = torch.randint(0, 100_000, (hi - lo,), generator=g, device="cuda", dtype=torch.int64)
+                    ix[lo:hi] = torch.randint(0, 100, (hi - lo,), generator=g, device="cuda", dtype=torch.int64)
+                    um[lo:hi] = torch.randint(0, n_umis, (hi - lo,), generator=g, device="cuda", dtype=torch.int64)
+            elif name == "one_pair":
+                bc.fill_(7)
+                ix.fill_(3)
+            else:
+                raise SystemExit(f"unknown --matrix input {name}")
+            torch.cuda.synchronize()
+            ctx.serialize(cols[0], cols[1], cols[2], n, orig)
+            ctx.synchronize()
+            for c in cols:
+                c.free()
+        restore()
+        res = {"leg": "count_matrix", "input": name, "n": n}
+        res["device_copy"] = rounds(lambda: _check(lib.ibu_device_copy(ctx._c, _dptr(t), _dptr(d), 24 * n, st)))
+        res["swap_out_of_place"] = rounds(lambda: _check(lib.ibu_records_swap_umi_index(ctx._c, _dptr(d), _dptr(t), n, st)))
+        res["swap_in_place"] = rounds(lambda: _check(lib.ibu_records_swap_umi_index(ctx._c, _dptr(d), _dptr(d), n, st)), before=restore)
+        res["device_copy_again"] = rounds(lambda: _check(lib.ibu_device_copy(ctx._c, _dptr(t), _dptr(d), 24 * n, st)))
+        # the four steps, each from the state the one before it leaves
+        res["step_swap"] = rounds(lambda: _check(lib.ibu_records_swap_umi_index(ctx._c, _dptr(d), _dptr(d), n, st)), before=restore)
+        res["step_sort_swapped"] = rounds(lambda: _check(lib.ibu_sort_records(ctx._c, _dptr(d), _dptr(t), n, st)),
+                                          before=lambda: (restore(), _check(lib.ibu_records_swap_umi_index(ctx._c, _dptr(d), _dptr(d), n, st))))
+        res["pair_counts_size_query"] = rounds(lambda: _check(lib.ibu_pair_counts(ctx._c, _dptr(d), n, None, None, None, None, 0, C.byref(npairs), C.byref(ntriples), st)))
+        res["step_pair_counts"] = rounds(lambda: _check(lib.ibu_pair_counts(ctx._c, _dptr(d), n, *[_dptr(o) for o in outs], n, C.byref(npairs), C.byref(ntriples), st)))
+        res["reduce"] = rounds(lambda: _check(lib.ibu_reduce(ctx._c, _dptr(d), n, st)))
+        res["barcode_counts_on_the_swapped_sorted_records"] = rounds(
+            lambda: _check(lib.ibu_barcode_counts(ctx._c, _dptr(d), n, _dptr(outs[0]), _dptr(outs[1]), _dptr(outs[2]), n, C.byref(nb), C.byref(nbu), st)))
+        res["step_swap_back"] = rounds(lambda: _check(lib.ibu_records_swap_umi_index(ctx._c, _dptr(d), _dptr(d), n, st)))
+        res["sort_unswapped"] = rounds(lambda: _check(lib.ibu_sort_records(ctx._c, _dptr(d), _dptr(t), n, st)), before=restore)
+        ne, nm = C.c_size_t(), C.c_size_t()
+        res["count_matrix_call"] = rounds(lambda: _check(lib.ibu_count_matrix(ctx._c, _dptr(d), _dptr(t), n, 0, *[_dptr(o) for o in outs], n, C.byref(ne), C.byref(nm), st)),
+                                          before=restore)
+        ctx.synchronize()
+        assert (ne.value, nm.value) == (npairs.value, ntriples.value), (ne.value, nm.value, npairs.value, ntriples.value)
+        assert int(outs[2].download(np.uint64, ne.value).sum()) == n and int(outs[3].download(np.uint64, ne.value).sum()) == nm.value
+        res.update({"entries": ne.value, "molecules": nm.value, "csr_rows": nb.value})
+        cm = res["count_matrix_call"]["median_ms"]
+        res["swap_share_of_call"] = round((res["step_swap"]["median_ms"] + res["step_swap_back"]["median_ms"]) / cm, 3)
+        res["swap_vs_copy"] = {"out_of_place": round(res["swap_out_of_place"]["median_ms"] / res["device_copy"]["median_ms"], 3),
+                               "in_place": round(res["swap_in_place"]["median_ms"] / res["device_copy"]["median_ms"], 3)}
+        res["swap_GBps"] = round(48 * n / res["swap_out_of_place"]["median_ms"] / 1e6)
+        print(json.dumps(res), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--matrix", default="", help="count-matrix legs instead of the barcode leg: a comma list of inputs out of 1e5x100, own_pair, one_pair")
     ap.add_argument("--records", default="1e9")
     ap.add_argument("--lens", default="10,12;16,12")
     ap.add_argument("--rounds", type=int, default=5)
     ap.add_argument("--whitelist", type=int, default=0, help="K > 0: barcodes drawn from K distinct ones, skewed (rank ~ K u^3), as tools/sortbench.py --whitelist")
     a = ap.parse_args()
+    if a.matrix:
+        return matrix_legs(a)
     if a.whitelist:
         import torch                                         # before the library, as bench.py does
         torch.cuda.init()
