@@ -43,6 +43,18 @@ pub struct ibu_correct_counts_t {
     pub unmatched: u64,
 }
 #[repr(C)]
+#[derive(Default, Debug, Clone, Copy, PartialEq, Eq)]
+pub struct ibu_molecule_counts_t {
+    pub molecules: u64,
+    pub candidates: u64,
+    pub resolved: u64,
+    pub tied: u64,
+    pub reads_kept: u64,
+    pub reads_minor: u64,
+    pub reads_tied: u64,
+    pub reserved: u64,
+}
+#[repr(C)]
 #[derive(Default, Clone, Copy)]
 pub struct ibu_ring_config_t {
     pub slots: u32,
@@ -218,6 +230,8 @@ extern "C" {
     pub fn ibu_whitelist_destroy(wl: *mut ibu_whitelist_t);
     pub fn ibu_correct_barcodes(ctx: *mut ibu_ctx_t, wl: *const ibu_whitelist_t, d_records: *mut c_void, n: usize, max_mismatches: u32,
                                 d_class: *mut u8, counts: *mut ibu_correct_counts_t, stream: *mut c_void) -> i32;
+    pub fn ibu_classify_molecules(ctx: *mut ibu_ctx_t, d_sorted_records: *const c_void, n: usize, flags: u32, d_class: *mut u8,
+                                  counts: *mut ibu_molecule_counts_t, stream: *mut c_void) -> i32;
     pub fn ibu_select_records(ctx: *mut ibu_ctx_t, d_records: *const c_void, d_class: *const u8, n: usize, keep_mask: u32,
                               d_out: *mut c_void, cap: usize, n_out: *mut usize, stream: *mut c_void) -> i32;
     pub fn ibu_bgzf_scan(buf: *const u8, len: usize, is_final: i32, blocks: *mut ibu_inflate_block_t, cap: usize, n_blocks: *mut usize,

@@ -671,6 +671,16 @@ pub mod device {
             check(unsafe { ffi::ibu_correct_barcodes(self.raw, wl.raw, recs.ptr, n, max_mismatches, cls, &mut c, std::ptr::null_mut()) })?;
             Ok(c)
         }
+        /// `ibu_classify_molecules` over records sorted by (barcode, umi, index): one class byte per record into `class` (n bytes;
+        /// `None`: totals only) — 0 for the index its (barcode, umi) molecule was seen with strictly most often, 1 for the molecule's
+        /// other reads, 2 for every read of a molecule whose top is shared (`tie_first`: the first index at the top is kept, the
+        /// rest is 1).  `select_records(.., 1 << 0, ..)` then drops the chimeric reads.
+        pub fn classify_molecules(&self, sorted: &DeviceBuf, n: usize, class: Option<&DeviceBuf>, tie_first: bool) -> Result<ffi::ibu_molecule_counts_t> {
+            let mut c = ffi::ibu_molecule_counts_t::default();
+            let cls = class.map_or(std::ptr::null_mut(), |b| b.ptr as *mut u8);
+            check(unsafe { ffi::ibu_classify_molecules(self.raw, sorted.ptr, n, if tie_first { 1 } else { 0 }, cls, &mut c, std::ptr::null_mut()) })?;
+            Ok(c)
+        }
         /// Stable compaction by class (`ibu_select_records`): the records whose class has its bit set in `keep_mask`, in input
         /// order, into `out` (which must hold them: ask with `out = None` first).  Returns how many.
         pub fn select_records(&self, recs: &DeviceBuf, class: &DeviceBuf, n: usize, keep_mask: u32, out: Option<&DeviceBuf>) -> Result<usize> {

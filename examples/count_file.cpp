@@ -7,11 +7,16 @@
 // new: ibu_barcode_counts on the records as ibu_count_matrix leaves them with IBU_COUNT_LEAVE_SWAPPED ({barcode, index, umi})
 // returns each barcode and, as its "unique UMIs", its number of distinct indices; they are printed behind the matrix as
 //   #row<TAB>barcode<TAB>entries<TAB>reads
-//   count_file IN [WHITELIST.txt]
+//   count_file [--resolve | --resolve=first] IN [WHITELIST.txt]
 // WHITELIST.txt: one barcode per line, as many bases as the file's header says.
+// --resolve: a (barcode, UMI) molecule seen with several index values counts once, under the index with strictly the most reads, and
+// not at all when the top is shared (--resolve=first: under the smallest index at the top) — sort, ibu_classify_molecules,
+// ibu_select_records in front of the matrix; the seven totals go to stderr.
 #include <cstdio>
+#include <cstring>
 #include <fstream>
 #include <string>
+#include <utility>
 #include <vector>
 
 #include "ibu.hpp"
@@ -23,7 +28,11 @@ static std::string decode(uint64_t code, uint32_t len) {        // base i at bit
 }
 
 int main(int argc, char** argv) {
-  if (argc < 2) { std::fprintf(stderr, "usage: count_file IN [WHITELIST.txt]\n"); return 2; }
+  int resolve = 0;                                              // 1: --resolve, 2: --resolve=first
+  if (argc > 1 && !std::strcmp(argv[1], "--resolve")) resolve = 1;
+  if (argc > 1 && !std::strcmp(argv[1], "--resolve=first")) resolve = 2;
+  if (resolve) { --argc; ++argv; }
+  if (argc < 2) { std::fprintf(stderr, "usage: count_file [--resolve | --resolve=first] IN [WHITELIST.txt]\n"); return 2; }
   try {
     using namespace ibu;
     device::Context ctx(0);
@@ -58,6 +67,18 @@ int main(int argc, char** argv) {
                    (unsigned long long)c.corrected, (unsigned long long)c.ambiguous, (unsigned long long)c.unmatched, kept);
       recs = tmp.ptr();                                         // the kept records live in tmp; the input array is scratch from here on
       scratch = d_recs;
+    }
+    if (resolve && kept) {                                      // sort -> classify -> keep class 0: one index per molecule
+      ctx.sort_records(recs, scratch, kept);
+      device::DeviceBuffer d_class(ctx, kept);
+      const device::MoleculeCounts m = ctx.classify_molecules(recs, kept, d_class.as<uint8_t>(), resolve == 2);
+      const size_t before = kept;
+      kept = ctx.select_records(recs, d_class.as<uint8_t>(), before, 1u << IBU_MOLECULE_KEPT, scratch, before);
+      ctx.synchronize();
+      std::fprintf(stderr, "%zu records: molecules %llu, candidates %llu, resolved %llu, tied %llu; reads kept %llu, minor %llu, tied %llu\n", before,
+                   (unsigned long long)m.molecules, (unsigned long long)m.candidates, (unsigned long long)m.resolved, (unsigned long long)m.tied,
+                   (unsigned long long)m.reads_kept, (unsigned long long)m.reads_minor, (unsigned long long)m.reads_tied);
+      std::swap(recs, scratch);
     }
     // the matrix; the records stay {barcode, index, umi} so that the row lengths can be read off them
     const auto entries = ctx.count_matrix(recs, scratch, kept, 0, /*leave_swapped=*/true);

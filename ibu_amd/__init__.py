@@ -14,7 +14,7 @@ from collections import namedtuple
 import numpy as np
 
 from . import _lib
-from ._lib import CAllocProbe, CCorrectCounts, CDecodeSink, CErrorDetail, CKeyPlan, CHeader, CNumaInfo, CProcessorVTable, CRecord, CReduceResult, CRingConfig, CStreamStats
+from ._lib import CAllocProbe, CCorrectCounts, CDecodeSink, CMoleculeCounts, CErrorDetail, CKeyPlan, CHeader, CNumaInfo, CProcessorVTable, CRecord, CReduceResult, CRingConfig, CStreamStats
 
 lib = _lib.load()
 
@@ -27,6 +27,11 @@ BATCH_SIZE = 1024 * 1024  # mmap.rs:284
 
 PROC_REDUCE, PROC_DECODE = 1, 2
 COUNT_LEAVE_SWAPPED = 1  # ibu_count_matrix flags (IBU_COUNT_LEAVE_SWAPPED)
+MOLECULE_KEPT, MOLECULE_MINOR, MOLECULE_TIED = 0, 1, 2  # the classes of ibu_classify_molecules (IBU_MOLECULE_*)
+MOLECULES_TIE_FIRST = 1  # ibu_classify_molecules flags (IBU_MOLECULES_TIE_FIRST)
+
+#: the totals of one ibu_classify_molecules call (ibu_molecule_counts_t without its reserved word)
+MoleculeCounts = namedtuple("MoleculeCounts", "molecules candidates resolved tied reads_kept reads_minor reads_tied")
 
 #: numpy view of a `&[Record]` (bytemuck::cast_slice)
 REC_DTYPE = np.dtype([("barcode", "<u8"), ("umi", "<u8"), ("index", "<u8")])
@@ -945,6 +950,22 @@ class Context:
                                     *[_dptr(o) for o in outs], cap, C.byref(ne), C.byref(nm), stream))
         self.synchronize(stream)
         return tuple(o.download(np.uint64, count=ne.value) for o in outs)
+
+    def classify_molecules(self, d_sorted_records, n, d_class=None, tie_first=False, counts=True, stream=None):
+        """ibu_classify_molecules over n device records sorted by (barcode, umi, index): one class byte per record — MOLECULE_KEPT
+        for the index its (barcode, umi) molecule was seen with strictly most often, MOLECULE_MINOR for the molecule's other
+        reads, MOLECULE_TIED for all reads of a molecule whose top is shared (tie_first: the first index at the top is kept and
+        the rest is minor instead).  -> (d_class, MoleculeCounts).  d_class: n bytes of device memory; None allocates them, False
+        asks for the totals only (and returns None in its place).  counts=False returns None for the totals and does not wait
+        for them.  select_records(d_records, d_class, n, keep_mask=1 << MOLECULE_KEPT) then drops the chimeric reads."""
+        if d_class is None:
+            d_class = self.alloc(max(n, 16))
+        elif d_class is False:
+            d_class = None
+        c = CMoleculeCounts() if counts else None
+        _check(lib.ibu_classify_molecules(self._c, _dptr(d_sorted_records), n, MOLECULES_TIE_FIRST if tie_first else 0,
+                                          _dptr(d_class), C.byref(c) if counts else None, stream))
+        return d_class, (MoleculeCounts(*[int(getattr(c, f)) for f in MoleculeCounts._fields]) if counts else None)
 
     # barcode correction against a whitelist
     def correct_barcodes(self, wl, d_records, n, max_mismatches=1, d_class=None, counts=True, stream=None):

@@ -34,6 +34,11 @@ class CCorrectCounts(C.Structure):  # ibu_correct_counts_t
     _fields_ = [("exact", u64), ("corrected", u64), ("ambiguous", u64), ("unmatched", u64)]
 
 
+class CMoleculeCounts(C.Structure):  # ibu_molecule_counts_t
+    _fields_ = [("molecules", u64), ("candidates", u64), ("resolved", u64), ("tied", u64), ("reads_kept", u64), ("reads_minor", u64),
+                ("reads_tied", u64), ("reserved", u64)]
+
+
 class CRingConfig(C.Structure):  # ibu_ring_config_t
     _fields_ = [("slots", u32), ("slot_records", u32), ("feeder_threads", u32), ("reserved", u32)]
 
@@ -152,6 +157,7 @@ SIGNATURES = {
     "ibu_whitelist_create": (i32, [vp, vp, sz, u32, vp, P(vp)]),
     "ibu_whitelist_info": (i32, [vp, P(u32), P(sz), P(sz)]),
     "ibu_whitelist_destroy": (None, [vp]),
+    "ibu_classify_molecules": (i32, [vp, vp, sz, u32, vp, P(CMoleculeCounts), vp]),
     "ibu_correct_barcodes": (i32, [vp, vp, vp, sz, u32, vp, P(CCorrectCounts), vp]),
     "ibu_select_records": (i32, [vp, vp, vp, sz, u32, vp, sz, P(sz), vp]),
     "ibu_bgzf_scan": (i32, [vp, sz, i32, P(CInflateBlock), sz, P(sz), P(sz), P(C.c_uint64)]),

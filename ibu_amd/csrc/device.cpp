@@ -917,6 +917,39 @@ extern "C" int32_t ibu_pair_counts(ibu_ctx_t* ctx, const void* d_sorted_records,
                             d_records_per_pair, d_distinct_third, st));
   return IBU_OK;
 }
+// One index per (w0, w1) molecule: the candidate with strictly the most records (k_aggregate.hip; the rule: include/ibu_hip.h).
+extern "C" int32_t ibu_classify_molecules(ibu_ctx_t* ctx, const void* d_sorted_records, size_t n, uint32_t flags, uint8_t* d_class,
+                                          ibu_molecule_counts_t* counts, void* stream) {
+  int32_t rc = check_ctx(ctx);
+  if (rc) return rc;
+  if (flags & ~(uint32_t)IBU_MOLECULES_TIE_FIRST) return err_arg("unknown bit in flags");
+  if (counts) *counts = ibu_molecule_counts_t{0, 0, 0, 0, 0, 0, 0, 0};
+  if (n == 0) return IBU_OK;
+  if (!d_sorted_records || !aligned8(d_sorted_records)) return err_arg("d_sorted_records must be non-NULL and 8-byte aligned");
+  if (n >= (1ull << 40)) return err_arg("classify_molecules handles fewer than 2^40 records per call");
+  hipStream_t st = pick_stream(ctx, stream);
+  rc = ensure_sort_scratch(ctx, molecules_scratch_bytes(n));
+  if (rc) return rc;
+  IBU_HIP(launch_runs_count(ctx->cfg, d_sorted_records, n, ctx->d_sort_scratch, ctx->sort_scratch_bytes, false, st, true));
+  IBU_HIP(hipMemcpyAsync(ctx->h_pinned, ctx->d_sort_scratch, 2 * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
+  IBU_HIP(hipStreamSynchronize(st));
+  const uint64_t molecules = ctx->h_pinned[0], candidates = ctx->h_pinned[1];
+  rc = ensure_runs_scratch(ctx, molecules_run_scratch_bytes(candidates));
+  if (rc) return rc;
+  IBU_HIP(launch_molecules_classify(ctx->cfg, d_sorted_records, n, ctx->d_sort_scratch, ctx->d_runs_scratch, candidates,
+                                    (flags & IBU_MOLECULES_TIE_FIRST) != 0, d_class, st));
+  if (!counts) return IBU_OK;
+  IBU_HIP(hipMemcpyAsync(ctx->h_pinned, ctx->d_runs_scratch, 5 * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
+  IBU_HIP(hipStreamSynchronize(st));
+  counts->molecules = molecules;
+  counts->candidates = candidates;
+  counts->resolved = ctx->h_pinned[0];
+  counts->tied = ctx->h_pinned[1];
+  counts->reads_kept = ctx->h_pinned[2];
+  counts->reads_minor = ctx->h_pinned[3];
+  counts->reads_tied = ctx->h_pinned[4];
+  return IBU_OK;
+}
 extern "C" int32_t ibu_count_matrix(ibu_ctx_t* ctx, void* d_records, void* d_tmp, size_t n, uint32_t flags, uint64_t* d_barcodes,
                                     uint64_t* d_indices, uint64_t* d_reads, uint64_t* d_umis, size_t cap, size_t* n_entries,
                                     size_t* n_molecules, void* stream) {

@@ -125,6 +125,13 @@ hipError_t launch_runs_emit(const LaunchCfg&, const void* recs, size_t n, const 
                             uint64_t n_pairs, uint64_t* barcodes, uint64_t* counts, uint64_t* uniq, hipStream_t st);
 hipError_t launch_pairs_emit(const LaunchCfg&, const void* recs, size_t n, const void* scratch, void* run_scratch, uint64_t n_pairs,
                              uint64_t n_triples, uint64_t* first, uint64_t* second, uint64_t* counts, uint64_t* distinct, hipStream_t st);
+// one index per molecule (ibu_classify_molecules, k_aggregate.hip).  launch_runs_count(pair_level = true) on a scratch of
+// molecules_scratch_bytes(n) comes first; with its second total (the candidates) the caller sizes the run scratch.  Leaves one class
+// byte per record in d_class (nullable) and u64[5] at the front of run_scratch: resolved and tied molecules, records of class 0, 1, 2.
+size_t molecules_scratch_bytes(size_t n);
+size_t molecules_run_scratch_bytes(uint64_t candidates);
+hipError_t launch_molecules_classify(const LaunchCfg&, const void* recs, size_t n, void* scratch, void* run_scratch, uint64_t candidates,
+                                     bool tie_first, uint8_t* d_class, hipStream_t st);
 // record i of dst = {w0, w2, w1} of record i of src; dst == src (in place) or disjoint (k_records.hip)
 hipError_t launch_swap_fields(const LaunchCfg&, const void* src, void* dst, size_t n, hipStream_t st);
 // barcode correction against a whitelist (k_whitelist.hip).  The table: `slots` 64-bit keys (a power of two, at least 2 w), all ones =

@@ -362,6 +362,7 @@ class MmapReader {
 namespace device {
 class Whitelist;
 using CorrectCounts = ibu_correct_counts_t;
+using MoleculeCounts = ibu_molecule_counts_t;
 // one entry of ibu_pair_counts / ibu_count_matrix: (barcode, index, reads, distinct UMIs) on the count-matrix path
 struct MatrixEntry { uint64_t first, second, records, distinct; };
 inline int device_count() { int32_t n = 0; return ibu_device_count(&n) == IBU_OK ? n : 0; }
@@ -442,6 +443,13 @@ class Context {
                                         void* st = nullptr);
   inline void correct_barcodes_async(const Whitelist& wl, void* d_recs, size_t n, uint32_t max_mismatches = 1, uint8_t* d_class = nullptr,
                                      void* st = nullptr);
+  // one index per (barcode, umi) molecule of sorted records (ibu_classify_molecules): d_class (n bytes, or nullptr for the totals
+  // only) gets IBU_MOLECULE_KEPT / _MINOR / _TIED per record; select_records(.., 1u << IBU_MOLECULE_KEPT, ..) drops the chimeric reads
+  MoleculeCounts classify_molecules(const void* d_sorted, size_t n, uint8_t* d_class, bool tie_first = false, void* st = nullptr) {
+    MoleculeCounts c{};
+    check(ibu_classify_molecules(c_, d_sorted, n, tie_first ? IBU_MOLECULES_TIE_FIRST : 0u, d_class, &c, st));
+    return c;
+  }
   // stable compaction by class (ibu_select_records) -> how many records went to d_out (capacity `cap` records); d_out == nullptr
   // and cap == 0: only count
   size_t select_records(const void* d_recs, const uint8_t* d_class, size_t n, uint32_t keep_mask, void* d_out, size_t cap, void* st = nullptr) {

@@ -539,6 +539,50 @@ int32_t ibu_pair_counts(ibu_ctx_t* ctx, const void* d_sorted_records, size_t n, 
 int32_t ibu_count_matrix(ibu_ctx_t* ctx, void* d_records, void* d_tmp, size_t n, uint32_t flags, uint64_t* d_barcodes,
                          uint64_t* d_indices, uint64_t* d_reads, uint64_t* d_umis, size_t cap, size_t* n_entries, size_t* n_molecules,
                          void* stream);
+/* One index per molecule, on the device (k_aggregate.hip) — the step between ibu_sort_records and the count matrix that drops
+ * chimeric reads: a (barcode, umi) seen with two or more index values (PCR chimeras, index hopping, multi-mapped reads) would
+ * otherwise be counted once under every one of them.  The reference has no such function; the semantics are this library's and are
+ * stated in full here.  Write w0, w1, w2 for the three 64-bit words of a record in storage order.
+ *   A MOLECULE is a maximal run of consecutive records with equal (w0, w1).
+ *   A CANDIDATE is a maximal run of consecutive records with equal (w0, w1, w2).  Its `reads` is its length.
+ *   For a molecule, `best` is the largest `reads` among its candidates.
+ * Every record gets one class byte:
+ *   0 kept   its candidate is the only one of its molecule with reads == best (a molecule with one candidate included)
+ *   1 minor  its molecule has exactly one candidate at best, and this is another one
+ *   2 tied   its molecule has two or more candidates at best (all records of the molecule, the smaller candidates too)
+ * flags: IBU_MOLECULES_TIE_FIRST changes the tied case only — in a tied molecule the first candidate at best in input order is
+ * class 0 and every other record of the molecule is class 1 (on sorted input that candidate has the smallest index); class 2 then
+ * never occurs.  Any other bit is IBU_ERR_INVALID_ARG, and nothing is touched.
+ * On records sorted by (barcode, umi, index) the runs are the molecules and their indices.  On unsorted input the result is the same
+ * run-level computation on the runs as they stand: a molecule that is interrupted and returns is two molecules, as ibu_barcode_counts
+ * and ibu_pair_counts document for themselves.  The records are never written.
+ * d_class (nullable: totals only): n bytes.  counts (nullable): molecules / candidates = the runs of equal (w0, w1) / of equal
+ * (w0, w1, w2); resolved = molecules with two or more candidates and exactly one at best; tied = molecules with two or more at best
+ * (counted under IBU_MOLECULES_TIE_FIRST too); reads_kept + reads_minor + reads_tied = n, the records of each class; reserved = 0.
+ * ibu_select_records(..., keep_mask = 1 << IBU_MOLECULE_KEPT) then gives the chimera-free records in input order, still sorted.
+ * Records 8-byte aligned: a 16-byte aligned array takes the tiled path, an 8- but not 16-byte aligned one peels one record, as
+ * ibu_pair_counts does.  n < 2^40.  n == 0 is OK: nothing is touched and all totals are 0.  A NULL context is an error.
+ * Synchronises `stream` once (the candidate and molecule totals come back to size the scratch); the class writes may still be queued
+ * on return.  With counts != NULL it waits a second time, for the totals, which are final only behind the verdicts.
+ * Traffic: the records are read twice (count, emit); 8 B per candidate travel once each way (the candidate table: first row, and
+ * whether it begins a molecule), the verdict is 1 B per candidate, the class write 1 B per record — filled from the table and from
+ * 16 B of head ballots per 128 records the emit pass keeps, not from the records.  A molecule of any number of candidates costs the
+ * same per candidate (a segmented scan per 1024 candidates, a second one over the blocks).  Scratch: the context's sort scratch for
+ * the per-segment tables and the ballots (n / 8 bytes), and 9.1 B per candidate of its run scratch (8 table + 1 verdict + 68 B per
+ * 1024 candidates of block summaries), grown on demand. */
+#define IBU_MOLECULE_KEPT 0
+#define IBU_MOLECULE_MINOR 1
+#define IBU_MOLECULE_TIED 2
+#define IBU_MOLECULES_TIE_FIRST 1u
+typedef struct ibu_molecule_counts {
+  uint64_t molecules, candidates;                 /* runs of equal (w0,w1) / of equal (w0,w1,w2) */
+  uint64_t resolved;                              /* molecules with >= 2 candidates and exactly one at best */
+  uint64_t tied;                                  /* molecules with >= 2 candidates at best (counted under TIE_FIRST too) */
+  uint64_t reads_kept, reads_minor, reads_tied;   /* records per class; their sum is n */
+  uint64_t reserved;                              /* 0 */
+} ibu_molecule_counts_t;
+int32_t ibu_classify_molecules(ibu_ctx_t* ctx, const void* d_sorted_records, size_t n, uint32_t flags, uint8_t* d_class,
+                               ibu_molecule_counts_t* counts, void* stream);
 /* Barcode correction against a whitelist, on the device (k_whitelist.hip) — the step between a load and ibu_sort_records /
  * ibu_barcode_counts that makes the latter's "a caller that knows a bound (its whitelist)" true of real input.  The reference has
  * no such function (as it has no sort and no aggregation); the semantics are this library's and are stated in full here.

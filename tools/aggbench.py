@@ -4,6 +4,7 @@ timed by phase — the size query (count pass + scan + 16-byte read-back) and th
 into preallocated device arrays, no download.
   python tools/aggbench.py [--records 1e9] [--lens 10,12] [--rounds 5]
   python tools/aggbench.py --matrix 1e5x100,own_pair,one_pair [--records 1e9]     the count-matrix legs (matrix_legs below)
+  python tools/aggbench.py --molecules [--records 1e9] [--reads-per-molecule 4] [--second-candidate 0.05]     ibu_classify_molecules (molecule_legs below)
 bc_len 10 gives 2^20 distinct barcodes (a single-cell whitelist's order of magnitude); 16 gives ~n runs of length one."""
 import argparse
 import ctypes as C
@@ -134,14 +135,95 @@ def matrix_legs(a):
         print(json.dumps(res), flush=True)
 
 
+def molecule_legs(a):
+    """--molecules: ibu_classify_molecules on resident sorted 16/12 records, timed with events on a side stream (the first round
+    is the warm-up), against ibu_pair_counts with outputs, ibu_reduce (one plain read) and ibu_device_copy on the same arrays.
+    The records: --reads-per-molecule consecutive records per (barcode, umi), 4096 molecules per barcode; a share
+    --second-candidate of the molecules has its last read (half of them: its last two reads — a tie at four reads) under the next
+    index."""
+    import numpy as np
+    import torch                                             # before the library, as bench.py does
+    torch.cuda.init()
+    import ibu_amd as ia
+    from ibu_amd import _dptr, _check, lib, _lib
+
+    ctx = ia.Context(0)
+    side = torch.cuda.Stream()
+    st = side.cuda_stream
+    n = int(float(a.records.split(",")[0]))
+    rpm = a.reads_per_molecule
+    cols = [ctx.alloc(8 * n) for _ in range(3)]
+    bc, um, ix = (torch.as_tensor(c, device="cuda").view(torch.int64) for c in cols)
+    cut = int(a.second_candidate * (1 << 20))
+    for lo in range(0, n, 1 << 26):
+        hi = min(n, lo + (1 << 26))
+        i = torch.arange(lo, hi, device="cuda", dtype=torch.int64)
+        mol, k = i // rpm, i % rpm
+        h = ((mol * 0x1E3779B97F4A7C15) >> 20) & 0xFFFFF    # 20 pseudo-random bits per molecule
+        second = (h < cut) & (k >= rpm - 1 - (h & 1))
+        bc[lo:hi], um[lo:hi] = mol >> 12, mol & 4095
+        ix[lo:hi] = ((h >> 8) % 100) * 2 + second.to(torch.int64)
+    del i, mol, k, h, second
+    torch.cuda.synchronize()
+    d, t, d_class = ctx.alloc(24 * n), ctx.alloc(24 * n), ctx.alloc(n)
+    ctx.serialize(cols[0], cols[1], cols[2], n, d)
+    ctx.synchronize()
+    for c in cols:
+        c.free()
+    assert ctx.is_sorted(d, n)
+    cap = n // rpm + 16
+    outs = [ctx.alloc(8 * cap) for _ in range(4)]
+
+    def timed(fn):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record(side)
+        fn()
+        e1.record(side)
+        e1.synchronize()
+        return e0.elapsed_time(e1)
+
+    def rounds(fn):
+        v = [timed(fn) for _ in range(a.rounds + 1)][1:]
+        return {"median_ms": round(statistics.median(v), 3), "min_ms": round(min(v), 3), "max_ms": round(max(v), 3)}
+
+    counts = _lib.CMoleculeCounts()
+    npairs, ntriples = C.c_size_t(), C.c_size_t()
+    res = {"leg": "classify_molecules", "n": n, "reads_per_molecule": rpm, "second_candidate": a.second_candidate}
+    res["device_copy"] = rounds(lambda: _check(lib.ibu_device_copy(ctx._c, _dptr(t), _dptr(d), 24 * n, st)))
+    res["reduce"] = rounds(lambda: _check(lib.ibu_reduce(ctx._c, _dptr(d), n, st)))
+    res["pair_counts"] = rounds(lambda: _check(lib.ibu_pair_counts(ctx._c, _dptr(d), n, *[_dptr(o) for o in outs], cap, C.byref(npairs), C.byref(ntriples), st)))
+    res["classify_classes_only"] = rounds(lambda: _check(lib.ibu_classify_molecules(ctx._c, _dptr(d), n, 0, _dptr(d_class), None, st)))
+    res["classify_totals_only"] = rounds(lambda: _check(lib.ibu_classify_molecules(ctx._c, _dptr(d), n, 0, None, C.byref(counts), st)))
+    res["classify"] = rounds(lambda: _check(lib.ibu_classify_molecules(ctx._c, _dptr(d), n, 0, _dptr(d_class), C.byref(counts), st)))
+    res["classify_tie_first"] = rounds(lambda: _check(lib.ibu_classify_molecules(ctx._c, _dptr(d), n, 1, _dptr(d_class), C.byref(counts), st)))
+    res["pair_counts_again"] = rounds(lambda: _check(lib.ibu_pair_counts(ctx._c, _dptr(d), n, *[_dptr(o) for o in outs], cap, C.byref(npairs), C.byref(ntriples), st)))
+    _check(lib.ibu_classify_molecules(ctx._c, _dptr(d), n, 0, _dptr(d_class), C.byref(counts), st))
+    ctx.synchronize()
+    assert (counts.molecules, counts.candidates) == (npairs.value, ntriples.value)
+    assert counts.reads_kept + counts.reads_minor + counts.reads_tied == n
+    cls = torch.as_tensor(d_class, device="cuda").view(torch.uint8)[:n]
+    assert [int((cls == c).sum()) for c in (0, 1, 2)] == [counts.reads_kept, counts.reads_minor, counts.reads_tied]
+    res.update({k: int(getattr(counts, k)) for k in ("molecules", "candidates", "resolved", "tied", "reads_kept", "reads_minor", "reads_tied")})
+    pc = min(res["pair_counts"]["median_ms"], res["pair_counts_again"]["median_ms"])
+    res["classify_vs_pair_counts"] = round(res["classify"]["median_ms"] / pc, 3)
+    res["classes_only_vs_pair_counts"] = round(res["classify_classes_only"]["median_ms"] / pc, 3)
+    res["totals_only_vs_pair_counts"] = round(res["classify_totals_only"]["median_ms"] / pc, 3)
+    print(json.dumps(res), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--molecules", action="store_true", help="the ibu_classify_molecules legs instead of the barcode leg")
+    ap.add_argument("--reads-per-molecule", type=int, default=4)
+    ap.add_argument("--second-candidate", type=float, default=0.05, help="--molecules: the share of molecules with a second index")
     ap.add_argument("--matrix", default="", help="count-matrix legs instead of the barcode leg: a comma list of inputs out of 1e5x100, own_pair, one_pair")
     ap.add_argument("--records", default="1e9")
     ap.add_argument("--lens", default="10,12;16,12")
     ap.add_argument("--rounds", type=int, default=5)
     ap.add_argument("--whitelist", type=int, default=0, help="K > 0: barcodes drawn from K distinct ones, skewed (rank ~ K u^3), as tools/sortbench.py --whitelist")
     a = ap.parse_args()
+    if a.molecules:
+        return molecule_legs(a)
     if a.matrix:
         return matrix_legs(a)
     if a.whitelist:
