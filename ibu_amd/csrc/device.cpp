@@ -693,6 +693,16 @@ static int32_t ensure_runs_scratch(ibu_ctx* ctx, size_t need) {
   ctx->runs_scratch_bytes = need;
   return IBU_OK;
 }
+// The first half of every run-length aggregation: a count scratch of `need` bytes, the count pass, and its two totals (runs, ranked
+// heads) read back into ctx->h_pinned[0..1].  Synchronises the stream.
+static int32_t runs_count_totals(ibu_ctx* ctx, const void* d_sorted_records, size_t n, size_t need, RunsCount what, hipStream_t st) {
+  int32_t rc = ensure_sort_scratch(ctx, need);
+  if (rc) return rc;
+  IBU_HIP(launch_runs_count(ctx->cfg, d_sorted_records, n, ctx->d_sort_scratch, ctx->sort_scratch_bytes, what, st));
+  IBU_HIP(hipMemcpyAsync(ctx->h_pinned, ctx->d_sort_scratch, 2 * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
+  IBU_HIP(hipStreamSynchronize(st));
+  return IBU_OK;
+}
 // BarcodeAnalyzer (parallel.rs:72-98) on sorted device records.
 extern "C" int32_t ibu_barcode_counts(ibu_ctx_t* ctx, const void* d_sorted_records, size_t n, uint64_t* d_barcodes,
                                       uint64_t* d_counts, uint64_t* d_unique_umis, size_t cap, size_t* n_barcodes,
@@ -706,16 +716,12 @@ extern "C" int32_t ibu_barcode_counts(ibu_ctx_t* ctx, const void* d_sorted_recor
   if (!d_sorted_records || !aligned8(d_sorted_records)) return err_arg("d_sorted_records must be non-NULL and 8-byte aligned");
   if (n >= (1ull << 40)) return err_arg("barcode_counts handles fewer than 2^40 records per call");
   hipStream_t st = pick_stream(ctx, stream);
-  rc = ensure_sort_scratch(ctx, runs_scratch_bytes(n));
-  if (rc) return rc;
   const bool size_query = !d_barcodes && !d_counts && cap == 0;
   // (with outputs to fill, the count pass keeps every segment's first few run heads: the emit pass then reads the records again only
   // where runs are short — k_aggregate.hip)
-  IBU_HIP(launch_runs_count(ctx->cfg, d_sorted_records, n, ctx->d_sort_scratch, ctx->sort_scratch_bytes, !size_query, st));
-  IBU_HIP(hipMemcpyAsync(ctx->h_pinned, ctx->d_sort_scratch, 2 * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
-  IBU_HIP(hipStreamSynchronize(st));
-  const uint64_t* tot = reinterpret_cast<const uint64_t*>(ctx->h_pinned);
-  const uint64_t runs = tot[0], pairs = tot[1];
+  rc = runs_count_totals(ctx, d_sorted_records, n, runs_scratch_bytes(n), size_query ? RunsCount::Barcode : RunsCount::BarcodeStash, st);
+  if (rc) return rc;
+  const uint64_t runs = ctx->h_pinned[0], pairs = ctx->h_pinned[1];
   *n_barcodes = runs;
   if (n_barcode_umi_pairs) *n_barcode_umi_pairs = pairs;
   if (size_query) return IBU_OK;
@@ -723,7 +729,7 @@ extern "C" int32_t ibu_barcode_counts(ibu_ctx_t* ctx, const void* d_sorted_recor
   if (runs > cap) return err_arg("output capacity is smaller than the number of distinct barcodes (see *n_barcodes)");
   rc = ensure_runs_scratch(ctx, runs_emit_scratch_bytes(runs));
   if (rc) return rc;
-  IBU_HIP(launch_runs_emit(ctx->cfg, d_sorted_records, n, ctx->d_sort_scratch, true, ctx->d_runs_scratch, runs, pairs, d_barcodes,
+  IBU_HIP(launch_runs_emit(ctx->cfg, d_sorted_records, n, ctx->d_sort_scratch, ctx->d_runs_scratch, runs, pairs, d_barcodes, nullptr,
                            d_counts, d_unique_umis, st));
   return IBU_OK;
 }
@@ -895,12 +901,9 @@ extern "C" int32_t ibu_pair_counts(ibu_ctx_t* ctx, const void* d_sorted_records,
   if (!d_sorted_records || !aligned8(d_sorted_records)) return err_arg("d_sorted_records must be non-NULL and 8-byte aligned");
   if (n >= (1ull << 40)) return err_arg("pair_counts handles fewer than 2^40 records per call");
   hipStream_t st = pick_stream(ctx, stream);
-  rc = ensure_sort_scratch(ctx, runs_scratch_bytes(n));
+  rc = runs_count_totals(ctx, d_sorted_records, n, runs_scratch_bytes(n), RunsCount::Pair, st);
   if (rc) return rc;
   const bool size_query = !d_first && !d_second && !d_records_per_pair && cap == 0;
-  IBU_HIP(launch_runs_count(ctx->cfg, d_sorted_records, n, ctx->d_sort_scratch, ctx->sort_scratch_bytes, false, st, true));
-  IBU_HIP(hipMemcpyAsync(ctx->h_pinned, ctx->d_sort_scratch, 2 * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
-  IBU_HIP(hipStreamSynchronize(st));
   const uint64_t pairs = ctx->h_pinned[0], triples = ctx->h_pinned[1];
   *n_pairs = pairs;
   if (n_triples) *n_triples = triples;
@@ -913,11 +916,11 @@ extern "C" int32_t ibu_pair_counts(ibu_ctx_t* ctx, const void* d_sorted_records,
                      (unsigned long long)cap, (unsigned long long)pairs);
   rc = ensure_runs_scratch(ctx, runs_emit_scratch_bytes(pairs));
   if (rc) return rc;
-  IBU_HIP(launch_pairs_emit(ctx->cfg, d_sorted_records, n, ctx->d_sort_scratch, ctx->d_runs_scratch, pairs, triples, d_first, d_second,
-                            d_records_per_pair, d_distinct_third, st));
+  IBU_HIP(launch_runs_emit(ctx->cfg, d_sorted_records, n, ctx->d_sort_scratch, ctx->d_runs_scratch, pairs, triples, d_first, d_second,
+                           d_records_per_pair, d_distinct_third, st));
   return IBU_OK;
 }
-// One index per (w0, w1) molecule: the candidate with strictly the most records (k_aggregate.hip; the rule: include/ibu_hip.h).
+// One index per (w0, w1) molecule: the candidate with strictly the most records (k_molecules.hip; the rule: include/ibu_hip.h).
 extern "C" int32_t ibu_classify_molecules(ibu_ctx_t* ctx, const void* d_sorted_records, size_t n, uint32_t flags, uint8_t* d_class,
                                           ibu_molecule_counts_t* counts, void* stream) {
   int32_t rc = check_ctx(ctx);
@@ -928,11 +931,8 @@ extern "C" int32_t ibu_classify_molecules(ibu_ctx_t* ctx, const void* d_sorted_r
   if (!d_sorted_records || !aligned8(d_sorted_records)) return err_arg("d_sorted_records must be non-NULL and 8-byte aligned");
   if (n >= (1ull << 40)) return err_arg("classify_molecules handles fewer than 2^40 records per call");
   hipStream_t st = pick_stream(ctx, stream);
-  rc = ensure_sort_scratch(ctx, molecules_scratch_bytes(n));
+  rc = runs_count_totals(ctx, d_sorted_records, n, molecules_scratch_bytes(n), RunsCount::Pair, st);
   if (rc) return rc;
-  IBU_HIP(launch_runs_count(ctx->cfg, d_sorted_records, n, ctx->d_sort_scratch, ctx->sort_scratch_bytes, false, st, true));
-  IBU_HIP(hipMemcpyAsync(ctx->h_pinned, ctx->d_sort_scratch, 2 * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
-  IBU_HIP(hipStreamSynchronize(st));
   const uint64_t molecules = ctx->h_pinned[0], candidates = ctx->h_pinned[1];
   rc = ensure_runs_scratch(ctx, molecules_run_scratch_bytes(candidates));
   if (rc) return rc;

@@ -115,17 +115,22 @@ hipError_t launch_partition_records(const LaunchCfg&, const void* recs, size_t n
 bool sort_elems_supported(const LaunchCfg&, const void* recs, const void* tmp, size_t capacity);
 hipError_t launch_sort_elems(const LaunchCfg&, const CompactPlan& pl, void* recs, void* tmp, size_t n, uint32_t prefix_passes, void* scratch,
                              size_t scratch_bytes, hipStream_t st);
-// per-barcode run-length aggregation of sorted records (k_aggregate.hip)
+// run-length aggregation of sorted records (k_aggregate.hip).  `scratch` holds at least runs_scratch_bytes(n) bytes and is 16-byte aligned.
 size_t runs_scratch_bytes(size_t n);
-// pair_level: runs of equal (w0, w1) with the distinct (w0, w1, w2) ranked inside them (ibu_pair_counts; keep_heads is not used there)
-hipError_t launch_runs_count(const LaunchCfg&, const void* recs, size_t n, void* scratch, size_t scratch_bytes, bool keep_heads, hipStream_t st,
-                             bool pair_level = false);
+// Barcode: runs of equal w0 with the distinct (w0, w1) ranked inside them; BarcodeStash: the same, and the stash that launch_runs_emit
+// at barcode level reads; Pair: runs of equal (w0, w1) with the distinct (w0, w1, w2) ranked inside them.
+enum class RunsCount { Barcode, BarcodeStash, Pair };
+// The count pass and its scan.  Leaves u64[2] at the front of `scratch`, runs and ranked heads, for the caller to read back, and
+// behind them the per-segment tables that the emit pass (or launch_molecules_classify) takes its bases from.
+hipError_t launch_runs_count(const LaunchCfg&, const void* recs, size_t n, void* scratch, size_t scratch_bytes, RunsCount what, hipStream_t st);
 size_t runs_emit_scratch_bytes(uint64_t n_runs);
-hipError_t launch_runs_emit(const LaunchCfg&, const void* recs, size_t n, const void* scratch, bool from_stash, void* run_scratch, uint64_t n_runs,
-                            uint64_t n_pairs, uint64_t* barcodes, uint64_t* counts, uint64_t* uniq, hipStream_t st);
-hipError_t launch_pairs_emit(const LaunchCfg&, const void* recs, size_t n, const void* scratch, void* run_scratch, uint64_t n_pairs,
-                             uint64_t n_triples, uint64_t* first, uint64_t* second, uint64_t* counts, uint64_t* distinct, hipStream_t st);
-// one index per molecule (ibu_classify_molecules, k_aggregate.hip).  launch_runs_count(pair_level = true) on a scratch of
+// The emit pass on the scratch launch_runs_count left, n_runs and n_ranked being its two totals.  second == NULL: barcode level,
+// after RunsCount::BarcodeStash; otherwise pair level, after RunsCount::Pair.  Leaves per run, in ascending key order, first[k]
+// (and second[k]) = its first (two) words, counts[k] = its records, distinct[k] (nullable) = the ranked heads in it.  run_scratch
+// (runs_emit_scratch_bytes(n_runs) bytes) holds the runs' first rows and ranks in between.
+hipError_t launch_runs_emit(const LaunchCfg&, const void* recs, size_t n, const void* scratch, void* run_scratch, uint64_t n_runs,
+                            uint64_t n_ranked, uint64_t* first, uint64_t* second, uint64_t* counts, uint64_t* distinct, hipStream_t st);
+// one index per molecule (ibu_classify_molecules, k_molecules.hip).  launch_runs_count(RunsCount::Pair) on a scratch of
 // molecules_scratch_bytes(n) comes first; with its second total (the candidates) the caller sizes the run scratch.  Leaves one class
 // byte per record in d_class (nullable) and u64[5] at the front of run_scratch: resolved and tied molecules, records of class 0, 1, 2.
 size_t molecules_scratch_bytes(size_t n);

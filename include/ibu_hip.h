@@ -539,7 +539,7 @@ int32_t ibu_pair_counts(ibu_ctx_t* ctx, const void* d_sorted_records, size_t n, 
 int32_t ibu_count_matrix(ibu_ctx_t* ctx, void* d_records, void* d_tmp, size_t n, uint32_t flags, uint64_t* d_barcodes,
                          uint64_t* d_indices, uint64_t* d_reads, uint64_t* d_umis, size_t cap, size_t* n_entries, size_t* n_molecules,
                          void* stream);
-/* One index per molecule, on the device (k_aggregate.hip) — the step between ibu_sort_records and the count matrix that drops
+/* One index per molecule, on the device (k_molecules.hip) — the step between ibu_sort_records and the count matrix that drops
  * chimeric reads: a (barcode, umi) seen with two or more index values (PCR chimeras, index hopping, multi-mapped reads) would
  * otherwise be counted once under every one of them.  The reference has no such function; the semantics are this library's and are
  * stated in full here.  Write w0, w1, w2 for the three 64-bit words of a record in storage order.
