@@ -69,11 +69,9 @@ hipError_t launch_fill2(uint64_t* p, uint64_t v0, uint64_t v1, hipStream_t st);
 bool trace_sort();   // IBU_TRACE_SORT set to anything but "" / "0" (read once): one stderr line per sort / probed allocation saying what was chosen
 hipError_t launch_sort_records(const LaunchCfg&, void* recs, void* tmp, size_t n, void* scratch,
                                size_t scratch_bytes, hipStream_t st, const uint64_t* known_words = nullptr /*u64[6]: OR x 3, AND x 3 of a superset: no census pass*/,
-                               int known_prefix = -1 /*>= 0: the 24-byte path's prefix length, estimated elsewhere (0 = all passes)*/,
-                               int* only_estimate = nullptr /*non-null: only estimate that prefix length for n_scale records like these*/,
-                               size_t n_scale = 0);
+                               int known_prefix = -1 /*>= 0: the 24-byte path's prefix length, estimated elsewhere (0 = all passes)*/);
 size_t sort_scratch_bytes(const LaunchCfg&, size_t n);
-size_t sort_prefix_estimate_tables(const LaunchCfg&, size_t n);   // bytes of `tmp` the only_estimate form of launch_sort_records writes (0: none)
+size_t sort_prefix_estimate_tables(const LaunchCfg&, size_t n);   // bytes of `tables` launch_estimate_prefix_records writes (0: none)
 int sort_num_variants();
 int sort_num_compact_variants();
 hipError_t launch_lower_bound(const void* recs, size_t n, const void* keys, size_t k, uint64_t* pos, hipStream_t st);
@@ -94,6 +92,11 @@ hipError_t launch_expand(const LaunchCfg&, const CompactPlan& pl, const void* el
 // (d_starts: u64[256] in `scratch`, the first element of every range); received elements -> sorted records.
 hipError_t launch_estimate_prefix(const LaunchCfg&, const void* recs, size_t n, size_t n_scale, void* tmp, const CompactPlan& pl,
                                   uint32_t* prefix_passes, hipStream_t st);
+// The same for the 24-byte path of launch_sort_records (more than 16 varying bytes): the prefix length a sort of n_scale records like
+// these n wants (0: all passes), from their census words (OR x 3, AND x 3) alone — what that sort takes as known_prefix.  `tables`:
+// sort_prefix_estimate_tables(cfg, n) bytes, 8-byte aligned; no sort scratch is touched.  Synchronises st.
+hipError_t launch_estimate_prefix_records(const LaunchCfg&, const void* recs, size_t n, size_t n_scale, const uint64_t words[6], void* tables,
+                                          int* prefix_passes, hipStream_t st);
 // What the host needs from a partition pass — the range starts (u64[256]) and, where taken, the census words (u64[8]) — exists as soon
 // as the pass's small scan kernel has run, BEFORE its scatter kernel (a third of the pass's time) has: with `early` the launcher copies
 // both into pinned host memory right there and records `ready` behind the copies, so that the caller can plan the exchange while the

@@ -485,7 +485,7 @@ int32_t sort_partition_first_records(ibu_ctx_t* const* ctxs, size_t W, ibu_sort_
         hipStream_t es = c->side_stream;
         hipError_t e = partitioned.ev[big] ? hipStreamWaitEvent(es, partitioned.ev[big], 0) : hipSuccess;
         if (e == hipSuccess)
-          e = launch_sort_records(c->cfg, shards[big].d_tmp, c->d_sort_scratch, shards[big].n, c->d_sort_scratch, c->sort_scratch_bytes, es, all_words, -1, &P, total);
+          e = launch_estimate_prefix_records(c->cfg, shards[big].d_tmp, shards[big].n, total, all_words, c->d_sort_scratch, &P, es);
         (void)hipStreamSynchronize(es);
         if (e != hipSuccess) { (void)hipGetLastError(); return -1; }   // (every owner estimates for itself then)
         return P;

@@ -18,8 +18,10 @@
 // (ibu_k_sort_sample_pairs*), long runs that are already in order pass through, other long runs escalate (one retry with a
 // longer prefix, then all passes).  One translation unit in five files (the host side takes the kernels' addresses): the kernels in
 // sort_census.hpp | sort_passes.hpp (24-byte passes) | sort_compact.hpp (compress, element passes, expand) | sort_finish.hpp
-// (finishing kernels + the sample estimate), included below; this file: shared definitions, host side (layout, variants,
-// launch_compact_passes, launch_sort_records), splitter search.  Per-barcode aggregation: k_aggregate.hip.
+// (finishing kernels + the sample estimate), included below; this file: shared definitions, host side, splitter search.  The host
+// side: layout and variants; the pass plumbing, every step once (SortScratch, launch_counts_bytes / launch_offsets, ElemScatter /
+// RecScatter, the two finish launchers); the decisions (estimate_prefix, launch_compact_passes behind sort_compact, the partition
+// passes, launch_sort_records as a sequence of phases).  Per-barcode aggregation: k_aggregate.hip.
 #include <stdio.h>
 #include <stdlib.h>
 
@@ -279,44 +281,76 @@ hipError_t launch_records_census(const LaunchCfg& cfg, const void* recs, size_t 
 }
 // The census of three SAMPLE ranges (first / middle / last 32 Ki records) — what the sort's speculation guesses its plan from; inputs
 // too small for three ranges get the exact census.  `exact` says which it was.
-static constexpr size_t kCensusSample = 32768;
+static constexpr size_t kSampleRecs = 32768;                  // a sample range, here and wherever the sort decides from samples
+static void launch_census_sample(const LaunchCfg& cfg, const void* recs, size_t n, u64* census, hipStream_t st) {   // n >= 4 kSampleRecs, 16-byte aligned
+  hipLaunchKernelGGL(ibu_k_sort_census_init, dim3(1), dim3(kCensusSlots * 8), 0, st, census);
+  const size_t starts[3] = {0, (n / 2) & ~(size_t)1, (n - kSampleRecs) & ~(size_t)1};   // even rows: 16-byte aligned
+  for (size_t s0 : starts) launch_census(cfg, static_cast<const u64*>(recs) + 3 * s0, kSampleRecs, census, nullptr, st);
+  hipLaunchKernelGGL(ibu_k_sort_census_fold, dim3(1), dim3(kCensusSlots), 0, st, census);
+}
 hipError_t launch_records_census_sample(const LaunchCfg& cfg, const void* recs, size_t n, uint64_t* d_census, bool* exact, hipStream_t st) {
   (void)hipGetLastError();
-  *exact = n < 4 * kCensusSample || (reinterpret_cast<uintptr_t>(recs) & 15u) != 0;
+  *exact = n < 4 * kSampleRecs || (reinterpret_cast<uintptr_t>(recs) & 15u) != 0;
   if (*exact) return launch_records_census(cfg, recs, n, d_census, st);
-  hipLaunchKernelGGL(ibu_k_sort_census_init, dim3(1), dim3(kCensusSlots * 8), 0, st, (u64*)d_census);
-  const size_t starts[3] = {0, (n / 2) & ~(size_t)1, (n - kCensusSample) & ~(size_t)1};   // even rows: 16-byte aligned
-  for (size_t s0 : starts) launch_census(cfg, static_cast<const u64*>(recs) + 3 * s0, kCensusSample, (u64*)d_census, nullptr, st);
-  hipLaunchKernelGGL(ibu_k_sort_census_fold, dim3(1), dim3(kCensusSlots), 0, st, (u64*)d_census);
+  launch_census_sample(cfg, recs, n, (u64*)d_census, st);
   return hipGetLastError();
+}
+// ---- the multi-GPU sort on 12-byte elements: partition first, sort once (multi_sort.cpp, round 4) -----------------------------------
+// Round 3 sorted every shard, exchanged the pieces between the splitters and sorted every owner's pieces AGAIN.  Now a shard is only
+// PARTITIONED before the exchange: its records become 12-byte elements (one plan for all shards, at most 11 varying bytes), every
+// element gets — in the same kernel — the number of its key range — how many of the (up to 255) splitters are not above it — in its free top byte, and one
+// ordinary element pass on that byte (count from the side stream, scan, scatter: the kernels of the sort) moves the elements into
+// range order; the scan's bin starts are the range boundaries, from which the caller cuts the owners' pieces.  The owner sorts the elements it received straight into records (launch_sort_elems: the
+// passes of the sort without its census and compress steps — the sender made the elements).
+extern "C" __global__ void __launch_bounds__(256)
+ibu_k_sort_stamp_bucket(ElemT<3>* __restrict__ elems, u64 n, const ElemT<3>* __restrict__ split, u32 nsplit, uint8_t* __restrict__ digits) {
+  __shared__ u32 sp[3 * 256];
+  for (u32 i = threadIdx.x; i < 3 * nsplit; i += blockDim.x) sp[i] = reinterpret_cast<const u32*>(split)[i];
+  __syncthreads();
+  const u64 stride = (u64)gridDim.x * blockDim.x;
+  for (u64 i = (u64)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
+    EV<3> e = ld_elem<3>(elems + i);
+    e.w[2] &= 0x00FFFFFFu;                                    // (zero already: at most 11 bytes vary)
+    const u32 g = range_of(sp, nsplit, e);
+    e.w[2] |= g << 24;
+    st_elem<3>(elems + i, e);
+    digits[i] = (uint8_t)g;
+  }
 }
 // records -> elements of W words (pl.k <= 4 W).  Records that start at an odd record of a larger array (8- but not 16-byte
 // aligned) are PEELED like everywhere else (kcommon.hpp): one record through the per-record kernel brings the rest to a
 // 16-byte boundary for the tiled kernel (the elements need no more than their 4-byte alignment).
-template <int W>
-static void launch_compress(const LaunchCfg& cfg, const CompactPlan& pl, const void* recs, size_t n, u32 first_byte, ElemT<W>* out,
-                            uint8_t* digits, hipStream_t st, u64* census = nullptr) {   // census: 16-byte aligned records only
+// census (nullable; 16-byte aligned records only): the exact census words are accumulated on the way.
+// STAMP (the partition pass): records -> stamped elements + the digit stream of the ranges: the tiled rows in ONE kernel
+// (ibu_k_sort_compress<.., STAMP>), the peeled head row and the rest rows (fewer than 129 in all) through the tail compress kernel
+// and the stamp kernel above.
+template <int W, bool STAMP = false>
+static void launch_compress(const LaunchCfg& cfg, const CompactPlan& pl, const void* recs, size_t n, u32 first_byte, ElemT<W>* out, uint8_t* digits,
+                            hipStream_t st, u64* census = nullptr, const ElemT<3>* split = nullptr, u32 nsplit = 0) {
   const size_t head = (reinterpret_cast<uintptr_t>(recs) & 15u) ? (n ? 1 : 0) : 0;
-  const size_t main_rows = ((n - head) / kTileRecs) * kTileRecs;
-  if (head)
-    hipLaunchKernelGGL(ibu_k_sort_compress_tail<W>, dim3(1), dim3(256), 0, st, (const u64*)recs, (u64)0, (u64)head, pl, first_byte, out, digits);
+  const size_t main_rows = ((n - head) / kTileRecs) * kTileRecs, done = head + main_rows;
+  uint8_t* const tail_digits = STAMP ? nullptr : digits;      // stamped: the stamp kernel writes the stream of the rows the tail kernel took
+  if (head) {
+    hipLaunchKernelGGL(ibu_k_sort_compress_tail<W>, dim3(1), dim3(256), 0, st, (const u64*)recs, (u64)0, (u64)head, pl, first_byte, out, tail_digits);
+    if constexpr (STAMP) hipLaunchKernelGGL(ibu_k_sort_stamp_bucket, dim3(1), dim3(256), 0, st, out, (u64)head, split, nsplit, digits);
+  }
   if (main_rows) {
     static std::atomic<int> occ[2];
     const u32 nt = (u32)(main_rows / kTileRecs);
     const uint8_t* base = static_cast<const uint8_t*>(recs) + 24 * head;
     if (census)
-      hipLaunchKernelGGL((ibu_k_sort_compress<true, W>), dim3(grid_for(nt, cfg.cus, resident_blocks<kBlock>(cfg, ibu_k_sort_compress<true, W>, 0, &occ[1]))),
-                         dim3(kBlock), 0, st, base, nt, pl, first_byte, out + head, digits ? digits + head : digits, census);
+      hipLaunchKernelGGL((ibu_k_sort_compress<true, W, STAMP>), dim3(grid_for(nt, cfg.cus, resident_blocks<kBlock>(cfg, ibu_k_sort_compress<true, W, STAMP>, 0, &occ[1]))),
+                         dim3(kBlock), 0, st, base, nt, pl, first_byte, out + head, digits ? digits + head : digits, census, split, nsplit);
     else
-      hipLaunchKernelGGL((ibu_k_sort_compress<false, W>), dim3(grid_for(nt, cfg.cus, resident_blocks<kBlock>(cfg, ibu_k_sort_compress<false, W>, 0, &occ[0]))),
-                         dim3(kBlock), 0, st, base, nt, pl, first_byte, out + head, digits ? digits + head : digits, (u64*)nullptr);
+      hipLaunchKernelGGL((ibu_k_sort_compress<false, W, STAMP>), dim3(grid_for(nt, cfg.cus, resident_blocks<kBlock>(cfg, ibu_k_sort_compress<false, W, STAMP>, 0, &occ[0]))),
+                         dim3(kBlock), 0, st, base, nt, pl, first_byte, out + head, digits ? digits + head : digits, (u64*)nullptr, split, nsplit);
   }
-  if (head + main_rows < n) {
-    hipLaunchKernelGGL(ibu_k_sort_compress_tail<W>, dim3(tail_grid(n - head - main_rows)), dim3(256), 0, st, (const u64*)recs,
-                       (u64)(head + main_rows), (u64)n, pl, first_byte, out, digits);
+  if (done < n) {
+    hipLaunchKernelGGL(ibu_k_sort_compress_tail<W>, dim3(tail_grid(n - done)), dim3(256), 0, st, (const u64*)recs, (u64)done, (u64)n, pl, first_byte, out,
+                       tail_digits);
+    if constexpr (STAMP) hipLaunchKernelGGL(ibu_k_sort_stamp_bucket, dim3(1), dim3(256), 0, st, out + done, (u64)(n - done), split, nsplit, digits + done);
     if (census)   // the rest rows of the census (each row also against its predecessor)
-      hipLaunchKernelGGL(ibu_k_sort_census_tail, dim3(tail_grid(n - head - main_rows)), dim3(256), 0, st, (const u64*)recs,
-                         (u64)(head + main_rows), (u64)n, census, (u32*)nullptr);
+      hipLaunchKernelGGL(ibu_k_sort_census_tail, dim3(tail_grid(n - done)), dim3(256), 0, st, (const u64*)recs, (u64)done, (u64)n, census, (u32*)nullptr);
   }
 }
 template <int W>
@@ -350,155 +384,291 @@ hipError_t launch_expand(const LaunchCfg& cfg, const CompactPlan& pl, const void
   return hipGetLastError();
 }
 
-// The compact-key path of launch_sort_records (see "COMPACT-KEY passes" above), W words per element.
-// passes[0 .. npass): the element bytes to sort by, ascending.  compressed: the elements (and the digit stream of
-// `digits_byte`) are already in place — the speculative path ran the compress pass itself.
-// W = 3: both element buffers live in tmp (12 n bytes each) and the last pass always writes the records.
-// W = 4: 16 n + 16 n bytes do not fit in tmp, so the second buffer is the head of the RECORD ARRAY (its contents are dead once
-//        the elements exist).  The last pass can write records into that array only while reading from tmp, i.e. when the
-//        pass count is odd; with an even count it stays an element pass (recs -> tmp) and an expand pass (tmp -> recs) follows.
-// finish_prefix = P > 0: PREFIX + FINISH on elements — only the top P of `passes` run (as element passes), then
-// ibu_k_sort_finish_elems completes the runs of equal prefix and writes the records; if it overflows (long runs), all passes run
-// after all, starting from the prefix-sorted elements wherever they ended (elems_at).  W = 4 needs an even P (the elements must
-// end in tmp: the records are written over the other buffer).
-template <int W>
-static hipError_t launch_compact_passes(const LaunchCfg& cfg, const CompactVariant& cv, void* recs, void* tmp, size_t n, uint8_t* sc,
-                                        const CompactPlan& pl, const u32* passes, u32 npass, hipStream_t st, bool compressed = false,
-                                        u32 digits_byte = 0, u32 finish_prefix = 0, ElemT<W>* elems_at = nullptr) {
-  const bool retried = (finish_prefix & 0x80000000u) != 0;    // the one retry with a longer prefix (see the overflow handling below)
-  finish_prefix &= 0x7FFFFFFFu;
-  const SortLayout L = sort_layout(cfg, n, cv.tile);
-  u64* binbase = reinterpret_cast<u64*>(sc + L.binbase);
-  u32* blocksum = reinterpret_cast<u32*>(sc + L.blocksum);
-  u64* blockoff = reinterpret_cast<u64*>(sc + L.blockoff);
-  uint16_t* counts = reinterpret_cast<uint16_t*>(sc + L.counts);
-  void* pos = sc + L.pos;                                     // u32 or u64 entries (L.idx64)
-  uint8_t* digits = sc + L.digits;
-  const void* k_scatter = L.idx64 ? cv.scatter64 : cv.scatter;
-  const void* k_scatter_last = L.idx64 ? cv.scatter_last64 : cv.scatter_last;
-  if (!k_scatter || !k_scatter_last) return hipErrorInvalidValue;   // (the caller only comes here with a shape that has them)
-  ElemT<W>* const half2 = W == 3 ? reinterpret_cast<ElemT<W>*>(static_cast<uint8_t*>(tmp) + 12 * n) : static_cast<ElemT<W>*>(recs);
-  ElemT<W>* src = elems_at ? elems_at : static_cast<ElemT<W>*>(tmp);
-  ElemT<W>* dst = src == half2 ? static_cast<ElemT<W>*>(tmp) : half2;
-  const bool fuse_last = W == 3 || (npass & 1u);
+// IBU_TRACE_SORT=1: one line per sort on stderr saying which path it took (tests assert on it; never set in production)
+bool trace_sort() {
+  static const bool on = [] { const char* v = getenv("IBU_TRACE_SORT"); return v && *v && *v != '0'; }();
+  return on;
+}
 
-  // every call, not once per process: the attribute belongs to the function ON THE CURRENT DEVICE, and a process may drive
-  // several GPUs through several contexts (a few microseconds against a sort of milliseconds)
-  hipError_t e;
-  if (cv.lds > 48 * 1024) {
-    e = hipFuncSetAttribute(k_scatter, hipFuncAttributeMaxDynamicSharedMemorySize, (int)cv.lds);
-    if (e != hipSuccess) return e;
-    e = hipFuncSetAttribute(k_scatter_last, hipFuncAttributeMaxDynamicSharedMemorySize, (int)cv.lds);
-    if (e != hipSuccess) return e;
+// ---- pass plumbing: every step of a radix pass exists once ------------------------------------------------------------------------
+#define IBU_TRY(call) do { const hipError_t e_ = (call); if (e_ != hipSuccess) return e_; } while (0)
+// "Copy a few words to the host and wait for them": every host round trip of the sort.
+static hipError_t read_back(void* host, const void* dev, size_t bytes, hipStream_t st) {
+  IBU_TRY(hipMemcpyAsync(host, dev, bytes, hipMemcpyDeviceToHost, st));
+  return hipStreamSynchronize(st);
+}
+// The scratch of one sort, typed: where SortLayout says its parts are.
+struct SortScratch {
+  SortLayout L;
+  u64 *census, *binbase, *blockoff;                           // census: the slots sit at the head of the scratch
+  u32 *overflow, *blocksum;                                   // overflow: the finishing kernel's flag (kMiscBytes)
+  uint16_t* counts;
+  void* pos;                                                  // u32 or u64 entries (L.idx64)
+  uint8_t* digits;
+  SortScratch(void* scratch, const SortLayout& l) : L(l) {
+    uint8_t* sc = static_cast<uint8_t*>(scratch);
+    census = reinterpret_cast<u64*>(sc), binbase = reinterpret_cast<u64*>(sc + L.binbase), blockoff = reinterpret_cast<u64*>(sc + L.blockoff);
+    overflow = reinterpret_cast<u32*>(sc + L.misc), blocksum = reinterpret_cast<u32*>(sc + L.blocksum);
+    counts = reinterpret_cast<uint16_t*>(sc + L.counts), pos = sc + L.pos, digits = sc + L.digits;
   }
-  const u32 first_pass = finish_prefix ? npass - finish_prefix : 0;
-  if (!compressed) launch_compress<W>(cfg, pl, recs, n, passes[first_pass], src, digits, st);
-  else if (digits_byte != passes[first_pass])
-    hipLaunchKernelGGL(ibu_k_sort_digits<W>, dim3((u32)cfg.cus * 8), dim3(256), 0, st, (const ElemT<W>*)src, (u64)n, passes[first_pass], digits);
-  // passes; the last one writes the records themselves (with a finishing pass behind them, none of them does)
-  const u32 wave_grid = (L.ntiles + kSortWaves - 1) / kSortWaves;
-  const u32 cap = (u32)cfg.cus * 8;
-  for (u32 pi = first_pass; pi < npass; ++pi) {
-    const u32 b = passes[pi];
-    hipLaunchKernelGGL(cv.counts_bytes, dim3(wave_grid < cap ? wave_grid : cap), dim3(kSortThreads), 0, st, (const uint8_t*)digits, (u64)n,
-                       L.ntiles, counts);
-    hipLaunchKernelGGL(ibu_k_sort_blocksums, dim3(L.nblocks), dim3(kSortThreads), 0, st, (const uint16_t*)counts, L.ntiles, L.tpb, blocksum);
-    hipLaunchKernelGGL(ibu_k_sort_blockscan, dim3(1), dim3(kSortThreads), 0, st, (const u32*)blocksum, L.nblocks, blockoff, binbase);
-    if (L.idx64)
-      hipLaunchKernelGGL(ibu_k_sort_tilepos<u64>, dim3(L.nblocks), dim3(kSortThreads), 0, st, (const uint16_t*)counts, L.ntiles, L.tpb,
-                         (const u64*)blockoff, (const u64*)binbase, static_cast<u64*>(pos));
-    else
-      hipLaunchKernelGGL(ibu_k_sort_tilepos<u32>, dim3(L.nblocks), dim3(kSortThreads), 0, st, (const uint16_t*)counts, L.ntiles, L.tpb,
-                         (const u64*)blockoff, (const u64*)binbase, static_cast<u32*>(pos));
-    const bool last = pi + 1 == npass, to_records = last && fuse_last && !finish_prefix;
-    u32 n32 = (u32)n, b_arg = b, nb_arg = last ? 4u * W : passes[pi + 1];   // 4 W: no digit stream behind the last pass
+};
+// Tile counts from the digit side stream the previous scatter (or the compress pass) left behind.
+typedef void (*CountsBytesFn)(const uint8_t*, u64, u32, uint16_t*);
+static void launch_counts_bytes(const LaunchCfg& cfg, CountsBytesFn counts_bytes, const SortScratch& S, size_t n, hipStream_t st) {
+  const u32 wave_grid = (S.L.ntiles + kSortWaves - 1) / kSortWaves, cap = (u32)cfg.cus * 8;
+  hipLaunchKernelGGL(counts_bytes, dim3(wave_grid < cap ? wave_grid : cap), dim3(kSortThreads), 0, st, (const uint8_t*)S.digits, (u64)n, S.L.ntiles, S.counts);
+}
+// Offsets from counts: block sums, the scan over the blocks, every tile's positions.  early (the partition passes): the host's share
+// of the pass is complete once the scan has run — hand it over before the scatter (kernels.h: PartitionEarly; early_census: the
+// census words to hand over with it, nullable).
+static hipError_t launch_offsets(const SortScratch& S, hipStream_t st, const PartitionEarly* early = nullptr, const u64* early_census = nullptr) {
+  const SortLayout& L = S.L;
+  hipLaunchKernelGGL(ibu_k_sort_blocksums, dim3(L.nblocks), dim3(kSortThreads), 0, st, (const uint16_t*)S.counts, L.ntiles, L.tpb, S.blocksum);
+  hipLaunchKernelGGL(ibu_k_sort_blockscan, dim3(1), dim3(kSortThreads), 0, st, (const u32*)S.blocksum, L.nblocks, S.blockoff, S.binbase);
+  if (early) {
+    IBU_TRY(hipMemcpyAsync(early->h_starts, S.binbase, 8 * kBins, hipMemcpyDeviceToHost, st));
+    if (early_census) IBU_TRY(hipMemcpyAsync(early->h_words, early_census, 64, hipMemcpyDeviceToHost, st));
+    IBU_TRY(hipEventRecord(early->ready, st));
+  }
+  if (L.idx64)
+    hipLaunchKernelGGL(ibu_k_sort_tilepos<u64>, dim3(L.nblocks), dim3(kSortThreads), 0, st, (const uint16_t*)S.counts, L.ntiles, L.tpb,
+                       (const u64*)S.blockoff, (const u64*)S.binbase, static_cast<u64*>(S.pos));
+  else
+    hipLaunchKernelGGL(ibu_k_sort_tilepos<u32>, dim3(L.nblocks), dim3(kSortThreads), 0, st, (const uint16_t*)S.counts, L.ntiles, L.tpb,
+                       (const u64*)S.blockoff, (const u64*)S.binbase, static_cast<u32*>(S.pos));
+  return hipSuccess;
+}
+// The scatter kernels take more LDS than a launch may ask for unannounced.  Every call of a launcher, not once per process: the
+// attribute belongs to the function ON THE CURRENT DEVICE, and a process may drive several GPUs through several contexts (a few
+// microseconds against a sort of milliseconds).
+static hipError_t allow_lds(const void* kernel, size_t lds) {
+  if (!kernel) return hipErrorInvalidValue;                   // (the callers only come here with a shape that has the kernel)
+  return lds > 48 * 1024 ? hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) : hipSuccess;
+}
+static u32 scatter_grid(const SortLayout& L) { return (L.ntiles + 7u) & ~7u; }   // multiple of 8: XCD-aware tile order
+// The scatter of an element pass on element byte b; nb: the byte whose digit stream it leaves for the next pass.  to_records: the
+// kernel that expands the elements into records on the way (a last pass).
+struct ElemScatter {
+  const CompactVariant& cv; const SortScratch& S; hipStream_t st;
+  const void* kernel(bool to_records) const { return S.L.idx64 ? (to_records ? cv.scatter_last64 : cv.scatter64) : (to_records ? cv.scatter_last : cv.scatter); }
+  hipError_t prepare(bool to_records) const { return allow_lds(kernel(to_records), cv.lds); }
+  hipError_t operator()(bool to_records, const void* src, void* dst, size_t n, u32 b, u32 nb, CompactPlan pl) const {
+    u32 n32 = (u32)n;
     u64 n64 = n;
-    const ElemT<W>* src_arg = src;
-    void* dst_arg = to_records ? recs : static_cast<void*>(dst);
-    const void* pos_arg = pos;
-    CompactPlan pl_arg = pl;
-    void* args[] = {&src_arg, &dst_arg, L.idx64 ? static_cast<void*>(&n64) : static_cast<void*>(&n32), &b_arg, &nb_arg, &pos_arg, &digits, &pl_arg};
-    u32 sgrid = (L.ntiles + 7u) & ~7u;                        // multiple of 8: XCD-aware tile order
-    e = hipLaunchKernel(to_records ? k_scatter_last : k_scatter, dim3(sgrid), dim3(cv.threads), args, cv.lds, st);
-    if (e != hipSuccess) return e;
-    ElemT<W>* t = src; src = dst; dst = t;
+    const void* pos = S.pos; uint8_t* digits = S.digits;
+    void* args[] = {&src, &dst, S.L.idx64 ? static_cast<void*>(&n64) : static_cast<void*>(&n32), &b, &nb, &pos, &digits, &pl};
+    return hipLaunchKernel(kernel(to_records), dim3(scatter_grid(S.L)), dim3(cv.threads), args, cv.lds, st);
   }
-  if (finish_prefix) {
+};
+// The scatter of a 24-byte pass on (field, shift), leaving the digits of (nfield, nshift).  from_stream: this pass's digit comes
+// from the side stream (field > 2: the partition pass).
+struct RecScatter {
+  const SweepVariant& sv; const SortScratch& S; hipStream_t st; bool from_stream;
+  const void* kernel() const { return from_stream ? (S.L.idx64 ? sv.scatter64_stream : sv.scatter32_stream) : (S.L.idx64 ? sv.scatter64 : sv.scatter32); }
+  hipError_t prepare() const { return allow_lds(kernel(), sv.lds); }
+  hipError_t operator()(const u64* src, u64* dst, size_t n, u32 field, u32 shift, u32 nfield, u32 nshift) const {
+    u64 n_arg = n;
+    void* pos = S.pos; uint8_t* digits = S.digits;
+    void* args[] = {&src, &dst, &n_arg, &field, &shift, &nfield, &nshift, &pos, &digits};
+    return hipLaunchKernel(kernel(), dim3(scatter_grid(S.L)), dim3(sv.threads), args, sv.lds, st);
+  }
+};
+
+// ---- the finishing step -------------------------------------------------------------------------------------------------------------
+// Workgroups of a finishing kernel per CU: a persistent grid, exactly resident (LDS and registers decide).  NOT capped by
+// cfg.blocks_per_cu, as resident_blocks (kernels.h) is.
+template <class K>
+static u32 finish_blocks_per_cu(K kernel, size_t lds, std::atomic<int>* cache) {
+  int per = cache->load(std::memory_order_relaxed);
+  if (per <= 0) {
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per, kernel, kSortThreads, lds) != hipSuccess || per <= 0) per = 1;
+    cache->store(per, std::memory_order_relaxed);
+  }
+  return (u32)per;
+}
+static hipError_t read_overflow(const SortScratch& S, hipStream_t st, bool* overflowed) {
+  u32 overflow = 0;
+  const hipError_t e = read_back(&overflow, S.overflow, 4, st);
+  *overflowed = overflow != 0;
+  return e;
+}
 #ifndef IBU_FINISH_T
 #define IBU_FINISH_T 1792
 #endif
 #ifndef IBU_FINISH_M
 #define IBU_FINISH_M 256
 #endif
-    // 1792-element tiles + 256 of look-ahead (eight elements per thread): 34 / 43 KiB of LDS and 126 / 156 VGPRs -> four / three
-    // workgroups per CU.  Measured at 1e9 records 16/12 (profiles r03_m, r03_n): (4096, 512) 12.2 ms, (3072, 256) 12.1, (2048, 512) 9.4,
-    // (2048, 256) 7.8-8.0 while it fitted 128 VGPRs and 9.9 once later edits had pushed it to 135 (three workgroups per CU: r03_ae),
-    // (2048, 128) 8.0, (1536, 256) 8.0, (1024, 256) 8.6, (1024, 128) 8.4; (1792, 256) 8.4 on the box where (2048, 256) took 9.9 (r03_af).
-    // tests/test_tools.py pins the register budgets.
-    constexpr int FT = IBU_FINISH_T, FM = IBU_FINISH_M;
-    typedef FinishElemShape<W, FT, FM> FS;
-    u32* d_overflow = reinterpret_cast<u32*>(sc + L.misc);
-    e = hipMemsetAsync(d_overflow, 0, 4, st);
-    if (e != hipSuccess) return e;
-    e = hipFuncSetAttribute(reinterpret_cast<const void*>(ibu_k_sort_finish_elems<W, FT, FM>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)FS::lds);
-    if (e != hipSuccess) return e;
-    EV<W> pm;                                                 // the prefix bytes as word masks
-    for (int w = 0; w < W; ++w) pm.w[w] = 0;
-    for (u32 pi = first_pass; pi < npass; ++pi) pm.w[passes[pi] >> 2] |= 255u << (8 * (passes[pi] & 3));
-    static std::atomic<int> focc;
-    int fper = focc.load(std::memory_order_relaxed);
-    if (fper <= 0) {                                          // persistent grid, exactly resident (LDS and registers decide)
-      if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&fper, ibu_k_sort_finish_elems<W, FT, FM>, kSortThreads, FS::lds) != hipSuccess || fper <= 0) fper = 1;
-      focc.store(fper, std::memory_order_relaxed);
-    }
-    const u32 ftiles = (u32)((n + FT - 1) / FT), fgrid = (u32)fper * (u32)cfg.cus;
-    hipLaunchKernelGGL((ibu_k_sort_finish_elems<W, FT, FM>), dim3(ftiles < fgrid ? ftiles : fgrid), dim3(kSortThreads), FS::lds, st, (const ElemT<W>*)src, recs,
-                       (u64)n, pm, pl, d_overflow);
-    u32 overflow = 0;
-    e = hipMemcpyAsync(&overflow, d_overflow, 4, hipMemcpyDeviceToHost, st);
-    if (e != hipSuccess) return e;
-    e = hipStreamSynchronize(st);
-    if (e != hipSuccess) return e;
-    if (!overflow) return hipGetLastError();
-    // Long runs of equal prefix.  The prefix-sorted elements are a permutation of the input's, so anything may follow.  A heavy
-    // prefix usually is a heavy BARCODE whose records the next key bytes (the UMI) spread again: ONE retry with a prefix that
-    // reaches at least two bytes past the barcode (and is at least three bytes longer; W = 4: even, the elements must end in tmp)
-    // is cheaper than all passes when it still saves two of them — and if that overflows too, all passes run.
-    u32 nbar = 0;                                             // element bytes that come from the barcode (the most significant ones)
-    for (u32 j = 0; j < pl.k && j < 4u * W; ++j)
-      if (((pl.csel[j >> 2][0] >> (8 * (j & 3))) & 255u) != 0x0Cu) ++nbar;
-    u32 longer = finish_prefix + 3 > nbar + 2 ? finish_prefix + 3 : nbar + 2;   // at least two bytes past the barcode
-    if (W == 4) longer += longer & 1u;
-    if (!retried && longer + 2 <= npass) {
-      if (trace_sort()) fprintf(stderr, "ibu sort: n=%zu prefix+finish overflowed (long runs of equal prefix): retrying with prefix_passes=%u of %u\n", n, longer, npass);
-      return launch_compact_passes<W>(cfg, cv, recs, tmp, n, sc, pl, passes, npass, st, true, 0xFFFFFFFFu, longer | 0x80000000u, src);
-    }
-    if (trace_sort()) fprintf(stderr, "ibu sort: n=%zu prefix+finish overflowed (long runs of equal prefix): all %u passes\n", n, npass);
-    return launch_compact_passes<W>(cfg, cv, recs, tmp, n, sc, pl, passes, npass, st, true, 0xFFFFFFFFu, 0, src);   // elements: a permutation of the input's
-  }
-  if (!fuse_last) launch_expand_w<W>(cfg, pl, src, n, recs, st);   // W = 4, even pass count: the elements ended in tmp
-  return hipGetLastError();
+// Elements whose top `nprefix` sort bytes (prefix_bytes) are in order -> records; *overflowed: runs of equal prefix too long for it.
+// 1792-element tiles + 256 of look-ahead (eight elements per thread): 34 / 43 KiB of LDS and 126 / 156 VGPRs -> four / three
+// workgroups per CU.  Measured at 1e9 records 16/12 (profiles r03_m, r03_n): (4096, 512) 12.2 ms, (3072, 256) 12.1, (2048, 512) 9.4,
+// (2048, 256) 7.8-8.0 while it fitted 128 VGPRs and 9.9 once later edits had pushed it to 135 (three workgroups per CU: r03_ae),
+// (2048, 128) 8.0, (1536, 256) 8.0, (1024, 256) 8.6, (1024, 128) 8.4; (1792, 256) 8.4 on the box where (2048, 256) took 9.9 (r03_af).
+// tests/test_tools.py pins the register budgets.
+template <int W>
+static hipError_t launch_finish_elems(const LaunchCfg& cfg, const SortScratch& S, const ElemT<W>* src, void* recs, size_t n, const u32* prefix_bytes,
+                                      u32 nprefix, const CompactPlan& pl, hipStream_t st, bool* overflowed) {
+  constexpr int FT = IBU_FINISH_T, FM = IBU_FINISH_M;
+  typedef FinishElemShape<W, FT, FM> FS;
+  IBU_TRY(hipMemsetAsync(S.overflow, 0, 4, st));
+  IBU_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(ibu_k_sort_finish_elems<W, FT, FM>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)FS::lds));
+  EV<W> pm;                                                   // the prefix bytes as word masks
+  for (int w = 0; w < W; ++w) pm.w[w] = 0;
+  for (u32 i = 0; i < nprefix; ++i) pm.w[prefix_bytes[i] >> 2] |= 255u << (8 * (prefix_bytes[i] & 3));
+  static std::atomic<int> occ;
+  const u32 ftiles = (u32)((n + FT - 1) / FT), fgrid = finish_blocks_per_cu(ibu_k_sort_finish_elems<W, FT, FM>, FS::lds, &occ) * (u32)cfg.cus;
+  hipLaunchKernelGGL((ibu_k_sort_finish_elems<W, FT, FM>), dim3(ftiles < fgrid ? ftiles : fgrid), dim3(kSortThreads), FS::lds, st, src, recs, (u64)n, pm, pl, S.overflow);
+  return read_overflow(S, st, overflowed);
+}
+// The same on 24-byte records whose prefix bytes (the masks pm) are in order: tmp -> recs.  The caller zeroed S.overflow in front
+// of the prefix passes.
+static hipError_t launch_finish_records(const LaunchCfg& cfg, const SortScratch& S, const void* tmp, void* recs, size_t n, const u64 pm[3], hipStream_t st, bool* overflowed) {
+  typedef FinishShape<kFinishT, kFinishM> FS;
+  const u64 nblk = (n + kFinishT - 1) / kFinishT;
+  auto launch = [&](auto kernel, u64 grid) -> hipError_t {
+    IBU_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)FS::lds));
+    hipLaunchKernelGGL(kernel, dim3((u32)(nblk < grid ? nblk : grid)), dim3(kSortThreads), FS::lds, st, (const u64*)tmp, static_cast<u64*>(recs), (u64)n, pm[0],
+                       pm[1], pm[2], S.overflow);
+    return read_overflow(S, st, overflowed);
+  };
+  static std::atomic<int> occ;
+  if ((reinterpret_cast<uintptr_t>(tmp) & 15u) == 0)          // persistent, prefetching form
+    return launch(ibu_k_sort_finish<kFinishT, kFinishM, true>, (u64)finish_blocks_per_cu(ibu_k_sort_finish<kFinishT, kFinishM, true>, FS::lds, &occ) * (u64)cfg.cus);
+  return launch(ibu_k_sort_finish<kFinishT, kFinishM, false>, nblk);
 }
 
-// IBU_TRACE_SORT=1: one line per sort on stderr saying which path it took (tests assert on it; never set in production)
-bool trace_sort() {
-  static const bool on = [] { const char* v = getenv("IBU_TRACE_SORT"); return v && *v && *v != '0'; }();
-  return on;
+// ---- the compact-key path (see "COMPACT-KEY passes" above) ------------------------------------------------------------------------
+// What the caller of the compact passes has already put in place: nothing (the passes compress the records themselves), the
+// elements in tmp (elems), or the elements and the digit stream of element byte `digits_byte` (the speculative compress pass).
+struct ElemsGiven { bool elems = false, digits = false; u32 digits_byte = 0; };
+// After an overflow of prefix + finish with `prefix` bytes: the prefix of the ONE retry.  A heavy prefix usually is a heavy BARCODE
+// whose records the next key bytes (the UMI) spread again: a prefix that reaches at least two bytes past the barcode (and is at least
+// three bytes longer; W = 4: even, the elements must end in tmp).
+template <int W>
+static u32 longer_prefix(const CompactPlan& pl, u32 prefix) {
+  u32 nbar = 0;                                               // element bytes that come from the barcode (the most significant ones)
+  for (u32 j = 0; j < pl.k && j < 4u * W; ++j)
+    if (((pl.csel[j >> 2][0] >> (8 * (j & 3))) & 255u) != 0x0Cu) ++nbar;
+  u32 longer = prefix + 3 > nbar + 2 ? prefix + 3 : nbar + 2; // at least two bytes past the barcode
+  if (W == 4) longer += longer & 1u;
+  return longer;
 }
-// PREFIX + FINISH on the elements?  Only if the runs of equal prefix are going to be short: a pair count over a sample says
-// (ibu_k_sort_sample_pairs; the tables live in tmp, which nothing uses at that point).  `sorted_bytes`: the passes the plain path
-// would run (the element bytes it sorts on are the top `sorted_bytes` of the plan's k).  *P = the prefix to use, 0 = none.
+// The compact passes on elements of W words.  passes[0 .. npass): the element bytes to sort by, ascending.
+// W = 3: both element buffers live in tmp (12 n bytes each) and the last pass always writes the records.
+// W = 4: 16 n + 16 n bytes do not fit in tmp, so the second buffer is the head of the RECORD ARRAY (its contents are dead once
+//        the elements exist).  The last pass can write records into that array only while reading from tmp, i.e. when the
+//        pass count is odd; with an even count it stays an element pass (recs -> tmp) and an expand pass (tmp -> recs) follows.
+// prefix = P > 0: PREFIX + FINISH on elements — only the top P of `passes` run (as element passes), then
+// ibu_k_sort_finish_elems completes the runs of equal prefix and writes the records.  W = 4 needs an even P (the elements must
+// end in tmp: the records are written over the other buffer).  If the finish overflows (long runs of equal prefix), the
+// prefix-sorted elements are a permutation of the input's, so anything may follow, from wherever they ended (src): ONE retry with
+// a longer prefix (longer_prefix) is cheaper than all passes when it still saves two of them — and if that overflows too, all
+// passes run.  So this is a loop over at most three attempts whose state is src / dst, `given` and `prefix`.
+template <int W>
+static hipError_t launch_compact_passes(const LaunchCfg& cfg, const CompactVariant& cv, void* recs, void* tmp, size_t n, void* scratch,
+                                        const CompactPlan& pl, const u32* passes, u32 npass, hipStream_t st, ElemsGiven given, u32 prefix) {
+  const SortScratch S(scratch, sort_layout(cfg, n, cv.tile));
+  const ElemScatter scatter{cv, S, st};
+  IBU_TRY(scatter.prepare(false));
+  IBU_TRY(scatter.prepare(true));
+  ElemT<W>* src = static_cast<ElemT<W>*>(tmp);
+  ElemT<W>* dst = W == 3 ? reinterpret_cast<ElemT<W>*>(static_cast<uint8_t*>(tmp) + 12 * n) : static_cast<ElemT<W>*>(recs);
+  const bool fuse_last = W == 3 || (npass & 1u);
+  for (int attempt = 0;; ++attempt) {
+    const u32 first_pass = prefix ? npass - prefix : 0;
+    if (!given.elems) launch_compress<W>(cfg, pl, recs, n, passes[first_pass], src, S.digits, st);
+    else if (!given.digits || given.digits_byte != passes[first_pass])
+      hipLaunchKernelGGL(ibu_k_sort_digits<W>, dim3((u32)cfg.cus * 8), dim3(256), 0, st, (const ElemT<W>*)src, (u64)n, passes[first_pass], S.digits);
+    // passes; the last one writes the records themselves (with a finishing pass behind them, none of them does)
+    for (u32 pi = first_pass; pi < npass; ++pi) {
+      launch_counts_bytes(cfg, cv.counts_bytes, S, n, st);
+      IBU_TRY(launch_offsets(S, st));
+      const bool last = pi + 1 == npass, to_records = last && fuse_last && !prefix;
+      IBU_TRY(scatter(to_records, src, to_records ? recs : static_cast<void*>(dst), n, passes[pi], last ? 4u * W : passes[pi + 1], pl));   // 4 W: no digit stream behind the last pass
+      ElemT<W>* t = src; src = dst; dst = t;
+    }
+    if (!prefix) {
+      if (!fuse_last) launch_expand_w<W>(cfg, pl, src, n, recs, st);   // W = 4, even pass count: the elements ended in tmp
+      return hipGetLastError();
+    }
+    bool overflowed = false;
+    IBU_TRY(launch_finish_elems<W>(cfg, S, src, recs, n, passes + first_pass, npass - first_pass, pl, st, &overflowed));
+    if (!overflowed) return hipGetLastError();
+    const u32 longer = longer_prefix<W>(pl, prefix);
+    if (attempt == 0 && longer + 2 <= npass) {
+      if (trace_sort()) fprintf(stderr, "ibu sort: n=%zu prefix+finish overflowed (long runs of equal prefix): retrying with prefix_passes=%u of %u\n", n, longer, npass);
+      prefix = longer;
+    } else {
+      if (trace_sort()) fprintf(stderr, "ibu sort: n=%zu prefix+finish overflowed (long runs of equal prefix): all %u passes\n", n, npass);
+      prefix = 0;
+    }
+    given = ElemsGiven{true};                                 // the elements at src; no digit stream of the next first pass
+  }
+}
+// The one entry to the compact passes: 12-byte elements on the shape the caller picked for them (cv12) while at most 12 bytes
+// vary, 16-byte elements on cfg's shape for those otherwise.
+static const CompactVariant& compact_variant_of(const LaunchCfg& cfg, const CompactVariant& cv12, const CompactPlan& pl) {
+  return pl.k <= 12 ? cv12 : pick_compact16(cfg);
+}
+static hipError_t sort_compact(const LaunchCfg& cfg, const CompactVariant& cv12, void* recs, void* tmp, size_t n, void* scratch, const CompactPlan& pl,
+                               const u32* passes, u32 npass, hipStream_t st, ElemsGiven given, u32 prefix) {
+  const CompactVariant& cv = compact_variant_of(cfg, cv12, pl);
+  return pl.k <= 12 ? launch_compact_passes<3>(cfg, cv, recs, tmp, n, scratch, pl, passes, npass, st, given, prefix)
+                    : launch_compact_passes<4>(cfg, cv, recs, tmp, n, scratch, pl, passes, npass, st, given, prefix);
+}
+
+// ---- PREFIX + FINISH: how long a prefix?  A pair count over a sample says (sort_finish.hpp: ibu_k_sort_sample_pairs*) -------------
+// cfg.sort_hybrid: 0 = never, 1 = when at least three passes are saved, 2 = whenever one is (tests).  The finishing pass costs about
+// as much as two element passes (14 B read with the look-ahead + 24 B written per record), the plain path's last pass half a pass
+// more than the others.
+static u32 prefix_margin(const LaunchCfg& cfg) { return cfg.sort_hybrid == 2 ? 1u : 3u; }
+static bool prefix_worth_it(const LaunchCfg& cfg, u32 P, u32 sorted_bytes) { return P + prefix_margin(cfg) <= sorted_bytes; }
+static size_t prefix_table_bytes(u32 slots) { return 128 + (size_t)slots * 12 * kMaxPrefix; }
+// The sample: `nranges` evenly spaced ranges of `per_range` records, counted in tables of `slots` slots per prefix length.
+struct PrefixSample { u32 slots, nranges, per_range; };
+// The estimate loop.  The key has `nbytes` bytes a prefix can be made of, of which the sort runs passes on `sorted_bytes`.
+// launch_window(first, grid, range_stride, keys, cnts, pairs) queues the pair count of the prefixes of first + 1 .. first +
+// kMaxPrefix bytes; the tables live at `tables` (prefix_table_bytes(slots): pairs | keys | counts).  Prefixes of 1 .. 8 bytes first;
+// keys that need more (a wide barcode from a whitelist: every barcode byte and then some of the UMI's) get a second and third look
+// at 9 .. 16 and 17 .. 24 bytes, as long as such a prefix would still save passes.  *P_out: the shortest prefix that leaves short
+// runs in a sort of n_scale records like these n (0: none does), *seg_out: the run length estimated for it.
+template <class LaunchWindow>
+static hipError_t estimate_prefix(const LaunchCfg& cfg, size_t n, size_t n_scale, void* tables, const PrefixSample& s, u32 nbytes, u32 sorted_bytes,
+                                  hipStream_t st, LaunchWindow&& launch_window, u32* P_out, double* seg_out) {
+  *P_out = 0;
+  *seg_out = 0;
+  const size_t m = (size_t)s.nranges * s.per_range;
+  const u64 range_stride = (n - s.per_range) / (s.nranges - 1);
+  uint8_t* tb = static_cast<uint8_t*>(tables);
+  u64* d_pairs = reinterpret_cast<u64*>(tb);
+  u64* d_keys = reinterpret_cast<u64*>(tb + 128);
+  u32* d_cnts = reinterpret_cast<u32*>(tb + 128 + (size_t)s.slots * 8 * kMaxPrefix);
+  for (u32 first = 0; !*P_out && first < nbytes && first + 1 + prefix_margin(cfg) <= sorted_bytes; first += (u32)kMaxPrefix) {
+    IBU_TRY(hipMemsetAsync(tb, 0, prefix_table_bytes(s.slots), st));
+    launch_window(first, dim3((u32)((m + 255) / 256)), range_stride, d_keys, d_cnts, d_pairs);
+    u64 pairs[2 * kMaxPrefix];                                 // [q]: pairs of equal (first + q + 1)-byte prefix; [kMaxPrefix + q]: the most frequent one's count (0: below 4)
+    IBU_TRY(read_back(pairs, d_pairs, sizeof pairs, st));
+    // a record shares its prefix with about 1 + (n / m) * (2 pairs / m) records: at most ~8 wanted (ranking is quadratic)
+    for (u32 q = 0; q < (u32)kMaxPrefix && first + q + 1 <= nbytes; ++q) {
+      const double seg = 1.0 + ((double)n_scale / (double)m) * (2.0 * (double)pairs[q] / (double)m);
+      const double heaviest = (double)pairs[kMaxPrefix + q] * ((double)n_scale / (double)m);   // estimated longest run
+      if (seg <= 8.0 && heaviest <= 128.0) { *P_out = first + q + 1; *seg_out = seg; break; }
+    }
+  }
+  return hipSuccess;
+}
+// PREFIX + FINISH on the elements?  Only if the runs of equal prefix are going to be short (the tables live in tmp, which nothing
+// uses at that point).  `sorted_bytes`: the passes the plain path would run (the element bytes it sorts on are the top
+// `sorted_bytes` of the plan's k).  *P_out = the prefix to use, 0 = none.
 // n_scale: the size of the whole the runs are estimated for — n, or (the multi-GPU sort) the records of ALL shards, of which these
 // n are taken for a sample.
 static hipError_t estimate_compact_prefix(const LaunchCfg& cfg, const void* recs, size_t n, void* tmp, const CompactPlan& plan, u32 sorted_bytes,
                                           hipStream_t st, u32* P_out, double* seg_out, size_t n_scale = 0) {
-  if (!n_scale) n_scale = n;
   *P_out = 0;
   *seg_out = 0;
   if (!cfg.sort_hybrid || (reinterpret_cast<uintptr_t>(tmp) & 7u) != 0) return hipSuccess;
   u32 slots = kPairSlotsMax;
-  while (slots > 256 && (size_t)slots * 12 * kMaxPrefix + 128 > n * 24) slots >>= 1;
-  if ((size_t)slots * 12 * kMaxPrefix + 128 > n * 24) return hipSuccess;
+  while (slots > 256 && prefix_table_bytes(slots) > n * 24) slots >>= 1;
+  if (prefix_table_bytes(slots) > n * 24) return hipSuccess;
   // the estimate's own sample: 48 evenly spaced ranges of 2048 records (98 304 records, spread over the input: input that is
   // grouped in stretches is seen for what it is); fewer and shorter ranges while the tables must be small (load factor <= 3/8)
   const size_t cap = (size_t)slots * 3 / 8;
@@ -507,98 +677,24 @@ static hipError_t estimate_compact_prefix(const LaunchCfg& cfg, const void* recs
   while (nranges > 3 && (size_t)nranges * per_range > n / 32) nranges /= 2;   // small inputs: a thirty-second of them is sample enough (the pair count of 49 152 samples was 75 of a 1e6-record sort's 255 us of kernels)
   if ((size_t)nranges * per_range > cap) per_range = (u32)(cap / nranges);
   if (per_range < 32 || (size_t)nranges * per_range > n) return hipSuccess;
-  const size_t m = (size_t)nranges * per_range;
-  const u64 range_stride = (n - per_range) / (nranges - 1);
-  uint8_t* tb = static_cast<uint8_t*>(tmp);
-  u64* d_pairs = reinterpret_cast<u64*>(tb);
-  u64* d_keys = reinterpret_cast<u64*>(tb + 128);
-  u32* d_cnts = reinterpret_cast<u32*>(tb + 128 + (size_t)slots * 8 * kMaxPrefix);
   const u64* r64 = static_cast<const u64*>(recs);
-  const u32 margin = cfg.sort_hybrid == 2 ? 1u : 3u;
   u32 P = 0;
-  // prefixes of 1 .. 8 bytes first; keys that need more (a wide barcode from a whitelist: every barcode byte and then some of the
-  // UMI's) get a second and third look at 9 .. 16 and 17 .. 24 bytes, as long as such a prefix would still save passes
-  for (u32 first = 0; !P && first < plan.k && first + 1 + margin <= sorted_bytes; first += (u32)kMaxPrefix) {
-    hipError_t e = hipMemsetAsync(tb, 0, 128 + (size_t)slots * 12 * kMaxPrefix, st);
-    if (e != hipSuccess) return e;
-    if (plan.k <= 12)
-      hipLaunchKernelGGL(ibu_k_sort_sample_pairs<3>, dim3((u32)((m + 255) / 256)), dim3(256), 0, st, r64, range_stride, nranges, per_range, plan, plan.k,
-                         first, slots, d_keys, d_cnts, d_pairs);
-    else
-      hipLaunchKernelGGL(ibu_k_sort_sample_pairs<4>, dim3((u32)((m + 255) / 256)), dim3(256), 0, st, r64, range_stride, nranges, per_range, plan, plan.k,
-                         first, slots, d_keys, d_cnts, d_pairs);
-    u64 pairs[2 * kMaxPrefix];                                 // [q]: pairs of equal (first + q + 1)-byte prefix; [kMaxPrefix + q]: the most frequent one's count (0: below 4)
-    e = hipMemcpyAsync(pairs, d_pairs, sizeof pairs, hipMemcpyDeviceToHost, st);
-    if (e != hipSuccess) return e;
-    e = hipStreamSynchronize(st);
-    if (e != hipSuccess) return e;
-    // a record shares its prefix with about 1 + (n / m) * (2 pairs / m) records: at most ~8 wanted (ranking is quadratic)
-    for (u32 q = 0; q < (u32)kMaxPrefix && first + q + 1 <= plan.k; ++q) {
-      const double seg = 1.0 + ((double)n_scale / (double)m) * (2.0 * (double)pairs[q] / (double)m);
-      const double heaviest = (double)pairs[kMaxPrefix + q] * ((double)n_scale / (double)m);   // estimated longest run
-      if (seg <= 8.0 && heaviest <= 128.0) { P = first + q + 1; *seg_out = seg; break; }
-    }
-  }
+  const hipError_t e = estimate_prefix(
+      cfg, n, n_scale ? n_scale : n, tmp, PrefixSample{slots, nranges, per_range}, plan.k, sorted_bytes, st,
+      [&](u32 first, dim3 grid, u64 range_stride, u64* d_keys, u32* d_cnts, u64* d_pairs) {
+        if (plan.k <= 12)
+          hipLaunchKernelGGL(ibu_k_sort_sample_pairs<3>, grid, dim3(256), 0, st, r64, range_stride, nranges, per_range, plan, plan.k, first, slots, d_keys, d_cnts, d_pairs);
+        else
+          hipLaunchKernelGGL(ibu_k_sort_sample_pairs<4>, grid, dim3(256), 0, st, r64, range_stride, nranges, per_range, plan, plan.k, first, slots, d_keys, d_cnts, d_pairs);
+      },
+      &P, seg_out);
+  if (e != hipSuccess) return e;
   if (P && plan.k > 12 && (P & 1u)) ++P;                       // 16-byte elements must end in tmp: an even number of passes
-  // worth it?  The finishing pass costs about as much as two element passes (14 B read with the look-ahead + 24 B written per
-  // record), the plain path's last pass half a pass more than the others
-  if (P && P + margin > sorted_bytes) P = 0;                   // not worth it / would reach into index bytes the passes do not sort on
+  if (P && !prefix_worth_it(cfg, P, sorted_bytes)) P = 0;      // not worth it / would reach into index bytes the passes do not sort on
   *P_out = P;
   return hipSuccess;
 }
 
-// ---- the multi-GPU sort on 12-byte elements: partition first, sort once (multi_sort.cpp, round 4) -----------------------------------
-// Round 3 sorted every shard, exchanged the pieces between the splitters and sorted every owner's pieces AGAIN.  Now a shard is only
-// PARTITIONED before the exchange: its records become 12-byte elements (one plan for all shards, at most 11 varying bytes), every
-// element gets — in the same kernel — the number of its key range — how many of the (up to 255) splitters are not above it — in its free top byte, and one
-// ordinary element pass on that byte (count from the side stream, scan, scatter: the kernels of the sort) moves the elements into
-// range order; the scan's bin starts are the range boundaries, from which the caller cuts the owners' pieces.  The owner sorts the elements it received straight into records (launch_sort_elems: the
-// passes of the sort without its census and compress steps — the sender made the elements).
-extern "C" __global__ void __launch_bounds__(256)
-ibu_k_sort_stamp_bucket(ElemT<3>* __restrict__ elems, u64 n, const ElemT<3>* __restrict__ split, u32 nsplit, uint8_t* __restrict__ digits) {
-  __shared__ u32 sp[3 * 256];
-  for (u32 i = threadIdx.x; i < 3 * nsplit; i += blockDim.x) sp[i] = reinterpret_cast<const u32*>(split)[i];
-  __syncthreads();
-  const u64 stride = (u64)gridDim.x * blockDim.x;
-  for (u64 i = (u64)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
-    EV<3> e = ld_elem<3>(elems + i);
-    e.w[2] &= 0x00FFFFFFu;                                    // (zero already: at most 11 bytes vary)
-    const u32 g = range_of(sp, nsplit, e);
-    e.w[2] |= g << 24;
-    st_elem<3>(elems + i, e);
-    digits[i] = (uint8_t)g;
-  }
-}
-// records -> stamped elements + the digit stream of the ranges: the tiled rows in ONE kernel (ibu_k_sort_compress<.., STAMP>), the
-// peeled head row and the rest rows (fewer than 129 in all) through the tail compress kernel and the stamp kernel above.
-// census (nullable; 16-byte aligned records only): the exact census words are accumulated on the way, as in the sort's speculative path.
-static void launch_compress_stamped(const LaunchCfg& cfg, const CompactPlan& pl, const void* recs, size_t n, ElemT<3>* out, uint8_t* digits,
-                                    const ElemT<3>* split, u32 nsplit, hipStream_t st, u64* census = nullptr) {
-  const size_t head = (reinterpret_cast<uintptr_t>(recs) & 15u) ? (n ? 1 : 0) : 0;
-  const size_t main_rows = ((n - head) / kTileRecs) * kTileRecs;
-  if (head) {
-    hipLaunchKernelGGL(ibu_k_sort_compress_tail<3>, dim3(1), dim3(256), 0, st, (const u64*)recs, (u64)0, (u64)head, pl, 0u, out, (uint8_t*)nullptr);
-    hipLaunchKernelGGL(ibu_k_sort_stamp_bucket, dim3(1), dim3(256), 0, st, out, (u64)head, split, nsplit, digits);
-  }
-  if (main_rows) {
-    static std::atomic<int> occ[2];
-    const u32 nt = (u32)(main_rows / kTileRecs);
-    if (census)
-      hipLaunchKernelGGL((ibu_k_sort_compress<true, 3, true>), dim3(grid_for(nt, cfg.cus, resident_blocks<kBlock>(cfg, ibu_k_sort_compress<true, 3, true>, 0, &occ[1]))),
-                         dim3(kBlock), 0, st, static_cast<const uint8_t*>(recs) + 24 * head, nt, pl, 0u, out + head, digits + head, census, split, nsplit);
-    else
-      hipLaunchKernelGGL((ibu_k_sort_compress<false, 3, true>), dim3(grid_for(nt, cfg.cus, resident_blocks<kBlock>(cfg, ibu_k_sort_compress<false, 3, true>, 0, &occ[0]))),
-                         dim3(kBlock), 0, st, static_cast<const uint8_t*>(recs) + 24 * head, nt, pl, 0u, out + head, digits + head, (u64*)nullptr, split, nsplit);
-  }
-  const size_t done = head + main_rows;
-  if (done < n) {
-    hipLaunchKernelGGL(ibu_k_sort_compress_tail<3>, dim3(tail_grid(n - done)), dim3(256), 0, st, (const u64*)recs, (u64)done, (u64)n, pl, 0u, out,
-                       (uint8_t*)nullptr);
-    hipLaunchKernelGGL(ibu_k_sort_stamp_bucket, dim3(1), dim3(256), 0, st, out + done, (u64)(n - done), split, nsplit, digits + done);
-    if (census)   // the rest rows of the census (each row also against its predecessor)
-      hipLaunchKernelGGL(ibu_k_sort_census_tail, dim3(tail_grid(n - done)), dim3(256), 0, st, (const u64*)recs, (u64)done, (u64)n, census, (u32*)nullptr);
-  }
-}
 static const CompactVariant* elems_variant(const LaunchCfg& cfg, size_t n, size_t scratch_bytes) {
   const CompactVariant* cv = pick_compact_for(cfg, n);
   if (!cv) cv = &kCompact[0];                                 // (sort_compact = 0 on this context: the default shape)
@@ -606,8 +702,7 @@ static const CompactVariant* elems_variant(const LaunchCfg& cfg, size_t n, size_
   if (n >= (1ull << 38) || (wide_idx && !cv->scatter64) || scratch_bytes < sort_layout(cfg, n, cv->tile).total) return nullptr;
   return cv;
 }
-hipError_t launch_estimate_prefix(const LaunchCfg& cfg, const void* recs, size_t n, size_t n_scale, void* tmp, const CompactPlan& pl,
-                                  uint32_t* prefix_passes, hipStream_t st) {
+hipError_t launch_estimate_prefix(const LaunchCfg& cfg, const void* recs, size_t n, size_t n_scale, void* tmp, const CompactPlan& pl, uint32_t* prefix_passes, hipStream_t st) {
   (void)hipGetLastError();
   double seg = 0;
   u32 P = 0;
@@ -617,6 +712,25 @@ hipError_t launch_estimate_prefix(const LaunchCfg& cfg, const void* recs, size_t
   if (e == hipSuccess) *prefix_passes = P;
   return e;
 }
+// One partition pass, on elements or on records: stamp(census) writes every row's key range into the digit side stream (and takes
+// the census words on the way where the caller wants them), one ordinary pass on that stream — counts, offsets, scatter() — moves
+// the rows into range order.  *d_starts: the scan's bin starts, u64[256] in the scratch: the first row of every range.
+template <class Stamp, class Scatter>
+static hipError_t partition_pass(const LaunchCfg& cfg, const SortScratch& S, CountsBytesFn counts_bytes, size_t n, Stamp&& stamp, Scatter&& scatter,
+                                 const uint64_t** d_starts, const uint64_t** d_census, hipStream_t st, const PartitionEarly* early) {
+  u64* census = d_census ? S.census : nullptr;
+  if (census) hipLaunchKernelGGL(ibu_k_sort_census_init, dim3(1), dim3(kCensusSlots * 8), 0, st, census);
+  stamp(census);
+  if (census) {
+    hipLaunchKernelGGL(ibu_k_sort_census_fold, dim3(1), dim3(kCensusSlots), 0, st, census);
+    *d_census = reinterpret_cast<const uint64_t*>(census);    // u64[8]: OR x 3, AND x 3, index drops, order drops — of exactly these n rows (records: [6], [7] not taken)
+  }
+  launch_counts_bytes(cfg, counts_bytes, S, n, st);
+  IBU_TRY(launch_offsets(S, st, early, census));
+  IBU_TRY(scatter());
+  *d_starts = reinterpret_cast<const uint64_t*>(S.binbase);
+  return hipGetLastError();
+}
 hipError_t launch_partition_elems(const LaunchCfg& cfg, const CompactPlan& pl, const void* recs, void* elems, size_t n, const void* d_split,
                                   uint32_t nsplit, void* out, void* scratch, size_t scratch_bytes, const uint64_t** d_starts,
                                   const uint64_t** d_census, hipStream_t st, const PartitionEarly* early) {
@@ -625,56 +739,16 @@ hipError_t launch_partition_elems(const LaunchCfg& cfg, const CompactPlan& pl, c
   if (d_census && (reinterpret_cast<uintptr_t>(recs) & 15u)) return hipErrorInvalidValue;
   const CompactVariant* cv = elems_variant(cfg, n, scratch_bytes);
   if (!cv) return hipErrorInvalidValue;
-  uint8_t* sc = static_cast<uint8_t*>(scratch);
-  const SortLayout L = sort_layout(cfg, n, cv->tile);
-  u64* binbase = reinterpret_cast<u64*>(sc + L.binbase);
-  u32* blocksum = reinterpret_cast<u32*>(sc + L.blocksum);
-  u64* blockoff = reinterpret_cast<u64*>(sc + L.blockoff);
-  uint16_t* counts = reinterpret_cast<uint16_t*>(sc + L.counts);
-  void* pos = sc + L.pos;
-  uint8_t* digits = sc + L.digits;
-  const void* k_scatter = L.idx64 ? cv->scatter64 : cv->scatter;
-  hipError_t e;
-  if (cv->lds > 48 * 1024) {
-    e = hipFuncSetAttribute(k_scatter, hipFuncAttributeMaxDynamicSharedMemorySize, (int)cv->lds);
-    if (e != hipSuccess) return e;
-  }
-  const u32 cap = (u32)cfg.cus * 8;
-  u64* census = d_census ? reinterpret_cast<u64*>(sc) : nullptr;   // the census slots sit at the head of the scratch (SortLayout)
-  if (census) hipLaunchKernelGGL(ibu_k_sort_census_init, dim3(1), dim3(kCensusSlots * 8), 0, st, census);
-  launch_compress_stamped(cfg, pl, recs, n, static_cast<ElemT<3>*>(elems), digits, static_cast<const ElemT<3>*>(d_split), nsplit, st, census);
-  if (census) {
-    hipLaunchKernelGGL(ibu_k_sort_census_fold, dim3(1), dim3(kCensusSlots), 0, st, census);
-    *d_census = reinterpret_cast<const uint64_t*>(census);    // u64[8]: OR x 3, AND x 3, index drops, order drops — of exactly these n records
-  }
-  const u32 wave_grid = (L.ntiles + kSortWaves - 1) / kSortWaves;
-  hipLaunchKernelGGL(cv->counts_bytes, dim3(wave_grid < cap ? wave_grid : cap), dim3(kSortThreads), 0, st, (const uint8_t*)digits, (u64)n, L.ntiles,
-                     counts);
-  hipLaunchKernelGGL(ibu_k_sort_blocksums, dim3(L.nblocks), dim3(kSortThreads), 0, st, (const uint16_t*)counts, L.ntiles, L.tpb, blocksum);
-  hipLaunchKernelGGL(ibu_k_sort_blockscan, dim3(1), dim3(kSortThreads), 0, st, (const u32*)blocksum, L.nblocks, blockoff, binbase);
-  if (early) {                                                 // the host's share of the pass is complete here: hand it over before the scatter
-    e = hipMemcpyAsync(early->h_starts, binbase, 8 * kBins, hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess && census) e = hipMemcpyAsync(early->h_words, census, 64, hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess) e = hipEventRecord(early->ready, st);
-    if (e != hipSuccess) return e;
-  }
-  if (L.idx64)
-    hipLaunchKernelGGL(ibu_k_sort_tilepos<u64>, dim3(L.nblocks), dim3(kSortThreads), 0, st, (const uint16_t*)counts, L.ntiles, L.tpb,
-                       (const u64*)blockoff, (const u64*)binbase, static_cast<u64*>(pos));
-  else
-    hipLaunchKernelGGL(ibu_k_sort_tilepos<u32>, dim3(L.nblocks), dim3(kSortThreads), 0, st, (const uint16_t*)counts, L.ntiles, L.tpb,
-                       (const u64*)blockoff, (const u64*)binbase, static_cast<u32*>(pos));
-  u32 n32 = (u32)n, b_arg = 11, nb_arg = 12;                  // the owner byte; 12 = no digit stream behind this pass
-  u64 n64 = n;
-  const void* src_arg = elems;
-  void* dst_arg = out;
-  const void* pos_arg = pos;
-  CompactPlan pl_arg = CompactPlan();                         // (only a last pass expands)
-  void* args[] = {&src_arg, &dst_arg, L.idx64 ? static_cast<void*>(&n64) : static_cast<void*>(&n32), &b_arg, &nb_arg, &pos_arg, &digits, &pl_arg};
-  e = hipLaunchKernel(k_scatter, dim3((L.ntiles + 7u) & ~7u), dim3(cv->threads), args, cv->lds, st);
-  if (e != hipSuccess) return e;
-  *d_starts = reinterpret_cast<const uint64_t*>(binbase);                                  // u64[256]: first element of every owner's piece
-  return hipGetLastError();
+  const SortScratch S(scratch, sort_layout(cfg, n, cv->tile));
+  const ElemScatter scatter{*cv, S, st};
+  IBU_TRY(scatter.prepare(false));
+  return partition_pass(
+      cfg, S, cv->counts_bytes, n,
+      [&](u64* census) {
+        launch_compress<3, true>(cfg, pl, recs, n, 0, static_cast<ElemT<3>*>(elems), S.digits, st, census, static_cast<const ElemT<3>*>(d_split), nsplit);
+      },
+      [&] { return scatter(false, elems, out, n, 11, 12, CompactPlan()); },   // the owner byte; 12 = no digit stream behind this pass; the plan: only a last pass expands
+      d_starts, d_census, st, early);
 }
 // The same partition pass on 24-byte RECORDS (keys of more than 11 varying bytes, or buffers the element kernels cannot take): a
 // record's key range — how many of the up to 255 splitter records are not above it — goes into the digit side stream, and one
@@ -713,63 +787,28 @@ hipError_t launch_partition_records(const LaunchCfg& cfg, const void* recs, size
   if ((n + sv.tile - 1) / sv.tile >= (1ull << 31)) return hipErrorInvalidValue;
   const SortLayout L = sort_layout(cfg, n, sv.tile);
   if (scratch_bytes < L.total) return hipErrorInvalidValue;
-  uint8_t* sc = static_cast<uint8_t*>(scratch);
-  u64* binbase = reinterpret_cast<u64*>(sc + L.binbase);
-  u32* blocksum = reinterpret_cast<u32*>(sc + L.blocksum);
-  u64* blockoff = reinterpret_cast<u64*>(sc + L.blockoff);
-  uint16_t* counts = reinterpret_cast<uint16_t*>(sc + L.counts);
-  void* pos = sc + L.pos;
-  uint8_t* digits = sc + L.digits;
-  const void* scatter = L.idx64 ? sv.scatter64_stream : sv.scatter32_stream;
-  hipError_t e;
-  if (sv.lds > 48 * 1024) {
-    e = hipFuncSetAttribute(scatter, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sv.lds);
-    if (e != hipSuccess) return e;
-  }
-  const u32 cap = (u32)cfg.cus * 8;
-  const u64 want = (n + 255) / 256;
-  u64* census = d_census ? reinterpret_cast<u64*>(sc) : nullptr;   // the census slots sit at the head of the scratch (SortLayout)
-  if (census) {
-    hipLaunchKernelGGL(ibu_k_sort_census_init, dim3(1), dim3(kCensusSlots * 8), 0, st, census);
-    hipLaunchKernelGGL(ibu_k_sort_stamp_records<true>, dim3((u32)(want < cap ? want : cap)), dim3(256), 0, st, static_cast<const u64*>(recs), (u64)n,
-                       static_cast<const u64*>(d_split), nsplit, digits, census);
-    hipLaunchKernelGGL(ibu_k_sort_census_fold, dim3(1), dim3(kCensusSlots), 0, st, census);
-    *d_census = reinterpret_cast<const uint64_t*>(census);    // u64[8]: OR x 3, AND x 3 of exactly these n records ([6], [7]: not taken)
-  } else {
-    hipLaunchKernelGGL(ibu_k_sort_stamp_records<false>, dim3((u32)(want < cap ? want : cap)), dim3(256), 0, st, static_cast<const u64*>(recs), (u64)n,
-                       static_cast<const u64*>(d_split), nsplit, digits, (u64*)nullptr);
-  }
-  const u32 wave_grid = (L.ntiles + kSortWaves - 1) / kSortWaves;
-  hipLaunchKernelGGL(sv.counts_bytes, dim3(wave_grid < cap ? wave_grid : cap), dim3(kSortThreads), 0, st, (const uint8_t*)digits, (u64)n, L.ntiles, counts);
-  hipLaunchKernelGGL(ibu_k_sort_blocksums, dim3(L.nblocks), dim3(kSortThreads), 0, st, (const uint16_t*)counts, L.ntiles, L.tpb, blocksum);
-  hipLaunchKernelGGL(ibu_k_sort_blockscan, dim3(1), dim3(kSortThreads), 0, st, (const u32*)blocksum, L.nblocks, blockoff, binbase);
-  if (early) {                                                 // the host's share of the pass is complete here: hand it over before the scatter
-    e = hipMemcpyAsync(early->h_starts, binbase, 8 * kBins, hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess && census) e = hipMemcpyAsync(early->h_words, census, 64, hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess) e = hipEventRecord(early->ready, st);
-    if (e != hipSuccess) return e;
-  }
-  if (L.idx64)
-    hipLaunchKernelGGL(ibu_k_sort_tilepos<u64>, dim3(L.nblocks), dim3(kSortThreads), 0, st, (const uint16_t*)counts, L.ntiles, L.tpb,
-                       (const u64*)blockoff, (const u64*)binbase, static_cast<u64*>(pos));
-  else
-    hipLaunchKernelGGL(ibu_k_sort_tilepos<u32>, dim3(L.nblocks), dim3(kSortThreads), 0, st, (const uint16_t*)counts, L.ntiles, L.tpb,
-                       (const u64*)blockoff, (const u64*)binbase, static_cast<u32*>(pos));
-  u64 n_arg = n;
-  u32 f_arg = 3, s_arg = 0, nf_arg = 3, ns_arg = 0;           // this pass's digit: from the side stream; no pass follows
-  const u64* src_arg = static_cast<const u64*>(recs);
-  u64* dst_arg = static_cast<u64*>(out);
-  void* args[] = {&src_arg, &dst_arg, &n_arg, &f_arg, &s_arg, &nf_arg, &ns_arg, &pos, &digits};
-  e = hipLaunchKernel(scatter, dim3((L.ntiles + 7u) & ~7u), dim3(sv.threads), args, sv.lds, st);
-  if (e != hipSuccess) return e;
-  *d_starts = reinterpret_cast<const uint64_t*>(binbase);     // u64[256]: first record of every range
-  return hipGetLastError();
+  const SortScratch S(scratch, L);
+  const RecScatter scatter{sv, S, st, true};
+  IBU_TRY(scatter.prepare());
+  const u64 want = (n + 255) / 256, cap = (u64)cfg.cus * 8;
+  const dim3 stamp_grid((u32)(want < cap ? want : cap));
+  return partition_pass(
+      cfg, S, sv.counts_bytes, n,
+      [&](u64* census) {
+        if (census)
+          hipLaunchKernelGGL(ibu_k_sort_stamp_records<true>, stamp_grid, dim3(256), 0, st, static_cast<const u64*>(recs), (u64)n,
+                             static_cast<const u64*>(d_split), nsplit, S.digits, census);
+        else
+          hipLaunchKernelGGL(ibu_k_sort_stamp_records<false>, stamp_grid, dim3(256), 0, st, static_cast<const u64*>(recs), (u64)n,
+                             static_cast<const u64*>(d_split), nsplit, S.digits, (u64*)nullptr);
+      },
+      [&] { return scatter(static_cast<const u64*>(recs), static_cast<u64*>(out), n, 3, 0, 3, 0); },   // this pass's digit: from the side stream; no pass follows
+      d_starts, d_census, st, early);
 }
 bool sort_elems_supported(const LaunchCfg& cfg, const void* recs, const void* tmp, size_t capacity) {
   return cfg.sort_compact != 0 && capacity < (1ull << 38) && (reinterpret_cast<uintptr_t>(recs) & 15u) == 0 && (reinterpret_cast<uintptr_t>(tmp) & 15u) == 0;
 }
-hipError_t launch_sort_elems(const LaunchCfg& cfg, const CompactPlan& pl, void* recs, void* tmp, size_t n, uint32_t prefix_passes, void* scratch,
-                             size_t scratch_bytes, hipStream_t st) {
+hipError_t launch_sort_elems(const LaunchCfg& cfg, const CompactPlan& pl, void* recs, void* tmp, size_t n, uint32_t prefix_passes, void* scratch, size_t scratch_bytes, hipStream_t st) {
   (void)hipGetLastError();
   if (n == 0) return hipSuccess;
   if (pl.k > 12) return hipErrorInvalidValue;
@@ -781,123 +820,78 @@ hipError_t launch_sort_elems(const LaunchCfg& cfg, const CompactPlan& pl, void* 
   u32 P = prefix_passes;
   if (n < 8192 || P + 1 >= pl.k) P = 0;
   if (trace_sort()) fprintf(stderr, "ibu sort: n=%zu path=elements-received element_bytes=12 prefix_passes=%u of %u\n", n, P, pl.k);
-  return launch_compact_passes<3>(cfg, *cv, recs, tmp, n, static_cast<uint8_t*>(scratch), pl, ebytes, pl.k, st, true, 0xFFFFFFFFu, P,
-                                  static_cast<ElemT<3>*>(tmp));
+  return sort_compact(cfg, *cv, recs, tmp, n, scratch, pl, ebytes, pl.k, st, ElemsGiven{true}, P);   // the elements in tmp: the sender made them; no digit stream
 }
 
-// What launch_sort_records' sampled prefix estimate keeps in the head of `tmp` for n records (0: it would not sample) — for a caller
-// that hands it some other scratch as `tmp` (only_estimate).
-size_t sort_prefix_estimate_tables(const LaunchCfg& cfg, size_t n) {
-  const size_t table_bytes = 128 + (size_t)kPairSlotsMax * 12 * kMaxPrefix;
-  return (cfg.sort_hybrid && n >= 4 * (size_t)32768 && table_bytes <= n * 24) ? table_bytes : 0;
-}
-
-// Not purely asynchronous: the census result comes back to the host (one 64-byte read) to pick the passes; everything
-// after that is queued on `st`.
-// known_words (nullable): census words the caller already has for a SUPERSET of these records (the multi-GPU sort: the partition pass
-// took them over all shards) — OR x 3, AND x 3; no census pass runs, no record is assumed in index order or sorted, and the bytes
-// that vary in the superset get their passes (a byte that happens to be constant here costs one identity pass).
-// known_prefix (with known_words; the multi-GPU sort): >= 0 = the prefix length of the 24-byte prefix + finish path as somebody already
-// estimated it for the WHOLE these records are a key range of (0: all passes); -1: estimate here.  only_estimate (nullable): do nothing
-// but that estimate — for n_scale records like these — and return it in *only_estimate (tmp's head is the table scratch).
-hipError_t launch_sort_records(const LaunchCfg& cfg, void* recs, void* tmp, size_t n, void* scratch,
-                               size_t scratch_bytes, hipStream_t st, const uint64_t* known_words, int known_prefix, int* only_estimate,
-                               size_t n_scale) {
-  (void)hipGetLastError();
-  if (n < 2) return hipSuccess;
-  const SweepVariant& sv = pick_variant(cfg);
-  if ((n + sv.tile - 1) / sv.tile >= (1ull << 31)) return hipErrorInvalidValue;
-  const SortLayout L = sort_layout(cfg, n, sv.tile);
-  if (scratch_bytes < L.total) return hipErrorInvalidValue;
-  uint8_t* sc = static_cast<uint8_t*>(scratch);
-  u64* census = reinterpret_cast<u64*>(sc);
-  u64* binbase = reinterpret_cast<u64*>(sc + L.binbase);
-  u32* blocksum = reinterpret_cast<u32*>(sc + L.blocksum);
-  u64* blockoff = reinterpret_cast<u64*>(sc + L.blockoff);
-  uint16_t* counts = reinterpret_cast<uint16_t*>(sc + L.counts);
-  void* pos = sc + L.pos;
-  uint8_t* digits = sc + L.digits;
-
-  // Compact-key path (see "COMPACT-KEY passes"): records 16-byte aligned (the tiled compress kernel), tmp at least 4-byte
-  // aligned; from 2^32 records on (64-bit element indices) the shapes that carry those kernels (the defaults).  Whether at most
-  // 12 / 16 key bytes vary is the census' to say.
-  const CompactVariant* cv = pick_compact_for(cfg, n);
-  const bool wide_idx = n >= (1ull << 32) || cfg.sort_idx64;
-  const bool compact_ok = cv && n < (1ull << 38) && (!wide_idx || (cv->scatter64 && pick_compact16(cfg).scatter64)) &&
-                          (reinterpret_cast<uintptr_t>(recs) & 15u) == 0 &&
-                          (reinterpret_cast<uintptr_t>(tmp) & 3u) == 0 && scratch_bytes >= sort_layout(cfg, n, cv->tile).total &&
-                          scratch_bytes >= sort_layout(cfg, n, pick_compact16(cfg).tile).total;
-  hipError_t e;
-  // SPECULATION (large inputs): the census and the compress pass both read all the records.  A census of three SAMPLE
-  // ranges (first / middle / last 32 Ki records: tens of microseconds) guesses which bytes vary; the compress pass runs on
-  // that guess at once and accumulates the EXACT census on the way; afterwards the guess only has to COVER the truth (every
-  // byte that really varies is in the elements: bytes it carried needlessly are constant digits, their passes are skipped).
-  // A guess that missed a byte costs the compress pass it wasted, and the sort goes on from the exact census as before.
-  bool speculated = false;
+// ---- launch_sort_records and its phases -------------------------------------------------------------------------------------------
+// SPECULATION (large inputs): the census and the compress pass both read all the records.  A census of three SAMPLE
+// ranges (first / middle / last 32 Ki records: tens of microseconds) guesses which bytes vary; the compress pass runs on
+// that guess at once and accumulates the EXACT census on the way; afterwards the guess only has to COVER the truth (every
+// byte that really varies is in the elements: bytes it carried needlessly are constant digits, their passes are skipped).
+// A guess that missed a byte costs the compress pass it wasted, and the sort goes on from the exact census as before.
+struct Speculation {
+  bool done = false;                                          // the elements of plan `gpl` are in tmp, the digit stream of byte gfirst in the scratch, the exact census queued
   CompactPlan gpl;
-  u64 g[8] = {0, 0, 0, 0, 0, 0, 0, 0}, gmask[3] = {0, 0, 0};
-  u32 gfirst = 0, hybP = 0;
+  u64 gmask[3] = {0, 0, 0};                                   // the key bytes the guess carries
+  u32 gfirst = 0, hybP = 0;                                   // hybP: the prefix estimated on the elements of the guess (0: none)
   double hyb_seg = 0;
-  static constexpr size_t kSample = 32768;
-  // cfg.sort_guess: 0 = never, 1 = inputs of 2^17 records and more (the three sample ranges must fit), k > 1 = of k records and more.
-  // (Rounds 1-2 started at 2^23: one read of the records saved against one more host round trip.  With prefix + finish behind the
-  // guess the sizes in between gain 2x — 3e5 / 1e6 / 4e6 records: 0.42 / 0.75 / 1.07 ms -> 0.27 / 0.42 / 0.58 ms.)
-  const size_t guess_min = cfg.sort_guess == 1 ? 4 * kSample : ((size_t)cfg.sort_guess > 4 * kSample ? (size_t)cfg.sort_guess : 4 * kSample);
-  if (!known_words && compact_ok && cfg.sort_guess && n >= guess_min) {
+};
+// cfg.sort_guess: 0 = never, 1 = inputs of 2^17 records and more (the three sample ranges must fit), k > 1 = of k records and more.
+// (Rounds 1-2 started at 2^23: one read of the records saved against one more host round trip.  With prefix + finish behind the
+// guess the sizes in between gain 2x — 3e5 / 1e6 / 4e6 records: 0.42 / 0.75 / 1.07 ms -> 0.27 / 0.42 / 0.58 ms.)
+static bool speculation_wanted(const LaunchCfg& cfg, size_t n) {
+  const size_t guess_min = cfg.sort_guess == 1 ? 4 * kSampleRecs : ((size_t)cfg.sort_guess > 4 * kSampleRecs ? (size_t)cfg.sort_guess : 4 * kSampleRecs);
+  return cfg.sort_guess && n >= guess_min;
+}
+static hipError_t speculate(const LaunchCfg& cfg, const CompactVariant& cv12, const void* recs, void* tmp, size_t n, void* scratch, u64* census, hipStream_t st, Speculation* sp) {
+  u64 g[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+  launch_census_sample(cfg, recs, n, census, st);
+  IBU_TRY(read_back(g, census, sizeof g, st));
+  compact_plan_init(reinterpret_cast<const uint64_t*>(g), reinterpret_cast<const uint64_t*>(g + 3), &sp->gpl);
+  const CompactPlan& gpl = sp->gpl;
+  // g[7] == 0: no sample row is smaller than its predecessor — the input may well be sorted already, and then the
+  // read-only census below (24 B/record) answers that; a speculative compress pass (37 B/record) would be spent first.
+  if (g[7] != 0 && gpl.k >= 1 && gpl.k <= 16) {               // 12-byte elements, or 16-byte ones for 13 .. 16 varying bytes
+    for (int f = 0; f < 3; ++f)
+      for (u32 b = 0; b < 8; ++b)
+        if (((g[f] ^ g[3 + f]) >> (8 * b)) & 255u) sp->gmask[f] |= 255ull << (8 * b);
+    sp->gfirst = (g[6] == 0 && gpl.index_bytes < gpl.k) ? gpl.index_bytes : 0;   // the sample's guess of the first sorted byte
+    IBU_TRY(estimate_compact_prefix(cfg, recs, n, tmp, gpl, gpl.k - sp->gfirst, st, &sp->hybP, &sp->hyb_seg));
+    if (sp->hybP) sp->gfirst = gpl.k - sp->hybP;              // the digit stream the compress pass leaves: the first prefix pass's
     hipLaunchKernelGGL(ibu_k_sort_census_init, dim3(1), dim3(kCensusSlots * 8), 0, st, census);
-    const size_t starts[3] = {0, (n / 2) & ~(size_t)1, (n - kSample) & ~(size_t)1};   // even rows: 16-byte aligned
-    for (size_t s0 : starts) launch_census(cfg, static_cast<const u64*>(recs) + 3 * s0, kSample, census, nullptr, st);
-    hipLaunchKernelGGL(ibu_k_sort_census_fold, dim3(1), dim3(kCensusSlots), 0, st, census);
-    e = hipMemcpyAsync(g, census, sizeof g, hipMemcpyDeviceToHost, st);
-    if (e != hipSuccess) return e;
-    e = hipStreamSynchronize(st);
-    if (e != hipSuccess) return e;
-    compact_plan_init(reinterpret_cast<const uint64_t*>(g), reinterpret_cast<const uint64_t*>(g + 3), &gpl);
-    // g[7] == 0: no sample row is smaller than its predecessor — the input may well be sorted already, and then the
-    // read-only census below (24 B/record) answers that; a speculative compress pass (37 B/record) would be spent first.
-    if (g[7] != 0 && gpl.k >= 1 && gpl.k <= 16) {           // 12-byte elements, or 16-byte ones for 13 .. 16 varying bytes
-      for (int f = 0; f < 3; ++f)
-        for (u32 b = 0; b < 8; ++b)
-          if (((g[f] ^ g[3 + f]) >> (8 * b)) & 255u) gmask[f] |= 255ull << (8 * b);
-      gfirst = (g[6] == 0 && gpl.index_bytes < gpl.k) ? gpl.index_bytes : 0;   // the sample's guess of the first sorted byte
-      e = estimate_compact_prefix(cfg, recs, n, tmp, gpl, gpl.k - gfirst, st, &hybP, &hyb_seg);
-      if (e != hipSuccess) return e;
-      if (hybP) gfirst = gpl.k - hybP;                       // the digit stream the compress pass leaves: the first prefix pass's
-      hipLaunchKernelGGL(ibu_k_sort_census_init, dim3(1), dim3(kCensusSlots * 8), 0, st, census);
-      if (gpl.k <= 12) launch_compress<3>(cfg, gpl, recs, n, gfirst, static_cast<ElemT<3>*>(tmp), sc + sort_layout(cfg, n, cv->tile).digits, st, census);
-      else launch_compress<4>(cfg, gpl, recs, n, gfirst, static_cast<ElemT<4>*>(tmp), sc + sort_layout(cfg, n, pick_compact16(cfg).tile).digits, st, census);
-      speculated = true;
-    } else if (g[7] == 0 && trace_sort()) {
-      fprintf(stderr, "ibu sort: n=%zu samples in order: read-only census first\n", n);
-    }
+    uint8_t* digits = SortScratch(scratch, sort_layout(cfg, n, compact_variant_of(cfg, cv12, gpl).tile)).digits;
+    if (gpl.k <= 12) launch_compress<3>(cfg, gpl, recs, n, sp->gfirst, static_cast<ElemT<3>*>(tmp), digits, st, census);
+    else launch_compress<4>(cfg, gpl, recs, n, sp->gfirst, static_cast<ElemT<4>*>(tmp), digits, st, census);
+    sp->done = true;
+  } else if (g[7] == 0 && trace_sort()) {
+    fprintf(stderr, "ibu sort: n=%zu samples in order: read-only census first\n", n);
   }
-  u64 c[8];
+  return hipSuccess;
+}
+// The census words c[8] (OR x 3, AND x 3, index drops, order drops): the caller's (known_words: of a superset, nothing known about
+// the order), or read back from the census — which the speculative compress pass has queued already (census_queued) or which runs
+// here.
+static hipError_t census_words(const LaunchCfg& cfg, const void* recs, size_t n, u64* census, const uint64_t* known_words, bool census_queued, hipStream_t st, u64 c[8]) {
   if (known_words) {
     for (int w = 0; w < 6; ++w) c[w] = known_words[w];
     c[6] = c[7] = 1;                 // nothing is known about the order
     if (trace_sort()) fprintf(stderr, "ibu sort: n=%zu census words given by the caller: no census pass\n", n);
-  } else {
-    if (!speculated) {
-      hipLaunchKernelGGL(ibu_k_sort_census_init, dim3(1), dim3(kCensusSlots * 8), 0, st, census);
-      launch_census(cfg, recs, n, census, nullptr, st);
-    }
-    hipLaunchKernelGGL(ibu_k_sort_census_fold, dim3(1), dim3(kCensusSlots), 0, st, census);
-    e = hipMemcpyAsync(c, census, sizeof c, hipMemcpyDeviceToHost, st);
-    if (e != hipSuccess) return e;
-    e = hipStreamSynchronize(st);
-    if (e != hipSuccess) return e;
-  }
-  if (c[7] == 0) {                   // no record is smaller than its predecessor: already sorted
-    if (trace_sort()) fprintf(stderr, "ibu sort: n=%zu already sorted%s\n", n, speculated ? " (a speculative compress pass was spent)" : "");   // spent only when the samples saw a drop and the whole did not: impossible, the samples are rows of the whole
     return hipSuccess;
   }
-
-  // which digits vary.  The sort is stable and the index is the LEAST significant field: if the input already runs in
-  // non-decreasing index order (the usual case: records are written in read order), ties on (barcode, umi) keep that
-  // order and the index passes are the identity — 7 passes instead of 11 at 16/12.
-  struct Pass { u32 field, shift; } passes[kDigits];
+  if (!census_queued) {
+    hipLaunchKernelGGL(ibu_k_sort_census_init, dim3(1), dim3(kCensusSlots * 8), 0, st, census);
+    launch_census(cfg, recs, n, census, nullptr, st);
+  }
+  hipLaunchKernelGGL(ibu_k_sort_census_fold, dim3(1), dim3(kCensusSlots), 0, st, census);
+  return read_back(c, census, 8 * sizeof(u64), st);
+}
+// Which digits vary.  The sort is stable and the index is the LEAST significant field: if the input already runs in
+// non-decreasing index order (the usual case: records are written in read order), ties on (barcode, umi) keep that
+// order and the index passes are the identity — 7 passes instead of 11 at 16/12.
+struct Pass { u32 field, shift; };
+static const int kFieldOrder[3] = {2, 1, 0};  // least significant first: index, umi, barcode
+static int passes_from_census(const u64 c[8], Pass passes[kDigits]) {
   int npass = 0;
-  static const int kFieldOrder[3] = {2, 1, 0};  // least significant first: index, umi, barcode
   for (int fo = 0; fo < 3; ++fo) {
     const int f = kFieldOrder[fo];
     if (f == 2 && c[6] == 0) continue;
@@ -905,223 +899,227 @@ hipError_t launch_sort_records(const LaunchCfg& cfg, void* recs, void* tmp, size
     for (u32 b = 0; b < 8; ++b)
       if ((varying >> (8 * b)) & 255u) passes[npass++] = {(u32)f, 8 * b};   // constant digits: the pass would be the identity
   }
-  if (compact_ok && npass > 0 && !only_estimate) {
-    u32 ebytes[16], ne = 0;
-    if (speculated) {
-      bool covered = true;
-      for (int f = 0; f < 3; ++f)
-        if ((c[f] ^ c[3 + f]) & ~gmask[f]) covered = false;
-      if (covered) {                                        // the elements in tmp hold every byte that varies
-        CompactPlan pl = gpl;
-        u32 j = 0;
-        for (int fo = 0; fo < 3; ++fo) {
-          const int f = kFieldOrder[fo];
-          pl.base[f] = c[3 + f] & ~gmask[f];
-          for (u32 b = 0; b < 8; ++b)
-            if ((gmask[f] >> (8 * b)) & 255u) {             // element byte j = byte b of field f
-              const bool varies = ((c[f] ^ c[3 + f]) >> (8 * b)) & 255u, sorted_on = !(f == 2 && c[6] == 0);
-              if (varies && sorted_on) ebytes[ne++] = j;
-              ++j;
-            }
-        }
-        // prefix + finish: the prefix the estimate was made for must be the top hybP SORTED bytes of the elements
-        if (ne && hybP && hybP < ne && ebytes[ne - hybP] == pl.k - hybP) {
-          if (trace_sort())
-            fprintf(stderr, "ibu sort: n=%zu path=compact-prefix+finish element_bytes=%d prefix_passes=%u of %u estimated_run=%.2f\n", n,
-                    pl.k <= 12 ? 12 : 16, hybP, ne, hyb_seg);
-          return pl.k <= 12 ? launch_compact_passes<3>(cfg, *cv, recs, tmp, n, sc, pl, ebytes, ne, st, true, gfirst, hybP)
-                            : launch_compact_passes<4>(cfg, pick_compact16(cfg), recs, tmp, n, sc, pl, ebytes, ne, st, true, gfirst, hybP);
-        }
-        if (ne) {
-          if (trace_sort())
-            fprintf(stderr, "ibu sort: n=%zu path=compact-speculated element_bytes=%d passes=%u first_digit_guess=%s\n", n, pl.k <= 12 ? 12 : 16, ne,
-                    gfirst == ebytes[0] ? "hit" : "miss");
-          return pl.k <= 12 ? launch_compact_passes<3>(cfg, *cv, recs, tmp, n, sc, pl, ebytes, ne, st, true, gfirst)
-                            : launch_compact_passes<4>(cfg, pick_compact16(cfg), recs, tmp, n, sc, pl, ebytes, ne, st, true, gfirst);
-        }
+  return npass;
+}
+// Did the guess cover the truth (the exact words c)?  Then the elements in tmp hold every byte that varies: *pl = their plan with
+// the exact base, ebytes[0 .. *ne) = the element bytes that vary and are sorted on.
+static bool covered_plan(const Speculation& sp, const u64 c[8], CompactPlan* pl, u32 ebytes[16], u32* ne) {
+  for (int f = 0; f < 3; ++f)
+    if ((c[f] ^ c[3 + f]) & ~sp.gmask[f]) return false;
+  *pl = sp.gpl;
+  u32 j = 0;
+  for (int fo = 0; fo < 3; ++fo) {
+    const int f = kFieldOrder[fo];
+    pl->base[f] = c[3 + f] & ~sp.gmask[f];
+    for (u32 b = 0; b < 8; ++b)
+      if ((sp.gmask[f] >> (8 * b)) & 255u) {                  // element byte j = byte b of field f
+        const bool varies = ((c[f] ^ c[3 + f]) >> (8 * b)) & 255u, sorted_on = !(f == 2 && c[6] == 0);
+        if (varies && sorted_on) ebytes[(*ne)++] = j;
+        ++j;
       }
-      if (trace_sort()) fprintf(stderr, "ibu sort: n=%zu guess did not cover the varying bytes\n", n);
-    }
-    CompactPlan pl;
-    compact_plan_init(reinterpret_cast<const uint64_t*>(c), reinterpret_cast<const uint64_t*>(c + 3), &pl);
-    if (pl.k <= 16) {
-      for (u32 j = c[6] == 0 ? pl.index_bytes : 0; j < pl.k; ++j) ebytes[ne++] = j;   // input in index order: the index bytes ride along unsorted
-      // prefix + finish on the exact plan (inputs below the speculation threshold, or whose guess was not taken): the same estimate
-      if (ne && n >= 8192 && !speculated) {
-        u32 P = 0;
-        double seg = 0;
-        e = estimate_compact_prefix(cfg, recs, n, tmp, pl, ne, st, &P, &seg);
-        if (e != hipSuccess) return e;
-        if (P && P < ne) {
-          if (trace_sort())
-            fprintf(stderr, "ibu sort: n=%zu path=compact-prefix+finish element_bytes=%d prefix_passes=%u of %u estimated_run=%.2f (exact plan)\n", n,
-                    pl.k <= 12 ? 12 : 16, P, ne, seg);
-          return pl.k <= 12 ? launch_compact_passes<3>(cfg, *cv, recs, tmp, n, sc, pl, ebytes, ne, st, false, 0, P)
-                            : launch_compact_passes<4>(cfg, pick_compact16(cfg), recs, tmp, n, sc, pl, ebytes, ne, st, false, 0, P);
-        }
-      }
-      if (ne) {
-        if (trace_sort()) fprintf(stderr, "ibu sort: n=%zu path=compact element_bytes=%d passes=%u\n", n, pl.k <= 12 ? 12 : 16, ne);
-        return pl.k <= 12 ? launch_compact_passes<3>(cfg, *cv, recs, tmp, n, sc, pl, ebytes, ne, st)
-                          : launch_compact_passes<4>(cfg, pick_compact16(cfg), recs, tmp, n, sc, pl, ebytes, ne, st);
-      }
-    }
   }
-  const void* scatter = L.idx64 ? sv.scatter64 : sv.scatter32;
-  if (sv.lds > 48 * 1024) {   // per call: the attribute is per device (see launch_compact_passes)
-    e = hipFuncSetAttribute(scatter, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sv.lds);
-    if (e != hipSuccess) return e;
+  return true;
+}
+// The compact path: from the covered guess where there is one, from the exact plan otherwise.  *sorted = false: not taken (more
+// than 16 bytes vary).
+static hipError_t sort_compact_path(const LaunchCfg& cfg, const CompactVariant& cv12, void* recs, void* tmp, size_t n, void* scratch, const Speculation& sp,
+                                    const u64 c[8], hipStream_t st, bool* sorted) {
+  *sorted = true;
+  CompactPlan pl;
+  u32 ebytes[16], ne = 0;
+  if (sp.done) {
+    if (covered_plan(sp, c, &pl, ebytes, &ne) && ne) {
+      // prefix + finish: the prefix the estimate was made for must be the top hybP SORTED bytes of the elements
+      const u32 P = (sp.hybP && sp.hybP < ne && ebytes[ne - sp.hybP] == pl.k - sp.hybP) ? sp.hybP : 0;
+      if (trace_sort() && P)
+        fprintf(stderr, "ibu sort: n=%zu path=compact-prefix+finish element_bytes=%d prefix_passes=%u of %u estimated_run=%.2f\n", n, pl.k <= 12 ? 12 : 16, P, ne, sp.hyb_seg);
+      else if (trace_sort())
+        fprintf(stderr, "ibu sort: n=%zu path=compact-speculated element_bytes=%d passes=%u first_digit_guess=%s\n", n, pl.k <= 12 ? 12 : 16, ne,
+                sp.gfirst == ebytes[0] ? "hit" : "miss");
+      return sort_compact(cfg, cv12, recs, tmp, n, scratch, pl, ebytes, ne, st, ElemsGiven{true, true, sp.gfirst}, P);
+    }
+    if (trace_sort()) fprintf(stderr, "ibu sort: n=%zu guess did not cover the varying bytes\n", n);
+    ne = 0;
   }
+  compact_plan_init(reinterpret_cast<const uint64_t*>(c), reinterpret_cast<const uint64_t*>(c + 3), &pl);
+  if (pl.k <= 16)
+    for (u32 j = c[6] == 0 ? pl.index_bytes : 0; j < pl.k; ++j) ebytes[ne++] = j;   // input in index order: the index bytes ride along unsorted
+  if (!ne) { *sorted = false; return hipSuccess; }
+  // prefix + finish on the exact plan (inputs below the speculation threshold, or whose samples were in order): the same estimate.
+  // NOT after a guess that did not cover: that sort has had its estimate.
+  u32 P = 0;
+  double seg = 0;
+  if (n >= 8192 && !sp.done) {
+    IBU_TRY(estimate_compact_prefix(cfg, recs, n, tmp, pl, ne, st, &P, &seg));
+    if (P >= ne) P = 0;
+  }
+  if (trace_sort() && P)
+    fprintf(stderr, "ibu sort: n=%zu path=compact-prefix+finish element_bytes=%d prefix_passes=%u of %u estimated_run=%.2f (exact plan)\n", n,
+            pl.k <= 12 ? 12 : 16, P, ne, seg);
+  else if (trace_sort())
+    fprintf(stderr, "ibu sort: n=%zu path=compact element_bytes=%d passes=%u\n", n, pl.k <= 12 ? 12 : 16, ne);
+  return sort_compact(cfg, cv12, recs, tmp, n, scratch, pl, ebytes, ne, st, ElemsGiven(), P);
+}
 
+// LSD passes on 24-byte records over ps[0 .. np) (least significant first), ping-pong between recs and tmp.  want_in_tmp: where the
+// result is wanted.  The first pass's counting kernel reads every record anyway: when the parity of np would leave the result in
+// the other array, it also copies the records across (24 B/record) and the passes start from there.
+static hipError_t launch_record_passes(const LaunchCfg& cfg, const SweepVariant& sv, const SortScratch& S, const RecScatter& scatter, void* recs, void* tmp,
+                                       size_t n, const Pass* ps, int np, bool want_in_tmp, hipStream_t st) {
+  const SortLayout& L = S.L;
   const u32 nfull = (u32)(n / sv.tile);          // tiles with all T records
-  const u32 wave_grid = (L.ntiles + kSortWaves - 1) / kSortWaves;
   const u32 cap = (u32)cfg.cus * 8;
-  // LSD passes over ps[0 .. np) (least significant first), ping-pong between recs and tmp.  want_in_tmp: where the result is
-  // wanted.  The first pass's counting kernel reads every record anyway: when the parity of np would leave the result in
-  // the other array, it also copies the records across (24 B/record) and the passes start from there.
-  auto lsd = [&](const Pass* ps, int np, bool want_in_tmp) -> hipError_t {
-    u64* src = static_cast<u64*>(recs);
-    u64* dst = static_cast<u64*>(tmp);
-    const bool stage = ((np & 1) != 0) != want_in_tmp;
-    for (int p = 0; p < np; ++p) {
-      // counts of every tile: from the records for the first pass, from the digit side stream afterwards
-      if (p == 0) {
-        const bool aligned = ((reinterpret_cast<uintptr_t>(src) | (stage ? reinterpret_cast<uintptr_t>(dst) : 0)) & 15u) == 0;
-        const u32 fast = aligned ? nfull : 0;
-        if (fast)
-          hipLaunchKernelGGL(sv.counts_recs, dim3(fast < cap ? fast : cap), dim3(kSortThreads), 0, st, (const uint8_t*)src, fast,
-                             ps[p].field, ps[p].shift, counts, stage ? reinterpret_cast<uint8_t*>(dst) : (uint8_t*)nullptr);
-        if (fast < L.ntiles)
-          hipLaunchKernelGGL(sv.counts_tail, dim3(L.ntiles - fast), dim3(kSortThreads), 0, st, (const u64*)src, (u64)n, fast,
-                             ps[p].field, ps[p].shift, counts, stage ? dst : (u64*)nullptr);
-        if (stage) { u64* t = src; src = dst; dst = t; }   // the records now sit in the other array
-      } else {
-        hipLaunchKernelGGL(sv.counts_bytes, dim3(wave_grid < cap ? wave_grid : cap), dim3(kSortThreads), 0, st, (const uint8_t*)digits,
-                           (u64)n, L.ntiles, counts);
-      }
-      hipLaunchKernelGGL(ibu_k_sort_blocksums, dim3(L.nblocks), dim3(kSortThreads), 0, st, (const uint16_t*)counts, L.ntiles, L.tpb, blocksum);
-      hipLaunchKernelGGL(ibu_k_sort_blockscan, dim3(1), dim3(kSortThreads), 0, st, (const u32*)blocksum, L.nblocks, blockoff, binbase);
-      if (L.idx64)
-        hipLaunchKernelGGL(ibu_k_sort_tilepos<u64>, dim3(L.nblocks), dim3(kSortThreads), 0, st, (const uint16_t*)counts, L.ntiles, L.tpb,
-                           (const u64*)blockoff, (const u64*)binbase, static_cast<u64*>(pos));
-      else
-        hipLaunchKernelGGL(ibu_k_sort_tilepos<u32>, dim3(L.nblocks), dim3(kSortThreads), 0, st, (const uint16_t*)counts, L.ntiles, L.tpb,
-                           (const u64*)blockoff, (const u64*)binbase, static_cast<u32*>(pos));
-      const bool last = p + 1 == np;
-      const u32 nf = last ? 3u : ps[p + 1].field, ns = last ? 0u : ps[p + 1].shift;
-      u64 n_arg = n;
-      u32 f_arg = ps[p].field, s_arg = ps[p].shift, nf_arg = nf, ns_arg = ns;
-      const u64* src_arg = src;
-      void* args[] = {&src_arg, &dst, &n_arg, &f_arg, &s_arg, &nf_arg, &ns_arg, &pos, &digits};
-      hipError_t le = hipLaunchKernel(scatter, dim3((L.ntiles + 7u) & ~7u), dim3(sv.threads), args, sv.lds, st);   // multiple of 8: XCD-aware tile order
-      if (le != hipSuccess) return le;
-      u64* t = src; src = dst; dst = t;
+  u64* src = static_cast<u64*>(recs);
+  u64* dst = static_cast<u64*>(tmp);
+  const bool stage = ((np & 1) != 0) != want_in_tmp;
+  for (int p = 0; p < np; ++p) {
+    // counts of every tile: from the records for the first pass, from the digit side stream afterwards
+    if (p == 0) {
+      const bool aligned = ((reinterpret_cast<uintptr_t>(src) | (stage ? reinterpret_cast<uintptr_t>(dst) : 0)) & 15u) == 0;
+      const u32 fast = aligned ? nfull : 0;
+      if (fast)
+        hipLaunchKernelGGL(sv.counts_recs, dim3(fast < cap ? fast : cap), dim3(kSortThreads), 0, st, (const uint8_t*)src, fast,
+                           ps[p].field, ps[p].shift, S.counts, stage ? reinterpret_cast<uint8_t*>(dst) : (uint8_t*)nullptr);
+      if (fast < L.ntiles)
+        hipLaunchKernelGGL(sv.counts_tail, dim3(L.ntiles - fast), dim3(kSortThreads), 0, st, (const u64*)src, (u64)n, fast,
+                           ps[p].field, ps[p].shift, S.counts, stage ? dst : (u64*)nullptr);
+      if (stage) { u64* t = src; src = dst; dst = t; }   // the records now sit in the other array
+    } else {
+      launch_counts_bytes(cfg, sv.counts_bytes, S, n, st);
     }
-    return hipGetLastError();
-  };
-
-  // PREFIX + FINISH (see ibu_k_sort_finish): P = the fewest prefix bytes that leave about 64 records per segment of well-spread
-  // keys; worth it when at least three passes are saved.  cfg.sort_hybrid: 0 = never, 1 = auto, 2 = whenever a pass is saved
-  // (tests).  The result of the P passes is wanted in tmp: the finishing kernel writes the records back into `recs`.
-  {
-    // P: ranking inside a segment is quadratic in its length (measured at 1e9 records: 1.5 ms per record of average segment
-    // length, against 10.3 ms for one more prefix pass), so the prefix is chosen to leave at most ~8 records per segment
-    const size_t n_est = n_scale ? n_scale : n;               // the size the runs are estimated for
-    int P = 1;
-    for (u64 segs = 256; n_est / segs > 8 && P < 8; segs <<= 8) ++P;
-    // ... of WELL-SPREAD keys.  From 2^17 records on the sample ranges say whether they are (ibu_k_sort_sample_pairs_recs: pairs of
-    // equal prefix and the most frequent prefix among 3 x 32 Ki sample records, tables in tmp): the shortest prefix with at most
-    // ~8 records per run and no heavy prefix is taken, which may be longer than the one n suggests — or none (P = 0: all passes).
-    static constexpr size_t kSampleW = 32768;
-    if (known_prefix >= 0) {
-      P = known_prefix ? (known_prefix < npass ? known_prefix : npass) : npass;
-    } else if (cfg.sort_hybrid && n >= 4 * kSampleW && (reinterpret_cast<uintptr_t>(tmp) & 7u) == 0) {
-      PrefixBytes pb;
-      pb = PrefixBytes();
-      for (int k = 0; k < npass && k < 24; ++k) { pb.field[k] = (uint8_t)passes[npass - 1 - k].field; pb.shift[k] = (uint8_t)passes[npass - 1 - k].shift; }
-      const u32 slots = kPairSlotsMax;                       // 25 MB of tables in tmp: from 1.05 M records on (below: P from n alone)
-      const size_t table_bytes = 128 + (size_t)slots * 12 * kMaxPrefix;
-      if (table_bytes <= n * 24) {
-        uint8_t* tb = static_cast<uint8_t*>(tmp);
-        const u32 per_range = 2048, nranges = 48;             // 48 evenly spaced ranges of 2048 records
-        const size_t m = (size_t)nranges * per_range;
-        const u64 range_stride = (n - per_range) / (nranges - 1);
-        const int est_margin = cfg.sort_hybrid == 2 ? 1 : 3;
-        int Pest = 0;
-        // prefixes of 1 .. 8 bytes, then (wide barcodes from a whitelist: all their bytes and some of the UMI's) 9 .. 16 and 17 .. 24,
-        // as long as such a prefix would still save passes
-        for (int first = 0; !Pest && first + 1 + est_margin <= npass; first += kMaxPrefix) {
-          pb.first = (u32)first;
-          pb.count = (u32)(npass < first + kMaxPrefix ? npass : first + kMaxPrefix);
-          e = hipMemsetAsync(tb, 0, table_bytes, st);
-          if (e != hipSuccess) return e;
-          hipLaunchKernelGGL(ibu_k_sort_sample_pairs_recs, dim3((u32)((m + 255) / 256)), dim3(256), 0, st, (const u64*)recs, range_stride, nranges,
-                             per_range, pb, slots, reinterpret_cast<u64*>(tb + 128),
-                             reinterpret_cast<u32*>(tb + 128 + (size_t)slots * 8 * kMaxPrefix), reinterpret_cast<u64*>(tb));
-          u64 pairs[2 * kMaxPrefix];
-          e = hipMemcpyAsync(pairs, tb, sizeof pairs, hipMemcpyDeviceToHost, st);
-          if (e != hipSuccess) return e;
-          e = hipStreamSynchronize(st);
-          if (e != hipSuccess) return e;
-          for (u32 q = 0; q < (u32)kMaxPrefix && pb.first + q + 1 <= pb.count; ++q) {
-            const double seg = 1.0 + ((double)n_est / (double)m) * (2.0 * (double)pairs[q] / (double)m);
-            const double heaviest = (double)pairs[kMaxPrefix + q] * ((double)n_est / (double)m);
-            if (seg <= 8.0 && heaviest <= 128.0) { Pest = (int)(pb.first + q + 1); break; }
-          }
-        }
-        if (trace_sort() && Pest != P) fprintf(stderr, "ibu sort: n=%zu sample estimate: prefix_passes=%d (well-spread keys would take %d)\n", n, Pest, P);
-        P = Pest ? Pest : npass;                              // npass: never worth it below
-      }
+    IBU_TRY(launch_offsets(S, st));
+    const bool last = p + 1 == np;
+    IBU_TRY(scatter(src, dst, n, ps[p].field, ps[p].shift, last ? 3u : ps[p + 1].field, last ? 0u : ps[p + 1].shift));
+    u64* t = src; src = dst; dst = t;
+  }
+  return hipGetLastError();
+}
+// What estimate_records_prefix keeps at `tables` for n records (0: it would not sample) — for a caller that has to provide them
+// (launch_estimate_prefix_records).
+size_t sort_prefix_estimate_tables(const LaunchCfg& cfg, size_t n) {
+  const size_t table_bytes = prefix_table_bytes(kPairSlotsMax);   // 25 MB of tables: from 1.05 M records on (below: P from n alone)
+  return (cfg.sort_hybrid && n >= 4 * kSampleRecs && table_bytes <= n * 24) ? table_bytes : 0;
+}
+// PREFIX + FINISH on 24-byte records (see ibu_k_sort_finish): *P_out = the fewest prefix bytes — of the npass varying ones — that
+// leave short runs in a sort of n_est records like these n (npass: none; never worth it below).
+static hipError_t estimate_records_prefix(const LaunchCfg& cfg, const void* recs, size_t n, size_t n_est, void* tables, const Pass* passes, int npass, hipStream_t st, int* P_out) {
+  // P: ranking inside a segment is quadratic in its length (measured at 1e9 records: 1.5 ms per record of average segment
+  // length, against 10.3 ms for one more prefix pass), so the prefix is chosen to leave at most ~8 records per segment
+  int P = 1;
+  for (u64 segs = 256; n_est / segs > 8 && P < 8; segs <<= 8) ++P;
+  // ... of WELL-SPREAD keys.  From 2^17 records on the sample ranges say whether they are (ibu_k_sort_sample_pairs_recs: pairs of
+  // equal prefix and the most frequent prefix among 48 evenly spaced ranges of 2048 records, tables at `tables`): the shortest
+  // prefix with at most ~8 records per run and no heavy prefix is taken, which may be longer than the one n suggests — or none.
+  if (sort_prefix_estimate_tables(cfg, n) && (reinterpret_cast<uintptr_t>(tables) & 7u) == 0) {
+    PrefixBytes pb;
+    pb = PrefixBytes();
+    for (int k = 0; k < npass && k < 24; ++k) { pb.field[k] = (uint8_t)passes[npass - 1 - k].field; pb.shift[k] = (uint8_t)passes[npass - 1 - k].shift; }
+    const PrefixSample sample{kPairSlotsMax, 48, 2048};
+    u32 Pest = 0;
+    double seg = 0;
+    const hipError_t e = estimate_prefix(
+        cfg, n, n_est, tables, sample, (u32)npass, (u32)npass, st,
+        [&](u32 first, dim3 grid, u64 range_stride, u64* d_keys, u32* d_cnts, u64* d_pairs) {
+          pb.first = first;
+          pb.count = (u32)npass < first + kMaxPrefix ? (u32)npass : first + kMaxPrefix;
+          hipLaunchKernelGGL(ibu_k_sort_sample_pairs_recs, grid, dim3(256), 0, st, (const u64*)recs, range_stride, sample.nranges, sample.per_range, pb,
+                             sample.slots, d_keys, d_cnts, d_pairs);
+        },
+        &Pest, &seg);
+    if (e != hipSuccess) return e;
+    if (trace_sort() && (int)Pest != P) fprintf(stderr, "ibu sort: n=%zu sample estimate: prefix_passes=%d (well-spread keys would take %d)\n", n, (int)Pest, P);
+    P = Pest ? (int)Pest : npass;                             // npass: never worth it below
+  }
+  *P_out = P;
+  return hipSuccess;
+}
+hipError_t launch_estimate_prefix_records(const LaunchCfg& cfg, const void* recs, size_t n, size_t n_scale, const uint64_t words[6], void* tables, int* prefix_passes, hipStream_t st) {
+  (void)hipGetLastError();
+  if (n < 2) return hipSuccess;
+  u64 c[8];
+  Pass passes[kDigits];
+  IBU_TRY(census_words(cfg, recs, n, nullptr, words, false, st, c));
+  const int npass = passes_from_census(c, passes);
+  int P = 0;
+  IBU_TRY(estimate_records_prefix(cfg, recs, n, n_scale ? n_scale : n, tables, passes, npass, st, &P));
+  *prefix_passes = P >= npass ? 0 : P;
+  return hipGetLastError();
+}
+// The 24-byte path: P passes over the most significant varying bytes (the result wanted in tmp) and the finishing kernel, which
+// writes the records back into `recs`, where that saves passes (prefix_worth_it); all passes otherwise — and after an overflow.
+static hipError_t sort_records_path(const LaunchCfg& cfg, const SweepVariant& sv, const SortScratch& S, void* recs, void* tmp, size_t n, const Pass* passes,
+                                    int npass, int known_prefix, hipStream_t st) {
+  const RecScatter scatter{sv, S, st, false};
+  IBU_TRY(scatter.prepare());
+  int P = 0;
+  if (known_prefix >= 0) P = known_prefix ? (known_prefix < npass ? known_prefix : npass) : npass;
+  else IBU_TRY(estimate_records_prefix(cfg, recs, n, n, tmp, passes, npass, st, &P));
+  if (cfg.sort_hybrid && prefix_worth_it(cfg, (u32)P, (u32)npass) && n < (1ull << 40)) {
+    IBU_TRY(hipMemsetAsync(S.overflow, 0, 4, st));
+    const Pass* ps = passes + (npass - P);       // the P most significant varying bytes
+    u64 pm[3] = {0, 0, 0};
+    for (int p = 0; p < P; ++p) pm[ps[p].field] |= 255ull << ps[p].shift;
+    IBU_TRY(launch_record_passes(cfg, sv, S, scatter, recs, tmp, n, ps, P, true, st));
+    bool overflowed = false;
+    IBU_TRY(launch_finish_records(cfg, S, tmp, recs, n, pm, st, &overflowed));
+    if (!overflowed) {
+      if (trace_sort()) fprintf(stderr, "ibu sort: n=%zu path=prefix+finish prefix_passes=%d of %d varying bytes\n", n, P, npass);
+      return hipSuccess;
     }
-    if (only_estimate) { *only_estimate = P >= npass ? 0 : P; return hipGetLastError(); }
-    const int margin = cfg.sort_hybrid == 2 ? 1 : 3;
-    if (cfg.sort_hybrid && npass >= P + margin && n < (1ull << 40)) {
-      u32* d_overflow = reinterpret_cast<u32*>(sc + L.misc);
-      e = hipMemsetAsync(d_overflow, 0, 4, st);
-      if (e != hipSuccess) return e;
-      const Pass* ps = passes + (npass - P);     // the P most significant varying bytes
-      u64 pm[3] = {0, 0, 0};
-      for (int p = 0; p < P; ++p) pm[ps[p].field] |= 255ull << ps[p].shift;
-      e = lsd(ps, P, true);
-      if (e != hipSuccess) return e;
-      typedef FinishShape<kFinishT, kFinishM> FS;
-      const u64 nblk = (n + kFinishT - 1) / kFinishT;
-      if ((reinterpret_cast<uintptr_t>(tmp) & 15u) == 0) {    // persistent, prefetching form
-        e = hipFuncSetAttribute(reinterpret_cast<const void*>(ibu_k_sort_finish<kFinishT, kFinishM, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)FS::lds);
-        if (e != hipSuccess) return e;
-        static std::atomic<int> focc;
-        int fper = focc.load(std::memory_order_relaxed);
-        if (fper <= 0) {
-          if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&fper, ibu_k_sort_finish<kFinishT, kFinishM, true>, kSortThreads, FS::lds) != hipSuccess || fper <= 0) fper = 1;
-          focc.store(fper, std::memory_order_relaxed);
-        }
-        const u64 fgrid = (u64)fper * (u64)cfg.cus;
-        hipLaunchKernelGGL((ibu_k_sort_finish<kFinishT, kFinishM, true>), dim3((u32)(nblk < fgrid ? nblk : fgrid)), dim3(kSortThreads), FS::lds, st, (const u64*)tmp,
-                           static_cast<u64*>(recs), (u64)n, pm[0], pm[1], pm[2], d_overflow);
-      } else {
-        e = hipFuncSetAttribute(reinterpret_cast<const void*>(ibu_k_sort_finish<kFinishT, kFinishM, false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)FS::lds);
-        if (e != hipSuccess) return e;
-        hipLaunchKernelGGL((ibu_k_sort_finish<kFinishT, kFinishM, false>), dim3((u32)nblk), dim3(kSortThreads), FS::lds, st, (const u64*)tmp,
-                           static_cast<u64*>(recs), (u64)n, pm[0], pm[1], pm[2], d_overflow);
-      }
-      u32 overflow = 0;
-      e = hipMemcpyAsync(&overflow, d_overflow, 4, hipMemcpyDeviceToHost, st);
-      if (e != hipSuccess) return e;
-      e = hipStreamSynchronize(st);
-      if (e != hipSuccess) return e;
-      if (!overflow) {
-        if (trace_sort()) fprintf(stderr, "ibu sort: n=%zu path=prefix+finish prefix_passes=%d of %d varying bytes\n", n, P, npass);
-        return hipSuccess;
-      }
-      // segments too long for the finishing kernel (heavy prefixes): the prefix-sorted records in tmp are a permutation of the
-      // input — copy them back and run every pass
-      if (trace_sort()) fprintf(stderr, "ibu sort: n=%zu prefix+finish overflowed (long runs of equal prefix): all %d passes\n", n, npass);
-      e = launch_copy(cfg, tmp, recs, n * 24, st);
-      if (e != hipSuccess) return e;
-    }
+    // segments too long for the finishing kernel (heavy prefixes): the prefix-sorted records in tmp are a permutation of the
+    // input — copy them back and run every pass
+    if (trace_sort()) fprintf(stderr, "ibu sort: n=%zu prefix+finish overflowed (long runs of equal prefix): all %d passes\n", n, npass);
+    IBU_TRY(launch_copy(cfg, tmp, recs, n * 24, st));
   }
   if (trace_sort()) fprintf(stderr, "ibu sort: n=%zu path=24-byte passes=%d\n", n, npass);
-  return lsd(passes, npass, false);
+  return launch_record_passes(cfg, sv, S, scatter, recs, tmp, n, passes, npass, false, st);
+}
+// Compact-key path (see "COMPACT-KEY passes"): records 16-byte aligned (the tiled compress kernel), tmp at least 4-byte
+// aligned; from 2^32 records on (64-bit element indices) the shapes that carry those kernels (the defaults).  Whether at most
+// 12 / 16 key bytes vary is the census' to say.  The shape of the 12-byte passes, or null: the compact path cannot be taken.
+static const CompactVariant* compact_path_variant(const LaunchCfg& cfg, const void* recs, const void* tmp, size_t n, size_t scratch_bytes) {
+  const CompactVariant* cv = pick_compact_for(cfg, n);
+  const bool wide_idx = n >= (1ull << 32) || cfg.sort_idx64;
+  const bool compact_ok = cv && n < (1ull << 38) && (!wide_idx || (cv->scatter64 && pick_compact16(cfg).scatter64)) && (reinterpret_cast<uintptr_t>(recs) & 15u) == 0 &&
+                          (reinterpret_cast<uintptr_t>(tmp) & 3u) == 0 && scratch_bytes >= sort_layout(cfg, n, cv->tile).total &&
+                          scratch_bytes >= sort_layout(cfg, n, pick_compact16(cfg).tile).total;
+  return compact_ok ? cv : nullptr;
+}
+// Not purely asynchronous: the census result comes back to the host (one 64-byte read) to pick the passes; everything
+// after that is queued on `st`.
+// known_words (nullable): census words the caller already has for a SUPERSET of these records (the multi-GPU sort: the partition pass
+// took them over all shards) — OR x 3, AND x 3; no census pass runs, no record is assumed in index order or sorted, and the bytes
+// that vary in the superset get their passes (a byte that happens to be constant here costs one identity pass).
+// known_prefix (with known_words; the multi-GPU sort): >= 0 = the prefix length of the 24-byte prefix + finish path as somebody already
+// estimated it for the WHOLE these records are a key range of (launch_estimate_prefix_records; 0: all passes); -1: estimate here.
+hipError_t launch_sort_records(const LaunchCfg& cfg, void* recs, void* tmp, size_t n, void* scratch,
+                               size_t scratch_bytes, hipStream_t st, const uint64_t* known_words, int known_prefix) {
+  (void)hipGetLastError();
+  if (n < 2) return hipSuccess;
+  const SweepVariant& sv = pick_variant(cfg);
+  if ((n + sv.tile - 1) / sv.tile >= (1ull << 31)) return hipErrorInvalidValue;
+  const SortLayout L = sort_layout(cfg, n, sv.tile);
+  if (scratch_bytes < L.total) return hipErrorInvalidValue;
+  const SortScratch S(scratch, L);
+  const CompactVariant* cv12 = compact_path_variant(cfg, recs, tmp, n, scratch_bytes);
+  Speculation sp;
+  if (!known_words && cv12 && speculation_wanted(cfg, n)) {
+    IBU_TRY(speculate(cfg, *cv12, recs, tmp, n, scratch, S.census, st, &sp));
+  }
+  u64 c[8];
+  IBU_TRY(census_words(cfg, recs, n, S.census, known_words, sp.done, st, c));
+  if (c[7] == 0) {                   // no record is smaller than its predecessor: already sorted
+    if (trace_sort()) fprintf(stderr, "ibu sort: n=%zu already sorted%s\n", n, sp.done ? " (a speculative compress pass was spent)" : "");   // spent only when the samples saw a drop and the whole did not: impossible, the samples are rows of the whole
+    return hipSuccess;
+  }
+  Pass passes[kDigits];
+  const int npass = passes_from_census(c, passes);
+  if (cv12 && npass > 0) {
+    bool sorted = false;
+    const hipError_t e = sort_compact_path(cfg, *cv12, recs, tmp, n, scratch, sp, c, st, &sorted);
+    if (e != hipSuccess || sorted) return e;
+  }
+  return sort_records_path(cfg, sv, S, recs, tmp, n, passes, npass, known_prefix, st);
 }
 
 // =====================================================================================================
