@@ -55,6 +55,18 @@ pub struct ibu_molecule_counts_t {
     pub reserved: u64,
 }
 #[repr(C)]
+#[derive(Default, Debug, Clone, Copy, PartialEq, Eq)]
+pub struct ibu_cell_counts_t {
+    pub barcodes: u64,
+    pub cells: u64,
+    pub threshold: u64,
+    pub baseline: u64,
+    pub reads_cells: u64,
+    pub reads_background: u64,
+    pub umis_cells: u64,
+    pub umis_background: u64,
+}
+#[repr(C)]
 #[derive(Default, Clone, Copy)]
 pub struct ibu_ring_config_t {
     pub slots: u32,
@@ -232,6 +244,8 @@ extern "C" {
                                 d_class: *mut u8, counts: *mut ibu_correct_counts_t, stream: *mut c_void) -> i32;
     pub fn ibu_classify_molecules(ctx: *mut ibu_ctx_t, d_sorted_records: *const c_void, n: usize, flags: u32, d_class: *mut u8,
                                   counts: *mut ibu_molecule_counts_t, stream: *mut c_void) -> i32;
+    pub fn ibu_call_cells(ctx: *mut ibu_ctx_t, d_sorted_records: *const c_void, n: usize, mode: u32, param: u64, flags: u32, d_class: *mut u8,
+                          counts: *mut ibu_cell_counts_t, stream: *mut c_void) -> i32;
     pub fn ibu_select_records(ctx: *mut ibu_ctx_t, d_records: *const c_void, d_class: *const u8, n: usize, keep_mask: u32,
                               d_out: *mut c_void, cap: usize, n_out: *mut usize, stream: *mut c_void) -> i32;
     pub fn ibu_bgzf_scan(buf: *const u8, len: usize, is_final: i32, blocks: *mut ibu_inflate_block_t, cap: usize, n_blocks: *mut usize,

@@ -681,6 +681,16 @@ pub mod device {
             check(unsafe { ffi::ibu_classify_molecules(self.raw, sorted.ptr, n, if tie_first { 1 } else { 0 }, cls, &mut c, std::ptr::null_mut()) })?;
             Ok(c)
         }
+        /// `ibu_call_cells` over sorted records: one class byte per record into `class` (n bytes; `None`: totals only) — 0 where
+        /// the record's barcode has at least the threshold of UMIs (`by_reads`: of reads), 1 otherwise.  `mode` / `param`: 0 = the
+        /// threshold itself, 1 = the top `param` barcodes and those tied with the last, 2 = a tenth of the 99th percentile of the
+        /// top `param` (expected cells).  `select_records(.., 1 << 0, ..)` then keeps the records of the cells.
+        pub fn call_cells(&self, sorted: &DeviceBuf, n: usize, mode: u32, param: u64, by_reads: bool, class: Option<&DeviceBuf>) -> Result<ffi::ibu_cell_counts_t> {
+            let mut c = ffi::ibu_cell_counts_t::default();
+            let cls = class.map_or(std::ptr::null_mut(), |b| b.ptr as *mut u8);
+            check(unsafe { ffi::ibu_call_cells(self.raw, sorted.ptr, n, mode, param, if by_reads { 1 } else { 0 }, cls, &mut c, std::ptr::null_mut()) })?;
+            Ok(c)
+        }
         /// Stable compaction by class (`ibu_select_records`): the records whose class has its bit set in `keep_mask`, in input
         /// order, into `out` (which must hold them: ask with `out = None` first).  Returns how many.
         pub fn select_records(&self, recs: &DeviceBuf, class: &DeviceBuf, n: usize, keep_mask: u32, out: Option<&DeviceBuf>) -> Result<usize> {

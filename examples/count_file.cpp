@@ -7,12 +7,16 @@
 // new: ibu_barcode_counts on the records as ibu_count_matrix leaves them with IBU_COUNT_LEAVE_SWAPPED ({barcode, index, umi})
 // returns each barcode and, as its "unique UMIs", its number of distinct indices; they are printed behind the matrix as
 //   #row<TAB>barcode<TAB>entries<TAB>reads
-//   count_file [--resolve | --resolve=first] IN [WHITELIST.txt]
+//   count_file [--resolve | --resolve=first] [--cells=min:T|top:K|expected:E] IN [WHITELIST.txt]
 // WHITELIST.txt: one barcode per line, as many bases as the file's header says.
 // --resolve: a (barcode, UMI) molecule seen with several index values counts once, under the index with strictly the most reads, and
 // not at all when the top is shared (--resolve=first: under the smallest index at the top) — sort, ibu_classify_molecules,
 // ibu_select_records in front of the matrix; the seven totals go to stderr.
+// --cells: the matrix of the cells only — sort (unless --resolve already did), ibu_call_cells on the per-barcode UMI counts (min:T a
+// fixed minimum, top:K the K largest barcodes and those tied with the last, expected:E a tenth of the 99th percentile of the top
+// E), ibu_select_records of the class IBU_CELL; the eight totals go to stderr.
 #include <cstdio>
+#include <cstdlib>
 #include <cstring>
 #include <fstream>
 #include <string>
@@ -27,12 +31,36 @@ static std::string decode(uint64_t code, uint32_t len) {        // base i at bit
   return s;
 }
 
+// "min:T" / "top:K" / "expected:E" -> the mode and parameter of ibu_call_cells; false when it is none of them
+static bool parse_cells(const char* s, uint32_t* mode, uint64_t* param) {
+  static const struct { const char* name; uint32_t mode; } kinds[] = {{"min:", IBU_CELLS_MIN}, {"top:", IBU_CELLS_TOP}, {"expected:", IBU_CELLS_ORDMAG}};
+  for (const auto& k : kinds) {
+    const size_t len = std::strlen(k.name);
+    if (std::strncmp(s, k.name, len)) continue;
+    char* end = nullptr;
+    if (s[len] < '0' || s[len] > '9') return false;
+    *param = std::strtoull(s + len, &end, 10);
+    *mode = k.mode;
+    return *end == 0 && (k.mode == IBU_CELLS_MIN || *param > 0);
+  }
+  return false;
+}
+
 int main(int argc, char** argv) {
   int resolve = 0;                                              // 1: --resolve, 2: --resolve=first
-  if (argc > 1 && !std::strcmp(argv[1], "--resolve")) resolve = 1;
-  if (argc > 1 && !std::strcmp(argv[1], "--resolve=first")) resolve = 2;
-  if (resolve) { --argc; ++argv; }
-  if (argc < 2) { std::fprintf(stderr, "usage: count_file [--resolve | --resolve=first] IN [WHITELIST.txt]\n"); return 2; }
+  bool cells = false, bad = false;
+  uint32_t cells_mode = 0;
+  uint64_t cells_param = 0;
+  for (; argc > 1 && !std::strncmp(argv[1], "--", 2); --argc, ++argv) {
+    if (!std::strcmp(argv[1], "--resolve")) resolve = 1;
+    else if (!std::strcmp(argv[1], "--resolve=first")) resolve = 2;
+    else if (!std::strncmp(argv[1], "--cells=", 8) && parse_cells(argv[1] + 8, &cells_mode, &cells_param)) cells = true;
+    else bad = true;
+  }
+  if (argc < 2 || bad) {
+    std::fprintf(stderr, "usage: count_file [--resolve | --resolve=first] [--cells=min:T|top:K|expected:E] IN [WHITELIST.txt]\n");
+    return 2;
+  }
   try {
     using namespace ibu;
     device::Context ctx(0);
@@ -78,6 +106,19 @@ int main(int argc, char** argv) {
       std::fprintf(stderr, "%zu records: molecules %llu, candidates %llu, resolved %llu, tied %llu; reads kept %llu, minor %llu, tied %llu\n", before,
                    (unsigned long long)m.molecules, (unsigned long long)m.candidates, (unsigned long long)m.resolved, (unsigned long long)m.tied,
                    (unsigned long long)m.reads_kept, (unsigned long long)m.reads_minor, (unsigned long long)m.reads_tied);
+      std::swap(recs, scratch);
+    }
+    if (cells && kept) {                                        // sorted records -> the class of every barcode -> the records of the cells
+      if (!resolve) ctx.sort_records(recs, scratch, kept);
+      device::DeviceBuffer d_class(ctx, kept);
+      const device::CellCounts c = ctx.call_cells(recs, kept, cells_mode, cells_param, d_class.as<uint8_t>());
+      const size_t before = kept;
+      kept = ctx.select_records(recs, d_class.as<uint8_t>(), before, 1u << IBU_CELL, scratch, before);
+      ctx.synchronize();
+      std::fprintf(stderr, "%zu records: barcodes %llu, cells %llu, threshold %llu, baseline %llu; reads of cells %llu, of background %llu; "
+                   "umis of cells %llu, of background %llu\n", before, (unsigned long long)c.barcodes, (unsigned long long)c.cells,
+                   (unsigned long long)c.threshold, (unsigned long long)c.baseline, (unsigned long long)c.reads_cells,
+                   (unsigned long long)c.reads_background, (unsigned long long)c.umis_cells, (unsigned long long)c.umis_background);
       std::swap(recs, scratch);
     }
     // the matrix; the records stay {barcode, index, umi} so that the row lengths can be read off them

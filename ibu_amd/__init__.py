@@ -14,7 +14,7 @@ from collections import namedtuple
 import numpy as np
 
 from . import _lib
-from ._lib import CAllocProbe, CCorrectCounts, CDecodeSink, CMoleculeCounts, CErrorDetail, CKeyPlan, CHeader, CNumaInfo, CProcessorVTable, CRecord, CReduceResult, CRingConfig, CStreamStats
+from ._lib import CAllocProbe, CCellCounts, CCorrectCounts, CDecodeSink, CMoleculeCounts, CErrorDetail, CKeyPlan, CHeader, CNumaInfo, CProcessorVTable, CRecord, CReduceResult, CRingConfig, CStreamStats
 
 lib = _lib.load()
 
@@ -30,6 +30,11 @@ COUNT_LEAVE_SWAPPED = 1  # ibu_count_matrix flags (IBU_COUNT_LEAVE_SWAPPED)
 MOLECULE_KEPT, MOLECULE_MINOR, MOLECULE_TIED = 0, 1, 2  # the classes of ibu_classify_molecules (IBU_MOLECULE_*)
 MOLECULES_TIE_FIRST = 1  # ibu_classify_molecules flags (IBU_MOLECULES_TIE_FIRST)
 
+CELL, CELL_BACKGROUND = 0, 1  # the classes of ibu_call_cells (IBU_CELL, IBU_CELL_BACKGROUND)
+CELLS_MIN, CELLS_TOP, CELLS_ORDMAG = 0, 1, 2  # its modes (IBU_CELLS_*)
+CELLS_BY_READS = 1  # its flag (IBU_CELLS_BY_READS)
+#: the totals of one ibu_call_cells call (ibu_cell_counts_t)
+CellCounts = namedtuple("CellCounts", "barcodes cells threshold baseline reads_cells reads_background umis_cells umis_background")
 #: the totals of one ibu_classify_molecules call (ibu_molecule_counts_t without its reserved word)
 MoleculeCounts = namedtuple("MoleculeCounts", "molecules candidates resolved tied reads_kept reads_minor reads_tied")
 
@@ -966,6 +971,30 @@ class Context:
         _check(lib.ibu_classify_molecules(self._c, _dptr(d_sorted_records), n, MOLECULES_TIE_FIRST if tie_first else 0,
                                           _dptr(d_class), C.byref(c) if counts else None, stream))
         return d_class, (MoleculeCounts(*[int(getattr(c, f)) for f in MoleculeCounts._fields]) if counts else None)
+
+    def call_cells(self, d_sorted_records, n, *, min_umis=None, top=None, expected_cells=None, by_reads=False, d_class=None, counts=True,
+                   stream=None):
+        """ibu_call_cells over n sorted device records: one class byte per record — CELL where its barcode's UMI count (by_reads:
+        its read count) reaches the threshold, CELL_BACKGROUND otherwise.  Exactly one of min_umis (the threshold itself), top (the
+        K barcodes with the largest counts, and those tied with the K-th) and expected_cells (a tenth of the count at the 99th
+        percentile of the top expected_cells barcodes) must be given.  -> (d_class, CellCounts).  d_class: n bytes of device
+        memory; None allocates them, False asks for the totals only (and returns None in its place).  counts=False returns None
+        for the totals and does not wait for them.  select_records(d_records, d_class, n, keep_mask=1 << CELL) then keeps the
+        records of the cells."""
+        given = [(m, p) for m, p in ((CELLS_MIN, min_umis), (CELLS_TOP, top), (CELLS_ORDMAG, expected_cells)) if p is not None]
+        if len(given) != 1:
+            raise ValueError("exactly one of min_umis, top and expected_cells must be given")
+        mode, param = given[0]
+        if param < 0 or param >= 1 << 64:
+            raise ValueError("the parameter must fit an unsigned 64-bit integer")
+        if d_class is None:
+            d_class = self.alloc(max(n, 16))
+        elif d_class is False:
+            d_class = None
+        c = CCellCounts() if counts else None
+        _check(lib.ibu_call_cells(self._c, _dptr(d_sorted_records), n, mode, param, CELLS_BY_READS if by_reads else 0, _dptr(d_class),
+                                  C.byref(c) if counts else None, stream))
+        return d_class, (CellCounts(*[int(getattr(c, f)) for f in CellCounts._fields]) if counts else None)
 
     # barcode correction against a whitelist
     def correct_barcodes(self, wl, d_records, n, max_mismatches=1, d_class=None, counts=True, stream=None):

@@ -39,6 +39,11 @@ class CMoleculeCounts(C.Structure):  # ibu_molecule_counts_t
                 ("reads_tied", u64), ("reserved", u64)]
 
 
+class CCellCounts(C.Structure):  # ibu_cell_counts_t
+    _fields_ = [("barcodes", u64), ("cells", u64), ("threshold", u64), ("baseline", u64), ("reads_cells", u64), ("reads_background", u64),
+                ("umis_cells", u64), ("umis_background", u64)]
+
+
 class CRingConfig(C.Structure):  # ibu_ring_config_t
     _fields_ = [("slots", u32), ("slot_records", u32), ("feeder_threads", u32), ("reserved", u32)]
 
@@ -158,6 +163,7 @@ SIGNATURES = {
     "ibu_whitelist_info": (i32, [vp, P(u32), P(sz), P(sz)]),
     "ibu_whitelist_destroy": (None, [vp]),
     "ibu_classify_molecules": (i32, [vp, vp, sz, u32, vp, P(CMoleculeCounts), vp]),
+    "ibu_call_cells": (i32, [vp, vp, sz, u32, u64, u32, vp, P(CCellCounts), vp]),
     "ibu_correct_barcodes": (i32, [vp, vp, vp, sz, u32, vp, P(CCorrectCounts), vp]),
     "ibu_select_records": (i32, [vp, vp, vp, sz, u32, vp, sz, P(sz), vp]),
     "ibu_bgzf_scan": (i32, [vp, sz, i32, P(CInflateBlock), sz, P(sz), P(sz), P(C.c_uint64)]),

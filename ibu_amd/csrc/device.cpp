@@ -950,6 +950,61 @@ extern "C" int32_t ibu_classify_molecules(ibu_ctx_t* ctx, const void* d_sorted_r
   counts->reads_tied = ctx->h_pinned[4];
   return IBU_OK;
 }
+// Which barcodes are cells: one threshold on the per-barcode UMI (or read) count (k_cells.hip; the rule: include/ibu_hip.h).
+extern "C" int32_t ibu_call_cells(ibu_ctx_t* ctx, const void* d_sorted_records, size_t n, uint32_t mode, uint64_t param, uint32_t flags,
+                                  uint8_t* d_class, ibu_cell_counts_t* counts, void* stream) {
+  int32_t rc = check_ctx(ctx);
+  if (rc) return rc;
+  if (mode > IBU_CELLS_ORDMAG) return err_arg("unknown mode");
+  if (flags & ~(uint32_t)IBU_CELLS_BY_READS) return err_arg("unknown bit in flags");
+  if (mode != IBU_CELLS_MIN && param == 0) return err_arg("param must be at least 1 in the TOP and ORDMAG modes");
+  if (n && (!d_sorted_records || !aligned8(d_sorted_records))) return err_arg("d_sorted_records must be non-NULL and 8-byte aligned");
+  if (n >= (1ull << 40)) return err_arg("call_cells handles fewer than 2^40 records per call");
+  if (counts) {   // (behind the last argument check: a refused call leaves the totals alone)
+    *counts = ibu_cell_counts_t{0, 0, 0, 0, 0, 0, 0, 0};
+    if (mode == IBU_CELLS_MIN) counts->threshold = param;
+  }
+  if (n == 0) return IBU_OK;
+  hipStream_t st = pick_stream(ctx, stream);
+  rc = runs_count_totals(ctx, d_sorted_records, n, cells_scratch_bytes(n), RunsCount::Barcode, st);
+  if (rc) return rc;
+  const uint64_t barcodes = ctx->h_pinned[0], pairs = ctx->h_pinned[1];
+  rc = ensure_runs_scratch(ctx, cells_run_scratch_bytes(barcodes));
+  if (rc) return rc;
+  IBU_HIP(launch_cells_call(ctx->cfg, d_sorted_records, n, ctx->d_sort_scratch, ctx->d_runs_scratch, barcodes, pairs, mode, param,
+                            (flags & IBU_CELLS_BY_READS) != 0, d_class, st));
+  if (!counts) return IBU_OK;
+  IBU_HIP(hipMemcpyAsync(ctx->h_pinned, ctx->d_runs_scratch, 7 * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
+  IBU_HIP(hipStreamSynchronize(st));
+  counts->barcodes = barcodes;
+  counts->cells = ctx->h_pinned[0];
+  counts->reads_cells = ctx->h_pinned[1];
+  counts->reads_background = ctx->h_pinned[2];
+  counts->umis_cells = ctx->h_pinned[3];
+  counts->umis_background = ctx->h_pinned[4];
+  counts->threshold = ctx->h_pinned[5];
+  counts->baseline = ctx->h_pinned[6];
+  return IBU_OK;
+}
+// TEST HOOK, not part of the ABI (not declared in include/ibu_hip.h, no binding): the selection ibu_call_cells runs, on a caller's
+// array — *value = the rank-th largest (1 <= rank <= n) of n device values below 2^40.  Records cannot reach the digit passes above
+// bit 31 at any size a test can afford; tests/test_gpu_cells.py reaches them through this.  Synchronises.
+extern "C" int32_t ibu_test_rank_select(ibu_ctx_t* ctx, const uint64_t* d_values, size_t n, uint64_t rank, uint64_t* value, void* stream) {
+  int32_t rc = check_ctx(ctx);
+  if (rc) return rc;
+  if (!value) return err_arg("value is NULL");
+  if (n == 0 || rank == 0 || rank > n) return err_arg("rank must be in 1..n");
+  if (!d_values || !aligned8(d_values)) return err_arg("d_values must be non-NULL and 8-byte aligned");
+  if (n >= (1ull << 40)) return err_arg("rank_select handles fewer than 2^40 values per call");
+  hipStream_t st = pick_stream(ctx, stream);
+  rc = ensure_runs_scratch(ctx, rank_select_work_bytes());
+  if (rc) return rc;
+  IBU_HIP(launch_rank_select(ctx->cfg, d_values, n, rank, ctx->d_runs_scratch, st));
+  IBU_HIP(hipMemcpyAsync(ctx->h_pinned, ctx->d_runs_scratch, sizeof(uint64_t), hipMemcpyDeviceToHost, st));
+  IBU_HIP(hipStreamSynchronize(st));
+  *value = ctx->h_pinned[0];
+  return IBU_OK;
+}
 extern "C" int32_t ibu_count_matrix(ibu_ctx_t* ctx, void* d_records, void* d_tmp, size_t n, uint32_t flags, uint64_t* d_barcodes,
                                     uint64_t* d_indices, uint64_t* d_reads, uint64_t* d_umis, size_t cap, size_t* n_entries,
                                     size_t* n_molecules, void* stream) {

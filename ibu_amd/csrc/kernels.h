@@ -140,6 +140,18 @@ size_t molecules_scratch_bytes(size_t n);
 size_t molecules_run_scratch_bytes(uint64_t candidates);
 hipError_t launch_molecules_classify(const LaunchCfg&, const void* recs, size_t n, void* scratch, void* run_scratch, uint64_t candidates,
                                      bool tie_first, uint8_t* d_class, hipStream_t st);
+// cell calling (ibu_call_cells, k_cells.hip).  launch_runs_count(RunsCount::Barcode) on a scratch of cells_scratch_bytes(n) comes
+// first; with its two totals (barcodes, pairs) the caller sizes the run scratch.  mode / param: IBU_CELLS_MIN / _TOP / _ORDMAG and
+// their parameter (ibu_hip.h).  Leaves one class byte per record in d_class (nullable) and u64[7] at the front of run_scratch: cells,
+// reads of cells / of background, umis of cells / of background, threshold, baseline.
+size_t cells_scratch_bytes(size_t n);
+size_t cells_run_scratch_bytes(uint64_t barcodes);
+hipError_t launch_cells_call(const LaunchCfg&, const void* recs, size_t n, void* scratch, void* run_scratch, uint64_t barcodes, uint64_t pairs,
+                             uint32_t mode, uint64_t param, bool by_reads, uint8_t* d_class, hipStream_t st);
+// The rank-th largest (1 <= rank <= count) of `count` device values below 2^40, by radix selection on the device: leaves it in the
+// first u64 of `work` (rank_select_work_bytes() bytes, 8-byte aligned).
+size_t rank_select_work_bytes();
+hipError_t launch_rank_select(const LaunchCfg&, const uint64_t* values, uint64_t count, uint64_t rank, void* work, hipStream_t st);
 // record i of dst = {w0, w2, w1} of record i of src; dst == src (in place) or disjoint (k_records.hip)
 hipError_t launch_swap_fields(const LaunchCfg&, const void* src, void* dst, size_t n, hipStream_t st);
 // barcode correction against a whitelist (k_whitelist.hip).  The table: `slots` 64-bit keys (a power of two, at least 2 w), all ones =

@@ -34,7 +34,8 @@ __device__ __forceinline__ u32 wave_segment() { return blockIdx.x * kSortWaves +
 static inline dim3 seg_grid(const SegPlan& sp) { return dim3((sp.nseg + kSortWaves - 1) / kSortWaves); }
 
 // The count scratch (byte offsets): totals u64[2] | seg_heads u32[2][cap] | seg_base u64[2][cap], scanned | stash [cap][kStashHeads]
-// | the molecule walk's ballots u64[2 (n / 128) + 4].  It is a function of n alone, so that a scratch sized before the records' base is
+// | the ballots a fill pass turns into class bytes, u64[2 (n / 128) + 4] (ranked heads: ibu_classify_molecules; run heads:
+// ibu_call_cells; one region, one call at a time).  It is a function of n alone, so that a scratch sized before the records' base is
 // known fits them at any alignment: cap = runs_nseg(n) segments, while a plan has sp.nseg = runs_nseg(sp.main) <= cap of them (one
 // fewer where peeling a record moves the last tile into the rest).  The tables are PLACED by cap and INDEXED with sp.nseg as their row
 // length, [row * sp.nseg + seg], which stays inside them.
@@ -49,7 +50,7 @@ static inline RunsLayout runs_layout(size_t n) {
   L.stash = up(L.seg_base + 2 * sizeof(u64) * cap, 16);
   L.runs_bytes = L.stash + sizeof(RunStash) * kStashHeads * cap;    // ibu_barcode_counts, ibu_pair_counts
   L.mol_masks = up(L.runs_bytes, 16);
-  L.mol_bytes = L.mol_masks + sizeof(u64) * (2 * (n / kTileRecs) + 4);   // ibu_classify_molecules
+  L.mol_bytes = L.mol_masks + sizeof(u64) * (2 * (n / kTileRecs) + 4);   // ibu_classify_molecules, ibu_call_cells
   return L;
 }
 template <class T> static inline T* scratch_at(const void* scratch, size_t off) {
@@ -80,16 +81,21 @@ struct NoSink {
   // records 64 step .. 64 step + 63.
   __device__ __forceinline__ void tile_ballots(u64 tile, u64 even, u64 odd) const {}
   __device__ __forceinline__ void end_ballots(u32 which, u32 step, u64 m) const {}
+  // The same steps, the ballots of RUN heads (a subset of the ranked heads), laid out alike.
+  __device__ __forceinline__ void tile_run_ballots(u64 tile, u64 even, u64 odd) const {}
+  __device__ __forceinline__ void end_run_ballots(u32 which, u32 step, u64 m) const {}
 };
 
 // One step of a walk: every lane brings record `row` (a) and, in a tiled step, `row + 1` (b) with their head flags.  Ranks them in
-// the wave, hands the ranked heads to the sink and adds the step to the counts; leaves the two ballots of ranked heads.
+// the wave, hands the ranked heads to the sink and adds the step to the counts; leaves the two ballots of ranked heads (even, odd)
+// and the two of run heads (run_even, run_odd).
 template <class S>
 struct RunRanks {
   const S& sink;
-  u64 p1, p2, lt_mask, c1, c2, even, odd;
+  u64 p1, p2, lt_mask, c1, c2, even, odd, run_even, run_odd;
   __device__ __forceinline__ void step(u64 row, const Rec& a, bool a1, bool a2, const Rec& b, bool b1, bool b2) {
     const u64 ma1 = __ballot(a1), mb1 = __ballot(b1);
+    run_even = ma1; run_odd = mb1;
     even = __ballot(a2); odd = __ballot(b2);
     const u64 k = p1 + c1 + (u64)(__popcll(ma1 & lt_mask) + __popcll(mb1 & lt_mask));
     const u64 q = p2 + c2 + (u64)(__popcll(even & lt_mask) + __popcll(odd & lt_mask));
@@ -108,7 +114,7 @@ struct RunRanks {
 template <int D, class S>
 __device__ __forceinline__ void runs_segment(const u64* __restrict__ recs, const SegPlan& sp, u32 seg, uint8_t* tile, u32 lane, u64 p1,
                                              u64 p2, u64& c1, u64& c2, const S& sink) {
-  RunRanks<S> ranks{sink, p1, p2, (1ull << lane) - 1, 0, 0, 0, 0};
+  RunRanks<S> ranks{sink, p1, p2, (1ull << lane) - 1, 0, 0, 0, 0, 0, 0};
   const Rec none{0, 0, 0};
   if (seg == 0 || seg == sp.nseg - 1) {                     // wave-uniform: the untiled ends (< 128 rows each)
     const u64 base = seg == 0 ? 0 : sp.head + sp.main;
@@ -122,7 +128,10 @@ __device__ __forceinline__ void runs_segment(const u64* __restrict__ recs, const
       bool h1, h2;
       run_head<D>(prev, cur, i > 0, h1, h2);
       ranks.step(i, cur, valid && h1, valid && h2, none, false, false);
-      if (lane == 0) sink.end_ballots(seg == 0 ? 0u : 1u, (u32)((i0 - base) / kWave), ranks.even);
+      if (lane == 0) {
+        sink.end_ballots(seg == 0 ? 0u : 1u, (u32)((i0 - base) / kWave), ranks.even);
+        sink.end_run_ballots(seg == 0 ? 0u : 1u, (u32)((i0 - base) / kWave), ranks.run_even);
+      }
     }
     c1 = ranks.c1; c2 = ranks.c2;
     return;
@@ -151,7 +160,10 @@ __device__ __forceinline__ void runs_segment(const u64* __restrict__ recs, const
     run_head<D>(prev, x, lane > 0 || have_prev, xa, xb);
     run_head<D>(x, y, true, ya, yb);
     ranks.step(begin + (u64)t * kTileRecs + 2 * lane, x, xa, xb, y, ya, yb);
-    if (lane == 0) sink.tile_ballots((begin - sp.head) / kTileRecs + t, ranks.even, ranks.odd);
+    if (lane == 0) {
+      sink.tile_ballots((begin - sp.head) / kTileRecs + t, ranks.even, ranks.odd);
+      sink.tile_run_ballots((begin - sp.head) / kTileRecs + t, ranks.run_even, ranks.run_odd);
+    }
     carry = load_rec<D>(reinterpret_cast<const u64*>(tile + (kTileRecs - 1) * 24));   // same address in every lane: one broadcast read
     have_prev = true;
     if (!more) break;

@@ -363,6 +363,7 @@ namespace device {
 class Whitelist;
 using CorrectCounts = ibu_correct_counts_t;
 using MoleculeCounts = ibu_molecule_counts_t;
+using CellCounts = ibu_cell_counts_t;
 // one entry of ibu_pair_counts / ibu_count_matrix: (barcode, index, reads, distinct UMIs) on the count-matrix path
 struct MatrixEntry { uint64_t first, second, records, distinct; };
 inline int device_count() { int32_t n = 0; return ibu_device_count(&n) == IBU_OK ? n : 0; }
@@ -448,6 +449,14 @@ class Context {
   MoleculeCounts classify_molecules(const void* d_sorted, size_t n, uint8_t* d_class, bool tie_first = false, void* st = nullptr) {
     MoleculeCounts c{};
     check(ibu_classify_molecules(c_, d_sorted, n, tie_first ? IBU_MOLECULES_TIE_FIRST : 0u, d_class, &c, st));
+    return c;
+  }
+  // which barcodes of sorted records are cells (ibu_call_cells): mode IBU_CELLS_MIN / _TOP / _ORDMAG with its parameter, flags 0 or
+  // IBU_CELLS_BY_READS; d_class (n bytes, or nullptr for the totals only) gets IBU_CELL / IBU_CELL_BACKGROUND per record;
+  // select_records(.., 1u << IBU_CELL, ..) keeps the records of the cells
+  CellCounts call_cells(const void* d_sorted, size_t n, uint32_t mode, uint64_t param, uint8_t* d_class, uint32_t flags = 0, void* st = nullptr) {
+    CellCounts c{};
+    check(ibu_call_cells(c_, d_sorted, n, mode, param, flags, d_class, &c, st));
     return c;
   }
   // stable compaction by class (ibu_select_records) -> how many records went to d_out (capacity `cap` records); d_out == nullptr

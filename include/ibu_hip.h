@@ -583,6 +583,54 @@ typedef struct ibu_molecule_counts {
 } ibu_molecule_counts_t;
 int32_t ibu_classify_molecules(ibu_ctx_t* ctx, const void* d_sorted_records, size_t n, uint32_t flags, uint8_t* d_class,
                                ibu_molecule_counts_t* counts, void* stream);
+/* Cell calling on the device (k_cells.hip): which barcodes of sorted records are cells — the cut by per-barcode UMI count that every
+ * single-cell pipeline makes before the matrix is used (real input has 10-100 times more barcodes than cells: ambient RNA, empty
+ * droplets).  The reference has no such function; the semantics are this library's and are stated in full here.  Write w0, w1 for
+ * the first two 64-bit words of a record in storage order.
+ *   A BARCODE is a maximal run of consecutive records with equal w0 — the runs of ibu_barcode_counts.
+ *   Its `reads` is the length of the run; its `umis` the number of positions in the run whose w1 differs from the record before it
+ *   (the first position counts) — what ibu_barcode_counts returns as unique_umis.
+ *   The METRIC of a barcode is its umis, or its reads under the flag IBU_CELLS_BY_READS.
+ * Let B be the number of barcodes and m(1) >= m(2) >= ... >= m(B) their metrics in descending order.  Every mode comes down to one
+ * integer threshold T, and a barcode is a cell iff its metric >= T:
+ *   IBU_CELLS_MIN     T = param (T = 0: every barcode is a cell); baseline = 0.
+ *   IBU_CELLS_TOP     param = K >= 1: T = m(min(K, B)).  The barcodes tied with the K-th are all cells, so cells >= min(K, B);
+ *                     baseline = 0.
+ *   IBU_CELLS_ORDMAG  param = the expected number of cells E >= 1: E' = min(E, B), baseline = m(E' / 100 + 1) with integer division
+ *                     (the 99th percentile of the top E', no interpolation), T = (baseline + 9) / 10 — a tenth of it, rounded up.
+ * Every record gets the class of its barcode: IBU_CELL (0) or IBU_CELL_BACKGROUND (1).  ibu_select_records(..., keep_mask =
+ * 1 << IBU_CELL) then gives the records of the cells in input order, still sorted.
+ * d_class (nullable: totals only): n bytes.  counts (nullable): barcodes = B; cells = the class-0 barcodes; threshold = T; baseline as
+ * above; reads_cells + reads_background = n, the records of each class; umis_cells + umis_background = the (barcode, umi) pair
+ * total of ibu_barcode_counts — UMI totals under IBU_CELLS_BY_READS as well.
+ * On unsorted input the result is the same run-level computation on the runs as they stand (a barcode that is interrupted and
+ * returns is two barcodes), as ibu_barcode_counts documents for itself.  The records are never written.
+ * IBU_ERR_INVALID_ARG: an unknown mode, an unknown bit in flags, param == 0 in the TOP and ORDMAG modes (checked first, whatever n
+ * is), a NULL or misaligned d_sorted_records with n > 0, n >= 2^40 — a refused call touches nothing, `counts` included.  n == 0 is
+ * OK: nothing is touched and all totals are 0, except threshold = param in the MIN mode.  A NULL context is an error.  Records 8-byte aligned: a 16-byte aligned array takes the tiled path, an 8- but not 16-byte aligned one peels
+ * one record, as ibu_pair_counts does.
+ * Synchronises `stream` once (the barcode and pair totals come back to size the scratch); the class writes may still be queued on
+ * return.  With counts != NULL it waits a second time, for the totals.  The threshold of the TOP and ORDMAG modes is found on the
+ * device — a radix selection over the B metrics, five digit passes — with no host round trip in between.
+ * Traffic: the records are read twice (count, emit; two of their three words); 24 B per barcode are written and read (first row, pair
+ * rank, metric), the selection reads the B metrics once per digit, the verdict is 1 B per barcode and the class write 1 B per
+ * record — filled from the verdicts and from 16 B of run-head ballots per 128 records the emit pass keeps, not from the records.
+ * No atomic per record or per barcode.  Scratch: the context's sort scratch for the per-segment tables and the ballots (n / 8
+ * bytes), and 25 B per barcode (+ 10 KiB of histograms) of its run scratch, grown on demand. */
+#define IBU_CELL 0
+#define IBU_CELL_BACKGROUND 1
+#define IBU_CELLS_MIN 0u    /* param = T */
+#define IBU_CELLS_TOP 1u    /* param = K >= 1 */
+#define IBU_CELLS_ORDMAG 2u /* param = expected cells E >= 1 */
+#define IBU_CELLS_BY_READS 1u /* flag: the metric is reads, not umis */
+typedef struct ibu_cell_counts {
+  uint64_t barcodes, cells;                 /* runs of equal w0 / those of class 0 */
+  uint64_t threshold, baseline;             /* T / m(E' / 100 + 1) in the ORDMAG mode, else 0 */
+  uint64_t reads_cells, reads_background;   /* records per class; their sum is n */
+  uint64_t umis_cells, umis_background;     /* (barcode, umi) pairs per class */
+} ibu_cell_counts_t;
+int32_t ibu_call_cells(ibu_ctx_t* ctx, const void* d_sorted_records, size_t n, uint32_t mode, uint64_t param, uint32_t flags,
+                       uint8_t* d_class, ibu_cell_counts_t* counts, void* stream);
 /* Barcode correction against a whitelist, on the device (k_whitelist.hip) — the step between a load and ibu_sort_records /
  * ibu_barcode_counts that makes the latter's "a caller that knows a bound (its whitelist)" true of real input.  The reference has
  * no such function (as it has no sort and no aggregation); the semantics are this library's and are stated in full here.

@@ -5,6 +5,7 @@ into preallocated device arrays, no download.
   python tools/aggbench.py [--records 1e9] [--lens 10,12] [--rounds 5]
   python tools/aggbench.py --matrix 1e5x100,own_pair,one_pair [--records 1e9]     the count-matrix legs (matrix_legs below)
   python tools/aggbench.py --molecules [--records 1e9] [--reads-per-molecule 4] [--second-candidate 0.05]     ibu_classify_molecules (molecule_legs below)
+  python tools/aggbench.py --cells [--records 1e9] [--reads-per-molecule 4]     ibu_call_cells (cell_legs below)
 bc_len 10 gives 2^20 distinct barcodes (a single-cell whitelist's order of magnitude); 16 gives ~n runs of length one."""
 import argparse
 import ctypes as C
@@ -211,8 +212,122 @@ def molecule_legs(a):
     print(json.dumps(res), flush=True)
 
 
+def knee_layout(torch, n, rpm, device, seed=0x1B0000B):
+    """The input of --cells: one cell per 1e4 records of about 2000 molecules (at four reads each), fifty times as many background
+    barcodes of 1-3 molecules, shuffled, rpm records per molecule.  -> (umis, starts, ends, n_cells, n_background) per barcode in
+    row order: its molecules and its rows [starts, ends).  The rows add up to n EXACTLY: what the rounded random sizes leave over is
+    spread over the cells in whole molecules, and the n % rpm records that remain are one more, partial, molecule of the last
+    barcode (counted in its umis)."""
+    n_cells = max(1, n // 10_000)
+    n_bg = 50 * n_cells
+    g = torch.Generator(device=device).manual_seed(seed)
+    mols = n // rpm
+    mean = max(4.0, (mols - 2.0 * n_bg) / n_cells)
+    cell = (mean * (0.75 + 0.5 * torch.rand(n_cells, generator=g, device=device, dtype=torch.float64))).to(torch.int64).clamp_(min=4)
+    bg = torch.randint(1, 4, (n_bg,), generator=g, device=device, dtype=torch.int64)
+    diff = mols - int(cell.sum()) - int(bg.sum())
+    cell += diff // n_cells                                  # (floor division and a non-negative remainder, whatever the sign)
+    cell[:diff % n_cells] += 1
+    if int(cell.min()) < 4:
+        raise SystemExit(f"--cells: {n} records are too few for {n_cells} cells and {n_bg} background barcodes")
+    umis = torch.cat([cell, bg])[torch.randperm(n_cells + n_bg, generator=g, device=device)]
+    reads = umis * rpm
+    if n % rpm:
+        reads[-1] += n % rpm
+        umis[-1] += 1
+    ends = torch.cumsum(reads, 0)
+    assert int(ends[-1]) == n
+    return umis, ends - reads, ends, n_cells, n_bg
+
+
+def knee_fill(torch, i, starts, ends, rpm):
+    """Rows i (a tensor of row numbers) of the layout above -> their (barcode, umi) words."""
+    b = torch.bucketize(i, ends, right=True)
+    return b, (i - starts[b]) // rpm
+
+
+def cell_legs(a):
+    """--cells: ibu_call_cells in its three modes on resident sorted 16/12 records with a knee, timed with events on a side stream
+    (the first round is the warm-up), against ibu_barcode_counts with outputs, ibu_classify_molecules, ibu_reduce (one plain read)
+    and ibu_device_copy on the same arrays.  The records: one cell per 1e4 records (1e5 at 1e9) of about 2000 molecules, fifty
+    times as many background barcodes of 1-3 molecules scattered among them, --reads-per-molecule records per molecule."""
+    import torch                                             # before the library, as bench.py does
+    torch.cuda.init()
+    import ibu_amd as ia
+    from ibu_amd import _dptr, _check, lib, _lib
+
+    ctx = ia.Context(0)
+    side = torch.cuda.Stream()
+    st = side.cuda_stream
+    n = int(float(a.records.split(",")[0]))
+    rpm = a.reads_per_molecule
+    umis, starts, ends, n_cells, n_bg = knee_layout(torch, n, rpm, "cuda")
+    cols = [ctx.alloc(8 * n) for _ in range(3)]
+    bc, um, ix = (torch.as_tensor(c, device="cuda").view(torch.int64) for c in cols)
+    for lo in range(0, n, 1 << 26):
+        hi = min(n, lo + (1 << 26))
+        i = torch.arange(lo, hi, device="cuda", dtype=torch.int64)
+        bc[lo:hi], um[lo:hi] = knee_fill(torch, i, starts, ends, rpm)
+        ix[lo:hi] = 0
+    del i
+    torch.cuda.synchronize()
+    d, t, d_class = ctx.alloc(24 * n), ctx.alloc(24 * n), ctx.alloc(n)
+    ctx.serialize(cols[0], cols[1], cols[2], n, d)
+    ctx.synchronize()
+    for c in cols:
+        c.free()
+    assert ctx.is_sorted(d, n)
+    cap = n_cells + n_bg
+    outs = [ctx.alloc(8 * cap) for _ in range(3)]
+
+    def timed(fn):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record(side)
+        fn()
+        e1.record(side)
+        e1.synchronize()
+        return e0.elapsed_time(e1)
+
+    def rounds(fn):
+        v = [timed(fn) for _ in range(a.rounds + 1)][1:]
+        return {"median_ms": round(statistics.median(v), 3), "min_ms": round(min(v), 3), "max_ms": round(max(v), 3)}
+
+    counts, mcounts = _lib.CCellCounts(), _lib.CMoleculeCounts()
+    nb, npairs = C.c_size_t(), C.c_size_t()
+    cells = lambda mode, param, cls=True, tot=True, flags=0: rounds(lambda: _check(lib.ibu_call_cells(
+        ctx._c, _dptr(d), n, mode, param, flags, _dptr(d_class) if cls else None, C.byref(counts) if tot else None, st)))
+    res = {"leg": "call_cells", "n": n, "reads_per_molecule": rpm, "cells_laid": n_cells, "background_laid": n_bg}
+    res["device_copy"] = rounds(lambda: _check(lib.ibu_device_copy(ctx._c, _dptr(t), _dptr(d), 24 * n, st)))
+    res["reduce"] = rounds(lambda: _check(lib.ibu_reduce(ctx._c, _dptr(d), n, st)))
+    res["barcode_counts"] = rounds(lambda: _check(lib.ibu_barcode_counts(ctx._c, _dptr(d), n, *[_dptr(o) for o in outs], cap, C.byref(nb), C.byref(npairs), st)))
+    res["classify_molecules"] = rounds(lambda: _check(lib.ibu_classify_molecules(ctx._c, _dptr(d), n, 0, _dptr(d_class), C.byref(mcounts), st)))
+    res["cells_min"] = cells(ia.CELLS_MIN, 200)
+    res["cells_min_classes_only"] = cells(ia.CELLS_MIN, 200, tot=False)
+    res["cells_min_totals_only"] = cells(ia.CELLS_MIN, 200, cls=False)
+    res["cells_top"] = cells(ia.CELLS_TOP, n_cells)
+    res["cells_ordmag"] = cells(ia.CELLS_ORDMAG, n_cells)
+    res["cells_ordmag_by_reads"] = cells(ia.CELLS_ORDMAG, n_cells, flags=ia.CELLS_BY_READS)
+    res["classify_molecules_again"] = rounds(lambda: _check(lib.ibu_classify_molecules(ctx._c, _dptr(d), n, 0, _dptr(d_class), C.byref(mcounts), st)))
+    _check(lib.ibu_call_cells(ctx._c, _dptr(d), n, ia.CELLS_ORDMAG, n_cells, 0, _dptr(d_class), C.byref(counts), st))
+    ctx.synchronize()
+    res.update({k: int(getattr(counts, k)) for k, _ in _lib.CCellCounts._fields_})
+    cm = min(res["classify_molecules"]["median_ms"], res["classify_molecules_again"]["median_ms"])
+    for k in ("cells_min", "cells_top", "cells_ordmag"):
+        res[k + "_vs_classify_molecules"] = round(res[k]["median_ms"] / cm, 3)
+    res["top_minus_min_ms"] = round(res["cells_top"]["median_ms"] - res["cells_min"]["median_ms"], 3)
+    res["ordmag_minus_min_ms"] = round(res["cells_ordmag"]["median_ms"] - res["cells_min"]["median_ms"], 3)
+    print(json.dumps(res), flush=True)                       # (before the checks: a run that fails one still leaves its times)
+    assert counts.barcodes == nb.value and counts.umis_cells + counts.umis_background == npairs.value
+    assert counts.reads_cells + counts.reads_background == n
+    cls = torch.as_tensor(d_class, device="cuda").view(torch.uint8)[:n]
+    assert [int((cls == c).sum()) for c in (0, 1)] == [counts.reads_cells, counts.reads_background]
+    assert counts.barcodes == n_cells + n_bg and npairs.value == int(umis.sum()), "every barcode and molecule that was laid"
+    assert counts.cells == int((umis >= counts.threshold).sum()), "the cells are the barcodes that were laid with that many molecules"
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--cells", action="store_true", help="the ibu_call_cells legs instead of the barcode leg")
     ap.add_argument("--molecules", action="store_true", help="the ibu_classify_molecules legs instead of the barcode leg")
     ap.add_argument("--reads-per-molecule", type=int, default=4)
     ap.add_argument("--second-candidate", type=float, default=0.05, help="--molecules: the share of molecules with a second index")
@@ -224,6 +339,8 @@ def main():
     a = ap.parse_args()
     if a.molecules:
         return molecule_legs(a)
+    if a.cells:
+        return cell_legs(a)
     if a.matrix:
         return matrix_legs(a)
     if a.whitelist:
