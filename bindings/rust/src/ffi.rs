@@ -67,6 +67,14 @@ pub struct ibu_cell_counts_t {
     pub umis_background: u64,
 }
 #[repr(C)]
+#[derive(Default, Debug, Clone, Copy, PartialEq, Eq)]
+pub struct ibu_saturation_point_t {
+    pub threshold: u64,
+    pub reads: u64,
+    pub barcodes: u64,
+    pub molecules: u64,
+}
+#[repr(C)]
 #[derive(Default, Clone, Copy)]
 pub struct ibu_ring_config_t {
     pub slots: u32,
@@ -246,6 +254,10 @@ extern "C" {
                                   counts: *mut ibu_molecule_counts_t, stream: *mut c_void) -> i32;
     pub fn ibu_call_cells(ctx: *mut ibu_ctx_t, d_sorted_records: *const c_void, n: usize, mode: u32, param: u64, flags: u32, d_class: *mut u8,
                           counts: *mut ibu_cell_counts_t, stream: *mut c_void) -> i32;
+    pub fn ibu_subsample_class(ctx: *mut ibu_ctx_t, n: usize, first_row: u64, seed: u64, threshold: u64, d_class: *mut u8, n_kept: *mut usize,
+                               stream: *mut c_void) -> i32;
+    pub fn ibu_saturation_curve(ctx: *mut ibu_ctx_t, d_sorted_records: *const c_void, n: usize, first_row: u64, seed: u64, thresholds: *const u64,
+                                k: u32, points: *mut ibu_saturation_point_t, stream: *mut c_void) -> i32;
     pub fn ibu_select_records(ctx: *mut ibu_ctx_t, d_records: *const c_void, d_class: *const u8, n: usize, keep_mask: u32,
                               d_out: *mut c_void, cap: usize, n_out: *mut usize, stream: *mut c_void) -> i32;
     pub fn ibu_bgzf_scan(buf: *const u8, len: usize, is_final: i32, blocks: *mut ibu_inflate_block_t, cap: usize, n_blocks: *mut usize,

@@ -691,6 +691,26 @@ pub mod device {
             check(unsafe { ffi::ibu_call_cells(self.raw, sorted.ptr, n, mode, param, if by_reads { 1 } else { 0 }, cls, &mut c, std::ptr::null_mut()) })?;
             Ok(c)
         }
+        /// `ibu_subsample_class`: a reproducible random subset of `n` rows — one class byte per row into `class` (n bytes; `None`:
+        /// the count only), 0 where the row's number `splitmix64(splitmix64(seed) + first_row + row)` is below `threshold` (all
+        /// ones keeps every row), 1 elsewhere.  No record is read, so the subset depends on the order of the records it is applied
+        /// to.  Returns the number kept.  `select_records(.., 1 << 0, ..)` then makes the subset.
+        pub fn subsample_class(&self, n: usize, first_row: u64, seed: u64, threshold: u64, class: Option<&DeviceBuf>) -> Result<usize> {
+            let mut k = 0usize;
+            let cls = class.map_or(std::ptr::null_mut(), |b| b.ptr as *mut u8);
+            check(unsafe { ffi::ibu_subsample_class(self.raw, n, first_row, seed, threshold, cls, &mut k, std::ptr::null_mut()) })?;
+            Ok(k)
+        }
+        /// `ibu_saturation_curve` over sorted records: for each of 1 ..= 32 non-decreasing `thresholds` the reads kept at it and
+        /// the barcodes / (barcode, umi) molecules with at least one kept read, from one read of the records.
+        pub fn saturation_curve(&self, sorted: &DeviceBuf, n: usize, first_row: u64, seed: u64, thresholds: &[u64]) -> Result<Vec<ffi::ibu_saturation_point_t>> {
+            let mut points = vec![ffi::ibu_saturation_point_t::default(); thresholds.len()];
+            let k = u32::try_from(thresholds.len()).unwrap_or(u32::MAX);
+            check(unsafe {
+                ffi::ibu_saturation_curve(self.raw, sorted.ptr, n, first_row, seed, thresholds.as_ptr(), k, points.as_mut_ptr(), std::ptr::null_mut())
+            })?;
+            Ok(points)
+        }
         /// Stable compaction by class (`ibu_select_records`): the records whose class has its bit set in `keep_mask`, in input
         /// order, into `out` (which must hold them: ask with `out = None` first).  Returns how many.
         pub fn select_records(&self, recs: &DeviceBuf, class: &DeviceBuf, n: usize, keep_mask: u32, out: Option<&DeviceBuf>) -> Result<usize> {

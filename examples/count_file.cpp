@@ -7,7 +7,7 @@
 // new: ibu_barcode_counts on the records as ibu_count_matrix leaves them with IBU_COUNT_LEAVE_SWAPPED ({barcode, index, umi})
 // returns each barcode and, as its "unique UMIs", its number of distinct indices; they are printed behind the matrix as
 //   #row<TAB>barcode<TAB>entries<TAB>reads
-//   count_file [--resolve | --resolve=first] [--cells=min:T|top:K|expected:E] IN [WHITELIST.txt]
+//   count_file [--resolve | --resolve=first] [--cells=min:T|top:K|expected:E] [--subsample=F[:seed]] [--saturation=K] IN [WHITELIST.txt]
 // WHITELIST.txt: one barcode per line, as many bases as the file's header says.
 // --resolve: a (barcode, UMI) molecule seen with several index values counts once, under the index with strictly the most reads, and
 // not at all when the top is shared (--resolve=first: under the smallest index at the top) — sort, ibu_classify_molecules,
@@ -15,6 +15,13 @@
 // --cells: the matrix of the cells only — sort (unless --resolve already did), ibu_call_cells on the per-barcode UMI counts (min:T a
 // fixed minimum, top:K the K largest barcodes and those tied with the last, expected:E a tenth of the 99th percentile of the top
 // E), ibu_select_records of the class IBU_CELL; the eight totals go to stderr.
+// --subsample=F[:seed]: the matrix of a reproducible random fraction F of the reads (seed: 0 unless given) — behind the last of the
+// steps above, on the sorted records (the subset depends on their order): ibu_subsample_class, ibu_select_records of the class
+// IBU_SAMPLE_KEPT; the count goes to stderr.
+// --saturation=K (1 .. 32): the saturation curve of the records the matrix is counted from, sorted, before their fields are exchanged
+// (ibu_saturation_curve, one read of the records), K evenly spaced depths 1/K .. 1, in front of the matrix as
+//   #saturation<TAB>fraction<TAB>reads<TAB>barcodes<TAB>molecules<TAB>saturation
+// with saturation = 1 - molecules / reads.
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -46,19 +53,45 @@ static bool parse_cells(const char* s, uint32_t* mode, uint64_t* param) {
   return false;
 }
 
+// "K" -> 1 .. 32 points; false otherwise
+static bool parse_saturation(const char* s, uint32_t* k) {
+  char* end = nullptr;
+  if (s[0] < '0' || s[0] > '9') return false;
+  const unsigned long long v = std::strtoull(s, &end, 10);
+  *k = (uint32_t)(v <= IBU_SATURATION_MAX_POINTS ? v : 0);
+  return *end == 0 && *k >= 1;
+}
+// "F" or "F:seed" -> a fraction >= 0 and a seed; false otherwise
+static bool parse_subsample(const char* s, double* fraction, uint64_t* seed) {
+  char* end = nullptr;
+  if (!((s[0] >= '0' && s[0] <= '9') || s[0] == '.')) return false;
+  *fraction = std::strtod(s, &end);
+  *seed = 0;
+  if (end == s || !(*fraction >= 0)) return false;
+  if (*end == 0) return true;
+  if (*end != ':' || end[1] < '0' || end[1] > '9') return false;
+  const char* t = end + 1;
+  *seed = std::strtoull(t, &end, 10);
+  return *end == 0;
+}
+
 int main(int argc, char** argv) {
   int resolve = 0;                                              // 1: --resolve, 2: --resolve=first
-  bool cells = false, bad = false;
-  uint32_t cells_mode = 0;
-  uint64_t cells_param = 0;
+  bool cells = false, bad = false, subsample = false;
+  uint32_t cells_mode = 0, saturation = 0;
+  uint64_t cells_param = 0, sample_seed = 0;
+  double sample_fraction = 1;
   for (; argc > 1 && !std::strncmp(argv[1], "--", 2); --argc, ++argv) {
     if (!std::strcmp(argv[1], "--resolve")) resolve = 1;
     else if (!std::strcmp(argv[1], "--resolve=first")) resolve = 2;
     else if (!std::strncmp(argv[1], "--cells=", 8) && parse_cells(argv[1] + 8, &cells_mode, &cells_param)) cells = true;
+    else if (!std::strncmp(argv[1], "--subsample=", 12) && parse_subsample(argv[1] + 12, &sample_fraction, &sample_seed)) subsample = true;
+    else if (!std::strncmp(argv[1], "--saturation=", 13) && parse_saturation(argv[1] + 13, &saturation)) {}
     else bad = true;
   }
   if (argc < 2 || bad) {
-    std::fprintf(stderr, "usage: count_file [--resolve | --resolve=first] [--cells=min:T|top:K|expected:E] IN [WHITELIST.txt]\n");
+    std::fprintf(stderr, "usage: count_file [--resolve | --resolve=first] [--cells=min:T|top:K|expected:E] [--subsample=F[:seed]] [--saturation=K] "
+                 "IN [WHITELIST.txt]\n");
     return 2;
   }
   try {
@@ -120,6 +153,30 @@ int main(int argc, char** argv) {
                    (unsigned long long)c.threshold, (unsigned long long)c.baseline, (unsigned long long)c.reads_cells,
                    (unsigned long long)c.reads_background, (unsigned long long)c.umis_cells, (unsigned long long)c.umis_background);
       std::swap(recs, scratch);
+    }
+    bool sorted = (resolve || cells) && kept;                   // (ibu_select_records keeps the order)
+    if (subsample && kept) {                                    // sorted records -> a class per row -> the kept reads
+      if (!sorted) ctx.sort_records(recs, scratch, kept);
+      sorted = true;
+      device::DeviceBuffer d_class(ctx, kept);
+      const size_t before = kept;
+      ctx.subsample_class_async(before, device::Context::sample_threshold(sample_fraction), d_class.as<uint8_t>(), sample_seed);
+      kept = ctx.select_records(recs, d_class.as<uint8_t>(), before, 1u << IBU_SAMPLE_KEPT, scratch, before);
+      ctx.synchronize();
+      std::fprintf(stderr, "%zu records: subsample %g seed %llu; kept %zu\n", before, sample_fraction, (unsigned long long)sample_seed, kept);
+      std::swap(recs, scratch);
+    }
+    if (saturation) {                                           // K depths from one read of the sorted records
+      if (!sorted && kept) ctx.sort_records(recs, scratch, kept);
+      std::vector<uint64_t> thresholds(saturation);
+      for (uint32_t j = 1; j <= saturation; ++j)                // the floor of (j / K) 2^64; j == K: everything
+        thresholds[j - 1] = j == saturation ? UINT64_MAX : (uint64_t)((((unsigned __int128)j) << 64) / saturation);
+      const auto curve = ctx.saturation_curve(recs, kept, thresholds);
+      for (uint32_t j = 0; j < saturation; ++j) {
+        const device::SaturationPoint& p = curve[j];
+        std::printf("#saturation\t%.6f\t%llu\t%llu\t%llu\t%.6f\n", (double)(j + 1) / saturation, (unsigned long long)p.reads,
+                    (unsigned long long)p.barcodes, (unsigned long long)p.molecules, p.reads ? 1.0 - (double)p.molecules / (double)p.reads : 0.0);
+      }
     }
     // the matrix; the records stay {barcode, index, umi} so that the row lengths can be read off them
     const auto entries = ctx.count_matrix(recs, scratch, kept, 0, /*leave_swapped=*/true);

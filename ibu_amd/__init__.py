@@ -14,7 +14,7 @@ from collections import namedtuple
 import numpy as np
 
 from . import _lib
-from ._lib import CAllocProbe, CCellCounts, CCorrectCounts, CDecodeSink, CMoleculeCounts, CErrorDetail, CKeyPlan, CHeader, CNumaInfo, CProcessorVTable, CRecord, CReduceResult, CRingConfig, CStreamStats
+from ._lib import CAllocProbe, CCellCounts, CCorrectCounts, CDecodeSink, CMoleculeCounts, CErrorDetail, CKeyPlan, CHeader, CNumaInfo, CProcessorVTable, CRecord, CReduceResult, CRingConfig, CSaturationPoint, CStreamStats
 
 lib = _lib.load()
 
@@ -33,6 +33,10 @@ MOLECULES_TIE_FIRST = 1  # ibu_classify_molecules flags (IBU_MOLECULES_TIE_FIRST
 CELL, CELL_BACKGROUND = 0, 1  # the classes of ibu_call_cells (IBU_CELL, IBU_CELL_BACKGROUND)
 CELLS_MIN, CELLS_TOP, CELLS_ORDMAG = 0, 1, 2  # its modes (IBU_CELLS_*)
 CELLS_BY_READS = 1  # its flag (IBU_CELLS_BY_READS)
+SAMPLE_KEPT, SAMPLE_DROPPED = 0, 1  # the classes of ibu_subsample_class (IBU_SAMPLE_KEPT, IBU_SAMPLE_DROPPED)
+SATURATION_MAX_POINTS = 32
+#: one point of ibu_saturation_curve (ibu_saturation_point_t)
+SaturationPoint = namedtuple("SaturationPoint", "threshold reads barcodes molecules")
 #: the totals of one ibu_call_cells call (ibu_cell_counts_t)
 CellCounts = namedtuple("CellCounts", "barcodes cells threshold baseline reads_cells reads_background umis_cells umis_background")
 #: the totals of one ibu_classify_molecules call (ibu_molecule_counts_t without its reserved word)
@@ -791,6 +795,29 @@ def numa_of_pci(pci_bus_id, sysfs_root=None):
     return node.value, buf.value.decode(), usable.value
 
 
+def sample_threshold(fraction):
+    """The threshold of ibu_subsample_class / ibu_saturation_curve that keeps `fraction` of the reads, exactly: all ones for a
+    fraction of 1 or more, otherwise the floor of fraction * 2^64.  fraction: a float, an int or a fractions.Fraction."""
+    from fractions import Fraction
+    if fraction != fraction or fraction < 0:
+        raise ValueError("the fraction must be a number >= 0")
+    if fraction >= 1:
+        return (1 << 64) - 1
+    return int(Fraction(fraction) * (1 << 64))            # (Fraction of a float is exact, int() of a positive Fraction its floor)
+
+
+def _u64_arg(name, v):
+    if not 0 <= v < 1 << 64:
+        raise ValueError(f"{name} must fit an unsigned 64-bit integer")
+    return int(v)
+
+
+def _one_threshold(fraction, threshold):
+    if (fraction is None) == (threshold is None):
+        raise ValueError("exactly one of fraction and threshold must be given")
+    return sample_threshold(fraction) if threshold is None else _u64_arg("threshold", threshold)
+
+
 class Context:
     """ibu_ctx_t: one per host thread and GPU.  Every method launches asynchronously on
     `stream` (default: the context's own stream) unless it says it synchronises."""
@@ -995,6 +1022,47 @@ class Context:
         _check(lib.ibu_call_cells(self._c, _dptr(d_sorted_records), n, mode, param, CELLS_BY_READS if by_reads else 0, _dptr(d_class),
                                   C.byref(c) if counts else None, stream))
         return d_class, (CellCounts(*[int(getattr(c, f)) for f in CellCounts._fields]) if counts else None)
+
+    # read subsampling and the saturation curve
+    def subsample_class(self, n, d_class=None, *, fraction=None, threshold=None, seed=0, first_row=0, count=True, stream=None):
+        """ibu_subsample_class: one class byte for each of n rows — SAMPLE_KEPT where the row's number u(row) =
+        splitmix64(splitmix64(seed) + first_row + row) is below the threshold, SAMPLE_DROPPED otherwise; no record is read, so the
+        subset depends on the ORDER of the records it is applied to (apply it at one fixed stage, normally the sorted records).
+        Exactly one of fraction (see sample_threshold) and threshold (a u64; all ones keeps everything) must be given.
+        -> (d_class, n_kept).  d_class: n bytes of device memory; None allocates them, False asks for the count only (and returns
+        None in its place).  count=False returns None for the count and leaves the call asynchronous.
+        select_records(d_records, d_class, n, keep_mask=1 << SAMPLE_KEPT) then makes the subset."""
+        t = _one_threshold(fraction, threshold)
+        _u64_arg("seed", seed), _u64_arg("first_row", first_row)
+        if d_class is False and not count:
+            raise ValueError("d_class=False with count=False leaves nothing to do")
+        if d_class is None:
+            d_class = self.alloc(max(n, 16))
+        elif d_class is False:
+            d_class = None
+        k = C.c_size_t() if count else None
+        _check(lib.ibu_subsample_class(self._c, n, first_row, seed, t, _dptr(d_class), C.byref(k) if count else None, stream))
+        return d_class, (k.value if count else None)
+
+    def saturation_curve(self, d_sorted_records, n, *, fractions=None, thresholds=None, seed=0, first_row=0, stream=None):
+        """ibu_saturation_curve over n sorted device records: what would have been seen at each depth, from one read of the
+        records -> a list of SaturationPoint(threshold, reads, barcodes, molecules), one per depth: the reads kept at it, and the
+        runs of equal barcode / of equal (barcode, umi) with at least one kept read.  1 - molecules / reads is the sequencing
+        saturation at that depth.  Exactly one of fractions (each through sample_threshold) and thresholds (u64 values) must be
+        given: 1 .. 32 of them, non-decreasing.  seed / first_row as in subsample_class: the reads kept at a depth are the ones
+        subsample_class keeps at the same threshold."""
+        if (fractions is None) == (thresholds is None):
+            raise ValueError("exactly one of fractions and thresholds must be given")
+        ts = [sample_threshold(f) for f in fractions] if thresholds is None else [_u64_arg("threshold", t) for t in thresholds]
+        if not 1 <= len(ts) <= SATURATION_MAX_POINTS:
+            raise ValueError("between 1 and 32 depths must be given")
+        if any(b < a for a, b in zip(ts, ts[1:])):
+            raise ValueError("the depths must be non-decreasing")
+        _u64_arg("seed", seed), _u64_arg("first_row", first_row)
+        arr = (C.c_uint64 * len(ts))(*ts)
+        pts = (CSaturationPoint * len(ts))()
+        _check(lib.ibu_saturation_curve(self._c, _dptr(d_sorted_records), n, first_row, seed, arr, len(ts), pts, stream))
+        return [SaturationPoint(int(p.threshold), int(p.reads), int(p.barcodes), int(p.molecules)) for p in pts]
 
     # barcode correction against a whitelist
     def correct_barcodes(self, wl, d_records, n, max_mismatches=1, d_class=None, counts=True, stream=None):

@@ -44,6 +44,10 @@ class CCellCounts(C.Structure):  # ibu_cell_counts_t
                 ("umis_cells", u64), ("umis_background", u64)]
 
 
+class CSaturationPoint(C.Structure):  # ibu_saturation_point_t
+    _fields_ = [("threshold", u64), ("reads", u64), ("barcodes", u64), ("molecules", u64)]
+
+
 class CRingConfig(C.Structure):  # ibu_ring_config_t
     _fields_ = [("slots", u32), ("slot_records", u32), ("feeder_threads", u32), ("reserved", u32)]
 
@@ -164,6 +168,8 @@ SIGNATURES = {
     "ibu_whitelist_destroy": (None, [vp]),
     "ibu_classify_molecules": (i32, [vp, vp, sz, u32, vp, P(CMoleculeCounts), vp]),
     "ibu_call_cells": (i32, [vp, vp, sz, u32, u64, u32, vp, P(CCellCounts), vp]),
+    "ibu_subsample_class": (i32, [vp, sz, u64, u64, u64, vp, P(sz), vp]),
+    "ibu_saturation_curve": (i32, [vp, vp, sz, u64, u64, P(u64), u32, P(CSaturationPoint), vp]),
     "ibu_correct_barcodes": (i32, [vp, vp, vp, sz, u32, vp, P(CCorrectCounts), vp]),
     "ibu_select_records": (i32, [vp, vp, vp, sz, u32, vp, sz, P(sz), vp]),
     "ibu_bgzf_scan": (i32, [vp, sz, i32, P(CInflateBlock), sz, P(sz), P(sz), P(C.c_uint64)]),

@@ -75,7 +75,7 @@ extern "C" int32_t ibu_ctx_create(int32_t device, ibu_ctx_t** out) {
   if (rc == hipSuccess) rc = hipMalloc(reinterpret_cast<void**>(&ctx->d_status), 2 * sizeof(uint64_t));
   if (rc == hipSuccess) rc = hipMalloc(reinterpret_cast<void**>(&ctx->d_acc), kReduceAccBytes);
   if (rc == hipSuccess) rc = hipMalloc(reinterpret_cast<void**>(&ctx->d_flag), 16);
-  if (rc == hipSuccess) rc = hipHostMalloc(reinterpret_cast<void**>(&ctx->h_pinned), 16 * sizeof(uint64_t), hipHostMallocDefault);
+  if (rc == hipSuccess) rc = hipHostMalloc(reinterpret_cast<void**>(&ctx->h_pinned), 128 * sizeof(uint64_t), hipHostMallocDefault);
   if (rc == hipSuccess) rc = hipMemsetAsync(ctx->d_acc, 0, kReduceAccBytes, ctx->stream);
   if (rc == hipSuccess) rc = launch_fill2(ctx->d_status, ~0ull, 0, ctx->stream);
   if (rc == hipSuccess) rc = hipStreamSynchronize(ctx->stream);
@@ -984,6 +984,57 @@ extern "C" int32_t ibu_call_cells(ibu_ctx_t* ctx, const void* d_sorted_records, 
   counts->umis_background = ctx->h_pinned[4];
   counts->threshold = ctx->h_pinned[5];
   counts->baseline = ctx->h_pinned[6];
+  return IBU_OK;
+}
+// ---- read subsampling and the saturation curve (k_saturation.hip).  The semantics are this library's: include/ibu_hip.h.
+extern "C" int32_t ibu_subsample_class(ibu_ctx_t* ctx, size_t n, uint64_t first_row, uint64_t seed, uint64_t threshold, uint8_t* d_class,
+                                       size_t* n_kept, void* stream) {
+  int32_t rc = check_ctx(ctx);
+  if (rc) return rc;
+  if (!d_class && !n_kept) return err_arg("d_class and n_kept are both NULL: nothing to do");
+  if (n >= (1ull << 40)) return err_arg("subsample_class handles fewer than 2^40 rows per call");
+  if (n_kept) *n_kept = 0;
+  if (n == 0) return IBU_OK;
+  hipStream_t st = pick_stream(ctx, stream);
+  const uint64_t base = sample_base(seed, first_row);
+  if (!n_kept) {   // nothing to bring back: the launch stays asynchronous and touches no per-call state
+    IBU_HIP(launch_subsample(ctx->cfg, n, base, threshold, d_class, nullptr, st));
+    return IBU_OK;
+  }
+  rc = ensure_sort_scratch(ctx, kSubsampleAccBytes);
+  if (rc) return rc;
+  IBU_HIP(launch_subsample(ctx->cfg, n, base, threshold, d_class, static_cast<uint64_t*>(ctx->d_sort_scratch), st));
+  IBU_HIP(hipMemcpyAsync(ctx->h_pinned, ctx->d_sort_scratch, sizeof(uint64_t), hipMemcpyDeviceToHost, st));
+  IBU_HIP(hipStreamSynchronize(st));
+  *n_kept = ctx->h_pinned[0];
+  return IBU_OK;
+}
+extern "C" int32_t ibu_saturation_curve(ibu_ctx_t* ctx, const void* d_sorted_records, size_t n, uint64_t first_row, uint64_t seed,
+                                        const uint64_t* thresholds, uint32_t k, ibu_saturation_point_t* points, void* stream) {
+  int32_t rc = check_ctx(ctx);
+  if (rc) return rc;
+  if (k == 0 || k > IBU_SATURATION_MAX_POINTS) return err_arg("k must be 1..32");
+  if (!thresholds || !points) return err_arg("thresholds / points are NULL");
+  for (uint32_t j = 1; j < k; ++j)
+    if (thresholds[j] < thresholds[j - 1]) return err_arg("the thresholds must be non-decreasing");
+  if (n && (!d_sorted_records || !aligned8(d_sorted_records))) return err_arg("d_sorted_records must be non-NULL and 8-byte aligned");
+  if (n >= (1ull << 40)) return err_arg("saturation_curve handles fewer than 2^40 records per call");
+  if (n == 0) {
+    for (uint32_t j = 0; j < k; ++j) points[j] = ibu_saturation_point_t{thresholds[j], 0, 0, 0};
+    return IBU_OK;
+  }
+  hipStream_t st = pick_stream(ctx, stream);
+  rc = ensure_sort_scratch(ctx, saturation_scratch_bytes(n));
+  if (rc) return rc;
+  IBU_HIP(launch_saturation(ctx->cfg, d_sorted_records, n, sample_base(seed, first_row), thresholds, k, ctx->d_sort_scratch,
+                            ctx->sort_scratch_bytes, st));
+  static_assert(3 * kSaturationMaxPoints <= 128, "the points come back through h_pinned");
+  IBU_HIP(hipMemcpyAsync(ctx->h_pinned, static_cast<const uint8_t*>(ctx->d_sort_scratch) + saturation_points_offset(),
+                         3 * kSaturationMaxPoints * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
+  IBU_HIP(hipStreamSynchronize(st));
+  for (uint32_t j = 0; j < k; ++j)
+    points[j] = ibu_saturation_point_t{thresholds[j], ctx->h_pinned[j], ctx->h_pinned[kSaturationMaxPoints + j],
+                                       ctx->h_pinned[2 * kSaturationMaxPoints + j]};
   return IBU_OK;
 }
 // TEST HOOK, not part of the ABI (not declared in include/ibu_hip.h, no binding): the selection ibu_call_cells runs, on a caller's

@@ -209,12 +209,7 @@ ibu_k_reduce(const uint8_t* __restrict__ recs, u32 ntiles, u64 n_total, u64* __r
 // Synthetic records: flat u64 element e = 3*i + k of the record stream is splitmix64(seed + e)
 // masked for k = 0,1 and i for k = 2.  One 16-B chunk (two elements) per thread, coalesced.
 // =============================================================================================
-__device__ __forceinline__ u64 splitmix64(u64 z) {
-  z += 0x9E3779B97F4A7C15ull;
-  z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-  z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-  return z ^ (z >> 31);
-}
+// (splitmix64: kcommon.hpp)
 // Record-centric like K1': lane L of a wave builds records 2L and 2L+1 of its 128-record tile (4 splitmix64, no
 // division, no per-element branch), parks the 48 bytes in the wave's LDS slice (3 x ds_write_b128 at stride 48 B,
 // conflict-free) and the wave stores the tile as three coalesced dwordx4.  (The first version derived every u64

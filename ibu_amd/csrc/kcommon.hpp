@@ -279,6 +279,13 @@ __device__ __forceinline__ u32x4 expand_chunk(const uint8_t* tile, u32 rstride, 
   return o;
 }
 
+// Vigna's splitmix64 output function: the synthetic records (k_records.hip) and the number of a read (k_saturation.hip).
+__host__ __device__ __forceinline__ u64 splitmix64(u64 z) {
+  z += 0x9E3779B97F4A7C15ull;
+  z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
+  z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
+  return z ^ (z >> 31);
+}
 __device__ __forceinline__ u64 mask2(u32 len) { return len >= 32 ? ~0ull : ((1ull << (2 * len)) - 1); }
 
 // ---- runtime-length fields: the code stream ----------------------------------------------------------------------------

@@ -152,6 +152,21 @@ hipError_t launch_cells_call(const LaunchCfg&, const void* recs, size_t n, void*
 // first u64 of `work` (rank_select_work_bytes() bytes, 8-byte aligned).
 size_t rank_select_work_bytes();
 hipError_t launch_rank_select(const LaunchCfg&, const uint64_t* values, uint64_t count, uint64_t rank, void* work, hipStream_t st);
+// read subsampling and the saturation curve (ibu_subsample_class, ibu_saturation_curve, k_saturation.hip).  The number of a read is
+// splitmix64(base + row) with base = sample_base(seed, first_row); kept at a threshold: ibu_hip.h.
+uint64_t sample_base(uint64_t seed, uint64_t first_row);
+// One class byte per row into d_class (nullable: the count alone).  acc (nullable): kSubsampleAccBytes, 8-byte aligned; the launcher
+// zeroes it and leaves the number of kept rows in its first word.
+static constexpr size_t kSubsampleAccBytes = (size_t)kReduceSlots * sizeof(uint64_t);
+hipError_t launch_subsample(const LaunchCfg&, size_t n, uint64_t base, uint64_t threshold, uint8_t* d_class, uint64_t* acc, hipStream_t st);
+// The curve at k <= kSaturationMaxPoints non-decreasing thresholds (a host array), one read of the records.  Leaves u64[3][32] —
+// reads, barcodes, molecules of every point — saturation_points_offset() bytes into `scratch` (saturation_scratch_bytes(n) bytes,
+// 16-byte aligned).
+static constexpr uint32_t kSaturationMaxPoints = 32;
+size_t saturation_scratch_bytes(size_t n);
+size_t saturation_points_offset();
+hipError_t launch_saturation(const LaunchCfg&, const void* recs, size_t n, uint64_t base, const uint64_t* thresholds, uint32_t k, void* scratch,
+                             size_t scratch_bytes, hipStream_t st);
 // record i of dst = {w0, w2, w1} of record i of src; dst == src (in place) or disjoint (k_records.hip)
 hipError_t launch_swap_fields(const LaunchCfg&, const void* src, void* dst, size_t n, hipStream_t st);
 // barcode correction against a whitelist (k_whitelist.hip).  The table: `slots` 64-bit keys (a power of two, at least 2 w), all ones =

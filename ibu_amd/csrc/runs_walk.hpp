@@ -1,6 +1,7 @@
 // runs_walk.hpp — the segment walk over SORTED records that k_aggregate.hip (barcode and pair counts) and k_molecules.hip (one index
 // per molecule) share: the cut of the rows into segments (SegPlan), the count scratch both address (RunsLayout), the walk itself
-// (runs_segment) with the sinks' interface (NoSink), and the body of every kernel that runs it (runs_kernel).
+// (runs_segment) with the sinks' interface (NoSink), and the body of every kernel that runs it (runs_kernel).  k_cells.hip (cell
+// calling) and k_saturation.hip (the saturation curve: a per-run minimum carried from tile to tile through NoSink::records) walk it too.
 #pragma once
 #include "kcommon.hpp"
 #include "kernels.h"
@@ -84,6 +85,11 @@ struct NoSink {
   // The same steps, the ballots of RUN heads (a subset of the ranked heads), laid out alike.
   __device__ __forceinline__ void tile_run_ballots(u64 tile, u64 even, u64 odd) const {}
   __device__ __forceinline__ void end_run_ballots(u32 which, u32 step, u64 m) const {}
+  // Every step, in EVERY lane, whether it holds a head or not: the lane's record `row` (a) with its run-head flag a1 and its
+  // ranked-head flag a2, and, in a tiled step (pair), record `row + 1` (b) with b1 / b2.  A lane past the end of an untiled step
+  // comes with a row at or behind the segment's end and both flags false.  What a sink carries from step to step (a per-run
+  // reduction: k_saturation.hip) lives in `mutable` members of the sink.
+  __device__ __forceinline__ void records(u64 row, bool a1, bool a2, bool b1, bool b2, bool pair) const {}
 };
 
 // One step of a walk: every lane brings record `row` (a) and, in a tiled step, `row + 1` (b) with their head flags.  Ranks them in
@@ -93,7 +99,8 @@ template <class S>
 struct RunRanks {
   const S& sink;
   u64 p1, p2, lt_mask, c1, c2, even, odd, run_even, run_odd;
-  __device__ __forceinline__ void step(u64 row, const Rec& a, bool a1, bool a2, const Rec& b, bool b1, bool b2) {
+  __device__ __forceinline__ void step(u64 row, const Rec& a, bool a1, bool a2, const Rec& b, bool b1, bool b2, bool pair) {
+    sink.records(row, a1, a2, b1, b2, pair);
     const u64 ma1 = __ballot(a1), mb1 = __ballot(b1);
     run_even = ma1; run_odd = mb1;
     even = __ballot(a2); odd = __ballot(b2);
@@ -127,7 +134,7 @@ __device__ __forceinline__ void runs_segment(const u64* __restrict__ recs, const
       if (lane == 0 && valid && i > 0) prev = load_rec<D>(recs + 3 * (i - 1));
       bool h1, h2;
       run_head<D>(prev, cur, i > 0, h1, h2);
-      ranks.step(i, cur, valid && h1, valid && h2, none, false, false);
+      ranks.step(i, cur, valid && h1, valid && h2, none, false, false, false);
       if (lane == 0) {
         sink.end_ballots(seg == 0 ? 0u : 1u, (u32)((i0 - base) / kWave), ranks.even);
         sink.end_run_ballots(seg == 0 ? 0u : 1u, (u32)((i0 - base) / kWave), ranks.run_even);
@@ -159,7 +166,7 @@ __device__ __forceinline__ void runs_segment(const u64* __restrict__ recs, const
     bool xa, xb, ya, yb;
     run_head<D>(prev, x, lane > 0 || have_prev, xa, xb);
     run_head<D>(x, y, true, ya, yb);
-    ranks.step(begin + (u64)t * kTileRecs + 2 * lane, x, xa, xb, y, ya, yb);
+    ranks.step(begin + (u64)t * kTileRecs + 2 * lane, x, xa, xb, y, ya, yb, true);
     if (lane == 0) {
       sink.tile_ballots((begin - sp.head) / kTileRecs + t, ranks.even, ranks.odd);
       sink.tile_run_ballots((begin - sp.head) / kTileRecs + t, ranks.run_even, ranks.run_odd);

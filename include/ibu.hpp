@@ -17,6 +17,7 @@
 //   — (new: device path)                   ibu::device::Context, DeviceBuffer; Writer::write_batch_device,
 //                                          MmapReader::process_device_*, Reader::process_device_*
 #pragma once
+#include <cmath>
 #include <cstdint>
 #include <cstdio>
 #include <cstring>
@@ -364,6 +365,7 @@ class Whitelist;
 using CorrectCounts = ibu_correct_counts_t;
 using MoleculeCounts = ibu_molecule_counts_t;
 using CellCounts = ibu_cell_counts_t;
+using SaturationPoint = ibu_saturation_point_t;
 // one entry of ibu_pair_counts / ibu_count_matrix: (barcode, index, reads, distinct UMIs) on the count-matrix path
 struct MatrixEntry { uint64_t first, second, records, distinct; };
 inline int device_count() { int32_t n = 0; return ibu_device_count(&n) == IBU_OK ? n : 0; }
@@ -458,6 +460,38 @@ class Context {
     CellCounts c{};
     check(ibu_call_cells(c_, d_sorted, n, mode, param, flags, d_class, &c, st));
     return c;
+  }
+  // a reproducible random subset of n rows (ibu_subsample_class): d_class (n bytes, or nullptr for the count only) gets
+  // IBU_SAMPLE_KEPT where the row's number splitmix64(splitmix64(seed) + first_row + row) is below `threshold` (all ones keeps every
+  // row) and IBU_SAMPLE_DROPPED elsewhere; no record is read.  Returns the number kept (synchronises).  subsample_class_async: no
+  // count, nothing synchronised.  select_records(.., 1u << IBU_SAMPLE_KEPT, ..) then makes the subset
+  size_t subsample_class(size_t n, uint64_t threshold, uint8_t* d_class, uint64_t seed = 0, uint64_t first_row = 0, void* st = nullptr) {
+    size_t k = 0;
+    check(ibu_subsample_class(c_, n, first_row, seed, threshold, d_class, &k, st));
+    return k;
+  }
+  void subsample_class_async(size_t n, uint64_t threshold, uint8_t* d_class, uint64_t seed = 0, uint64_t first_row = 0, void* st = nullptr) {
+    check(ibu_subsample_class(c_, n, first_row, seed, threshold, d_class, nullptr, st));
+  }
+  // the threshold that keeps `fraction` of the reads: all ones from 1 on, otherwise the floor of fraction * 2^64 (exact: a double
+  // below 1 times 2^64 is a whole number below 2^64)
+  static uint64_t sample_threshold(double fraction) {
+    if (!(fraction >= 0)) {
+      ibu_error_detail_t d{};
+      d.code = IBU_ERR_INVALID_ARG;
+      snprintf(d.message, sizeof d.message, "Invalid argument: the fraction must be a number >= 0");
+      throw IbuError(IBU_ERR_INVALID_ARG, d);
+    }
+    return fraction >= 1 ? UINT64_MAX : (uint64_t)std::ldexp(fraction, 64);
+  }
+  // what would have been seen at each of 1 .. 32 non-decreasing thresholds, from one read of the sorted records
+  // (ibu_saturation_curve): per point the kept reads and the barcodes / (barcode, umi) molecules with a kept read
+  std::vector<SaturationPoint> saturation_curve(const void* d_sorted, size_t n, const std::vector<uint64_t>& thresholds, uint64_t seed = 0,
+                                                uint64_t first_row = 0, void* st = nullptr) {
+    std::vector<SaturationPoint> points(thresholds.size());
+    check(ibu_saturation_curve(c_, d_sorted, n, first_row, seed, thresholds.data(), (uint32_t)(thresholds.size() > 0xFFFFFFFFu ? 0xFFFFFFFFu : thresholds.size()),
+                               points.data(), st));
+    return points;
   }
   // stable compaction by class (ibu_select_records) -> how many records went to d_out (capacity `cap` records); d_out == nullptr
   // and cap == 0: only count

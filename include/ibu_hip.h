@@ -631,6 +631,56 @@ typedef struct ibu_cell_counts {
 } ibu_cell_counts_t;
 int32_t ibu_call_cells(ibu_ctx_t* ctx, const void* d_sorted_records, size_t n, uint32_t mode, uint64_t param, uint32_t flags,
                        uint8_t* d_class, ibu_cell_counts_t* counts, void* stream);
+/* Read subsampling and the saturation curve, on the device (k_saturation.hip): a reproducible random subset of the reads — what
+ * brings samples of different depth to a common depth — and the number every single-cell summary reports first: how many distinct
+ * molecules and barcodes would have been seen at a fraction of the reads.  The reference has nothing like this; the semantics are
+ * this library's and are stated in full here.  Write w0, w1 for the first two 64-bit words of a record in storage order, and
+ * splitmix64(z) for: z += 0x9E3779B97F4A7C15; z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9; z = (z ^ (z >> 27)) * 0x94D049BB133111EB;
+ * z ^ (z >> 31) — all modulo 2^64 (splitmix64(0) = 0xE220A8397B1DCDAF).
+ *   THE NUMBER OF A READ  u(row) = splitmix64(splitmix64(seed) + first_row + row), the sums modulo 2^64.  `row` is the record's
+ *     position in the array given to the call, `first_row` a caller's offset, so that the pieces of a larger array hash as the whole
+ *     would.  The records' contents do not enter: two identical records are two reads.  The result therefore DEPENDS ON THE ORDER
+ *     of the records — apply it at one fixed stage of a pipeline, normally the sorted records.
+ *   KEPT  a read is kept at a threshold t (64 bits, unsigned) iff u(row) < t, or t == UINT64_MAX, which keeps every read; t == 0
+ *     keeps none.  The sets are nested: a read kept at t is kept at every larger t.  A fraction f of the reads is the threshold
+ *     floor(f * 2^64), f >= 1 is UINT64_MAX.
+ * ibu_subsample_class: d_class[row] = IBU_SAMPLE_KEPT (0) or IBU_SAMPLE_DROPPED (1) for the n rows; no record is read.
+ * ibu_select_records(..., keep_mask = 1 << IBU_SAMPLE_KEPT) then gives the subset in input order, still sorted.  d_class (nullable:
+ * the count only): n bytes at any alignment.  n_kept (nullable): the number of kept rows; non-NULL synchronises `stream`, NULL leaves
+ * the call asynchronous (as `counts` of ibu_correct_barcodes, and under its rule of one such call in flight per context).  n == 0 is
+ * OK and touches nothing (*n_kept = 0).  IBU_ERR_INVALID_ARG: n >= 2^40; d_class == NULL together with n_kept == NULL, a call with
+ * nothing to do — a refused call leaves *n_kept alone.  A NULL context is an error.  Writes 1 B per row, sixteen rows per lane and
+ * store where the alignment of d_class allows; no atomic per row.
+ * ibu_saturation_curve: `thresholds` is a HOST array of 1 <= k <= IBU_SATURATION_MAX_POINTS values, non-decreasing (duplicates are
+ * allowed), `points` a HOST array of k structs.  For point j: threshold = thresholds[j];
+ *   reads      the reads kept at thresholds[j];
+ *   barcodes   the maximal runs of consecutive records with equal w0 that have at least one kept read;
+ *   molecules  the same for the runs of equal (w0, w1).
+ * On records sorted by (barcode, umi, index), 1 - molecules / reads is the sequencing saturation at that depth; on records that went
+ * through ibu_records_swap_umi_index and the sort, `molecules` counts the (barcode, index) pairs with a kept read — the non-zero
+ * entries of the count matrix, "genes detected".  At UINT64_MAX the three are n, the runs of ibu_barcode_counts and those of
+ * ibu_pair_counts.  On unsorted input the result is the same computation on the runs as they stand, as ibu_barcode_counts documents
+ * for itself.  The records are never written.
+ * IBU_ERR_INVALID_ARG, with nothing touched, `points` included: k == 0, k > 32, a threshold below the one before it, NULL
+ * thresholds or points, a NULL or misaligned d_sorted_records with n > 0, n >= 2^40.  A NULL context is an error.  n == 0 is OK:
+ * every point is {threshold, 0, 0, 0}.  Records 8-byte aligned: a 16-byte aligned array takes the tiled path, an 8- but not 16-byte
+ * aligned one peels one record, as ibu_pair_counts does.  Synchronises `stream` once.
+ * Traffic: the records are read ONCE for all k points (two of their three words are looked at): every read falls into the bin
+ * "number of thresholds <= u", a run into the smallest bin of its reads, and the curve is the three histograms read cumulatively.
+ * 408 B per 8192 records of per-segment counters are written and read once; runs that span segments are stitched by a segmented
+ * min-scan over the segments (n / 8192 entries whatever the run lengths).  No atomic per record.  Scratch: the context's sort
+ * scratch, 408 B per 8192 records (+ 2 KiB), grown on demand. */
+#define IBU_SAMPLE_KEPT 0
+#define IBU_SAMPLE_DROPPED 1
+#define IBU_SATURATION_MAX_POINTS 32u
+typedef struct ibu_saturation_point {
+  uint64_t threshold;                       /* thresholds[j] */
+  uint64_t reads, barcodes, molecules;      /* kept reads / runs of equal w0 / of equal (w0, w1) with a kept read */
+} ibu_saturation_point_t;
+int32_t ibu_subsample_class(ibu_ctx_t* ctx, size_t n, uint64_t first_row, uint64_t seed, uint64_t threshold, uint8_t* d_class,
+                            size_t* n_kept, void* stream);
+int32_t ibu_saturation_curve(ibu_ctx_t* ctx, const void* d_sorted_records, size_t n, uint64_t first_row, uint64_t seed,
+                             const uint64_t* thresholds, uint32_t k, ibu_saturation_point_t* points, void* stream);
 /* Barcode correction against a whitelist, on the device (k_whitelist.hip) — the step between a load and ibu_sort_records /
  * ibu_barcode_counts that makes the latter's "a caller that knows a bound (its whitelist)" true of real input.  The reference has
  * no such function (as it has no sort and no aggregation); the semantics are this library's and are stated in full here.

@@ -6,6 +6,7 @@ into preallocated device arrays, no download.
   python tools/aggbench.py --matrix 1e5x100,own_pair,one_pair [--records 1e9]     the count-matrix legs (matrix_legs below)
   python tools/aggbench.py --molecules [--records 1e9] [--reads-per-molecule 4] [--second-candidate 0.05]     ibu_classify_molecules (molecule_legs below)
   python tools/aggbench.py --cells [--records 1e9] [--reads-per-molecule 4]     ibu_call_cells (cell_legs below)
+  python tools/aggbench.py --saturation [--records 1e9] [--reads-per-molecule 4]     ibu_saturation_curve, ibu_subsample_class (saturation_legs below)
 bc_len 10 gives 2^20 distinct barcodes (a single-cell whitelist's order of magnitude); 16 gives ~n runs of length one."""
 import argparse
 import ctypes as C
@@ -136,6 +137,22 @@ def matrix_legs(a):
         print(json.dumps(res), flush=True)
 
 
+def molecule_fill(torch, i, rpm, cut):
+    """Rows i (a tensor of row numbers) of the input of --molecules and --saturation -> their (barcode, umi, index) words: rpm
+    consecutive records per molecule, 4096 molecules per barcode, and in a share cut / 2^20 of the molecules the last read (half of
+    them: the last two) under the next index."""
+    mol, k = i // rpm, i % rpm
+    h = ((mol * 0x1E3779B97F4A7C15) >> 20) & 0xFFFFF        # 20 pseudo-random bits per molecule
+    second = (h < cut) & (k >= rpm - 1 - (h & 1))
+    return mol >> 12, mol & 4095, ((h >> 8) % 100) * 2 + second.to(torch.int64)
+
+
+def molecule_layout(n, rpm):
+    """What molecule_fill lays in rows 0 .. n - 1 -> (barcodes, molecules): the last molecule and the last barcode may be partial."""
+    mols = (n + rpm - 1) // rpm
+    return (mols + 4095) // 4096, mols
+
+
 def molecule_legs(a):
     """--molecules: ibu_classify_molecules on resident sorted 16/12 records, timed with events on a side stream (the first round
     is the warm-up), against ibu_pair_counts with outputs, ibu_reduce (one plain read) and ibu_device_copy on the same arrays.
@@ -159,12 +176,8 @@ def molecule_legs(a):
     for lo in range(0, n, 1 << 26):
         hi = min(n, lo + (1 << 26))
         i = torch.arange(lo, hi, device="cuda", dtype=torch.int64)
-        mol, k = i // rpm, i % rpm
-        h = ((mol * 0x1E3779B97F4A7C15) >> 20) & 0xFFFFF    # 20 pseudo-random bits per molecule
-        second = (h < cut) & (k >= rpm - 1 - (h & 1))
-        bc[lo:hi], um[lo:hi] = mol >> 12, mol & 4095
-        ix[lo:hi] = ((h >> 8) % 100) * 2 + second.to(torch.int64)
-    del i, mol, k, h, second
+        bc[lo:hi], um[lo:hi], ix[lo:hi] = molecule_fill(torch, i, rpm, cut)
+    del i
     torch.cuda.synchronize()
     d, t, d_class = ctx.alloc(24 * n), ctx.alloc(24 * n), ctx.alloc(n)
     ctx.serialize(cols[0], cols[1], cols[2], n, d)
@@ -325,8 +338,100 @@ def cell_legs(a):
     assert counts.cells == int((umis >= counts.threshold).sum()), "the cells are the barcodes that were laid with that many molecules"
 
 
+def saturation_legs(a):
+    """--saturation: the ten-point ibu_saturation_curve, and ibu_subsample_class + ibu_select_records at fraction 0.5, on resident
+    sorted 16/12 records (the array --molecules lays), timed with events on a side stream (the first round is the warm-up).  In the
+    same run and on the same array: ibu_reduce (the plain read: the floor), the ibu_pair_counts size query (the same walk over the
+    same bytes: the curve's yardstick), ibu_select_records alone on the same classes, and a fill of n bytes (the subsample kernel's
+    yardstick).  Before anything is timed, the 1.0 point of the curve is checked against ibu_pair_counts / ibu_barcode_counts and
+    against what was laid."""
+    import torch                                             # before the library, as bench.py does
+    torch.cuda.init()
+    import ibu_amd as ia
+    from ibu_amd import _dptr, _check, lib, _lib
+
+    ctx = ia.Context(0)
+    side = torch.cuda.Stream()
+    st = side.cuda_stream
+    n = int(float(a.records.split(",")[0]))
+    rpm = a.reads_per_molecule
+    cols = [ctx.alloc(8 * n) for _ in range(3)]
+    bc, um, ix = (torch.as_tensor(c, device="cuda").view(torch.int64) for c in cols)
+    cut = int(a.second_candidate * (1 << 20))
+    for lo in range(0, n, 1 << 26):
+        hi = min(n, lo + (1 << 26))
+        i = torch.arange(lo, hi, device="cuda", dtype=torch.int64)
+        bc[lo:hi], um[lo:hi], ix[lo:hi] = molecule_fill(torch, i, rpm, cut)
+    del i
+    torch.cuda.synchronize()
+    d, t, d_class = ctx.alloc(24 * n), ctx.alloc(24 * n), ctx.alloc(n)
+    ctx.serialize(cols[0], cols[1], cols[2], n, d)
+    ctx.synchronize()
+    for c in cols:
+        c.free()
+    assert ctx.is_sorted(d, n)
+
+    def timed(fn):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record(side)
+        fn()
+        e1.record(side)
+        e1.synchronize()
+        return e0.elapsed_time(e1)
+
+    def rounds(fn):
+        v = [timed(fn) for _ in range(a.rounds + 1)][1:]
+        return {"median_ms": round(statistics.median(v), 3), "min_ms": round(min(v), 3), "max_ms": round(max(v), 3)}
+
+    K = 10
+    seed = 0x1B0000C
+    ts = (C.c_uint64 * K)(*[ia.sample_threshold(j / K) if j < K else (1 << 64) - 1 for j in range(1, K + 1)])
+    pts = (_lib.CSaturationPoint * K)()
+    npairs, ntriples, nb, nbu, kept, sel = C.c_size_t(), C.c_size_t(), C.c_size_t(), C.c_size_t(), C.c_size_t(), C.c_size_t()
+    curve = lambda: _check(lib.ibu_saturation_curve(ctx._c, _dptr(d), n, 0, seed, ts, K, pts, st))
+    pairs = lambda: _check(lib.ibu_pair_counts(ctx._c, _dptr(d), n, None, None, None, None, 0, C.byref(npairs), C.byref(ntriples), st))
+    # the check, before anything is timed
+    curve()
+    pairs()
+    _check(lib.ibu_barcode_counts(ctx._c, _dptr(d), n, None, None, None, 0, C.byref(nb), C.byref(nbu), st))
+    last = pts[K - 1]
+    assert (last.reads, last.barcodes, last.molecules) == (n, nb.value, npairs.value), ((last.reads, last.barcodes, last.molecules), n, nb.value, npairs.value)
+    assert (nb.value, npairs.value) == molecule_layout(n, rpm), "every barcode and molecule that was laid"
+    assert all(pts[j].reads <= pts[j + 1].reads and pts[j].molecules <= pts[j + 1].molecules for j in range(K - 1))
+    half = ia.sample_threshold(0.5)
+    sub = lambda want=True: _check(lib.ibu_subsample_class(ctx._c, n, 0, seed, half, _dptr(d_class), C.byref(kept) if want else None, st))
+    select = lambda: _check(lib.ibu_select_records(ctx._c, _dptr(d), _dptr(d_class), n, 1 << ia.SAMPLE_KEPT, _dptr(t), n, C.byref(sel), st))
+    sub()
+    select()
+    ctx.synchronize()
+    assert kept.value == sel.value == pts[4].reads, (kept.value, sel.value, pts[4].reads)
+    cls = torch.as_tensor(d_class, device="cuda").view(torch.uint8)[:n]
+    res = {"leg": "saturation", "n": n, "reads_per_molecule": rpm, "points": K,
+           "curve": [{"fraction": (j + 1) / K, "reads": pts[j].reads, "barcodes": pts[j].barcodes, "molecules": pts[j].molecules,
+                      "saturation": round(1 - pts[j].molecules / max(1, pts[j].reads), 6)} for j in range(K)]}
+    res["reduce"] = rounds(lambda: _check(lib.ibu_reduce(ctx._c, _dptr(d), n, st)))
+    res["pair_counts_size_query"] = rounds(pairs)
+    res["saturation_curve"] = rounds(curve)
+    res["pair_counts_size_query_again"] = rounds(pairs)
+    with torch.cuda.stream(side):
+        res["fill_n_bytes"] = rounds(lambda: cls.fill_(1))
+    res["subsample_class"] = rounds(lambda: sub(False))
+    res["subsample_class_with_count"] = rounds(sub)
+    res["select_records"] = rounds(select)
+    res["subsample_and_select"] = rounds(lambda: (sub(False), select()))
+    res["reduce_again"] = rounds(lambda: _check(lib.ibu_reduce(ctx._c, _dptr(d), n, st)))
+    pq = min(res["pair_counts_size_query"]["median_ms"], res["pair_counts_size_query_again"]["median_ms"])
+    rd = min(res["reduce"]["median_ms"], res["reduce_again"]["median_ms"])
+    res["curve_vs_size_query"] = round(res["saturation_curve"]["median_ms"] / pq, 3)
+    res["curve_vs_reduce"] = round(res["saturation_curve"]["median_ms"] / rd, 3)
+    res["subsample_vs_fill"] = round(res["subsample_class"]["median_ms"] / res["fill_n_bytes"]["median_ms"], 3)
+    res["subsample_and_select_vs_select"] = round(res["subsample_and_select"]["median_ms"] / res["select_records"]["median_ms"], 3)
+    print(json.dumps(res), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--saturation", action="store_true", help="the ibu_saturation_curve / ibu_subsample_class legs instead of the barcode leg")
     ap.add_argument("--cells", action="store_true", help="the ibu_call_cells legs instead of the barcode leg")
     ap.add_argument("--molecules", action="store_true", help="the ibu_classify_molecules legs instead of the barcode leg")
     ap.add_argument("--reads-per-molecule", type=int, default=4)
@@ -337,6 +442,8 @@ def main():
     ap.add_argument("--rounds", type=int, default=5)
     ap.add_argument("--whitelist", type=int, default=0, help="K > 0: barcodes drawn from K distinct ones, skewed (rank ~ K u^3), as tools/sortbench.py --whitelist")
     a = ap.parse_args()
+    if a.saturation:
+        return saturation_legs(a)
     if a.molecules:
         return molecule_legs(a)
     if a.cells:
