@@ -17,8 +17,10 @@
 // barcode: as before.  The pair level has no stash: entries are typically a sizeable fraction of the records (a count matrix has a few
 // reads per entry), and a segment with more than kStashHeads of them is walked again anyway.
 //
-// Launchers: launch_runs_count, launch_runs_emit (kernels.h); C ABI: ibu_barcode_counts, ibu_pair_counts (device.cpp).  The molecule
-// classification that builds on the pair-level count pass: k_molecules.hip.
+// ibu_k_class_fill: the pass that turns the ballots a walk kept into class bytes, for the molecule classification (k_molecules.hip,
+// on the pair-level count pass) and cell calling (k_cells.hip, on the barcode-level one).
+//
+// Launchers: launch_runs_count, launch_runs_emit, launch_class_fill (kernels.h); C ABI: ibu_barcode_counts, ibu_pair_counts (device.cpp).
 #include "runs_walk.hpp"
 
 namespace ibu {
@@ -123,6 +125,64 @@ ibu_k_runs_scan(const u32* __restrict__ seg_heads, u32 nseg, u64* __restrict__ s
   if (threadIdx.x == 0) totals[blockIdx.x] = carry;
 }
 
+// Class bytes from the ballots an emit pass kept (BallotSink, runs_walk.hpp): the heads' ordinals are the entries of `verdict`.  One
+// wave per segment, as in the walk; in a tiled segment lane L first takes tile L's two ballots and the wave ranks the tiles, then every
+// step serves two tiles: lanes 0-31 the first, lanes 32-63 the second, four consecutive records (two even, two odd positions of the
+// walk's lane pairs) per lane.  A record's entry = the heads that begin in front of the segment (seg_row: the scanned row of seg_base
+// that counts these heads) + the heads of the segment up to and including the record - 1: a record whose run began in an earlier
+// segment falls out of the same formula.  No record read, no LDS.
+template <bool WORDS>
+__global__ void __launch_bounds__(kSortThreads)
+ibu_k_class_fill(SegPlan sp, const u64* __restrict__ seg_row /*[nseg], scanned*/, const u64* __restrict__ masks,
+                 const uint8_t* __restrict__ verdict, uint8_t* __restrict__ d_class) {
+  const u32 lane = threadIdx.x & (kWave - 1), wib = threadIdx.x >> 6;
+  const u32 seg = blockIdx.x * kSortWaves + wib;
+  if (seg >= sp.nseg) return;                                 // wave-uniform
+  const u64 hbase = seg_row[seg];                             // heads that begin in front of the segment
+  const u64 ntiles_all = sp.main / kTileRecs;
+  if (seg == 0 || seg == sp.nseg - 1) {
+    const u64 begin = seg == 0 ? 0 : sp.head + sp.main, end = seg == 0 ? sp.head : sp.n;
+    u64 seen = 0;
+    for (u32 step = 0; step < 2; ++step) {
+      const u64 i = begin + (u64)step * kWave + lane;
+      if (begin + (u64)step * kWave >= end) break;             // wave-uniform
+      const u64 m = masks[end_ballots_at(ntiles_all, seg == 0 ? 0 : 1, step)];
+      if (i < end) d_class[i] = verdict[hbase + seen + (u64)__popcll(m & ((2ull << lane) - 1)) - 1];
+      seen += (u64)__popcll(m);
+    }
+    return;
+  }
+  const u64 begin = sp.head + (u64)(seg - 1) * kSegRecs, stop = sp.head + sp.main;
+  const u32 ntiles = (u32)(((begin + kSegRecs < stop ? begin + kSegRecs : stop) - begin) / kTileRecs);   // 1 .. 64
+  const u64 tile0 = (begin - sp.head) / kTileRecs;
+  u64 even = 0, odd = 0;
+  if (lane < ntiles) { even = masks[tile_ballots_at(tile0 + lane)]; odd = masks[tile_ballots_at(tile0 + lane) + 1]; }
+  const u32 mine = (u32)(__popcll(even) + __popcll(odd));
+  const u32 rank = wave_scan(mine, OpAdd{}) - mine;           // heads that begin in the segment's tiles in front of tile `lane`
+  const u32 l = lane & 31u;
+  const u64 below = (1ull << (2 * l)) - 1;
+  for (u32 step = 0; 2 * step < ntiles; ++step) {
+    const u32 tile = 2 * step + (lane >> 5);
+    const u64 ev = ((u64)__shfl((u32)(even >> 32), tile) << 32) | __shfl((u32)even, tile);
+    const u64 od = ((u64)__shfl((u32)(odd >> 32), tile) << 32) | __shfl((u32)odd, tile);
+    const u32 r0 = __shfl(rank, tile);
+    if (tile < ntiles) {
+      // records 4l .. 4l+3 of the tile = the walk's (lane 2l: even, odd), (lane 2l+1: even, odd)
+      const u64 k0 = hbase + r0 + (u64)(__popcll(ev & below) + __popcll(od & below)) + ((ev >> (2 * l)) & 1) - 1;
+      const u64 k1 = k0 + ((od >> (2 * l)) & 1);
+      const u64 k2 = k1 + ((ev >> (2 * l + 1)) & 1);
+      const u64 k3 = k2 + ((od >> (2 * l + 1)) & 1);
+      const u32 v0 = verdict[k0], v1 = verdict[k1], v2 = verdict[k2], v3 = verdict[k3];
+      uint8_t* out = d_class + begin + (u64)tile * kTileRecs + 4 * l;
+      if constexpr (WORDS) {
+        __builtin_nontemporal_store(v0 | (v1 << 8) | (v2 << 16) | (v3 << 24), reinterpret_cast<u32*>(out));
+      } else {
+        out[0] = (uint8_t)v0; out[1] = (uint8_t)v1; out[2] = (uint8_t)v2; out[3] = (uint8_t)v3;
+      }
+    }
+  }
+}
+
 size_t runs_scratch_bytes(size_t n) { return runs_layout(n).runs_bytes; }
 size_t runs_emit_scratch_bytes(uint64_t n_runs) { return 16 * (size_t)(n_runs ? n_runs : 1); }
 
@@ -157,11 +217,21 @@ hipError_t launch_runs_emit(const LaunchCfg& cfg, const void* recs, size_t n, co
   else
     hipLaunchKernelGGL(ibu_k_runs_emit, seg_grid(sp), dim3(kSortThreads), 0, st, (const u64*)recs, sp, base,
                        scratch_at<const u32>(scratch, L.seg_heads), scratch_at<const RunStash>(scratch, L.stash), (u64*)first, starts, rank);
-  u64 blocks = (n_runs + 255) / 256;
-  const u64 cap = (u64)cfg.cus * 8;
-  if (blocks > cap) blocks = cap;
-  hipLaunchKernelGGL(ibu_k_runs_finish, dim3((u32)(blocks ? blocks : 1)), dim3(256), 0, st, (const u64*)starts, (const u64*)rank, (u64)n_runs,
+  hipLaunchKernelGGL(ibu_k_runs_finish, dim3(capped_grid(cfg, n_runs, 256)), dim3(256), 0, st, (const u64*)starts, (const u64*)rank, (u64)n_runs,
                      (u64)n, (u64)n_ranked, (u64*)counts, (u64*)distinct);
+  return hipGetLastError();
+}
+// The last step of a launcher (what was launched in front of it keeps its error): words where the first tiled class byte is 4-byte
+// aligned, bytes elsewhere.
+hipError_t launch_class_fill(const LaunchCfg& cfg, const void* recs, size_t n, const void* scratch, bool ranked, const uint8_t* verdict,
+                             uint8_t* d_class, hipStream_t st) {
+  const SegPlan sp = seg_plan(cfg, recs, n);
+  const RunsLayout L = runs_layout(n);
+  const u64* seg_row = scratch_at<const u64>(scratch, L.seg_base) + (ranked ? sp.nseg : 0);
+  const u64* masks = scratch_at<const u64>(scratch, L.mol_masks);
+  const bool words = ((reinterpret_cast<uintptr_t>(d_class) + sp.head) & 3u) == 0;
+  hipLaunchKernelGGL(words ? ibu_k_class_fill<true> : ibu_k_class_fill<false>, seg_grid(sp), dim3(kSortThreads), 0, st, sp, seg_row, masks,
+                     verdict, d_class);
   return hipGetLastError();
 }
 

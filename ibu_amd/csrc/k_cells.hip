@@ -14,9 +14,8 @@
 //            top and narrows prefix and remaining rank in device memory).  launch_rank_select is the same on any array of values.
 //   verdict  one byte per barcode (metric >= T: 0, else 1) and the five sums, per wave with shuffles, per block in LDS, five atomics
 //            per block of a grid that is capped.
-//   fill     one wave per segment turns the ballots into each record's barcode number (popcounts, no record read, no LDS) and
-//            writes the verdicts as class bytes, four records per lane and store — ibu_k_molecules_fill of k_molecules.hip with
-//            the other ballots and the other base.
+//   fill     launch_class_fill of k_aggregate.hip: the ballots and the run heads' bases give each record's barcode number, the
+//            verdicts leave as class bytes.
 // Launchers: launch_cells_call, launch_rank_select (kernels.h); C ABI: ibu_call_cells (device.cpp; its test hook ibu_test_rank_select runs the selection alone).
 #include "runs_walk.hpp"
 
@@ -28,24 +27,20 @@ static constexpr u32 kSelectPasses = 5;                       // 8-bit digits of
 static constexpr u32 kSelectBins = 256;
 static_assert(kSelectBins == (u32)kSortThreads, "ibu_k_select_hist / _narrow: one thread per bin");
 
-struct CellEmit : NoSink {                                    // masks (nullable): u64[2 ntiles] of the tiles, then u64[2] of each end
-  u64* starts; u64* rank; u64* masks; u64 ntiles;
+struct CellEmit : BallotSink {                                // keeps the ballots of run heads
+  u64* starts; u64* rank;
   __device__ __forceinline__ void head(u64 b, u64 q, u64 row, u64, u64, bool run_head) const {
     if (!run_head) return;
     starts[b] = row;                                          // first record of barcode b
     rank[b] = q;                                              // (barcode, umi) pairs that begin in front of it
   }
-  __device__ __forceinline__ void tile_run_ballots(u64 tile, u64 even, u64 odd) const {
-    if (masks) { masks[2 * tile] = even; masks[2 * tile + 1] = odd; }
-  }
-  __device__ __forceinline__ void end_run_ballots(u32 which, u32 step, u64 m) const {
-    if (masks && step < 2) masks[2 * ntiles + 2 * which + step] = m;
-  }
+  __device__ __forceinline__ void tile_run_ballots(u64 tile, u64 even, u64 odd) const { keep_tile(tile, even, odd); }
+  __device__ __forceinline__ void end_run_ballots(u32 which, u32 step, u64 m) const { keep_end(which, step, m); }
 };
 extern "C" __global__ void __launch_bounds__(kSortThreads, 8)
 ibu_k_cells_emit(const u64* __restrict__ recs, SegPlan sp, const u64* __restrict__ seg_base /*[2][nseg], scanned*/, u64* __restrict__ starts,
                  u64* __restrict__ rank, u64* __restrict__ masks /*nullable*/) {
-  runs_kernel<1>(recs, sp, seg_base, nullptr, CellEmit{{}, starts, rank, masks, sp.main / kTileRecs});
+  runs_kernel<1>(recs, sp, seg_base, nullptr, CellEmit{{{}, masks, sp.main / kTileRecs}, starts, rank});
 }
 
 extern "C" __global__ void __launch_bounds__(kSortThreads)
@@ -93,12 +88,7 @@ ibu_k_select_narrow(const u64* __restrict__ hist /*[kSelectBins] of this pass*/,
   const u32 bin = kSelectBins - 1 - threadIdx.x;
   const u64 prefix = pass ? state[0] : 0, r = pass ? state[1] : rank0;
   const u64 c = hist[bin];
-  u64 inc = c;
-#pragma unroll
-  for (int d = 1; d < kWave; d <<= 1) {
-    const u64 up = shfl_up64(inc, d);
-    if (lane >= (u32)d) inc += up;
-  }
+  u64 inc = wave_scan(c, OpAdd{});
   if (lane == kWave - 1) wsum[wib] = inc;
   __syncthreads();                                            // (also: every thread has read the state before one of them writes it)
 #pragma unroll
@@ -108,26 +98,7 @@ ibu_k_select_narrow(const u64* __restrict__ hist /*[kSelectBins] of this pass*/,
   if (above < r && r <= inc) { state[0] = (prefix << 8) | bin; state[1] = r - above; }
 }
 
-// acc: [0] cells, [1] reads of cells, [2] of background, [3] umis of cells, [4] of background, [5] threshold, [6] baseline
-__device__ __forceinline__ void cell_accumulate(u64 (&t)[5], u64* acc, u64* lds /*[kSortWaves][5]*/) {
-  const u32 lane = threadIdx.x & (kWave - 1), wib = threadIdx.x >> 6;
-#pragma unroll
-  for (int k = 0; k < 5; ++k) {
-#pragma unroll
-    for (int m = 32; m >= 1; m >>= 1) {
-      const u32 lo = __shfl_xor((u32)t[k], m), hi = __shfl_xor((u32)(t[k] >> 32), m);
-      t[k] += ((u64)hi << 32) | lo;
-    }
-    if (lane == 0) lds[wib * 5 + k] = t[k];
-  }
-  __syncthreads();
-  if (threadIdx.x < 5) {
-    u64 s = 0;
-#pragma unroll
-    for (int w = 0; w < kSortWaves; ++w) s += lds[w * 5 + threadIdx.x];
-    if (s) atomicAdd(&acc[threadIdx.x], s);
-  }
-}
+// acc (block_accumulate): [0] cells, [1] reads of cells, [2] of background, [3] umis of cells, [4] of background, [5] threshold, [6] baseline
 // mode / param as in ibu_call_cells; selected: state[0] of the selection (TOP, ORDMAG), the metric at the rank asked for.
 extern "C" __global__ void __launch_bounds__(kSortThreads)
 ibu_k_cells_verdict(const u64* __restrict__ starts, const u64* __restrict__ rank, const u64* __restrict__ metric, u64 nb, u64 n, u64 npairs,
@@ -162,81 +133,12 @@ ibu_k_cells_verdict(const u64* __restrict__ starts, const u64* __restrict__ rank
     }
     if (verdict && b0 < nb) *reinterpret_cast<u32*>(verdict + b0) = packed;   // (the array is padded to a multiple of four)
   }
-  cell_accumulate(t, acc, accl);
-}
-
-// Class bytes from the ballots the emit pass kept.  One wave per segment, as in the walk; in a tiled segment lane L first takes tile
-// L's two ballots and the wave ranks the tiles, then every step serves two tiles: lanes 0-31 the first, lanes 32-63 the second, four
-// consecutive records (two even, two odd positions of the walk's lane pairs) per lane.  A record's barcode = the runs that begin in
-// front of the segment + the run heads of the segment up to and including the record - 1: a record whose run began in an earlier
-// segment falls out of the same formula.
-template <bool WORDS>
-__global__ void __launch_bounds__(kSortThreads)
-ibu_k_cells_fill(SegPlan sp, const u64* __restrict__ seg_base /*[2][nseg], scanned*/, const u64* __restrict__ masks,
-                 const uint8_t* __restrict__ verdict, uint8_t* __restrict__ d_class) {
-  const u32 lane = threadIdx.x & (kWave - 1), wib = threadIdx.x >> 6;
-  const u32 seg = blockIdx.x * kSortWaves + wib;
-  if (seg >= sp.nseg) return;                                 // wave-uniform
-  const u64 bbase = seg_base[seg];                            // barcodes that begin in front of the segment
-  const u64 ntiles_all = sp.main / kTileRecs;
-  if (seg == 0 || seg == sp.nseg - 1) {
-    const u64 begin = seg == 0 ? 0 : sp.head + sp.main, end = seg == 0 ? sp.head : sp.n;
-    u64 seen = 0;
-    for (u32 step = 0; step < 2; ++step) {
-      const u64 i = begin + (u64)step * kWave + lane;
-      if (begin + (u64)step * kWave >= end) break;             // wave-uniform
-      const u64 m = masks[2 * ntiles_all + 2 * (seg == 0 ? 0 : 1) + step];
-      if (i < end) d_class[i] = verdict[bbase + seen + (u64)__popcll(m & ((2ull << lane) - 1)) - 1];
-      seen += (u64)__popcll(m);
-    }
-    return;
-  }
-  const u64 begin = sp.head + (u64)(seg - 1) * kSegRecs, stop = sp.head + sp.main;
-  const u32 ntiles = (u32)(((begin + kSegRecs < stop ? begin + kSegRecs : stop) - begin) / kTileRecs);   // 1 .. 64
-  const u64 tile0 = (begin - sp.head) / kTileRecs;
-  u64 even = 0, odd = 0;
-  if (lane < ntiles) { even = masks[2 * (tile0 + lane)]; odd = masks[2 * (tile0 + lane) + 1]; }
-  const u32 mine = (u32)(__popcll(even) + __popcll(odd));
-  u32 rank = mine;
-#pragma unroll
-  for (int d = 1; d < kWave; d <<= 1) {
-    const u32 up = __shfl_up(rank, d);
-    if (lane >= (u32)d) rank += up;
-  }
-  rank -= mine;                                               // barcodes that begin in the segment's tiles in front of tile `lane`
-  const u32 l = lane & 31u;
-  const u64 below = (1ull << (2 * l)) - 1;
-  for (u32 step = 0; 2 * step < ntiles; ++step) {
-    const u32 tile = 2 * step + (lane >> 5);
-    const u64 ev = ((u64)__shfl((u32)(even >> 32), tile) << 32) | __shfl((u32)even, tile);
-    const u64 od = ((u64)__shfl((u32)(odd >> 32), tile) << 32) | __shfl((u32)odd, tile);
-    const u32 r0 = __shfl(rank, tile);
-    if (tile < ntiles) {
-      // records 4l .. 4l+3 of the tile = the walk's (lane 2l: even, odd), (lane 2l+1: even, odd)
-      const u64 k0 = bbase + r0 + (u64)(__popcll(ev & below) + __popcll(od & below)) + ((ev >> (2 * l)) & 1) - 1;
-      const u64 k1 = k0 + ((od >> (2 * l)) & 1);
-      const u64 k2 = k1 + ((ev >> (2 * l + 1)) & 1);
-      const u64 k3 = k2 + ((od >> (2 * l + 1)) & 1);
-      const u32 v0 = verdict[k0], v1 = verdict[k1], v2 = verdict[k2], v3 = verdict[k3];
-      uint8_t* out = d_class + begin + (u64)tile * kTileRecs + 4 * l;
-      if constexpr (WORDS) {
-        __builtin_nontemporal_store(v0 | (v1 << 8) | (v2 << 16) | (v3 << 24), reinterpret_cast<u32*>(out));
-      } else {
-        out[0] = (uint8_t)v0; out[1] = (uint8_t)v1; out[2] = (uint8_t)v2; out[3] = (uint8_t)v3;
-      }
-    }
-  }
+  block_accumulate(t, acc, accl);
 }
 
 // selection work: state u64[2] | .. 64: hist u64[kSelectPasses][kSelectBins]
 static constexpr size_t kSelectHist = 64;
 size_t rank_select_work_bytes() { return kSelectHist + sizeof(u64) * kSelectPasses * kSelectBins; }
-static u32 capped_grid(const LaunchCfg& cfg, u64 items, u64 per_block) {
-  u64 blocks = (items + per_block - 1) / per_block;
-  const u64 cap = (u64)cfg.cus * 8;
-  if (blocks > cap) blocks = cap;
-  return (u32)(blocks ? blocks : 1);
-}
 hipError_t launch_rank_select(const LaunchCfg& cfg, const uint64_t* values, uint64_t count, uint64_t rank, void* work, hipStream_t st) {
   (void)hipGetLastError();
   if (count == 0 || rank == 0 || rank > count) return hipErrorInvalidValue;
@@ -298,12 +200,7 @@ hipError_t launch_cells_call(const LaunchCfg& cfg, const void* recs, size_t n, v
   }
   hipLaunchKernelGGL(ibu_k_cells_verdict, dim3(capped_grid(cfg, barcodes, kCellBlock)), dim3(kSortThreads), 0, st, (const u64*)starts,
                      (const u64*)rank, (const u64*)metric, (u64)barcodes, (u64)n, (u64)pairs, mode, (u64)param, (const u64*)work, verdict, acc);
-  if (d_class) {
-    if (((reinterpret_cast<uintptr_t>(d_class) + sp.head) & 3u) == 0)
-      hipLaunchKernelGGL(ibu_k_cells_fill<true>, seg_grid(sp), dim3(kSortThreads), 0, st, sp, base, (const u64*)masks, (const uint8_t*)verdict, d_class);
-    else
-      hipLaunchKernelGGL(ibu_k_cells_fill<false>, seg_grid(sp), dim3(kSortThreads), 0, st, sp, base, (const u64*)masks, (const uint8_t*)verdict, d_class);
-  }
+  if (d_class) return launch_class_fill(cfg, recs, n, scratch, false, verdict, d_class, st);
   return hipGetLastError();
 }
 

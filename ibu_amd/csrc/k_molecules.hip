@@ -14,8 +14,8 @@
 //   chains   one workgroup runs the same segmented scan over the blocks' summaries, 1024 per round: a molecule that leaves its
 //            block gets its total at the block it began in.  fix: every block settles its two open pieces from those totals.  A
 //            molecule of any length costs a constant per candidate this way: 1e6 candidates are 977 blocks, one round here.
-//   fill     one wave per segment turns the ballots into each record's candidate number (popcounts, no record read, no LDS) and
-//            writes the verdicts as class bytes, four records per lane and store.
+//   fill     launch_class_fill of k_aggregate.hip: the ballots and the ranked heads' bases give each record's candidate number, the
+//            verdicts leave as class bytes.
 // Launcher: launch_molecules_classify (kernels.h); C ABI: ibu_classify_molecules (device.cpp).
 #include "runs_walk.hpp"
 
@@ -85,7 +85,8 @@ __device__ __forceinline__ u32 mol_class(const MolAgg& m, u64 c, u32 tie_first) 
   if (((m.key >> 2) & 3u) >= 2 && !tie_first) return 2;     // IBU_MOLECULE_TIED
   return c == m.first ? 0u : 1u;                            // KEPT : MINOR
 }
-// one candidate into a thread's five totals (static indices only: the array stays in registers)
+// one candidate into a thread's five totals (static indices only: the array stays in registers), which block_accumulate adds into
+// acc: [0] resolved molecules, [1] tied molecules, [2..4] records of class 0, 1, 2
 __device__ __forceinline__ void mol_tally(u64 (&t)[5], u32 cls, u64 reads, bool mol_head, u64 key) {
   t[2] += cls == 0 ? reads : 0;
   t[3] += cls == 1 ? reads : 0;
@@ -94,41 +95,17 @@ __device__ __forceinline__ void mol_tally(u64 (&t)[5], u32 cls, u64 reads, bool 
   t[0] += several && !top_shared ? 1 : 0;
   t[1] += several && top_shared ? 1 : 0;
 }
-// acc: [0] resolved molecules, [1] tied molecules, [2..4] records of class 0, 1, 2
-__device__ __forceinline__ void mol_accumulate(u64 (&t)[5], u64* acc, u64* lds /*[kSortWaves][5]*/) {
-  const u32 lane = threadIdx.x & (kWave - 1), wib = threadIdx.x >> 6;
-#pragma unroll
-  for (int k = 0; k < 5; ++k) {
-#pragma unroll
-    for (int m = 32; m >= 1; m >>= 1) {
-      const u32 lo = __shfl_xor((u32)t[k], m), hi = __shfl_xor((u32)(t[k] >> 32), m);
-      t[k] += ((u64)hi << 32) | lo;
-    }
-    if (lane == 0) lds[wib * 5 + k] = t[k];
-  }
-  __syncthreads();
-  if (threadIdx.x < 5) {
-    u64 s = 0;
-#pragma unroll
-    for (int w = 0; w < kSortWaves; ++w) s += lds[w * 5 + threadIdx.x];
-    if (s) atomicAdd(&acc[threadIdx.x], s);
-  }
-}
 
-struct MolEmit : NoSink {                                   // masks (nullable): u64[2 ntiles] of the tiles, then u64[2] of each end
-  u64* table; u64* masks; u64 ntiles;
+struct MolEmit : BallotSink {                               // keeps the ballots of triple heads
+  u64* table;
   __device__ __forceinline__ void head(u64, u64 c, u64 row, u64, u64, bool mol_head) const { table[c] = row | (mol_head ? kMolHead : 0); }
-  __device__ __forceinline__ void tile_ballots(u64 tile, u64 even, u64 odd) const {
-    if (masks) { masks[2 * tile] = even; masks[2 * tile + 1] = odd; }
-  }
-  __device__ __forceinline__ void end_ballots(u32 which, u32 step, u64 m) const {
-    if (masks && step < 2) masks[2 * ntiles + 2 * which + step] = m;
-  }
+  __device__ __forceinline__ void tile_ballots(u64 tile, u64 even, u64 odd) const { keep_tile(tile, even, odd); }
+  __device__ __forceinline__ void end_ballots(u32 which, u32 step, u64 m) const { keep_end(which, step, m); }
 };
 extern "C" __global__ void __launch_bounds__(kSortThreads, 8)
 ibu_k_molecules_emit(const u64* __restrict__ recs, SegPlan sp, const u64* __restrict__ seg_base /*[2][nseg], scanned*/, u64* __restrict__ table,
                      u64* __restrict__ masks /*nullable*/) {
-  runs_kernel<2>(recs, sp, seg_base, nullptr, MolEmit{{}, table, masks, sp.main / kTileRecs});
+  runs_kernel<2>(recs, sp, seg_base, nullptr, MolEmit{{{}, masks, sp.main / kTileRecs}, table});
 }
 
 // What a verdict block leaves for the chain scan: the aggregate of the candidates in front of its first molecule head (`lead`, all
@@ -211,7 +188,7 @@ ibu_k_molecules_verdict(const u64* __restrict__ table, u64 ncand, u64 n, u32 tie
     sm.lead_len = s_lead_len; sm.trail_off = s_trail_off; sm.has_head = nheads ? 1u : 0u; sm.open = open;
     summary[blockIdx.x] = sm;
   }
-  mol_accumulate(t, acc, accl);
+  block_accumulate(t, acc, accl);
 }
 
 // One workgroup.  Block j enters the scan as a segment start with its trail when it has a molecule head, and as its lead (all of
@@ -275,68 +252,7 @@ ibu_k_molecules_fix(const u64* __restrict__ table, u64 ncand, u64 n, u32 tie_fir
       mol_tally(t, cls, next - (table[c] & kRowMask), piece == 1 && i == lo /*the molecule head is here*/, f.key);
     }
   }
-  mol_accumulate(t, acc, accl);
-}
-
-// Class bytes from the ballots the emit pass kept.  One wave per segment, as in the walk; in a tiled segment lane L first takes tile
-// L's two ballots and the wave ranks the tiles, then every step serves two tiles: lanes 0-31 the first, lanes 32-63 the second, four
-// consecutive records (two even, two odd positions of the walk's lane pairs) per lane.
-template <bool WORDS>
-__global__ void __launch_bounds__(kSortThreads)
-ibu_k_molecules_fill(SegPlan sp, const u64* __restrict__ seg_base /*[2][nseg], scanned*/, const u64* __restrict__ masks,
-                     const uint8_t* __restrict__ verdict, uint8_t* __restrict__ d_class) {
-  const u32 lane = threadIdx.x & (kWave - 1), wib = threadIdx.x >> 6;
-  const u32 seg = blockIdx.x * kSortWaves + wib;
-  if (seg >= sp.nseg) return;                               // wave-uniform
-  const u64 cbase = seg_base[sp.nseg + seg];                // candidates that begin in front of the segment
-  const u64 ntiles_all = sp.main / kTileRecs;
-  if (seg == 0 || seg == sp.nseg - 1) {
-    const u64 begin = seg == 0 ? 0 : sp.head + sp.main, end = seg == 0 ? sp.head : sp.n;
-    u64 seen = 0;
-    for (u32 step = 0; step < 2; ++step) {
-      const u64 i = begin + (u64)step * kWave + lane;
-      if (begin + (u64)step * kWave >= end) break;           // wave-uniform
-      const u64 m = masks[2 * ntiles_all + 2 * (seg == 0 ? 0 : 1) + step];
-      if (i < end) d_class[i] = verdict[cbase + seen + (u64)__popcll(m & ((2ull << lane) - 1)) - 1];
-      seen += (u64)__popcll(m);
-    }
-    return;
-  }
-  const u64 begin = sp.head + (u64)(seg - 1) * kSegRecs, stop = sp.head + sp.main;
-  const u32 ntiles = (u32)(((begin + kSegRecs < stop ? begin + kSegRecs : stop) - begin) / kTileRecs);   // 1 .. 64
-  const u64 tile0 = (begin - sp.head) / kTileRecs;
-  u64 even = 0, odd = 0;
-  if (lane < ntiles) { even = masks[2 * (tile0 + lane)]; odd = masks[2 * (tile0 + lane) + 1]; }
-  const u32 mine = (u32)(__popcll(even) + __popcll(odd));
-  u32 rank = mine;
-#pragma unroll
-  for (int d = 1; d < kWave; d <<= 1) {
-    const u32 up = __shfl_up(rank, d);
-    if (lane >= (u32)d) rank += up;
-  }
-  rank -= mine;                                             // candidates that begin in the segment's tiles in front of tile `lane`
-  const u32 l = lane & 31u;
-  const u64 below = (1ull << (2 * l)) - 1;
-  for (u32 step = 0; 2 * step < ntiles; ++step) {
-    const u32 tile = 2 * step + (lane >> 5);
-    const u64 ev = ((u64)__shfl((u32)(even >> 32), tile) << 32) | __shfl((u32)even, tile);
-    const u64 od = ((u64)__shfl((u32)(odd >> 32), tile) << 32) | __shfl((u32)odd, tile);
-    const u32 r0 = __shfl(rank, tile);
-    if (tile < ntiles) {
-      // records 4l .. 4l+3 of the tile = the walk's (lane 2l: even, odd), (lane 2l+1: even, odd)
-      const u64 k0 = cbase + r0 + (u64)(__popcll(ev & below) + __popcll(od & below)) + ((ev >> (2 * l)) & 1) - 1;
-      const u64 k1 = k0 + ((od >> (2 * l)) & 1);
-      const u64 k2 = k1 + ((ev >> (2 * l + 1)) & 1);
-      const u64 k3 = k2 + ((od >> (2 * l + 1)) & 1);
-      const u32 v0 = verdict[k0], v1 = verdict[k1], v2 = verdict[k2], v3 = verdict[k3];
-      uint8_t* out = d_class + begin + (u64)tile * kTileRecs + 4 * l;
-      if constexpr (WORDS) {
-        __builtin_nontemporal_store(v0 | (v1 << 8) | (v2 << 16) | (v3 << 24), reinterpret_cast<u32*>(out));
-      } else {
-        out[0] = (uint8_t)v0; out[1] = (uint8_t)v1; out[2] = (uint8_t)v2; out[3] = (uint8_t)v3;
-      }
-    }
-  }
+  block_accumulate(t, acc, accl);
 }
 
 // run scratch: acc u64[8] | table u64[ncand] | verdict bytes | summaries | chain starts | chain totals
@@ -380,12 +296,7 @@ hipError_t launch_molecules_classify(const LaunchCfg& cfg, const void* recs, siz
   hipLaunchKernelGGL(ibu_k_molecules_chains, dim3(1), dim3(kSortThreads), 0, st, (const MolSummary*)summary, L.nblk, chain_start, chain_full);
   hipLaunchKernelGGL(ibu_k_molecules_fix, dim3(L.nblk), dim3(kSortThreads), 0, st, (const u64*)table, (u64)candidates, (u64)n,
                      tie_first ? 1u : 0u, (const MolSummary*)summary, (const u32*)chain_start, (const MolFull*)chain_full, verdict, acc);
-  if (d_class) {
-    if (((reinterpret_cast<uintptr_t>(d_class) + sp.head) & 3u) == 0)
-      hipLaunchKernelGGL(ibu_k_molecules_fill<true>, seg_grid(sp), dim3(kSortThreads), 0, st, sp, base, (const u64*)masks, (const uint8_t*)verdict, d_class);
-    else
-      hipLaunchKernelGGL(ibu_k_molecules_fill<false>, seg_grid(sp), dim3(kSortThreads), 0, st, sp, base, (const u64*)masks, (const uint8_t*)verdict, d_class);
-  }
+  if (d_class) return launch_class_fill(cfg, recs, n, scratch, true, verdict, d_class, st);
   return hipGetLastError();
 }
 

@@ -136,11 +136,6 @@ ibu_k_swap_fields(const uint8_t* src, u32 ntiles, uint8_t* dst) {
 // loop: a lane's dwordx4 always lands on the same two field slots because the wave stride
 // (3072 B = 384 u64) is a multiple of 3.
 // =============================================================================================
-__device__ __forceinline__ u64 shfl_xor_u64(u64 v, int m) {
-  u32 lo = __shfl_xor((u32)v, m), hi = __shfl_xor((u32)(v >> 32), m);
-  return ((u64)hi << 32) | lo;
-}
-
 extern "C" __global__ void __launch_bounds__(kBlock, 8)
 ibu_k_reduce(const uint8_t* __restrict__ recs, u32 ntiles, u64 n_total, u64* __restrict__ acc) {
   __shared__ u64 part[kWavesPerBlock][6];
@@ -184,10 +179,12 @@ ibu_k_reduce(const uint8_t* __restrict__ recs, u32 ntiles, u64 n_total, u64* __r
       for (int g = 0; g < 3; ++g)
         if (f == (u32)g) { S[g] += s[k][h]; X[g] ^= x[k][h]; }
     }
+  // (the butterfly is written out, here and in ibu_k_reduce_tail / _fold: as two wave_reduce calls, the sums and then the XORs, the
+  // streaming loop above is allocated differently and the tail and the fold take 10 and 17 more VGPRs)
 #pragma unroll
   for (int m = 32; m >= 1; m >>= 1)
 #pragma unroll
-    for (int g = 0; g < 3; ++g) { S[g] += shfl_xor_u64(S[g], m); X[g] ^= shfl_xor_u64(X[g], m); }
+    for (int g = 0; g < 3; ++g) { S[g] += shfl_xor64(S[g], m); X[g] ^= shfl_xor64(X[g], m); }
   if (lane == 0)
 #pragma unroll
     for (int g = 0; g < 3; ++g) { part[wib][g] = S[g]; part[wib][3 + g] = X[g]; }
@@ -312,7 +309,7 @@ ibu_k_mismatch(const u64* __restrict__ a, const u64* __restrict__ b, u64 nwords,
       if (a[c] != b[c]) best = c < best ? c : best;
   }
 #pragma unroll
-  for (int m = 32; m >= 1; m >>= 1) { const u64 o = shfl_xor_u64(best, m); best = o < best ? o : best; }
+  for (int m = 32; m >= 1; m >>= 1) { const u64 o = shfl_xor64(best, m); best = o < best ? o : best; }
   if ((threadIdx.x & (kWave - 1)) == 0 && best != ~0ull) atomicMin(first, best);
 }
 extern "C" __global__ void ibu_k_copy_bytes(const uint8_t* __restrict__ src, uint8_t* __restrict__ dst, u64 off, u64 n) {
@@ -352,7 +349,7 @@ extern "C" __global__ void ibu_k_reduce_tail(const u64* __restrict__ recs, u64 r
 #pragma unroll
   for (int m = 32; m >= 1; m >>= 1)
 #pragma unroll
-    for (int g = 0; g < 3; ++g) { S[g] += shfl_xor_u64(S[g], m); X[g] ^= shfl_xor_u64(X[g], m); }
+    for (int g = 0; g < 3; ++g) { S[g] += shfl_xor64(S[g], m); X[g] ^= shfl_xor64(X[g], m); }
   if ((threadIdx.x & (kWave - 1)) == 0) {
     u64* slot = acc + 8 * (blockIdx.x & (kReduceSlots - 1));
 #pragma unroll
@@ -372,7 +369,7 @@ extern "C" __global__ void ibu_k_reduce_fold(u64* acc) {
   for (int m = 32; m >= 1; m >>= 1)
 #pragma unroll
     for (int w = 0; w < 7; ++w) {
-      const u64 o = shfl_xor_u64(v[w], m);
+      const u64 o = shfl_xor64(v[w], m);
       v[w] = w < 4 ? v[w] + o : v[w] ^ o;
     }
 #pragma unroll

@@ -91,11 +91,7 @@ struct SatSink : NoSink {
     // the lane's own stretch (a, b) at both depths, then the inclusive scan over the wave
     const u32 both = sat_min(ba, bb);
     u32 x = (b1 ? bb | kSatFlag : a1 ? both | kSatFlag : both) | ((b2 ? bb | kSatFlag : a2 ? both | kSatFlag : both) << 16);
-#pragma unroll
-    for (int d = 1; d < kWave; d <<= 1) {
-      const u32 p = __shfl_up(x, d);
-      if (lane >= (u32)d) x = sat_join(p, x);
-    }
+    x = wave_scan(x, [](u32 p, u32 v) { return sat_join(p, v); });
     u32 ex = __shfl_up(x, 1);
     if (lane == 0) ex = kSatNone | (kSatNone << 16);
     const u32 last = __shfl(x, kWave - 1);
@@ -132,11 +128,6 @@ struct SatSink : NoSink {
   }
 };
 
-__device__ __forceinline__ u32 sat_wave_min(u32 v) {
-#pragma unroll
-  for (int m = 32; m >= 1; m >>= 1) v = sat_min(v, __shfl_xor(v, m));
-  return v;
-}
 // a segment's summary at one depth: leading min | trailing min << 8 | has a head << 16
 __device__ __forceinline__ u32 sat_summary(u32 seen, u32 lead, u32 open) {
   return seen ? (lead | (open << 8) | (1u << 16)) : (open | (open << 8));
@@ -162,7 +153,7 @@ ibu_k_saturation_walk(const u64* __restrict__ recs, SegPlan sp, SatThresholds th
   const SatSink sink{{}, search[wib], base, end, lane, nbits, kSatNone, kSatNone, 0, 0, kSatNone, kSatNone, 0, 0, 0};
   u64 c1, c2;
   runs_segment<1>(recs, sp, seg, lds + wib * kTileBytes, lane, 0, 0, c1, c2, sink);
-  const u32 lead1 = sat_wave_min(sink.lead1), lead2 = sat_wave_min(sink.lead2);
+  const u32 lead1 = wave_reduce(sink.lead1, OpMin{}), lead2 = wave_reduce(sink.lead2, OpMin{});
   u32* row = hist + (size_t)seg * kSatRow;
   if (lane < kSatBins) {                                      // (the counters above bin K are never read: sat_tally)
     row[lane] = sink.reads;
@@ -210,12 +201,7 @@ ibu_k_saturation_stitch(const u32* __restrict__ summary /*[nseg][2]*/, u32 nseg,
       sm[k] = s0 + k < nseg ? summary[2 * (size_t)(s0 + k) + depth] : (kSatNone | (kSatNone << 8));
       run = sat_join1(run, (sm[k] >> 16) ? (((sm[k] >> 8) & 0xFFu) | kSatFlag) : (sm[k] & 0xFFu));
     }
-    u32 inc = run;
-#pragma unroll
-    for (int d = 1; d < kWave; d <<= 1) {
-      const u32 p = __shfl_up(inc, d);
-      if (lane >= (u32)d) inc = sat_join1(p, inc);
-    }
+    const u32 inc = wave_scan(run, [](u32 p, u32 v) { return sat_join1(p, v); });
     if (lane == kWave - 1) wv[wib] = inc;
     __syncthreads();
     u32 in = carry, all = carry;                              // open in front of this wave / behind the last one
@@ -295,8 +281,7 @@ ibu_k_subsample(u64 n, u64 base, u64 threshold, u64 front, u64 units, uint8_t* _
     }
   }
   if (!acc) return;                                           // (uniform)
-#pragma unroll
-  for (int m = 32; m >= 1; m >>= 1) kept += __shfl_xor(kept, m);
+  kept = wave_reduce(kept, OpAdd{});
   if (lane == 0) wsum[wib] = kept;
   __syncthreads();
   if (threadIdx.x == 0) {
@@ -309,12 +294,7 @@ ibu_k_subsample(u64 n, u64 base, u64 threshold, u64 front, u64 units, uint8_t* _
 extern "C" __global__ void __launch_bounds__(kWave)
 ibu_k_subsample_fold(u64* __restrict__ acc) {                 // leaves the total in acc[0]
   static_assert(kReduceSlots == kWave, "one lane per slot");
-  u64 v = acc[threadIdx.x];
-#pragma unroll
-  for (int m = 32; m >= 1; m >>= 1) {
-    const u32 lo = __shfl_xor((u32)v, m), hi = __shfl_xor((u32)(v >> 32), m);
-    v += ((u64)hi << 32) | lo;
-  }
+  const u64 v = wave_reduce(acc[threadIdx.x], OpAdd{});
   if (threadIdx.x == 0) acc[0] = v;
 }
 
@@ -330,10 +310,7 @@ hipError_t launch_subsample(const LaunchCfg& cfg, size_t n, uint64_t base, uint6
   u64 front = d_class ? (u64)((16 - (reinterpret_cast<uintptr_t>(d_class) & 15u)) & 15u) : 0;
   front = front < n ? front : n;
   const u64 units = (n - front) / 16;
-  u64 blocks = (units + kSortThreads - 1) / kSortThreads;
-  const u64 cap = (u64)cfg.cus * 8;
-  blocks = blocks > cap ? cap : blocks;
-  hipLaunchKernelGGL(ibu_k_subsample, dim3((u32)(blocks ? blocks : 1)), dim3(kSortThreads), 0, st, (u64)n, (u64)base, (u64)threshold, front, units,
+  hipLaunchKernelGGL(ibu_k_subsample, dim3(capped_grid(cfg, units, kSortThreads)), dim3(kSortThreads), 0, st, (u64)n, (u64)base, (u64)threshold, front, units,
                      d_class, (u64*)acc);
   if (acc) hipLaunchKernelGGL(ibu_k_subsample_fold, dim3(1), dim3(kWave), 0, st, (u64*)acc);
   return hipGetLastError();
@@ -369,10 +346,8 @@ hipError_t launch_saturation(const LaunchCfg& cfg, const void* recs, size_t n, u
   u32 nbits = 1;
   while ((1u << nbits) < k + 1) ++nbits;                      // 1 .. 6
   hipLaunchKernelGGL(ibu_k_saturation_walk, seg_grid(sp), dim3(kSortThreads), 0, st, (const u64*)recs, sp, th, nbits, (u64)base, hist, summary);
-  u32 blocks = (sp.nseg + 63) / 64;                           // 32 rows or more per half workgroup
-  const u32 cap = (u32)cfg.cus * 4;
-  blocks = blocks > cap ? cap : blocks;
-  hipLaunchKernelGGL(ibu_k_saturation_sum, dim3(blocks), dim3(kSortThreads), 0, st, (const u32*)hist, sp.nseg, totals);
+  // 32 rows or more per half workgroup
+  hipLaunchKernelGGL(ibu_k_saturation_sum, dim3(capped_grid(cfg, sp.nseg, 64, 4)), dim3(kSortThreads), 0, st, (const u32*)hist, sp.nseg, totals);
   hipLaunchKernelGGL(ibu_k_saturation_stitch, dim3(2), dim3(kSortThreads), 0, st, (const u32*)summary, sp.nseg, totals);
   hipLaunchKernelGGL(ibu_k_saturation_points, dim3(1), dim3(kWave), 0, st, (const u64*)totals, k, scratch_at<u64>(scratch, L.points));
   return hipGetLastError();

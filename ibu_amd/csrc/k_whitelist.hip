@@ -54,13 +54,8 @@ ibu_k_whitelist_build(const u64* __restrict__ codes, u64 w, u64 high /*~mask2(bc
       s = (s + 1) & mask;
     }
   }
-#pragma unroll
-  for (int m = 32; m >= 1; m >>= 1) {
-    const u32 lo = __shfl_xor((u32)first_bad, m), hi = __shfl_xor((u32)(first_bad >> 32), m);
-    const u64 o = ((u64)hi << 32) | lo;
-    first_bad = o < first_bad ? o : first_bad;
-    fresh += __shfl_xor(fresh, m);
-  }
+  first_bad = wave_reduce(first_bad, OpMin{});
+  fresh = wave_reduce(fresh, OpAdd{});
   if ((threadIdx.x & (kWave - 1)) == 0) {
     if (first_bad != kEmpty) atomicMin(&status[0], first_bad);
     if (fresh) atomicAdd(&status[1], (u64)fresh);
@@ -227,13 +222,7 @@ extern "C" __global__ void ibu_k_correct_fold(u64* acc) {
   u64 v[4];
 #pragma unroll
   for (int c = 0; c < 4; ++c) v[c] = acc[4 * lane + c];
-#pragma unroll
-  for (int m = 32; m >= 1; m >>= 1)
-#pragma unroll
-    for (int c = 0; c < 4; ++c) {
-      const u32 lo = __shfl_xor((u32)v[c], m), hi = __shfl_xor((u32)(v[c] >> 32), m);
-      v[c] += ((u64)hi << 32) | lo;
-    }
+  wave_reduce(v, OpAdd{});
   if (lane == 0)
 #pragma unroll
     for (int c = 0; c < 4; ++c) acc[c] = v[c];
@@ -260,8 +249,7 @@ ibu_k_select_count(const uint8_t* __restrict__ cls, u64 n, u32 nunits, u32 keep_
     u32 k = 0;
 #pragma unroll 8
     for (u32 r = 0; r < kSelRounds; ++r) k += sel_keep(cls, (u64)u * kSelUnit + r * kWave + lane, n, keep_mask);
-#pragma unroll
-    for (int m = 32; m >= 1; m >>= 1) k += __shfl_xor(k, m);
+    k = wave_reduce(k, OpAdd{});
     if (lane == 0) units[1 + u] = k;
   }
 }
@@ -278,12 +266,7 @@ ibu_k_select_scan(u64* __restrict__ units, u32 nunits) {
     u64 sum = 0;
     for (u32 k = 0; k < kScanPer; ++k)
       if (first + k < nunits) sum += units[1 + first + k];
-    u64 inc = sum;
-#pragma unroll
-    for (int d = 1; d < kWave; d <<= 1) {
-      const u32 lo = __shfl_up((u32)inc, d), hi = __shfl_up((u32)(inc >> 32), d);
-      if (lane >= (u32)d) inc += ((u64)hi << 32) | lo;
-    }
+    const u64 inc = wave_scan(sum, OpAdd{});
     if (lane == kWave - 1) wsum[wib] = inc;
     __syncthreads();
     u64 off = carry, tot = 0;

@@ -525,17 +525,64 @@ template <class T> static inline T* adv(T* p, size_t bytes) {
   return p ? reinterpret_cast<T*>(reinterpret_cast<uintptr_t>(p) + bytes) : p;
 }
 static inline u32 tail_grid(u64 rows) { return (u32)((rows + 255) / 256); }
+// A grid-stride kernel over `items`: the workgroups that cover them once at per_block each, at most blocks_per_cu per CU, at least one.
+static inline u32 capped_grid(const LaunchCfg& cfg, u64 items, u64 per_block, u32 blocks_per_cu = 8) {
+  u64 blocks = (items + per_block - 1) / per_block;
+  const u64 cap = (u64)cfg.cus * blocks_per_cu;
+  if (blocks > cap) blocks = cap;
+  return (u32)(blocks ? blocks : 1);
+}
+
+// ---- wave primitives ---------------------------------------------------------------------------
+// The 64-bit shuffles (the builtins move 32 bits), the butterfly and the Hillis-Steele scan over the 64 lanes of a wave, each
+// written once.  `op` is a functor or a lambda.  Not for the loops of the tuned kernels (BadRows::flush above, wl_flush_totals, the
+// sort's census and scan, mol_block_scan, the inflate): their register allocation moves with the shape of these loops, and they
+// stay written out.
+__device__ __forceinline__ u64 shfl_xor64(u64 v, int m) {
+  u32 lo = __shfl_xor((u32)v, m), hi = __shfl_xor((u32)(v >> 32), m);
+  return ((u64)hi << 32) | lo;
+}
+__device__ __forceinline__ u64 shfl_up64(u64 v, int d) {
+  u32 lo = __shfl_up((u32)v, d), hi = __shfl_up((u32)(v >> 32), d);
+  return ((u64)hi << 32) | lo;
+}
+__device__ __forceinline__ u32 shfl_xor_lanes(u32 v, int m) { return __shfl_xor(v, m); }
+__device__ __forceinline__ u64 shfl_xor_lanes(u64 v, int m) { return shfl_xor64(v, m); }
+__device__ __forceinline__ u32 shfl_up_lanes(u32 v, int d) { return __shfl_up(v, d); }
+__device__ __forceinline__ u64 shfl_up_lanes(u64 v, int d) { return shfl_up64(v, d); }
+struct OpAdd { template <class T> __device__ __forceinline__ T operator()(T a, T b) const { return a + b; } };
+struct OpMin { template <class T> __device__ __forceinline__ T operator()(T a, T b) const { return b < a ? b : a; } };
+// op over the 64 lanes (u32 or u64), the result in every lane; the array form reduces K values side by side.
+template <class T, class Op>
+__device__ __forceinline__ T wave_reduce(T v, Op op) {
+#pragma unroll
+  for (int m = 32; m >= 1; m >>= 1) v = op(v, shfl_xor_lanes(v, m));
+  return v;
+}
+template <class T, int K, class Op>
+__device__ __forceinline__ void wave_reduce(T (&v)[K], Op op) {
+#pragma unroll
+  for (int m = 32; m >= 1; m >>= 1)
+#pragma unroll
+    for (int k = 0; k < K; ++k) v[k] = op(v[k], shfl_xor_lanes(v[k], m));
+}
+// Inclusive scan: lane L gets op(.. op(op(v0, v1), v2) .., vL) for an associative op(front, back).
+template <class T, class Op>
+__device__ __forceinline__ T wave_scan(T v, Op op) {
+  const u32 lane = threadIdx.x & (kWave - 1);
+#pragma unroll
+  for (int d = 1; d < kWave; d <<= 1) {
+    const T front = shfl_up_lanes(v, d);
+    if (lane >= (u32)d) v = op(front, v);
+  }
+  return v;
+}
 
 // Block-wide exclusive scan of one u32 per thread over the first 256 threads of the block (every thread of the block
 // must call; threads >= 256 pass 0 and get garbage).  Leaves the total in *total.
 __device__ __forceinline__ u32 block_exclusive_scan(u32 v, u32* wsum /*[4] shared*/, u32* total) {
   const u32 lane = threadIdx.x & (kWave - 1), wib = threadIdx.x >> 6;
-  u32 inc = v;
-#pragma unroll
-  for (int d = 1; d < kWave; d <<= 1) {
-    const u32 t = __shfl_up(inc, d);
-    if (lane >= (u32)d) inc += t;
-  }
+  const u32 inc = wave_scan(v, OpAdd{});
   if (lane == kWave - 1 && wib < 4) wsum[wib] = inc;
   __syncthreads();
   u32 off = 0, tot = 0;

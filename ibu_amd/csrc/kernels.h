@@ -133,6 +133,10 @@ size_t runs_emit_scratch_bytes(uint64_t n_runs);
 // (runs_emit_scratch_bytes(n_runs) bytes) holds the runs' first rows and ranks in between.
 hipError_t launch_runs_emit(const LaunchCfg&, const void* recs, size_t n, const void* scratch, void* run_scratch, uint64_t n_runs,
                             uint64_t n_ranked, uint64_t* first, uint64_t* second, uint64_t* counts, uint64_t* distinct, hipStream_t st);
+// Class bytes from the ballots an emit pass left in `scratch` (the count scratch of the same recs and n): record i gets
+// verdict[the ordinal of the head it belongs to], ranked heads (ranked: launch_molecules_classify) or run heads (launch_cells_call).
+hipError_t launch_class_fill(const LaunchCfg&, const void* recs, size_t n, const void* scratch, bool ranked, const uint8_t* verdict,
+                             uint8_t* d_class, hipStream_t st);
 // one index per molecule (ibu_classify_molecules, k_molecules.hip).  launch_runs_count(RunsCount::Pair) on a scratch of
 // molecules_scratch_bytes(n) comes first; with its second total (the candidates) the caller sizes the run scratch.  Leaves one class
 // byte per record in d_class (nullable) and u64[5] at the front of run_scratch: resolved and tied molecules, records of class 0, 1, 2.

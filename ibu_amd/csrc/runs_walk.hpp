@@ -1,7 +1,8 @@
 // runs_walk.hpp — the segment walk over SORTED records that k_aggregate.hip (barcode and pair counts) and k_molecules.hip (one index
 // per molecule) share: the cut of the rows into segments (SegPlan), the count scratch both address (RunsLayout), the walk itself
-// (runs_segment) with the sinks' interface (NoSink), and the body of every kernel that runs it (runs_kernel).  k_cells.hip (cell
-// calling) and k_saturation.hip (the saturation curve: a per-run minimum carried from tile to tile through NoSink::records) walk it too.
+// (runs_segment) with the sinks' interface (NoSink) and the sink that keeps the ballots for the class fill (BallotSink), the body of
+// every kernel that runs it (runs_kernel), and the totals of a workgroup (block_accumulate).  k_cells.hip (cell calling) and
+// k_saturation.hip (the saturation curve: a per-run minimum carried from tile to tile through NoSink::records) walk it too.
 #pragma once
 #include "kcommon.hpp"
 #include "kernels.h"
@@ -13,11 +14,6 @@ static constexpr int kSortWaves = kSortThreads / kWave;
 static constexpr int kSegRecs = 8192;
 static constexpr u32 kStashHeads = 32;
 struct __attribute__((aligned(16))) RunStash { u64 barcode; u32 row_off; u32 pair_local; };
-
-__device__ __forceinline__ u64 shfl_up64(u64 v, int d) {
-  const u32 lo = __shfl_up((u32)v, d), hi = __shfl_up((u32)(v >> 32), d);
-  return ((u64)hi << 32) | lo;
-}
 
 // The rows are cut into SEGMENTS, one per wave, no barrier anywhere: segment 0 = the peeled rows in front of the first 16-B aligned
 // record (at most one), segments 1 .. S = 8 Ki records each (64 tiles), segment S+1 = the n % 128 rest.
@@ -35,9 +31,9 @@ __device__ __forceinline__ u32 wave_segment() { return blockIdx.x * kSortWaves +
 static inline dim3 seg_grid(const SegPlan& sp) { return dim3((sp.nseg + kSortWaves - 1) / kSortWaves); }
 
 // The count scratch (byte offsets): totals u64[2] | seg_heads u32[2][cap] | seg_base u64[2][cap], scanned | stash [cap][kStashHeads]
-// | the ballots a fill pass turns into class bytes, u64[2 (n / 128) + 4] (ranked heads: ibu_classify_molecules; run heads:
-// ibu_call_cells; one region, one call at a time).  It is a function of n alone, so that a scratch sized before the records' base is
-// known fits them at any alignment: cap = runs_nseg(n) segments, while a plan has sp.nseg = runs_nseg(sp.main) <= cap of them (one
+// | the ballots the class fill turns into class bytes, u64[2 (n / 128) + 4]: (even, odd) of every tile, then two steps of each
+// untiled end (BallotSink below; ranked heads: ibu_classify_molecules; run heads: ibu_call_cells; one region, one call at a time).
+// It is a function of n alone, so that a scratch sized before the records' base is known fits them at any alignment: cap = runs_nseg(n) segments, while a plan has sp.nseg = runs_nseg(sp.main) <= cap of them (one
 // fewer where peeling a record moves the last tile into the rest).  The tables are PLACED by cap and INDEXED with sp.nseg as their row
 // length, [row * sp.nseg + seg], which stays inside them.
 struct RunsLayout { size_t totals, seg_heads, seg_base, stash, runs_bytes, mol_masks, mol_bytes; };
@@ -90,6 +86,21 @@ struct NoSink {
   // comes with a row at or behind the segment's end and both flags false.  What a sink carries from step to step (a per-run
   // reduction: k_saturation.hip) lives in `mutable` members of the sink.
   __device__ __forceinline__ void records(u64 row, bool a1, bool a2, bool b1, bool b2, bool pair) const {}
+};
+
+// The sinks that keep a walk's ballots for the class fill (k_aggregate.hip) store them here, and the fill finds them here: masks
+// (nullable in a sink: nothing kept) = u64[2 ntiles], tile t's (even, odd) at 2t, then u64[2] per untiled end, its first two steps
+// (an end has fewer than 128 rows).  MolEmit keeps the ranked heads' ballots this way, CellEmit the run heads'.
+__host__ __device__ constexpr u64 tile_ballots_at(u64 tile) { return 2 * tile; }
+__host__ __device__ constexpr u64 end_ballots_at(u64 ntiles, u32 which, u32 step) { return 2 * ntiles + 2 * which + step; }
+struct BallotSink : NoSink {
+  u64* masks; u64 ntiles;
+  __device__ __forceinline__ void keep_tile(u64 tile, u64 even, u64 odd) const {
+    if (masks) { masks[tile_ballots_at(tile)] = even; masks[tile_ballots_at(tile) + 1] = odd; }
+  }
+  __device__ __forceinline__ void keep_end(u32 which, u32 step, u64 m) const {
+    if (masks && step < 2) masks[end_ballots_at(ntiles, which, step)] = m;
+  }
 };
 
 // One step of a walk: every lane brings record `row` (a) and, in a tiled step, `row + 1` (b) with their head flags.  Ranks them in
@@ -193,6 +204,24 @@ __device__ __forceinline__ void runs_kernel(const u64* __restrict__ recs, const 
   runs_segment<D>(recs, sp, seg, lds + wib * kTileBytes, lane, seg_base ? seg_base[seg] : 0, seg_base ? seg_base[sp.nseg + seg] : 0, c1, c2,
                   sink);
   if (seg_heads && lane == 0) { seg_heads[seg] = (u32)c1; seg_heads[sp.nseg + seg] = (u32)c2; }
+}
+
+// K totals of a workgroup of kSortThreads, one u64 per thread and total: per wave with shuffles, per workgroup in LDS, then one
+// atomic per non-zero total and workgroup.  Every thread of the workgroup calls (a barrier).  Static indices only: t stays in registers.
+template <int K>
+__device__ __forceinline__ void block_accumulate(u64 (&t)[K], u64* acc, u64* lds /*[kSortWaves][K]*/) {
+  const u32 lane = threadIdx.x & (kWave - 1), wib = threadIdx.x >> 6;
+  wave_reduce(t, OpAdd{});
+#pragma unroll
+  for (int k = 0; k < K; ++k)
+    if (lane == 0) lds[wib * K + k] = t[k];
+  __syncthreads();
+  if (threadIdx.x < K) {
+    u64 s = 0;
+#pragma unroll
+    for (int w = 0; w < kSortWaves; ++w) s += lds[w * K + threadIdx.x];
+    if (s) atomicAdd(&acc[threadIdx.x], s);
+  }
 }
 
 }  // namespace ibu

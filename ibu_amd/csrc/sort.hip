@@ -38,14 +38,6 @@ static constexpr int kSortWaves = kSortThreads / kWave;       // 4
 static constexpr int kBins = 256;
 static constexpr int kDigits = 24;                            // 3 fields x 8 bytes
 
-__device__ __forceinline__ u64 shfl_xor64(u64 v, int m) {
-  u32 lo = __shfl_xor((u32)v, m), hi = __shfl_xor((u32)(v >> 32), m);
-  return ((u64)hi << 32) | lo;
-}
-__device__ __forceinline__ u64 shfl_up64(u64 v, int d) {
-  u32 lo = __shfl_up((u32)v, d), hi = __shfl_up((u32)(v >> 32), d);
-  return ((u64)hi << 32) | lo;
-}
 // Match-any on an 8-bit digit: the lanes of the wave (among `valid`) whose digit equals this lane's, as two 32-bit halves, and from
 // them the lane's rank among its peers and the peers' count.  Written for the instructions it should become — per bit one
 // v_bfe_i32 (0 or ~0), one v_cmp (the ballot), two v_xnor with the ballot's halves as scalar operands, two v_and: six VALU —

@@ -155,7 +155,7 @@ def test_kernels_are_in_the_code_object_without_scratch():
     from ibu_amd import _lib
     ks = kernel_resources.all_kernels(_lib.SO_PATH)
     for k in ("ibu_k_cells_emit", "ibu_k_cells_table", "ibu_k_select_hist", "ibu_k_select_narrow", "ibu_k_cells_verdict",
-              "ibu::ibu_k_cells_fill<true>", "ibu::ibu_k_cells_fill<false>"):
+              "ibu::ibu_k_class_fill<true>", "ibu::ibu_k_class_fill<false>"):
         assert k in ks, k
         assert ks[k].get("private_segment_fixed_size", 0) == 0 and not ks[k].get("uses_dynamic_stack", 0), (k, ks[k])
 

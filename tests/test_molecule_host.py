@@ -124,8 +124,10 @@ def test_entry_point_exists_in_every_layer():
 def test_kernels_are_in_the_code_object():
     from ibu_amd import _lib
     out = subprocess.run(["strings", "-a", _lib.SO_PATH], capture_output=True, text=True).stdout
-    for k in ("ibu_k_molecules_emit", "ibu_k_molecules_verdict", "ibu_k_molecules_chains", "ibu_k_molecules_fix", "ibu_k_molecules_fill"):
+    for k in ("ibu_k_molecules_emit", "ibu_k_molecules_verdict", "ibu_k_molecules_chains", "ibu_k_molecules_fix", "ibu_k_class_fill"):
         assert k in out, k
+    for k in ("ibu_k_molecules_fill", "ibu_k_cells_fill"):   # one class fill (k_aggregate.hip) serves both
+        assert k not in out, k
 
 
 def test_classify_molecules_fails_loudly_without_gpu():
