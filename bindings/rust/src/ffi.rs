@@ -68,6 +68,30 @@ pub struct ibu_cell_counts_t {
 }
 #[repr(C)]
 #[derive(Default, Debug, Clone, Copy, PartialEq, Eq)]
+pub struct ibu_barcode_limits_t {
+    pub min_reads: u64,
+    pub max_reads: u64,
+    pub min_pairs: u64,
+    pub max_pairs: u64,
+    pub min_triples: u64,
+    pub max_triples: u64,
+    pub set_num: u64,
+    pub set_den: u64,
+    pub set_of: u32,
+    pub reserved: u32,
+}
+#[repr(C)]
+#[derive(Default, Debug, Clone, Copy, PartialEq, Eq)]
+pub struct ibu_barcode_filter_counts_t {
+    pub barcodes: u64,
+    pub barcodes_by_class: [u64; 4],
+    pub reads_by_class: [u64; 4],
+    pub triples_passed: u64,
+    pub set_triples_passed: u64,
+    pub reserved: u64,
+}
+#[repr(C)]
+#[derive(Default, Debug, Clone, Copy, PartialEq, Eq)]
 pub struct ibu_saturation_point_t {
     pub threshold: u64,
     pub reads: u64,
@@ -254,6 +278,12 @@ extern "C" {
                                   counts: *mut ibu_molecule_counts_t, stream: *mut c_void) -> i32;
     pub fn ibu_call_cells(ctx: *mut ibu_ctx_t, d_sorted_records: *const c_void, n: usize, mode: u32, param: u64, flags: u32, d_class: *mut u8,
                           counts: *mut ibu_cell_counts_t, stream: *mut c_void) -> i32;
+    pub fn ibu_barcode_metrics(ctx: *mut ibu_ctx_t, d_records: *const c_void, n: usize, d_set: *const u64, set_bits: u64, set_word: u32,
+                               d_barcodes: *mut u64, d_reads: *mut u64, d_pairs: *mut u64, d_triples: *mut u64, d_set_reads: *mut u64,
+                               d_set_triples: *mut u64, cap: usize, n_barcodes: *mut usize, stream: *mut c_void) -> i32;
+    pub fn ibu_filter_barcodes(ctx: *mut ibu_ctx_t, d_records: *const c_void, n: usize, d_set: *const u64, set_bits: u64, set_word: u32,
+                               limits: *const ibu_barcode_limits_t, d_class: *mut u8, counts: *mut ibu_barcode_filter_counts_t,
+                               stream: *mut c_void) -> i32;
     pub fn ibu_subsample_class(ctx: *mut ibu_ctx_t, n: usize, first_row: u64, seed: u64, threshold: u64, d_class: *mut u8, n_kept: *mut usize,
                                stream: *mut c_void) -> i32;
     pub fn ibu_saturation_curve(ctx: *mut ibu_ctx_t, d_sorted_records: *const c_void, n: usize, first_row: u64, seed: u64, thresholds: *const u64,

@@ -691,6 +691,39 @@ pub mod device {
             check(unsafe { ffi::ibu_call_cells(self.raw, sorted.ptr, n, mode, param, if by_reads { 1 } else { 0 }, cls, &mut c, std::ptr::null_mut()) })?;
             Ok(c)
         }
+        /// `ibu_barcode_metrics`: one (barcode, reads, pairs, triples, set reads, set triples) per maximal run of records with
+        /// equal first word, in input order — its records, the (w0, w1) pairs and (w0, w1, w2) triples that begin in it, and its
+        /// records / triples whose word `set_word` (1 or 2) is in the feature set: `set` = a device bitmap and its number of bits
+        /// (`None`: the empty set).  On swapped-and-sorted records with `set_word = 1`: pairs are features detected, triples UMIs.
+        pub fn barcode_metrics(&self, recs: &DeviceBuf, n: usize, set: Option<(&DeviceBuf, u64)>, set_word: u32) -> Result<Vec<[u64; 6]>> {
+            let (bits, nbits) = set.map_or((std::ptr::null(), 0u64), |(b, k)| (b.ptr as *const u64, k));
+            let mut nb = 0usize;
+            check(unsafe {
+                ffi::ibu_barcode_metrics(self.raw, recs.ptr, n, bits, nbits, set_word, std::ptr::null_mut(), std::ptr::null_mut(), std::ptr::null_mut(),
+                                         std::ptr::null_mut(), std::ptr::null_mut(), std::ptr::null_mut(), 0, &mut nb, std::ptr::null_mut())
+            })?;
+            if nb == 0 {
+                return Ok(Vec::new());
+            }
+            let (a, b, c, d, e, f) = (self.alloc(8 * nb)?, self.alloc(8 * nb)?, self.alloc(8 * nb)?, self.alloc(8 * nb)?, self.alloc(8 * nb)?, self.alloc(8 * nb)?);
+            check(unsafe {
+                ffi::ibu_barcode_metrics(self.raw, recs.ptr, n, bits, nbits, set_word, a.ptr as *mut u64, b.ptr as *mut u64, c.ptr as *mut u64,
+                                         d.ptr as *mut u64, e.ptr as *mut u64, f.ptr as *mut u64, nb, &mut nb, std::ptr::null_mut())
+            })?;
+            let host = self.download_columns(&[&a, &b, &c, &d, &e, &f], nb)?;
+            Ok((0..nb).map(|k| [host[k], host[nb + k], host[2 * nb + k], host[3 * nb + k], host[4 * nb + k], host[5 * nb + k]]).collect())
+        }
+        /// `ibu_filter_barcodes`: one class byte per record into `class` (n bytes; `None`: totals only), the class of its barcode —
+        /// 0 pass, 1 a count below its minimum, 2 a count above its non-zero maximum, 3 the share of the feature set above
+        /// `set_num / set_den`.  A default `limits` passes everything.  `select_records(.., 1 << 0, ..)` then keeps the passing barcodes.
+        pub fn filter_barcodes(&self, recs: &DeviceBuf, n: usize, set: Option<(&DeviceBuf, u64)>, set_word: u32, limits: &ffi::ibu_barcode_limits_t,
+                               class: Option<&DeviceBuf>) -> Result<ffi::ibu_barcode_filter_counts_t> {
+            let (bits, nbits) = set.map_or((std::ptr::null(), 0u64), |(b, k)| (b.ptr as *const u64, k));
+            let mut c = ffi::ibu_barcode_filter_counts_t::default();
+            let cls = class.map_or(std::ptr::null_mut(), |b| b.ptr as *mut u8);
+            check(unsafe { ffi::ibu_filter_barcodes(self.raw, recs.ptr, n, bits, nbits, set_word, limits, cls, &mut c, std::ptr::null_mut()) })?;
+            Ok(c)
+        }
         /// `ibu_subsample_class`: a reproducible random subset of `n` rows — one class byte per row into `class` (n bytes; `None`:
         /// the count only), 0 where the row's number `splitmix64(splitmix64(seed) + first_row + row)` is below `threshold` (all
         /// ones keeps every row), 1 elsewhere.  No record is read, so the subset depends on the order of the records it is applied

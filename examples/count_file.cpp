@@ -22,6 +22,14 @@
 // (ibu_saturation_curve, one read of the records), K evenly spaced depths 1/K .. 1, in front of the matrix as
 //   #saturation<TAB>fraction<TAB>reads<TAB>barcodes<TAB>molecules<TAB>saturation
 // with saturation = 1 - molecules / reads.
+//   count_file ... [--qc=minfeat:A[,maxfeat:B][,minumi:C][,maxset:NUM/DEN]] [--set=FILE] IN [WHITELIST.txt]
+// --qc: the matrix of the barcodes that pass the per-barcode QC filter — behind the steps above the fields are exchanged and the
+// records sorted ONCE by (barcode, index, umi), ibu_filter_barcodes classes every barcode by its features detected (minfeat, maxfeat:
+// too few, implausibly many), its UMIs (minumi) and the share of its UMIs whose index is in the set (maxset: above NUM/DEN),
+// ibu_select_records keeps the class IBU_BARCODE_PASS, and the matrix and its row lengths are counted from the kept records as they
+// stand (ibu_pair_counts, ibu_barcode_counts): no second sort.  The four class totals go to stderr.
+// --set=FILE (with --qc): the feature set, one index value per line (mitochondrial genes, spike-ins).
+#include <cerrno>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -75,9 +83,67 @@ static bool parse_subsample(const char* s, double* fraction, uint64_t* seed) {
   return *end == 0;
 }
 
+// "minfeat:A[,maxfeat:B][,minumi:C][,maxset:NUM/DEN]" -> the limits of ibu_filter_barcodes on {barcode, index, umi} records (pairs are
+// features, triples UMIs); every key at most once, minfeat among them; false otherwise
+static bool parse_qc(const char* s, ibu_barcode_limits_t* lim) {
+  *lim = ibu_barcode_limits_t{};
+  unsigned seen = 0;
+  for (;;) {
+    static const char* const keys[] = {"minfeat:", "maxfeat:", "minumi:", "maxset:"};
+    unsigned k = 0;
+    while (k < 4 && std::strncmp(s, keys[k], std::strlen(keys[k]))) ++k;
+    if (k == 4 || (seen >> k & 1)) return false;
+    seen |= 1u << k;
+    s += std::strlen(keys[k]);
+    char* end = nullptr;
+    if (*s < '0' || *s > '9') return false;
+    errno = 0;
+    const uint64_t v = std::strtoull(s, &end, 10);
+    if (errno == ERANGE) return false;                         // more than 64 bits
+    if (k == 0) lim->min_pairs = v;
+    if (k == 1) lim->max_pairs = v;
+    if (k == 2) lim->min_triples = v;
+    if (k == 3) {
+      if (*end != '/' || end[1] < '0' || end[1] > '9') return false;
+      lim->set_num = v;
+      lim->set_den = std::strtoull(end + 1, &end, 10);
+      lim->set_of = 1;                                          // the share of UMIs
+      if (errno == ERANGE || lim->set_den == 0 || lim->set_den >= (1ull << 24) || lim->set_num > lim->set_den) return false;
+    }
+    if (*end == 0) return (seen & 1u) != 0;
+    if (*end != ',') return false;
+    s = end + 1;
+  }
+}
+
+// one index value per line -> the bitmap of ibu_filter_barcodes and its number of bits (the largest value + 1)
+static std::vector<uint64_t> read_set(const char* path, uint64_t* bits) {
+  std::ifstream f(path);
+  if (!f) throw std::runtime_error(std::string("cannot open ") + path);
+  std::vector<uint64_t> values;
+  std::string line;
+  *bits = 0;
+  while (std::getline(f, line)) {
+    while (!line.empty() && (line.back() == '\r' || line.back() == ' ' || line.back() == '\t')) line.pop_back();
+    if (line.empty()) continue;
+    char* end = nullptr;
+    errno = 0;
+    const uint64_t v = std::strtoull(line.c_str(), &end, 10);
+    if (line[0] < '0' || line[0] > '9' || *end != 0) throw std::runtime_error("the set file has a line that is not an index value: " + line);
+    if (errno == ERANGE || v >= (1ull << 32)) throw std::runtime_error("the set file has an index value of 2^32 or more: " + line);
+    values.push_back(v);
+    if (v + 1 > *bits) *bits = v + 1;
+  }
+  std::vector<uint64_t> words((*bits + 63) / 64 + 1, 0);
+  for (uint64_t v : values) words[v >> 6] |= 1ull << (v & 63);
+  return words;
+}
+
 int main(int argc, char** argv) {
   int resolve = 0;                                              // 1: --resolve, 2: --resolve=first
-  bool cells = false, bad = false, subsample = false;
+  bool cells = false, bad = false, subsample = false, qc = false;
+  ibu_barcode_limits_t qc_limits{};
+  const char* set_path = nullptr;
   uint32_t cells_mode = 0, saturation = 0;
   uint64_t cells_param = 0, sample_seed = 0;
   double sample_fraction = 1;
@@ -87,11 +153,14 @@ int main(int argc, char** argv) {
     else if (!std::strncmp(argv[1], "--cells=", 8) && parse_cells(argv[1] + 8, &cells_mode, &cells_param)) cells = true;
     else if (!std::strncmp(argv[1], "--subsample=", 12) && parse_subsample(argv[1] + 12, &sample_fraction, &sample_seed)) subsample = true;
     else if (!std::strncmp(argv[1], "--saturation=", 13) && parse_saturation(argv[1] + 13, &saturation)) {}
+    else if (!std::strncmp(argv[1], "--qc=", 5) && parse_qc(argv[1] + 5, &qc_limits)) qc = true;
+    else if (!std::strncmp(argv[1], "--set=", 6) && argv[1][6]) set_path = argv[1] + 6;
     else bad = true;
   }
-  if (argc < 2 || bad) {
+  if (argc < 2 || bad || (set_path && !qc)) {
     std::fprintf(stderr, "usage: count_file [--resolve | --resolve=first] [--cells=min:T|top:K|expected:E] [--subsample=F[:seed]] [--saturation=K] "
-                 "IN [WHITELIST.txt]\n");
+                 "IN [WHITELIST.txt]\n"
+                 "       further options: [--qc=minfeat:A[,maxfeat:B][,minumi:C][,maxset:NUM/DEN]] [--set=FILE] (FILE: one index value per line)\n");
     return 2;
   }
   try {
@@ -179,7 +248,29 @@ int main(int argc, char** argv) {
       }
     }
     // the matrix; the records stay {barcode, index, umi} so that the row lengths can be read off them
-    const auto entries = ctx.count_matrix(recs, scratch, kept, 0, /*leave_swapped=*/true);
+    std::vector<device::MatrixEntry> entries;
+    if (qc) {                                                   // exchange, sort once, class every barcode, keep the passing ones, count them as they stand
+      uint64_t set_bits = 0;
+      std::vector<uint64_t> words(1, 0);
+      if (set_path) words = read_set(set_path, &set_bits);
+      device::DeviceBuffer d_set(ctx, 8 * words.size()), d_class(ctx, kept ? kept : 1);
+      d_set.upload(words);
+      ctx.swap_umi_index(recs, recs, kept);
+      if (kept) ctx.sort_records(recs, scratch, kept);
+      const size_t before = kept;
+      const device::BarcodeFilterCounts c =
+          ctx.filter_barcodes(recs, before, {set_bits ? d_set.as<uint64_t>() : nullptr, set_bits}, 1, qc_limits, d_class.as<uint8_t>());
+      if (before) kept = ctx.select_records(recs, d_class.as<uint8_t>(), before, 1u << IBU_BARCODE_PASS, scratch, before);
+      ctx.synchronize();
+      std::fprintf(stderr, "%zu records: barcodes %llu: pass %llu, low %llu, high %llu, set %llu; reads pass %llu, low %llu, high %llu, set %llu\n", before,
+                   (unsigned long long)c.barcodes, (unsigned long long)c.barcodes_by_class[0], (unsigned long long)c.barcodes_by_class[1],
+                   (unsigned long long)c.barcodes_by_class[2], (unsigned long long)c.barcodes_by_class[3], (unsigned long long)c.reads_by_class[0],
+                   (unsigned long long)c.reads_by_class[1], (unsigned long long)c.reads_by_class[2], (unsigned long long)c.reads_by_class[3]);
+      std::swap(recs, scratch);
+      entries = ctx.pair_counts(recs, kept);
+    } else {
+      entries = ctx.count_matrix(recs, scratch, kept, 0, /*leave_swapped=*/true);
+    }
     for (const device::MatrixEntry& e : entries)
       std::printf("%s\t%llu\t%llu\t%llu\n", decode(e.first, h.bc_len).c_str(), (unsigned long long)e.second, (unsigned long long)e.distinct,
                   (unsigned long long)e.records);

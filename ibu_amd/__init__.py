@@ -5,6 +5,11 @@ Header, Record, HEADER_SIZE, MAGIC, RECORD_SIZE, VERSION, IbuError, load_to_vec,
 Reader, Writer, ParallelProcessor, ParallelReader) over the C ABI of include/ibu_hip.h, plus
 the device context that exposes the HIP kernels.  All work happens in libibu_hip.so; this
 package binds it and nothing else (no numpy/torch arithmetic stands in for a kernel).
+
+The device pipeline of a single-cell run, every step on resident records: load -> Context.correct_barcodes -> select_records ->
+sort_records -> classify_molecules -> select_records -> call_cells -> select_records -> count_matrix(leave_swapped=True) ->
+filter_barcodes (the per-barcode QC filter: too few or too many features / UMIs, too large a share of a feature set built with
+Context.feature_bitmap; barcode_metrics returns the table itself) -> select_records -> pair_counts.
 """
 import copy
 import ctypes as C
@@ -14,7 +19,7 @@ from collections import namedtuple
 import numpy as np
 
 from . import _lib
-from ._lib import CAllocProbe, CCellCounts, CCorrectCounts, CDecodeSink, CMoleculeCounts, CErrorDetail, CKeyPlan, CHeader, CNumaInfo, CProcessorVTable, CRecord, CReduceResult, CRingConfig, CSaturationPoint, CStreamStats
+from ._lib import CAllocProbe, CBarcodeFilterCounts, CBarcodeLimits, CCellCounts, CCorrectCounts, CDecodeSink, CMoleculeCounts, CErrorDetail, CKeyPlan, CHeader, CNumaInfo, CProcessorVTable, CRecord, CReduceResult, CRingConfig, CSaturationPoint, CStreamStats
 
 lib = _lib.load()
 
@@ -33,6 +38,11 @@ MOLECULES_TIE_FIRST = 1  # ibu_classify_molecules flags (IBU_MOLECULES_TIE_FIRST
 CELL, CELL_BACKGROUND = 0, 1  # the classes of ibu_call_cells (IBU_CELL, IBU_CELL_BACKGROUND)
 CELLS_MIN, CELLS_TOP, CELLS_ORDMAG = 0, 1, 2  # its modes (IBU_CELLS_*)
 CELLS_BY_READS = 1  # its flag (IBU_CELLS_BY_READS)
+BARCODE_PASS, BARCODE_LOW, BARCODE_HIGH, BARCODE_SET = 0, 1, 2, 3  # the classes of ibu_filter_barcodes (IBU_BARCODE_*)
+#: the table of ibu_barcode_metrics: one numpy u64 column each, a row per barcode in input order
+BarcodeMetrics = namedtuple("BarcodeMetrics", "barcodes reads pairs triples set_reads set_triples")
+#: the totals of one ibu_filter_barcodes call (ibu_barcode_filter_counts_t without its reserved word); the by_class fields are 4-tuples
+BarcodeFilterCounts = namedtuple("BarcodeFilterCounts", "barcodes barcodes_by_class reads_by_class triples_passed set_triples_passed")
 SAMPLE_KEPT, SAMPLE_DROPPED = 0, 1  # the classes of ibu_subsample_class (IBU_SAMPLE_KEPT, IBU_SAMPLE_DROPPED)
 SATURATION_MAX_POINTS = 32
 #: one point of ibu_saturation_curve (ibu_saturation_point_t)
@@ -818,6 +828,28 @@ def _one_threshold(fraction, threshold):
     return sample_threshold(fraction) if threshold is None else _u64_arg("threshold", threshold)
 
 
+def feature_bitmap_words(values, n_bits):
+    """The bitmap ibu_barcode_metrics / ibu_filter_barcodes read as a feature set, as numpy u64 words: bit v & 63 of word v >> 6
+    is set for every v in `values` (integers in [0, n_bits)); (n_bits + 63) // 64 words, at least one."""
+    n_bits = int(n_bits)
+    if not 0 <= n_bits <= 1 << 32:
+        raise ValueError("n_bits must be in 0 .. 2^32")
+    v = np.asarray(values, dtype=np.uint64).ravel()
+    if len(v) and int(v.max()) >= n_bits:
+        raise ValueError("a value is not below n_bits")
+    words = np.zeros(max((n_bits + 63) // 64, 1), np.uint64)
+    np.bitwise_or.at(words, (v >> np.uint64(6)).astype(np.int64), np.uint64(1) << (v & np.uint64(63)))
+    return words
+
+
+def _feature_set(feature_set):
+    """None | (device bitmap, n_bits) -> (c_void_p | None, n_bits)."""
+    if feature_set is None:
+        return None, 0
+    d_set, bits = feature_set
+    return _dptr(d_set), _u64_arg("n_bits", bits)
+
+
 class Context:
     """ibu_ctx_t: one per host thread and GPU.  Every method launches asynchronously on
     `stream` (default: the context's own stream) unless it says it synchronises."""
@@ -1022,6 +1054,62 @@ class Context:
         _check(lib.ibu_call_cells(self._c, _dptr(d_sorted_records), n, mode, param, CELLS_BY_READS if by_reads else 0, _dptr(d_class),
                                   C.byref(c) if counts else None, stream))
         return d_class, (CellCounts(*[int(getattr(c, f)) for f in CellCounts._fields]) if counts else None)
+
+    # per-barcode QC metrics and the barcode filter
+    def feature_bitmap(self, values, n_bits):
+        """A feature set for barcode_metrics / filter_barcodes: the bitmap of n_bits bits (at most 2^32) with the bits `values`
+        set (integers in [0, n_bits); bit v is bit v & 63 of u64 word v >> 6), built in numpy and uploaded -> (DeviceBuffer, n_bits)."""
+        return self.upload(feature_bitmap_words(values, n_bits)), int(n_bits)
+
+    def barcode_metrics(self, d_records, n, feature_set=None, set_word=1, stream=None):
+        """ibu_barcode_metrics over n device records: one row per barcode (maximal run of equal first word), in input order ->
+        BarcodeMetrics(barcodes, reads, pairs, triples, set_reads, set_triples) as numpy u64 columns: the barcode, its records,
+        the runs of equal (w0, w1) and of equal (w0, w1, w2) that begin in it, and its records / triples whose word set_word (1 or
+        2) is in feature_set (what feature_bitmap returned; None: nothing is).  On records that went through swap_umi_index and
+        sort_records (what count_matrix(leave_swapped=True) leaves), with set_word=1: pairs are the features detected, triples
+        the UMIs, set_triples the UMIs in the set.  On ordinarily sorted records, with set_word=2: pairs = triples = UMIs."""
+        d_set, bits = _feature_set(feature_set)
+        nb = C.c_size_t()
+        _check(lib.ibu_barcode_metrics(self._c, _dptr(d_records), n, d_set, bits, set_word, None, None, None, None, None, None, 0,
+                                       C.byref(nb), stream))
+        u = nb.value
+        if u == 0:
+            return BarcodeMetrics(*[np.empty(0, np.uint64) for _ in range(6)])
+        outs = [self.alloc(max(8 * u, 16)) for _ in range(6)]
+        _check(lib.ibu_barcode_metrics(self._c, _dptr(d_records), n, d_set, bits, set_word, *[_dptr(o) for o in outs], u, C.byref(nb), stream))
+        self.synchronize(stream)
+        return BarcodeMetrics(*[o.download(np.uint64, count=u) for o in outs])
+
+    def filter_barcodes(self, d_records, n, feature_set=None, set_word=1, *, min_reads=0, max_reads=0, min_pairs=0, max_pairs=0,
+                        min_triples=0, max_triples=0, max_set_fraction=None, set_of="reads", d_class=None, counts=True, stream=None):
+        """ibu_filter_barcodes over n device records: one class byte per record, the class of its barcode — BARCODE_LOW where its
+        reads, pairs or triples (as barcode_metrics counts them) are below their minimum, else BARCODE_HIGH where one is above its
+        maximum (0: no maximum), else BARCODE_SET where its share in feature_set is above max_set_fraction = (num, den) —
+        set_x * den > num * x in integers, x the reads or (set_of="triples") the triples; equality passes — else BARCODE_PASS.
+        -> (d_class, BarcodeFilterCounts).  d_class: n bytes of device memory; None allocates them, False asks for the totals only
+        (and returns None in its place).  counts=False returns None for the totals and does not wait for them.
+        select_records(d_records, d_class, n, keep_mask=1 << BARCODE_PASS) then keeps the passing barcodes."""
+        if set_of not in ("reads", "triples"):
+            raise ValueError('set_of must be "reads" or "triples"')
+        num, den = (0, 0) if max_set_fraction is None else max_set_fraction
+        for name, v in (("min_reads", min_reads), ("max_reads", max_reads), ("min_pairs", min_pairs), ("max_pairs", max_pairs),
+                        ("min_triples", min_triples), ("max_triples", max_triples), ("max_set_fraction", num), ("max_set_fraction", den)):
+            _u64_arg(name, v)
+        if max_set_fraction is not None and not (0 < den < 1 << 24 and num <= den):
+            raise ValueError("max_set_fraction = (num, den) wants num <= den and 0 < den < 2^24")
+        d_set, bits = _feature_set(feature_set)
+        lim = CBarcodeLimits(min_reads, max_reads, min_pairs, max_pairs, min_triples, max_triples, num, den, 1 if set_of == "triples" else 0, 0)
+        if d_class is None:
+            d_class = self.alloc(max(n, 16))
+        elif d_class is False:
+            d_class = None
+        c = CBarcodeFilterCounts() if counts else None
+        _check(lib.ibu_filter_barcodes(self._c, _dptr(d_records), n, d_set, bits, set_word, C.byref(lim), _dptr(d_class),
+                                       C.byref(c) if counts else None, stream))
+        if not counts:
+            return d_class, None
+        return d_class, BarcodeFilterCounts(int(c.barcodes), tuple(int(x) for x in c.barcodes_by_class), tuple(int(x) for x in c.reads_by_class),
+                                            int(c.triples_passed), int(c.set_triples_passed))
 
     # read subsampling and the saturation curve
     def subsample_class(self, n, d_class=None, *, fraction=None, threshold=None, seed=0, first_row=0, count=True, stream=None):

@@ -44,6 +44,16 @@ class CCellCounts(C.Structure):  # ibu_cell_counts_t
                 ("umis_cells", u64), ("umis_background", u64)]
 
 
+class CBarcodeLimits(C.Structure):  # ibu_barcode_limits_t
+    _fields_ = [("min_reads", u64), ("max_reads", u64), ("min_pairs", u64), ("max_pairs", u64), ("min_triples", u64), ("max_triples", u64),
+                ("set_num", u64), ("set_den", u64), ("set_of", u32), ("reserved", u32)]
+
+
+class CBarcodeFilterCounts(C.Structure):  # ibu_barcode_filter_counts_t
+    _fields_ = [("barcodes", u64), ("barcodes_by_class", u64 * 4), ("reads_by_class", u64 * 4), ("triples_passed", u64),
+                ("set_triples_passed", u64), ("reserved", u64)]
+
+
 class CSaturationPoint(C.Structure):  # ibu_saturation_point_t
     _fields_ = [("threshold", u64), ("reads", u64), ("barcodes", u64), ("molecules", u64)]
 
@@ -169,6 +179,8 @@ SIGNATURES = {
     "ibu_classify_molecules": (i32, [vp, vp, sz, u32, vp, P(CMoleculeCounts), vp]),
     "ibu_call_cells": (i32, [vp, vp, sz, u32, u64, u32, vp, P(CCellCounts), vp]),
     "ibu_subsample_class": (i32, [vp, sz, u64, u64, u64, vp, P(sz), vp]),
+    "ibu_barcode_metrics": (i32, [vp, vp, sz, vp, u64, u32, vp, vp, vp, vp, vp, vp, sz, P(sz), vp]),
+    "ibu_filter_barcodes": (i32, [vp, vp, sz, vp, u64, u32, P(CBarcodeLimits), vp, P(CBarcodeFilterCounts), vp]),
     "ibu_saturation_curve": (i32, [vp, vp, sz, u64, u64, P(u64), u32, P(CSaturationPoint), vp]),
     "ibu_correct_barcodes": (i32, [vp, vp, vp, sz, u32, vp, P(CCorrectCounts), vp]),
     "ibu_select_records": (i32, [vp, vp, vp, sz, u32, vp, sz, P(sz), vp]),

@@ -986,6 +986,90 @@ extern "C" int32_t ibu_call_cells(ibu_ctx_t* ctx, const void* d_sorted_records, 
   counts->baseline = ctx->h_pinned[6];
   return IBU_OK;
 }
+// ---- per-barcode QC metrics and the barcode filter (k_metrics.hip).  The semantics are this library's: include/ibu_hip.h.
+static_assert(sizeof(ibu_barcode_limits_t) == sizeof(MetricsLimits) && offsetof(ibu_barcode_limits_t, set_of) == offsetof(MetricsLimits, set_of) &&
+                  offsetof(ibu_barcode_limits_t, set_num) == offsetof(MetricsLimits, set_num) && sizeof(ibu_barcode_filter_counts_t) == 96,
+              "ibu_hip.h and kernels.h disagree");
+static int32_t check_feature_set(const uint64_t* d_set, uint64_t set_bits, uint32_t set_word) {
+  if (!metrics_set_ok(d_set, set_bits, set_word))
+    return err_arg("the feature set: set_word must be 1 or 2, set_bits at most 2^32, d_set 8-byte aligned and non-NULL unless set_bits is 0");
+  return IBU_OK;
+}
+// The first half of both: the count pass and its five totals read back into ctx->h_pinned[0..4].  Synchronises the stream.
+static int32_t metrics_count_totals(ibu_ctx* ctx, const void* d_records, size_t n, const uint64_t* d_set, uint64_t set_bits, uint32_t set_word,
+                                    hipStream_t st) {
+  int32_t rc = ensure_sort_scratch(ctx, metrics_scratch_bytes(n));
+  if (rc) return rc;
+  IBU_HIP(launch_metrics_count(ctx->cfg, d_records, n, d_set, set_bits, set_word, ctx->d_sort_scratch, ctx->sort_scratch_bytes, st));
+  IBU_HIP(hipMemcpyAsync(ctx->h_pinned, ctx->d_sort_scratch, 5 * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
+  IBU_HIP(hipStreamSynchronize(st));
+  return IBU_OK;
+}
+extern "C" int32_t ibu_barcode_metrics(ibu_ctx_t* ctx, const void* d_records, size_t n, const uint64_t* d_set, uint64_t set_bits,
+                                       uint32_t set_word, uint64_t* d_barcodes, uint64_t* d_reads, uint64_t* d_pairs, uint64_t* d_triples,
+                                       uint64_t* d_set_reads, uint64_t* d_set_triples, size_t cap, size_t* n_barcodes, void* stream) {
+  int32_t rc = check_ctx(ctx);
+  if (rc) return rc;
+  if (!n_barcodes) return err_arg("n_barcodes is NULL");
+  rc = check_feature_set(d_set, set_bits, set_word);
+  if (rc) return rc;
+  if (n >= (1ull << 40)) return err_arg("barcode_metrics handles fewer than 2^40 records per call");
+  if (n && (!d_records || !aligned8(d_records))) return err_arg("d_records must be non-NULL and 8-byte aligned");
+  if (n && (!aligned8(d_barcodes) || !aligned8(d_reads) || !aligned8(d_pairs) || !aligned8(d_triples) || !aligned8(d_set_reads) ||
+            !aligned8(d_set_triples)))
+    return err_arg("the output arrays must be 8-byte aligned");
+  *n_barcodes = 0;
+  if (n == 0) return IBU_OK;
+  hipStream_t st = pick_stream(ctx, stream);
+  rc = metrics_count_totals(ctx, d_records, n, d_set, set_bits, set_word, st);
+  if (rc) return rc;
+  const uint64_t barcodes = ctx->h_pinned[0];
+  *n_barcodes = barcodes;
+  const bool any_column = d_barcodes || d_reads || d_pairs || d_triples || d_set_reads || d_set_triples;
+  if (!any_column) return IBU_OK;   // the size query (cap == 0), or a cap and nothing to write
+  if (barcodes > cap)
+    return set_error(IBU_ERR_INVALID_ARG, barcodes, cap, 0, "Invalid argument: output capacity %llu is smaller than the %llu barcodes (see *n_barcodes)",
+                     (unsigned long long)cap, (unsigned long long)barcodes);
+  rc = ensure_runs_scratch(ctx, metrics_run_scratch_bytes(barcodes));
+  if (rc) return rc;
+  IBU_HIP(launch_metrics_table(ctx->cfg, d_records, n, d_set, set_bits, set_word, ctx->d_sort_scratch, ctx->d_runs_scratch, barcodes, d_barcodes,
+                               d_reads, d_pairs, d_triples, d_set_reads, d_set_triples, st));
+  return IBU_OK;
+}
+extern "C" int32_t ibu_filter_barcodes(ibu_ctx_t* ctx, const void* d_records, size_t n, const uint64_t* d_set, uint64_t set_bits,
+                                       uint32_t set_word, const ibu_barcode_limits_t* limits, uint8_t* d_class,
+                                       ibu_barcode_filter_counts_t* counts, void* stream) {
+  int32_t rc = check_ctx(ctx);
+  if (rc) return rc;
+  rc = check_feature_set(d_set, set_bits, set_word);
+  if (rc) return rc;
+  if (!limits) return err_arg("limits is NULL");
+  const MetricsLimits lim{limits->min_reads, limits->max_reads, limits->min_pairs, limits->max_pairs, limits->min_triples, limits->max_triples,
+                          limits->set_num, limits->set_den, limits->set_of, 0};
+  if (!metrics_limits_ok(lim)) return err_arg("limits: set_of must be 0 (reads) or 1 (triples), and set_num <= set_den < 2^24");
+  if (n && (!d_records || !aligned8(d_records))) return err_arg("d_records must be non-NULL and 8-byte aligned");
+  if (n >= (1ull << 40)) return err_arg("filter_barcodes handles fewer than 2^40 records per call");
+  if (counts) *counts = ibu_barcode_filter_counts_t{};   // (behind the last argument check: a refused call leaves the totals alone)
+  if (n == 0) return IBU_OK;
+  hipStream_t st = pick_stream(ctx, stream);
+  rc = metrics_count_totals(ctx, d_records, n, d_set, set_bits, set_word, st);
+  if (rc) return rc;
+  const uint64_t barcodes = ctx->h_pinned[0];
+  rc = ensure_runs_scratch(ctx, metrics_run_scratch_bytes(barcodes));
+  if (rc) return rc;
+  IBU_HIP(launch_metrics_filter(ctx->cfg, d_records, n, d_set, set_bits, set_word, ctx->d_sort_scratch, ctx->d_runs_scratch, barcodes, lim, d_class, st));
+  if (!counts) return IBU_OK;
+  IBU_HIP(hipMemcpyAsync(ctx->h_pinned, ctx->d_runs_scratch, 10 * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
+  IBU_HIP(hipStreamSynchronize(st));
+  counts->barcodes = barcodes;
+  for (int c = 0; c < 4; ++c) {
+    counts->barcodes_by_class[c] = ctx->h_pinned[c];
+    counts->reads_by_class[c] = ctx->h_pinned[4 + c];
+  }
+  counts->triples_passed = ctx->h_pinned[8];
+  counts->set_triples_passed = ctx->h_pinned[9];
+  return IBU_OK;
+}
 // ---- read subsampling and the saturation curve (k_saturation.hip).  The semantics are this library's: include/ibu_hip.h.
 extern "C" int32_t ibu_subsample_class(ibu_ctx_t* ctx, size_t n, uint64_t first_row, uint64_t seed, uint64_t threshold, uint8_t* d_class,
                                        size_t* n_kept, void* stream) {

@@ -183,6 +183,10 @@ ibu_k_class_fill(SegPlan sp, const u64* __restrict__ seg_row /*[nseg], scanned*/
   }
 }
 
+void launch_runs_scan(const u32* seg_heads, u32 nseg, u32 rows, u64* seg_base, u64* totals, hipStream_t st) {
+  hipLaunchKernelGGL(ibu_k_runs_scan, dim3(rows), dim3(kSortThreads), 0, st, seg_heads, nseg, seg_base, totals);
+}
+
 size_t runs_scratch_bytes(size_t n) { return runs_layout(n).runs_bytes; }
 size_t runs_emit_scratch_bytes(uint64_t n_runs) { return 16 * (size_t)(n_runs ? n_runs : 1); }
 
@@ -199,8 +203,7 @@ hipError_t launch_runs_count(const LaunchCfg& cfg, const void* recs, size_t n, v
                        scratch_at<RunStash>(scratch, L.stash));
   else
     hipLaunchKernelGGL(ibu_k_runs_count, seg_grid(sp), dim3(kSortThreads), 0, st, (const u64*)recs, sp, heads);
-  hipLaunchKernelGGL(ibu_k_runs_scan, dim3(2), dim3(kSortThreads), 0, st, (const u32*)heads, sp.nseg, scratch_at<u64>(scratch, L.seg_base),
-                     scratch_at<u64>(scratch, L.totals));
+  launch_runs_scan(heads, sp.nseg, 2, scratch_at<u64>(scratch, L.seg_base), scratch_at<u64>(scratch, L.totals), st);
   return hipGetLastError();
 }
 hipError_t launch_runs_emit(const LaunchCfg& cfg, const void* recs, size_t n, const void* scratch, void* run_scratch, uint64_t n_runs,

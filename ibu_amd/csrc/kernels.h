@@ -156,6 +156,30 @@ hipError_t launch_cells_call(const LaunchCfg&, const void* recs, size_t n, void*
 // first u64 of `work` (rank_select_work_bytes() bytes, 8-byte aligned).
 size_t rank_select_work_bytes();
 hipError_t launch_rank_select(const LaunchCfg&, const uint64_t* values, uint64_t count, uint64_t rank, void* work, hipStream_t st);
+// per-barcode QC metrics and the barcode filter (ibu_barcode_metrics, ibu_filter_barcodes, k_metrics.hip).  The feature set: `set`
+// (nullable with set_bits == 0) = a device bitmap of set_bits <= 2^32 bits, 8-byte aligned; set_word = 1 or 2, the record word that is
+// looked up.  launch_metrics_count on a scratch of metrics_scratch_bytes(n) comes first and leaves u64[5] at its front — barcodes,
+// pairs, triples, records in the set, triples in the set; with the first the caller sizes the run scratch.  launch_metrics_table
+// writes the columns (each nullable), launch_metrics_filter one class byte per record into d_class (nullable) and u64[10] at the
+// front of run_scratch: barcodes per class [4], records per class [4], triples and set triples of class 0.
+struct MetricsLimits {   // = ibu_barcode_limits_t (ibu_hip.h)
+  uint64_t min_reads, max_reads, min_pairs, max_pairs, min_triples, max_triples, set_num, set_den;
+  uint32_t set_of, reserved;
+};
+// what the launchers (and the C ABI in front of them) accept: set_word 1 or 2, set_bits <= 2^32, a set that is 8-byte aligned and
+// non-NULL unless set_bits == 0; set_of 0 or 1 and set_num <= set_den < 2^24
+bool metrics_set_ok(const uint64_t* set, uint64_t set_bits, uint32_t set_word);
+bool metrics_limits_ok(const MetricsLimits& limits);
+size_t metrics_scratch_bytes(size_t n);
+size_t metrics_run_scratch_bytes(uint64_t barcodes);
+hipError_t launch_metrics_count(const LaunchCfg&, const void* recs, size_t n, const uint64_t* set, uint64_t set_bits, uint32_t set_word,
+                                void* scratch, size_t scratch_bytes, hipStream_t st);
+hipError_t launch_metrics_table(const LaunchCfg&, const void* recs, size_t n, const uint64_t* set, uint64_t set_bits, uint32_t set_word,
+                                const void* scratch, void* run_scratch, uint64_t barcodes, uint64_t* d_barcodes, uint64_t* d_reads,
+                                uint64_t* d_pairs, uint64_t* d_triples, uint64_t* d_set_reads, uint64_t* d_set_triples, hipStream_t st);
+hipError_t launch_metrics_filter(const LaunchCfg&, const void* recs, size_t n, const uint64_t* set, uint64_t set_bits, uint32_t set_word,
+                                 void* scratch, void* run_scratch, uint64_t barcodes, const MetricsLimits& limits, uint8_t* d_class,
+                                 hipStream_t st);
 // read subsampling and the saturation curve (ibu_subsample_class, ibu_saturation_curve, k_saturation.hip).  The number of a read is
 // splitmix64(base + row) with base = sample_base(seed, first_row); kept at a threshold: ibu_hip.h.
 uint64_t sample_base(uint64_t seed, uint64_t first_row);

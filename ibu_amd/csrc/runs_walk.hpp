@@ -2,7 +2,8 @@
 // per molecule) share: the cut of the rows into segments (SegPlan), the count scratch both address (RunsLayout), the walk itself
 // (runs_segment) with the sinks' interface (NoSink) and the sink that keeps the ballots for the class fill (BallotSink), the body of
 // every kernel that runs it (runs_kernel), and the totals of a workgroup (block_accumulate).  k_cells.hip (cell calling) and
-// k_saturation.hip (the saturation curve: a per-run minimum carried from tile to tile through NoSink::records) walk it too.
+// k_saturation.hip (the saturation curve: a per-run minimum carried from tile to tile through NoSink::records) walk it too, and
+// k_metrics.hip (per-barcode QC metrics: three levels of heads and a set test, through NoSink::words).
 #pragma once
 #include "kcommon.hpp"
 #include "kernels.h"
@@ -66,6 +67,8 @@ __device__ __forceinline__ void run_head(const Rec& prev, const Rec& cur, bool h
   h1 = !has_prev || cur.w0 != prev.w0 || (D == 2 && cur.w1 != prev.w1);
   h2 = h1 || (D == 1 ? cur.w1 != prev.w1 : cur.w2 != prev.w2);
 }
+// The level above the runs of a D = 2 walk: the record begins a BARCODE, its w0 differs from the record before it (D = 1: a run head).
+__device__ __forceinline__ bool barcode_head(const Rec& prev, const Rec& cur, bool has_prev) { return !has_prev || cur.w0 != prev.w0; }
 
 // What a walk hands to its SINK.  A sink derives from NoSink and replaces what it needs; NoSink itself only counts, and whatever
 // feeds a body left empty (the ranks, the row) is never computed.
@@ -86,6 +89,11 @@ struct NoSink {
   // comes with a row at or behind the segment's end and both flags false.  What a sink carries from step to step (a per-run
   // reduction: k_saturation.hip) lives in `mutable` members of the sink.
   __device__ __forceinline__ void records(u64 row, bool a1, bool a2, bool b1, bool b2, bool pair) const {}
+  // The same steps, in every lane, with the records' WORDS and a third level of heads (k_metrics.hip): a / b as in `records`, va: a
+  // is a record (false in a lane past the end of an untiled step, where a is all zero), a0 / b0: the record begins a barcode — its
+  // w0 differs from the record before it — and a1, a2, b1, b2 the flags `records` gets.  a0 implies a1 implies a2.
+  __device__ __forceinline__ void words(u64 row, const Rec& a, bool va, bool a0, bool a1, bool a2, const Rec& b, bool b0, bool b1, bool b2,
+                                        bool pair) const {}
 };
 
 // The sinks that keep a walk's ballots for the class fill (k_aggregate.hip) store them here, and the fill finds them here: masks
@@ -110,8 +118,10 @@ template <class S>
 struct RunRanks {
   const S& sink;
   u64 p1, p2, lt_mask, c1, c2, even, odd, run_even, run_odd;
-  __device__ __forceinline__ void step(u64 row, const Rec& a, bool a1, bool a2, const Rec& b, bool b1, bool b2, bool pair) {
+  __device__ __forceinline__ void step(u64 row, const Rec& a, bool va, bool a0, bool a1, bool a2, const Rec& b, bool b0, bool b1, bool b2,
+                                       bool pair) {
     sink.records(row, a1, a2, b1, b2, pair);
+    sink.words(row, a, va, a0, a1, a2, b, b0, b1, b2, pair);
     const u64 ma1 = __ballot(a1), mb1 = __ballot(b1);
     run_even = ma1; run_odd = mb1;
     even = __ballot(a2); odd = __ballot(b2);
@@ -145,7 +155,7 @@ __device__ __forceinline__ void runs_segment(const u64* __restrict__ recs, const
       if (lane == 0 && valid && i > 0) prev = load_rec<D>(recs + 3 * (i - 1));
       bool h1, h2;
       run_head<D>(prev, cur, i > 0, h1, h2);
-      ranks.step(i, cur, valid && h1, valid && h2, none, false, false, false);
+      ranks.step(i, cur, valid, valid && barcode_head(prev, cur, i > 0), valid && h1, valid && h2, none, false, false, false, false);
       if (lane == 0) {
         sink.end_ballots(seg == 0 ? 0u : 1u, (u32)((i0 - base) / kWave), ranks.even);
         sink.end_run_ballots(seg == 0 ? 0u : 1u, (u32)((i0 - base) / kWave), ranks.run_even);
@@ -177,7 +187,8 @@ __device__ __forceinline__ void runs_segment(const u64* __restrict__ recs, const
     bool xa, xb, ya, yb;
     run_head<D>(prev, x, lane > 0 || have_prev, xa, xb);
     run_head<D>(x, y, true, ya, yb);
-    ranks.step(begin + (u64)t * kTileRecs + 2 * lane, x, xa, xb, y, ya, yb, true);
+    ranks.step(begin + (u64)t * kTileRecs + 2 * lane, x, true, barcode_head(prev, x, lane > 0 || have_prev), xa, xb, y, barcode_head(x, y, true), ya,
+               yb, true);
     if (lane == 0) {
       sink.tile_ballots((begin - sp.head) / kTileRecs + t, ranks.even, ranks.odd);
       sink.tile_run_ballots((begin - sp.head) / kTileRecs + t, ranks.run_even, ranks.run_odd);
@@ -205,6 +216,10 @@ __device__ __forceinline__ void runs_kernel(const u64* __restrict__ recs, const 
                   sink);
   if (seg_heads && lane == 0) { seg_heads[seg] = (u32)c1; seg_heads[sp.nseg + seg] = (u32)c2; }
 }
+
+// The scan of per-segment counts (ibu_k_runs_scan, k_aggregate.hip): seg_heads u32[rows][nseg] -> seg_base u64[rows][nseg], the
+// exclusive prefix of every row, and totals[rows], the row sums.  One workgroup per row.
+void launch_runs_scan(const u32* seg_heads, u32 nseg, u32 rows, u64* seg_base, u64* totals, hipStream_t st);
 
 // K totals of a workgroup of kSortThreads, one u64 per thread and total: per wave with shuffles, per workgroup in LDS, then one
 // atomic per non-zero total and workgroup.  Every thread of the workgroup calls (a barrier).  Static indices only: t stays in registers.

@@ -366,6 +366,13 @@ using CorrectCounts = ibu_correct_counts_t;
 using MoleculeCounts = ibu_molecule_counts_t;
 using CellCounts = ibu_cell_counts_t;
 using SaturationPoint = ibu_saturation_point_t;
+using BarcodeLimits = ibu_barcode_limits_t;
+using BarcodeFilterCounts = ibu_barcode_filter_counts_t;
+// one row of ibu_barcode_metrics: a barcode, its records, the (w0, w1) pairs and (w0, w1, w2) triples that begin in it, and its
+// records / triples in the feature set
+struct BarcodeMetrics { uint64_t barcode, reads, pairs, triples, set_reads, set_triples; };
+// a feature set of ibu_barcode_metrics / ibu_filter_barcodes: a device bitmap of `bits` bits (nullptr and 0: the empty set)
+struct FeatureSet { const uint64_t* d_bits = nullptr; uint64_t bits = 0; };
 // one entry of ibu_pair_counts / ibu_count_matrix: (barcode, index, reads, distinct UMIs) on the count-matrix path
 struct MatrixEntry { uint64_t first, second, records, distinct; };
 inline int device_count() { int32_t n = 0; return ibu_device_count(&n) == IBU_OK ? n : 0; }
@@ -459,6 +466,18 @@ class Context {
   CellCounts call_cells(const void* d_sorted, size_t n, uint32_t mode, uint64_t param, uint8_t* d_class, uint32_t flags = 0, void* st = nullptr) {
     CellCounts c{};
     check(ibu_call_cells(c_, d_sorted, n, mode, param, flags, d_class, &c, st));
+    return c;
+  }
+  // the per-barcode QC table (ibu_barcode_metrics): one row per run of equal first word, in input order; set_word (1 or 2) is the
+  // record word looked up in `set`.  On swapped-and-sorted records with set_word = 1: pairs = features detected, triples = UMIs
+  inline std::vector<BarcodeMetrics> barcode_metrics(const void* d_recs, size_t n, const FeatureSet& set = {}, uint32_t set_word = 1);
+  // the QC filter made from that table (ibu_filter_barcodes): d_class (n bytes, or nullptr for the totals only) gets the class of
+  // the record's barcode — IBU_BARCODE_PASS / _LOW / _HIGH / _SET; a zeroed BarcodeLimits passes everything;
+  // select_records(.., 1u << IBU_BARCODE_PASS, ..) keeps the passing barcodes
+  BarcodeFilterCounts filter_barcodes(const void* d_recs, size_t n, const FeatureSet& set, uint32_t set_word, const BarcodeLimits& limits,
+                                      uint8_t* d_class, void* st = nullptr) {
+    BarcodeFilterCounts c{};
+    check(ibu_filter_barcodes(c_, d_recs, n, set.d_bits, set.bits, set_word, &limits, d_class, &c, st));
     return c;
   }
   // a reproducible random subset of n rows (ibu_subsample_class): d_class (n bytes, or nullptr for the count only) gets
@@ -603,6 +622,20 @@ inline std::vector<MatrixEntry> Context::count_matrix(void* d_recs, void* d_tmp,
   auto ha = a.download<uint64_t>(ne), hb = b.download<uint64_t>(ne), hc = c.download<uint64_t>(ne), hd = d.download<uint64_t>(ne);
   out.reserve(ne);
   for (size_t k = 0; k < ne; ++k) out.push_back({ha[k], hb[k], hc[k], hd[k]});
+  return out;
+}
+inline std::vector<BarcodeMetrics> Context::barcode_metrics(const void* d_recs, size_t n, const FeatureSet& set, uint32_t set_word) {
+  size_t nb = 0;
+  check(ibu_barcode_metrics(c_, d_recs, n, set.d_bits, set.bits, set_word, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0, &nb, nullptr));
+  std::vector<BarcodeMetrics> out;
+  if (!nb) return out;
+  DeviceBuffer a(*this, 8 * nb), b(*this, 8 * nb), c(*this, 8 * nb), d(*this, 8 * nb), e(*this, 8 * nb), f(*this, 8 * nb);
+  check(ibu_barcode_metrics(c_, d_recs, n, set.d_bits, set.bits, set_word, a.as<uint64_t>(), b.as<uint64_t>(), c.as<uint64_t>(), d.as<uint64_t>(),
+                            e.as<uint64_t>(), f.as<uint64_t>(), nb, &nb, nullptr));
+  auto ha = a.download<uint64_t>(nb), hb = b.download<uint64_t>(nb), hc = c.download<uint64_t>(nb), hd = d.download<uint64_t>(nb),
+       he = e.download<uint64_t>(nb), hf = f.download<uint64_t>(nb);
+  out.reserve(nb);
+  for (size_t k = 0; k < nb; ++k) out.push_back({ha[k], hb[k], hc[k], hd[k], he[k], hf[k]});
   return out;
 }
 inline std::vector<std::tuple<uint64_t, uint64_t, uint64_t>> Context::barcode_counts(const void* d_sorted, size_t n) {

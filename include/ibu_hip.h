@@ -631,6 +631,85 @@ typedef struct ibu_cell_counts {
 } ibu_cell_counts_t;
 int32_t ibu_call_cells(ibu_ctx_t* ctx, const void* d_sorted_records, size_t n, uint32_t mode, uint64_t param, uint32_t flags,
                        uint8_t* d_class, ibu_cell_counts_t* counts, void* stream);
+/* Per-barcode QC metrics and the barcode filter, on the device (k_metrics.hip) — the step between "these barcodes are cells" and
+ * the matrix: per barcode its reads, UMIs, features detected and the share of its reads or UMIs that fall in a feature set
+ * (mitochondrial, ribosomal, spike-in), and the filter that drops barcodes with too few features, with implausibly many (doublets),
+ * or with too high a share.  The reference has no such function; the semantics are this library's and are stated in full here.
+ * Write w0, w1, w2 for the three 64-bit words of a record in storage order.
+ *   A BARCODE is a maximal run of consecutive records with equal w0.
+ *   A PAIR is a maximal run of consecutive records with equal (w0, w1).
+ *   A TRIPLE is a maximal run of consecutive records with equal (w0, w1, w2).
+ * A FEATURE SET is a device bitmap d_set of set_bits bits, stored as 8-byte aligned uint64_t words: value v is bit v & 63 of word
+ * v >> 6 ((set_bits + 63) / 64 words are read, nothing behind them).  set_word is 1 or 2.  A record is IN THE SET iff the value v of
+ * its word set_word satisfies v < set_bits and bit v is set.  d_set == NULL together with set_bits == 0: no record is in the set.
+ * set_bits <= 2^32.  All records of a triple agree in every word, so "a triple is in the set" is well defined.
+ * For barcode k, in input order: barcode[k] = w0; reads[k], pairs[k], triples[k] = its records, and the pairs and triples that begin
+ * in it; set_reads[k] = its records in the set; set_triples[k] = its triples in the set.
+ * Two uses:
+ *   on records that went through ibu_records_swap_umi_index and the sort (what IBU_COUNT_LEAVE_SWAPPED leaves), with set_word = 1:
+ *     pairs are features detected, triples are UMIs, set_triples are UMIs in the set;
+ *   on ordinarily sorted records behind ibu_classify_molecules and select, with set_word = 2: pairs equal triples and both are
+ *     UMIs, set_triples are UMIs in the set; features are not available in that order.
+ * Unsorted input gives the same computation on the runs as they stand (a barcode that is interrupted and returns is two barcodes),
+ * as ibu_barcode_counts documents for itself.  The records are never written.
+ *
+ * ibu_barcode_metrics: every output column is nullable on its own.  *n_barcodes = the number of barcodes.  Size query: all six
+ * columns NULL and cap == 0.  cap too small (with any column given): IBU_ERR_INVALID_ARG with *n_barcodes set and nothing written
+ * (detail.a = barcodes, detail.b = cap).  n == 0: OK, *n_barcodes = 0, nothing touched.  IBU_ERR_INVALID_ARG, with nothing touched
+ * (*n_barcodes included): set_word outside {1, 2}, set_bits > 2^32, NULL d_set with set_bits > 0, a misaligned d_set, a NULL
+ * n_barcodes, n >= 2^40, and, with n > 0, a NULL or misaligned d_records or a misaligned column.  A NULL context is an error.
+ * Records 8-byte aligned: a 16-byte aligned array takes the tiled path, an 8- but not 16-byte aligned one peels one record, as
+ * ibu_pair_counts does.  Synchronises `stream` once (the barcode total comes back to size the table); the writes may still be queued
+ * on return.
+ *
+ * ibu_filter_barcodes: every record gets the class byte of its barcode; the first class that applies wins:
+ *   IBU_BARCODE_PASS 0
+ *   IBU_BARCODE_LOW  1   reads < min_reads, pairs < min_pairs or triples < min_triples
+ *   IBU_BARCODE_HIGH 2   reads > max_reads, pairs > max_pairs or triples > max_triples, for the maxima that are not 0
+ *   IBU_BARCODE_SET  3   set_den != 0 and set_x * set_den > set_num * x, where (set_x, x) = (set_reads, reads) for set_of == 0 and
+ *                        (set_triples, triples) for set_of == 1 — the share of the set is above set_num / set_den
+ * A maximum of 0 means no maximum, set_den == 0 no set test: a zeroed limits struct passes everything.  The set test is integer
+ * arithmetic: equality passes and there is no float anywhere.  set_num <= set_den < 2^24 is required, so that with counts below 2^40
+ * no product overflows 64 bits.  ibu_select_records(..., keep_mask = 1 << IBU_BARCODE_PASS) then keeps the passing barcodes'
+ * records in input order, still sorted.
+ * d_class (nullable: totals only): n bytes at any alignment.  counts (nullable): barcodes = the number of barcodes;
+ * barcodes_by_class[c] / reads_by_class[c] = the barcodes / records of class c (the reads sum to n); triples_passed,
+ * set_triples_passed = the triples / set triples of the class-0 barcodes; reserved = 0.
+ * IBU_ERR_INVALID_ARG: the set errors above, a NULL limits, set_of > 1, set_num > set_den, set_den >= 2^24 (all checked whatever n
+ * is), a NULL or misaligned d_records with n > 0, n >= 2^40 — a refused call touches nothing, `counts` included.  n == 0 is OK:
+ * nothing is touched and all totals are 0.  A NULL context is an error.  Synchronises `stream` once (the barcode total comes back
+ * to size the scratch); the class writes may still be queued on return.  With counts != NULL it waits a second time, for the totals.
+ *
+ * Traffic of both: the records are read twice (count, emit), and one 8-byte word of the bitmap is gathered per record and pass (a
+ * set of 60 000 features is 7.5 KB and stays in cache); 40 B per barcode are written and read (the row, and the pairs, triples, set
+ * reads and set triples in front of it — the metrics are differences of neighbouring rows), the verdict is 1 B per barcode and the
+ * class write 1 B per record, filled from the verdicts and from 16 B of barcode-head ballots per 128 records the emit pass keeps.
+ * No atomic per record or per barcode.  Scratch: the context's sort scratch for the per-segment tables (536 B per 8192 records)
+ * and the ballots (n / 8 bytes), and 41 B per barcode (+ 128 B) of its run scratch, grown on demand. */
+#define IBU_BARCODE_PASS 0
+#define IBU_BARCODE_LOW 1
+#define IBU_BARCODE_HIGH 2
+#define IBU_BARCODE_SET 3
+typedef struct ibu_barcode_limits {
+  uint64_t min_reads, max_reads;       /* a maximum of 0: none */
+  uint64_t min_pairs, max_pairs;
+  uint64_t min_triples, max_triples;
+  uint64_t set_num, set_den;           /* set_den == 0: no set test; else set_num <= set_den < 2^24 */
+  uint32_t set_of;                     /* 0: the share of reads, 1: of triples */
+  uint32_t reserved;                   /* ignored */
+} ibu_barcode_limits_t;
+typedef struct ibu_barcode_filter_counts {
+  uint64_t barcodes;                   /* runs of equal w0 */
+  uint64_t barcodes_by_class[4];
+  uint64_t reads_by_class[4];          /* their sum is n */
+  uint64_t triples_passed, set_triples_passed;
+  uint64_t reserved;                   /* 0 */
+} ibu_barcode_filter_counts_t;
+int32_t ibu_barcode_metrics(ibu_ctx_t* ctx, const void* d_records, size_t n, const uint64_t* d_set, uint64_t set_bits, uint32_t set_word,
+                            uint64_t* d_barcodes, uint64_t* d_reads, uint64_t* d_pairs, uint64_t* d_triples, uint64_t* d_set_reads,
+                            uint64_t* d_set_triples, size_t cap, size_t* n_barcodes, void* stream);
+int32_t ibu_filter_barcodes(ibu_ctx_t* ctx, const void* d_records, size_t n, const uint64_t* d_set, uint64_t set_bits, uint32_t set_word,
+                            const ibu_barcode_limits_t* limits, uint8_t* d_class, ibu_barcode_filter_counts_t* counts, void* stream);
 /* Read subsampling and the saturation curve, on the device (k_saturation.hip): a reproducible random subset of the reads — what
  * brings samples of different depth to a common depth — and the number every single-cell summary reports first: how many distinct
  * molecules and barcodes would have been seen at a fraction of the reads.  The reference has nothing like this; the semantics are

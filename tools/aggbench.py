@@ -7,6 +7,7 @@ into preallocated device arrays, no download.
   python tools/aggbench.py --molecules [--records 1e9] [--reads-per-molecule 4] [--second-candidate 0.05]     ibu_classify_molecules (molecule_legs below)
   python tools/aggbench.py --cells [--records 1e9] [--reads-per-molecule 4]     ibu_call_cells (cell_legs below)
   python tools/aggbench.py --saturation [--records 1e9] [--reads-per-molecule 4]     ibu_saturation_curve, ibu_subsample_class (saturation_legs below)
+  python tools/aggbench.py --metrics [--records 1e9] [--reads-per-molecule 4]     ibu_barcode_metrics, ibu_filter_barcodes (metrics_legs below)
 bc_len 10 gives 2^20 distinct barcodes (a single-cell whitelist's order of magnitude); 16 gives ~n runs of length one."""
 import argparse
 import ctypes as C
@@ -338,6 +339,95 @@ def cell_legs(a):
     assert counts.cells == int((umis >= counts.threshold).sum()), "the cells are the barcodes that were laid with that many molecules"
 
 
+def metrics_legs(a):
+    """--metrics: ibu_barcode_metrics (all columns, with a 60 000-bit feature set and without a set; the size query) and
+    ibu_filter_barcodes (with classes, and totals only) on resident {barcode, index, umi} records in sorted order — the knee of
+    --cells with every molecule given a feature: four molecules per feature, feature numbers spread over 0 .. 60 000 — timed with
+    events on a side stream (the first round is the warm-up).  In the same run and on the same array: ibu_call_cells with classes
+    (the same two reads of the records and the same fill: the yardstick), the ibu_pair_counts size query (the same walk, once) and
+    ibu_reduce (the plain read: the floor)."""
+    import numpy as np
+    import torch                                             # before the library, as bench.py does
+    torch.cuda.init()
+    import ibu_amd as ia
+    from ibu_amd import _dptr, _check, lib, _lib
+
+    ctx = ia.Context(0)
+    side = torch.cuda.Stream()
+    st = side.cuda_stream
+    n = int(float(a.records.split(",")[0]))
+    rpm = a.reads_per_molecule
+    set_bits = 60_000
+    umis, starts, ends, n_cells, n_bg = knee_layout(torch, n, rpm, "cuda")
+    cols = [ctx.alloc(8 * n) for _ in range(3)]
+    bc, feat, um = (torch.as_tensor(c, device="cuda").view(torch.int64) for c in cols)
+    for lo in range(0, n, 1 << 26):
+        hi = min(n, lo + (1 << 26))
+        i = torch.arange(lo, hi, device="cuda", dtype=torch.int64)
+        b, m = knee_fill(torch, i, starts, ends, rpm)
+        bc[lo:hi], um[lo:hi] = b, m
+        feat[lo:hi] = ((m // 4) * 100 + b % 100).clamp_(max=set_bits + 99)   # ascending inside a barcode; a few above the set
+    del i, b, m
+    torch.cuda.synchronize()
+    d, d_class = ctx.alloc(24 * n), ctx.alloc(n)
+    ctx.serialize(cols[0], cols[1], cols[2], n, d)           # w1 = the feature, w2 = the umi: what the swap and the sort leave
+    ctx.synchronize()
+    for c in cols:
+        c.free()
+    assert ctx.is_sorted(d, n)
+    cap = n_cells + n_bg
+    outs = [ctx.alloc(8 * cap) for _ in range(6)]
+    d_set, _ = ctx.feature_bitmap(np.arange(0, set_bits, 16), set_bits)   # one feature in sixteen
+
+    def timed(fn):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record(side)
+        fn()
+        e1.record(side)
+        e1.synchronize()
+        return e0.elapsed_time(e1)
+
+    def rounds(fn):
+        v = [timed(fn) for _ in range(a.rounds + 1)][1:]
+        return {"median_ms": round(statistics.median(v), 3), "min_ms": round(min(v), 3), "max_ms": round(max(v), 3)}
+
+    nb, npairs, ntriples = C.c_size_t(), C.c_size_t(), C.c_size_t()
+    ccounts, fcounts = _lib.CCellCounts(), _lib.CBarcodeFilterCounts()
+    lim = _lib.CBarcodeLimits(0, 0, 200, 20 * 500, 0, 0, 1, 10, 1, 0)   # 200 features or more, not absurdly many, at most a tenth of the UMIs in the set
+    metrics = lambda s, bits, o, c: rounds(lambda: _check(lib.ibu_barcode_metrics(ctx._c, _dptr(d), n, _dptr(s), bits, 1, *[_dptr(x) for x in o], c, C.byref(nb), st)))
+    filt = lambda cls: rounds(lambda: _check(lib.ibu_filter_barcodes(ctx._c, _dptr(d), n, _dptr(d_set), set_bits, 1, C.byref(lim),
+                                                                     _dptr(d_class) if cls else None, C.byref(fcounts), st)))
+    cells = lambda: rounds(lambda: _check(lib.ibu_call_cells(ctx._c, _dptr(d), n, ia.CELLS_MIN, 200, 0, _dptr(d_class), C.byref(ccounts), st)))
+    res = {"leg": "barcode_metrics", "n": n, "reads_per_molecule": rpm, "cells_laid": n_cells, "background_laid": n_bg, "set_bits": set_bits}
+    res["reduce"] = rounds(lambda: _check(lib.ibu_reduce(ctx._c, _dptr(d), n, st)))
+    res["pair_counts_size_query"] = rounds(lambda: _check(lib.ibu_pair_counts(ctx._c, _dptr(d), n, None, None, None, None, 0, C.byref(npairs), C.byref(ntriples), st)))
+    res["call_cells_with_classes"] = cells()
+    res["metrics_size_query"] = metrics(d_set, set_bits, [None] * 6, 0)
+    res["metrics_with_set"] = metrics(d_set, set_bits, outs, cap)
+    res["metrics_without_set"] = metrics(None, 0, outs, cap)
+    res["filter_with_classes"] = filt(True)
+    res["filter_totals_only"] = filt(False)
+    res["call_cells_with_classes_again"] = cells()
+    res["metrics_with_set_again"] = metrics(d_set, set_bits, outs, cap)
+    _check(lib.ibu_filter_barcodes(ctx._c, _dptr(d), n, _dptr(d_set), set_bits, 1, C.byref(lim), _dptr(d_class), C.byref(fcounts), st))   # (the classes the checks look at)
+    ctx.synchronize()
+    cc = min(res["call_cells_with_classes"]["median_ms"], res["call_cells_with_classes_again"]["median_ms"])
+    ws = min(res["metrics_with_set"]["median_ms"], res["metrics_with_set_again"]["median_ms"])
+    res["metrics_with_set_vs_call_cells"] = round(ws / cc, 3)
+    res["metrics_without_set_vs_call_cells"] = round(res["metrics_without_set"]["median_ms"] / cc, 3)
+    res["filter_with_classes_vs_call_cells"] = round(res["filter_with_classes"]["median_ms"] / cc, 3)
+    res["with_set_vs_without_set"] = round(ws / res["metrics_without_set"]["median_ms"], 3)
+    res["size_query_vs_pair_counts_size_query"] = round(res["metrics_size_query"]["median_ms"] / res["pair_counts_size_query"]["median_ms"], 3)
+    res.update({"barcodes": int(fcounts.barcodes), "barcodes_by_class": list(fcounts.barcodes_by_class), "reads_by_class": list(fcounts.reads_by_class)})
+    print(json.dumps(res), flush=True)                       # (before the checks: a run that fails one still leaves its times)
+    table = [o.download(np.uint64, nb.value) for o in outs]
+    assert nb.value == n_cells + n_bg == fcounts.barcodes and int(table[1].sum()) == n and sum(fcounts.reads_by_class) == n
+    assert int(table[2].sum()) == npairs.value and int(table[3].sum()) == ntriples.value == int(umis.sum()), "every molecule that was laid"
+    assert bool((table[5] <= table[3]).all()) and 0 < int(table[5].sum()) < ntriples.value
+    cls = torch.as_tensor(d_class, device="cuda").view(torch.uint8)[:n]
+    assert [int((cls == c).sum()) for c in range(4)] == list(fcounts.reads_by_class)
+
+
 def saturation_legs(a):
     """--saturation: the ten-point ibu_saturation_curve, and ibu_subsample_class + ibu_select_records at fraction 0.5, on resident
     sorted 16/12 records (the array --molecules lays), timed with events on a side stream (the first round is the warm-up).  In the
@@ -432,6 +522,7 @@ def saturation_legs(a):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--saturation", action="store_true", help="the ibu_saturation_curve / ibu_subsample_class legs instead of the barcode leg")
+    ap.add_argument("--metrics", action="store_true", help="the ibu_barcode_metrics / ibu_filter_barcodes legs instead of the barcode leg")
     ap.add_argument("--cells", action="store_true", help="the ibu_call_cells legs instead of the barcode leg")
     ap.add_argument("--molecules", action="store_true", help="the ibu_classify_molecules legs instead of the barcode leg")
     ap.add_argument("--reads-per-molecule", type=int, default=4)
@@ -444,6 +535,8 @@ def main():
     a = ap.parse_args()
     if a.saturation:
         return saturation_legs(a)
+    if a.metrics:
+        return metrics_legs(a)
     if a.molecules:
         return molecule_legs(a)
     if a.cells:
