@@ -192,7 +192,8 @@ ibu_k_molecules_verdict(const u64* __restrict__ table, u64 ncand, u64 n, u32 tie
 }
 
 // One workgroup.  Block j enters the scan as a segment start with its trail when it has a molecule head, and as its lead (all of
-// it) otherwise; what is open in front of j, joined with j's lead, is the total of the molecule that ends in j.
+// it) otherwise; what is open in front of j, joined with j's lead, is the total of the molecule that ends in j.  A molecule that
+// ends on the last candidate of a block without a head ends in no block's lead: its total is what is open in front of the next block.
 extern "C" __global__ void __launch_bounds__(kSortThreads)
 ibu_k_molecules_chains(const MolSummary* __restrict__ summary, u32 nblk, u32* __restrict__ chain_start, MolFull* __restrict__ chain_full) {
   __shared__ MolScanLds scan;
@@ -221,6 +222,10 @@ ibu_k_molecules_chains(const MolSummary* __restrict__ summary, u32 nblk, u32* __
         if (sm.lead_len && run.s != kNoChain) {
           chain_start[j] = run.s;
           if (sm.has_head || j + 1 == nblk) { const MolAgg f = mol_combine(run, lead); chain_full[run.s] = MolFull{f.key, f.first}; }
+        } else if (!sm.lead_len && run.key && run.s != kNoChain) {
+          // a molecule head on the block's first candidate: the chain that came through blocks without a head ended on the last
+          // candidate of j - 1 (run.key == 0: j - 1 has a head and is not open, nothing comes in)
+          chain_full[run.s] = MolFull{run.key, run.first};
         }
         run = sm.has_head ? MolAgg{sm.trail_key, sm.trail_first, j} : mol_combine(run, lead);
       }

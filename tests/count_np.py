@@ -74,3 +74,50 @@ def make_records(rng, n, bc_len, n_barcodes, n_indices, n_umis, high_bit=True):
     r["umi"] = umis[rng.integers(0, n_umis, n)]
     r["index"] = idxs[(rng.random(n) ** 3 * n_indices).astype(np.int64)]   # skewed: the high indices are rare, so some pairs have one read
     return r
+
+
+# ---- dense, unequal per-segment head counts beyond 1024 segments (the scan of the per-segment counters, ibu_k_runs_scan) --------
+SEG = 8192                                                       # runs_walk.hpp: kSegRecs
+STASH_HEADS = 32                                                 # runs_walk.hpp: kStashHeads
+STASH_SEGMENTS = (3, 4, 6, 100, 102, 104, 106, 108, 253, 255, 256, 257, 259, 400, 401, 402, 406, 511, 512, 513, 640, 642, 644, 646, 767, 768,
+                  769, 899, 900, 902, 1019, 1020, 1021, 1023, 1024, 1025, 1027, 1028, 1029, 1030)
+
+
+def dense_runs(n, head, stash_segments=STASH_SEGMENTS):
+    """Sorted records with (w0, w1) runs of 1 - 7 records in a fixed pseudo-random pattern, about half of them beginning a barcode
+    and a new third word on two rows in five besides: the heads of a segment differ from its neighbours' at every level.  In the
+    tiled segments named (first row head + 8192 (j - 1)) the barcodes are long instead: j % 29 barcode heads, none where that is 0."""
+    rng = np.random.default_rng(0xC0F00)
+    starts = np.cumsum(rng.integers(1, 8, n // 2))
+    assert starts[-1] >= n
+    h2 = np.zeros(n, bool)
+    h2[0] = True
+    h2[starts[starts < n]] = True
+    h1 = h2 & (rng.random(n) < 0.5)
+    h1[0] = True
+    h3 = h2 | (rng.random(n) < 0.4)
+    for j in stash_segments:
+        a = head + SEG * (j - 1)
+        assert 0 < a and a + SEG <= n
+        h1[a:a + SEG] = False
+        at = a + 100 + 277 * np.arange(j % 29)
+        h1[at] = h2[at] = h3[at] = True
+    r = np.zeros(n, REC)
+    w = r.view(np.uint64).reshape(-1, 3)
+    w[:, 0], w[:, 1], w[:, 2] = np.cumsum(h1), np.cumsum(h2), np.cumsum(h3)
+    return r
+
+
+def barcode_counts(recs):
+    """-> (barcodes, counts, unique_umis), one entry per maximal run of equal w0 in input order: the run's length and the
+    positions in it whose w1 differs from the record before (the first counts)."""
+    w = _words(recs)
+    n = len(w)
+    head = np.ones(n, bool)
+    head[1:] = w[1:, 0] != w[:-1, 0]
+    ranked = head.copy()
+    ranked[1:] |= w[1:, 1] != w[:-1, 1]
+    starts = np.flatnonzero(head)
+    ends = np.append(starts[1:], n)
+    rank = np.concatenate([[0], np.cumsum(ranked)])
+    return w[starts, 0].copy(), (ends - starts).astype(np.uint64), (rank[ends] - rank[starts]).astype(np.uint64)

@@ -156,3 +156,58 @@ def test_count_file_example_compiles_with_the_resolve_option(tmp_path):
     for args in ([], ["--resolve"], ["--resolve=first"]):
         r = subprocess.run([str(exe), *args], capture_output=True, text=True)
         assert r.returncode == 2 and "usage: count_file" in r.stderr
+
+
+def test_candidate_layouts_of_the_block_seam_tests():
+    """tests/test_gpu_block_seams.py lays molecules at the boundaries of the 1024-candidate verdict blocks: the builder round-trips,
+    the numpy statement equals the brute force on every layout at the largest size, and the block sizes the layouts assume are
+    still the source's."""
+    # lay_candidates -> _runs gives the table back, for sorted records
+    reads, heads = [1, 2, 1, 1, 3, 1], [True, False, True, False, False, True]
+    recs = mnp.lay_candidates(reads, heads)
+    starts, mol = mnp._runs(recs)
+    assert starts.tolist() == [0, 1, 3, 4, 5, 8] and mol.tolist() == [0, 0, 1, 1, 1, 2] and len(recs) == 9
+    assert recs.tobytes() == mnp.cnp.sort_records(recs).tobytes()
+    assert [[r for _, r in m] for m in mnp.molecule_runs(recs)] == [[1, 2], [1, 1, 3], [1]]
+    ncand = mnp.BLOCK_SIZES[-1]
+    plan = mnp.seam_plan(ncand)
+    assert ncand == 1024 * 1031 + 7 and sum(len(a) for a in plan) > 150
+    brute_long = 0
+    for laid in plan:
+        reads, mol_head, pieces = mnp.seam_table(ncand, laid)
+        hd = np.flatnonzero(mol_head)
+        for (K, spec), p in zip(laid, pieces):
+            # the piece with a few molecules on either side, cut at molecule heads: whole molecules, classified as in the whole table
+            lo, hi = int(hd[max(np.searchsorted(hd, p["lo"]) - 3, 0)]), int(hd[min(np.searchsorted(hd, p["hi"]) + 3, len(hd) - 1)])
+            assert lo < p["lo"] and p["hi"] < hi
+            sub = {"head_checks": [(c - lo, h) for c, h in p["head_checks"]], "classes": [(c - lo, x, y) for c, x, y in p["classes"]]}
+            recs = mnp.lay_candidates(reads[lo:hi], mol_head[lo:hi])
+            want = {f: mnp.classify(recs, f) for f in (False, True)}
+            mnp.check_seam_table(reads[lo:hi], mol_head[lo:hi], [sub], recs, want)   # the round trip, and the piece lies where it says
+            rows = np.concatenate([[0], np.cumsum(reads[lo:hi])])
+            if spec[0] == "long":
+                # every candidate of the long molecule, from the rule by eye: the one with two reads is kept and the rest minor;
+                # with two of them, or none, all are tied, or the first at best is kept under tie_first
+                a, b, twos = p["lo"] - lo, p["hi"] - lo, [t - lo for t in p["twos"]]
+                c = np.arange(a, b)
+                if len(twos) == 1:
+                    plain = first = np.where(c == twos[0], mnp.KEPT, mnp.MINOR)
+                else:
+                    plain, first = np.full(b - a, mnp.TIED), np.where(c == (twos[0] if twos else a), mnp.KEPT, mnp.MINOR)
+                for f, exp in ((False, plain), (True, first)):
+                    assert (want[f][0][rows[a]:rows[b]] == np.repeat(exp, reads[lo:hi][a:b])).all(), spec
+                if spec[1] != "tie_round_seam":
+                    continue
+                brute_long += 1
+            for f in (False, True):
+                assert mnp.brute_force(recs, f)[0].tobytes() == want[f][0].tobytes(), (K, spec, f)
+    assert brute_long == 1
+    # the seams the layouts sit on are the source's
+    src = open(os.path.join(ROOT, "ibu_amd", "csrc", "k_molecules.hip")).read()
+    walk = open(os.path.join(ROOT, "ibu_amd", "csrc", "runs_walk.hpp")).read()
+    stitch = open(os.path.join(ROOT, "ibu_amd", "csrc", "k_saturation.hip")).read()
+    assert re.search(r"kMolItems = 4;", src) and re.search(r"kMolBlock = kSortThreads \* kMolItems;", src) and re.search(r"kSortThreads = 256;", walk)
+    assert re.search(r"base \+= kMolBlock\)", src), "the chains scan takes one block of summaries per round"
+    body = stitch[stitch.index("ibu_k_saturation_stitch("):stitch.index("ibu_k_saturation_points(")]
+    assert "s_base += 4 * kSortThreads" in body and "s_base + 4 * threadIdx.x" in body
+    assert mnp.MOL_BLOCK == 256 * 4
