@@ -44,6 +44,14 @@ pub struct ibu_correct_counts_t {
 }
 #[repr(C)]
 #[derive(Default, Debug, Clone, Copy, PartialEq, Eq)]
+pub struct ibu_resolve_counts_t {
+    pub examined: u64,
+    pub resolved: u64,
+    pub below_share: u64,
+    pub unseen: u64,
+}
+#[repr(C)]
+#[derive(Default, Debug, Clone, Copy, PartialEq, Eq)]
 pub struct ibu_molecule_counts_t {
     pub molecules: u64,
     pub candidates: u64,
@@ -193,6 +201,7 @@ pub enum ibu_mmap_t {}
 pub enum ibu_ctx_t {}
 pub enum ibu_stream_t {}
 pub enum ibu_whitelist_t {}
+pub enum ibu_abundance_t {}
 pub type ibu_write_fn = unsafe extern "C" fn(*mut c_void, *const u8, usize) -> i32;
 pub type ibu_flush_fn = unsafe extern "C" fn(*mut c_void) -> i32;
 pub type ibu_read_fn = unsafe extern "C" fn(*mut c_void, *mut u8, usize, *mut usize) -> i32;
@@ -274,6 +283,16 @@ extern "C" {
     pub fn ibu_whitelist_destroy(wl: *mut ibu_whitelist_t);
     pub fn ibu_correct_barcodes(ctx: *mut ibu_ctx_t, wl: *const ibu_whitelist_t, d_records: *mut c_void, n: usize, max_mismatches: u32,
                                 d_class: *mut u8, counts: *mut ibu_correct_counts_t, stream: *mut c_void) -> i32;
+    pub fn ibu_abundance_create(ctx: *mut ibu_ctx_t, wl: *const ibu_whitelist_t, stream: *mut c_void, out: *mut *mut ibu_abundance_t) -> i32;
+    pub fn ibu_abundance_reset(ab: *mut ibu_abundance_t, stream: *mut c_void) -> i32;
+    pub fn ibu_abundance_info(ab: *const ibu_abundance_t, device_bytes: *mut usize) -> i32;
+    pub fn ibu_abundance_destroy(ab: *mut ibu_abundance_t);
+    pub fn ibu_abundance_add(ctx: *mut ibu_ctx_t, ab: *mut ibu_abundance_t, d_records: *const c_void, d_class: *const u8, n: usize,
+                             class_mask: u32, stream: *mut c_void) -> i32;
+    pub fn ibu_abundance_counts(ctx: *mut ibu_ctx_t, ab: *const ibu_abundance_t, d_codes: *const u64, k: usize, d_counts: *mut u64,
+                                stream: *mut c_void) -> i32;
+    pub fn ibu_resolve_barcodes(ctx: *mut ibu_ctx_t, wl: *const ibu_whitelist_t, ab: *const ibu_abundance_t, d_records: *mut c_void, n: usize,
+                                num: u64, den: u64, d_class: *mut u8, counts: *mut ibu_resolve_counts_t, stream: *mut c_void) -> i32;
     pub fn ibu_classify_molecules(ctx: *mut ibu_ctx_t, d_sorted_records: *const c_void, n: usize, flags: u32, d_class: *mut u8,
                                   counts: *mut ibu_molecule_counts_t, stream: *mut c_void) -> i32;
     pub fn ibu_call_cells(ctx: *mut ibu_ctx_t, d_sorted_records: *const c_void, n: usize, mode: u32, param: u64, flags: u32, d_class: *mut u8,

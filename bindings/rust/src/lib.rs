@@ -671,6 +671,16 @@ pub mod device {
             check(unsafe { ffi::ibu_correct_barcodes(self.raw, wl.raw, recs.ptr, n, max_mismatches, cls, &mut c, std::ptr::null_mut()) })?;
             Ok(c)
         }
+        /// `ibu_resolve_barcodes`, in place over `n` device records and their class bytes: a record of class 2 (ambiguous) whose
+        /// best candidate holds at least `num / den` of the reads `ab` counted for its candidates (`best * den >= num * total`,
+        /// `best > 0`; `1 <= num <= den < 2^24`, `2 * num > den`) moves onto it and gets class `BARCODE_RESOLVED`.  Synchronises
+        /// and returns the four totals.  `select_records(.., 0b10011, ..)` then keeps exact, corrected and resolved records.
+        pub fn resolve_barcodes(&self, wl: &Whitelist, ab: &Abundance, recs: &DeviceBuf, n: usize, num: u64, den: u64, class: &DeviceBuf)
+                                -> Result<ffi::ibu_resolve_counts_t> {
+            let mut c = ffi::ibu_resolve_counts_t::default();
+            check(unsafe { ffi::ibu_resolve_barcodes(self.raw, wl.raw, ab.raw, recs.ptr, n, num, den, class.ptr as *mut u8, &mut c, std::ptr::null_mut()) })?;
+            Ok(c)
+        }
         /// `ibu_classify_molecules` over records sorted by (barcode, umi, index): one class byte per record into `class` (n bytes;
         /// `None`: totals only) — 0 for the index its (barcode, umi) molecule was seen with strictly most often, 1 for the molecule's
         /// other reads, 2 for every read of a molecule whose top is shared (`tie_first`: the first index at the top is kept, the
@@ -798,6 +808,49 @@ pub mod device {
     impl Drop for Whitelist<'_> {
         fn drop(&mut self) {
             unsafe { ffi::ibu_whitelist_destroy(self.raw) }
+        }
+    }
+    /// The class `resolve_barcodes` gives a record it resolves (`IBU_BARCODE_RESOLVED`).
+    pub const BARCODE_RESOLVED: u8 = 4;
+    /// `ibu_abundance_t`: one read counter per entry of a whitelist, all zero at first.  Borrows its whitelist (and through it the
+    /// context), so it cannot outlive either.
+    pub struct Abundance<'w> {
+        pub(crate) raw: *mut ffi::ibu_abundance_t,
+        ctx: *mut ffi::ibu_ctx_t,
+        _p: PhantomData<&'w ()>,
+    }
+    impl<'w> Abundance<'w> {
+        pub fn new<'c: 'w>(ctx: &'c Context, wl: &'w Whitelist<'c>) -> Result<Self> {
+            let mut raw = std::ptr::null_mut();
+            check(unsafe { ffi::ibu_abundance_create(ctx.raw, wl.raw, std::ptr::null_mut(), &mut raw) })?;
+            Ok(Self { raw, ctx: ctx.raw, _p: PhantomData })
+        }
+        /// `ibu_abundance_add` over `n` device records: the counter of a record's barcode grows by one where the barcode is in the
+        /// whitelist and the record contributes: every record without `class`, else those whose class `c < 8` has bit `c` of
+        /// `class_mask` set.  Asynchronous on the context's stream; accumulates over calls.
+        pub fn add(&self, recs: &DeviceBuf, n: usize, class: Option<&DeviceBuf>, class_mask: u32) -> Result<()> {
+            let cls = class.map_or(std::ptr::null(), |b| b.ptr as *const u8);
+            check(unsafe { ffi::ibu_abundance_add(self.ctx, self.raw, recs.ptr, cls, n, class_mask, std::ptr::null_mut()) })
+        }
+        /// `ibu_abundance_counts`: `counts[j]` = the counter of `codes[j]` (`k` u64 each, device memory), 0 for a code that is not
+        /// in the whitelist.  Asynchronous on the context's stream.
+        pub fn counts(&self, codes: &DeviceBuf, k: usize, counts: &DeviceBuf) -> Result<()> {
+            check(unsafe { ffi::ibu_abundance_counts(self.ctx, self.raw, codes.ptr as *const u64, k, counts.ptr as *mut u64, std::ptr::null_mut()) })
+        }
+        /// All counters back to zero.
+        pub fn reset(&self) -> Result<()> {
+            check(unsafe { ffi::ibu_abundance_reset(self.raw, std::ptr::null_mut()) })
+        }
+        /// Bytes of device memory the counters take.
+        pub fn device_bytes(&self) -> Result<usize> {
+            let mut bytes = 0usize;
+            check(unsafe { ffi::ibu_abundance_info(self.raw, &mut bytes) })?;
+            Ok(bytes)
+        }
+    }
+    impl Drop for Abundance<'_> {
+        fn drop(&mut self) {
+            unsafe { ffi::ibu_abundance_destroy(self.raw) }
         }
     }
     /// `ibu_stream_t`: iterate to pull one device-resident batch at a time.  An `Err` item is the source's error

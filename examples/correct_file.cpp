@@ -2,9 +2,11 @@
 // moves every barcode that has exactly one whitelist entry one substitution away onto that entry and drops what matches
 // nothing.  Read an IBU file, correct its barcodes against a whitelist on the GPU (ibu_correct_barcodes), keep the exact and
 // the corrected records (ibu_select_records), sort them and write them under a header with the sorted flag set.
-//   correct_file IN WHITELIST.txt OUT [--keep-ambiguous]
+//   correct_file IN WHITELIST.txt OUT [--keep-ambiguous] [--resolve[=NUM/DEN]]
 // WHITELIST.txt: one barcode per line, as many bases as the file's header says.  --keep-ambiguous: records with two or more
-// whitelist entries at distance one stay too (uncorrected).
+// whitelist entries at distance one stay too (uncorrected).  --resolve: such a record moves onto the candidate that holds at least
+// NUM/DEN (default 39/40) of the exactly matching reads among its candidates (ibu_abundance_add over the exact records, then
+// ibu_resolve_barcodes) and is kept; where no candidate does, it is dropped as before.
 #include <cstdio>
 #include <cstring>
 #include <fstream>
@@ -14,10 +16,21 @@
 #include "ibu.hpp"
 
 int main(int argc, char** argv) {
-  if (argc < 4) { std::fprintf(stderr, "usage: correct_file IN WHITELIST.txt OUT [--keep-ambiguous]\n"); return 2; }
+  if (argc < 4) { std::fprintf(stderr, "usage: correct_file IN WHITELIST.txt OUT [--keep-ambiguous] [--resolve[=NUM/DEN]]\n"); return 2; }
   uint32_t keep = 0b0011;                                       // classes 0 (exact) and 1 (corrected)
-  for (int i = 4; i < argc; ++i)
+  bool resolve = false;
+  unsigned long long num = 39, den = 40;
+  for (int i = 4; i < argc; ++i) {
     if (!std::strcmp(argv[i], "--keep-ambiguous")) keep |= 0b0100;
+    if (!std::strncmp(argv[i], "--resolve", 9) && (argv[i][9] == 0 || argv[i][9] == '=')) {
+      resolve = true;
+      keep |= 1u << IBU_BARCODE_RESOLVED;
+      if (argv[i][9] == '=' && std::sscanf(argv[i] + 10, "%llu/%llu", &num, &den) != 2) {
+        std::fprintf(stderr, "--resolve=NUM/DEN: two integers, e.g. --resolve=39/40\n");
+        return 2;
+      }
+    }
+  }
   try {
     using namespace ibu;
     device::Context ctx(0);
@@ -49,6 +62,12 @@ int main(int argc, char** argv) {
     ctx.sort_records(d_recs, tmp.ptr(), n);
     const size_t before = ctx.barcode_counts(d_recs, n).size();
     const device::CorrectCounts c = ctx.correct_barcodes(wl, d_recs, n, 1, d_class.as<uint8_t>());
+    device::ResolveCounts r{};
+    if (resolve) {
+      device::Abundance ab(ctx, wl);
+      ab.add(d_recs, n, d_class.as<uint8_t>(), 1u << 0);        // the prior: the exactly matching reads of every whitelist entry
+      r = ctx.resolve_barcodes(wl, ab, d_recs, n, d_class.as<uint8_t>(), num, den);
+    }
     const size_t kept = ctx.select_records(d_recs, d_class.as<uint8_t>(), n, keep, tmp.ptr(), n);
     ctx.sort_records(tmp.ptr(), d_recs, kept);                  // the input array is scratch from here on
     const size_t after = ctx.barcode_counts(tmp.ptr(), kept).size();
@@ -63,6 +82,10 @@ int main(int argc, char** argv) {
     std::printf("%zu records, whitelist of %zu (%zu distinct): exact %llu, corrected %llu, ambiguous %llu, unmatched %llu; kept %zu\n", n, w,
                 wl.n_distinct(), (unsigned long long)c.exact, (unsigned long long)c.corrected, (unsigned long long)c.ambiguous,
                 (unsigned long long)c.unmatched, kept);
+    if (resolve)
+      std::printf("ambiguous examined %llu: resolved %llu at a share of %llu/%llu, below the share %llu, no exact read among the candidates %llu\n",
+                  (unsigned long long)r.examined, (unsigned long long)r.resolved, num, den, (unsigned long long)r.below_share,
+                  (unsigned long long)r.unseen);
     std::printf("barcodes before %zu, after %zu\n", before, after);
   } catch (const std::exception& e) {
     std::fprintf(stderr, "error: %s\n", e.what());

@@ -6,8 +6,8 @@ Reader, Writer, ParallelProcessor, ParallelReader) over the C ABI of include/ibu
 the device context that exposes the HIP kernels.  All work happens in libibu_hip.so; this
 package binds it and nothing else (no numpy/torch arithmetic stands in for a kernel).
 
-The device pipeline of a single-cell run, every step on resident records: load -> Context.correct_barcodes -> select_records ->
-sort_records -> classify_molecules -> select_records -> call_cells -> select_records -> count_matrix(leave_swapped=True) ->
+The device pipeline of a single-cell run, every step on resident records: load -> Context.correct_barcodes (-> Abundance.add ->
+Context.resolve_barcodes: ambiguous barcodes to the candidate with nearly all of the exact reads) -> select_records -> sort_records -> classify_molecules -> select_records -> call_cells -> select_records -> count_matrix(leave_swapped=True) ->
 filter_barcodes (the per-barcode QC filter: too few or too many features / UMIs, too large a share of a feature set built with
 Context.feature_bitmap; barcode_metrics returns the table itself) -> select_records -> pair_counts.
 """
@@ -19,7 +19,7 @@ from collections import namedtuple
 import numpy as np
 
 from . import _lib
-from ._lib import CAllocProbe, CBarcodeFilterCounts, CBarcodeLimits, CCellCounts, CCorrectCounts, CDecodeSink, CMoleculeCounts, CErrorDetail, CKeyPlan, CHeader, CNumaInfo, CProcessorVTable, CRecord, CReduceResult, CRingConfig, CSaturationPoint, CStreamStats
+from ._lib import CAllocProbe, CBarcodeFilterCounts, CBarcodeLimits, CCellCounts, CCorrectCounts, CResolveCounts, CDecodeSink, CMoleculeCounts, CErrorDetail, CKeyPlan, CHeader, CNumaInfo, CProcessorVTable, CRecord, CReduceResult, CRingConfig, CSaturationPoint, CStreamStats
 
 lib = _lib.load()
 
@@ -39,6 +39,7 @@ CELL, CELL_BACKGROUND = 0, 1  # the classes of ibu_call_cells (IBU_CELL, IBU_CEL
 CELLS_MIN, CELLS_TOP, CELLS_ORDMAG = 0, 1, 2  # its modes (IBU_CELLS_*)
 CELLS_BY_READS = 1  # its flag (IBU_CELLS_BY_READS)
 BARCODE_PASS, BARCODE_LOW, BARCODE_HIGH, BARCODE_SET = 0, 1, 2, 3  # the classes of ibu_filter_barcodes (IBU_BARCODE_*)
+BARCODE_RESOLVED = 4  # the class ibu_resolve_barcodes gives a record it resolves (IBU_BARCODE_RESOLVED), beside 0..3 of ibu_correct_barcodes
 #: the table of ibu_barcode_metrics: one numpy u64 column each, a row per barcode in input order
 BarcodeMetrics = namedtuple("BarcodeMetrics", "barcodes reads pairs triples set_reads set_triples")
 #: the totals of one ibu_filter_barcodes call (ibu_barcode_filter_counts_t without its reserved word); the by_class fields are 4-tuples
@@ -1165,6 +1166,22 @@ class Context:
             return None
         return {"exact": c.exact, "corrected": c.corrected, "ambiguous": c.ambiguous, "unmatched": c.unmatched}
 
+    def resolve_barcodes(self, wl, ab, d_records, n, d_class, min_share=(39, 40), counts=True, stream=None):
+        """ibu_resolve_barcodes, in place over n device records and their class bytes (what correct_barcodes left): a record of
+        class 2 (ambiguous) whose best candidate — the whitelisted neighbour with the largest counter in the Abundance `ab` — holds
+        at least min_share = (num, den) of its candidates' counted reads (best * den >= num * total in integers, best > 0;
+        1 <= num <= den < 2^24 and 2 * num > den) moves onto that candidate and gets class BARCODE_RESOLVED; every other record
+        and class byte stays.  counts=True synchronises and returns {"examined", "resolved", "below_share", "unseen"};
+        counts=False leaves the call asynchronous and returns None.  select_records(..., keep_mask=0b10011) then keeps exact,
+        corrected and resolved records."""
+        num, den = min_share
+        c = CResolveCounts() if counts else None
+        _check(lib.ibu_resolve_barcodes(self._c, getattr(wl, "_c", None), getattr(ab, "_c", None), _dptr(d_records), n, _u64_arg("num", num),
+                                        _u64_arg("den", den), _dptr(d_class), C.byref(c) if counts else None, stream))
+        if not counts:
+            return None
+        return {"examined": c.examined, "resolved": c.resolved, "below_share": c.below_share, "unseen": c.unseen}
+
     def select_records(self, d_records, d_class, n, keep_mask=0b0011, stream=None):
         """ibu_select_records: the records whose class has its bit set in keep_mask (default: exact and corrected), in
         input order -> (DeviceBuffer, n_out).  One call, so one count pass and one synchronisation: the buffer has room for
@@ -1281,7 +1298,7 @@ class Context:
         if getattr(self, "_c", None):
             for b in list(getattr(self, "_buffers", ())):   # buffers that outlive the context would leak their HBM
                 b.free()
-            for w in list(getattr(self, "_whitelists", ())):   # a whitelist goes before its context
+            for w in list(getattr(self, "_whitelists", ())):   # a whitelist (and the abundances on it) goes before its context
                 w.close()
             lib.ibu_ctx_destroy(self._c)
             self._c = None
@@ -1297,6 +1314,7 @@ class Whitelist:
         h = C.c_void_p()
         _check(lib.ibu_whitelist_create(getattr(ctx, "_c", None), _dptr(d_codes), w, bc_len, stream, C.byref(h)))
         self._c, self.ctx = h, ctx
+        self._abundances = weakref.WeakSet()   # live Abundances on it
         ctx._whitelists.add(self)   # a context that closes first destroys what was built on it (Context.close)
         b, nd, db = C.c_uint32(), C.c_size_t(), C.c_size_t()
         _check(lib.ibu_whitelist_info(self._c, C.byref(b), C.byref(nd), C.byref(db)))
@@ -1325,8 +1343,14 @@ class Whitelist:
             d_ascii.free()
             d_codes.free()
 
+    def abundance(self, stream=None):
+        """A new Abundance on this whitelist: one read counter per entry, all zero."""
+        return Abundance(self.ctx, self, stream)
+
     def close(self):
         if getattr(self, "_c", None):
+            for a in list(getattr(self, "_abundances", ())):   # an abundance goes before its whitelist
+                a.close()
             lib.ibu_whitelist_destroy(self._c)
             self._c = None
 
@@ -1339,7 +1363,60 @@ class Whitelist:
         self.close()
 
 
-__all__ = ["Whitelist", "Header", "Record", "HEADER_SIZE", "MAGIC", "RECORD_SIZE", "VERSION", "IbuError", "load_to_vec",
+class Abundance:
+    """ibu_abundance_t: one u64 read counter per entry of a Whitelist, on the device (Whitelist.abundance()).  add() counts
+    records, Context.resolve_barcodes reads the counters.  Belongs to its whitelist and that whitelist's context; close it before
+    them (a whitelist that closes first closes it)."""
+
+    def __init__(self, ctx, wl, stream=None):
+        h = C.c_void_p()
+        _check(lib.ibu_abundance_create(getattr(ctx, "_c", None), getattr(wl, "_c", None), stream, C.byref(h)))
+        self._c, self.ctx, self.wl = h, ctx, wl
+        wl._abundances.add(self)
+        db = C.c_size_t()
+        _check(lib.ibu_abundance_info(self._c, C.byref(db)))
+        self.device_bytes = db.value
+
+    def add(self, d_records, n, d_class=None, class_mask=1, stream=None):
+        """ibu_abundance_add over n device records: the counter of a record's barcode (its low 2*bc_len bits) grows by one where
+        that barcode is in the whitelist and the record contributes — every record with d_class=None, else the records whose class
+        byte c < 8 has bit c of class_mask set (default: class 0, the exact hits).  Asynchronous; accumulates over calls."""
+        _check(lib.ibu_abundance_add(self.ctx._c, self._c, _dptr(d_records), _dptr(d_class), n, class_mask, stream))
+
+    def counts(self, codes, stream=None):
+        """ibu_abundance_counts: the counters of `codes` (host u64 values) as a numpy u64 array; 0 for a code that is not in the
+        whitelist.  Synchronises."""
+        a = np.ascontiguousarray(codes, dtype=np.uint64).reshape(-1)
+        if len(a) == 0:
+            return np.empty(0, np.uint64)
+        d_codes, d_out = self.ctx.upload(a), self.ctx.alloc(max(8 * len(a), 16))
+        try:
+            _check(lib.ibu_abundance_counts(self.ctx._c, self._c, d_codes.ptr, len(a), d_out.ptr, stream))
+            self.ctx.synchronize(stream)
+            return d_out.download(np.uint64, len(a))
+        finally:
+            d_codes.free()
+            d_out.free()
+
+    def reset(self, stream=None):
+        """All counters back to zero (asynchronous)."""
+        _check(lib.ibu_abundance_reset(self._c, stream))
+
+    def close(self):
+        if getattr(self, "_c", None):
+            lib.ibu_abundance_destroy(self._c)
+            self._c = None
+
+    __del__ = close
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
+
+
+__all__ = ["Whitelist", "Abundance", "Header", "Record", "HEADER_SIZE", "MAGIC", "RECORD_SIZE", "VERSION", "IbuError", "load_to_vec",
            "MmapReader", "Reader", "Writer", "ParallelProcessor", "ProcessError", "shard_range", "Context",
            "DeviceBuffer", "DeviceStream", "DeviceBatch", "numa_of_pci", "records_array", "key_plan", "REC_DTYPE", "device_count", "PROC_REDUCE", "PROC_DECODE",
            "DEFAULT_BUFFER_SIZE", "BATCH_SIZE"]

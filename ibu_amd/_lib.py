@@ -34,6 +34,10 @@ class CCorrectCounts(C.Structure):  # ibu_correct_counts_t
     _fields_ = [("exact", u64), ("corrected", u64), ("ambiguous", u64), ("unmatched", u64)]
 
 
+class CResolveCounts(C.Structure):  # ibu_resolve_counts_t
+    _fields_ = [("examined", u64), ("resolved", u64), ("below_share", u64), ("unseen", u64)]
+
+
 class CMoleculeCounts(C.Structure):  # ibu_molecule_counts_t
     _fields_ = [("molecules", u64), ("candidates", u64), ("resolved", u64), ("tied", u64), ("reads_kept", u64), ("reads_minor", u64),
                 ("reads_tied", u64), ("reserved", u64)]
@@ -184,6 +188,13 @@ SIGNATURES = {
     "ibu_saturation_curve": (i32, [vp, vp, sz, u64, u64, P(u64), u32, P(CSaturationPoint), vp]),
     "ibu_correct_barcodes": (i32, [vp, vp, vp, sz, u32, vp, P(CCorrectCounts), vp]),
     "ibu_select_records": (i32, [vp, vp, vp, sz, u32, vp, sz, P(sz), vp]),
+    "ibu_abundance_create": (i32, [vp, vp, vp, P(vp)]),
+    "ibu_abundance_reset": (i32, [vp, vp]),
+    "ibu_abundance_info": (i32, [vp, P(sz)]),
+    "ibu_abundance_destroy": (None, [vp]),
+    "ibu_abundance_add": (i32, [vp, vp, vp, vp, sz, u32, vp]),
+    "ibu_abundance_counts": (i32, [vp, vp, vp, sz, vp, vp]),
+    "ibu_resolve_barcodes": (i32, [vp, vp, vp, vp, sz, u64, u64, vp, P(CResolveCounts), vp]),
     "ibu_bgzf_scan": (i32, [vp, sz, i32, P(CInflateBlock), sz, P(sz), P(sz), P(C.c_uint64)]),
     "ibu_inflate_blocks_device": (i32, [vp, vp, vp, sz, vp, vp, vp, vp]),
     "ibu_device_alloc": (i32, [vp, sz, P(vp)]),

@@ -57,6 +57,7 @@ struct ibu_ctx {
   uint64_t* d_acc = nullptr;     // [count, sum0..2, xor0..2, pad]
   uint32_t* d_flag = nullptr;    // sortedness flag
   uint64_t* d_correct_acc = nullptr;  // the class totals of an ibu_correct_barcodes call that asks for them (kCorrectAccBytes, on first use)
+  uint64_t* d_resolve_acc = nullptr;  // the totals of an ibu_resolve_barcodes call that asks for them (kCorrectAccBytes, on first use)
   uint64_t* h_pinned = nullptr;  // 128 x u64 of pinned host memory for small read-backs
   void* d_sort_scratch = nullptr;
   size_t sort_scratch_bytes = 0;

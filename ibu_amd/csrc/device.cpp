@@ -105,6 +105,7 @@ extern "C" void ibu_ctx_destroy(ibu_ctx_t* ctx) {
   if (ctx->d_acc) (void)hipFree(ctx->d_acc);
   if (ctx->d_flag) (void)hipFree(ctx->d_flag);
   if (ctx->d_correct_acc) (void)hipFree(ctx->d_correct_acc);
+  if (ctx->d_resolve_acc) (void)hipFree(ctx->d_resolve_acc);
   if (ctx->h_pinned) (void)hipHostFree(ctx->h_pinned);
   if (ctx->h_part) (void)hipHostFree(ctx->h_part);
   if (ctx->side_stream) (void)hipStreamDestroy(ctx->side_stream);
@@ -829,6 +830,137 @@ extern "C" int32_t ibu_correct_barcodes(ibu_ctx_t* ctx, const ibu_whitelist_t* w
   counts->corrected = ctx->h_pinned[1];
   counts->ambiguous = ctx->h_pinned[2];
   counts->unmatched = ctx->h_pinned[3];
+  return IBU_OK;
+}
+// ---- whitelist abundance and the resolution of ambiguous barcodes (k_whitelist.hip) ----------------------------------------
+struct ibu_abundance {
+  ibu_ctx* ctx = nullptr;
+  const ibu_whitelist* wl = nullptr;
+  uint64_t* d_counters = nullptr;          // slots + 1: one per table slot, the last for the all-ones key
+  size_t device_bytes = 0;
+  std::atomic<uint64_t> offered{0};        // records offered to ibu_abundance_add since create / reset: no counter can pass it
+};
+static constexpr uint64_t kAbundanceMax = 1ull << 40;
+extern "C" int32_t ibu_abundance_create(ibu_ctx_t* ctx, const ibu_whitelist_t* wl, void* stream, ibu_abundance_t** out) {
+  if (!ctx) {   // as ibu_whitelist_create: say whether a device is missing altogether
+    int count = 0;
+    hipError_t e = hipGetDeviceCount(&count);
+    if (e != hipSuccess) return hip_fail(e, "hipGetDeviceCount");
+    if (count == 0) return set_error(IBU_ERR_NO_DEVICE, 0, 0, 0, "no HIP device: an abundance lives on a device context");
+    return err_arg("ctx is NULL");
+  }
+  int32_t rc = check_ctx(ctx);
+  if (rc) return rc;
+  if (!out) return err_arg("out is NULL");
+  *out = nullptr;
+  if (!wl) return err_arg("wl is NULL");
+  if (wl->ctx != ctx) return err_arg("the whitelist was created on another context");
+  hipStream_t st = pick_stream(ctx, stream);
+  ibu_abundance* ab = new ibu_abundance;
+  ab->ctx = ctx;
+  ab->wl = wl;
+  ab->device_bytes = (wl->slots + 1) * sizeof(uint64_t);
+  hipError_t e = ctx_malloc(ctx, reinterpret_cast<void**>(&ab->d_counters), ab->device_bytes);
+  if (e == hipSuccess) e = hipMemsetAsync(ab->d_counters, 0, ab->device_bytes, st);
+  if (e == hipSuccess) e = hipStreamSynchronize(st);
+  if (e != hipSuccess) {
+    ibu_abundance_destroy(ab);
+    return hip_fail(e, "ibu_abundance_create");
+  }
+  *out = ab;
+  return IBU_OK;
+}
+extern "C" int32_t ibu_abundance_reset(ibu_abundance_t* ab, void* stream) {
+  if (!ab) return err_arg("ab is NULL");
+  int32_t rc = check_ctx(ab->ctx);
+  if (rc) return rc;
+  IBU_HIP(hipMemsetAsync(ab->d_counters, 0, ab->device_bytes, pick_stream(ab->ctx, stream)));
+  ab->offered.store(0);
+  return IBU_OK;
+}
+extern "C" int32_t ibu_abundance_info(const ibu_abundance_t* ab, size_t* device_bytes) {
+  if (!ab) return err_arg("ab is NULL");
+  if (device_bytes) *device_bytes = ab->device_bytes;
+  return IBU_OK;
+}
+extern "C" void ibu_abundance_destroy(ibu_abundance_t* ab) {
+  if (!ab) return;
+  if (ab->d_counters) {
+    (void)hipSetDevice(ab->ctx->device);
+    (void)hipFree(ab->d_counters);   // (waits for launches that still add to or read the counters)
+  }
+  delete ab;
+}
+static int32_t check_abundance(const ibu_ctx* ctx, const ibu_abundance* ab) {
+  if (!ab) return err_arg("ab is NULL");
+  if (ab->ctx != ctx) return err_arg("the abundance was created on another context");
+  return IBU_OK;
+}
+static WhitelistTable table_of(const ibu_whitelist* wl) {
+  return WhitelistTable{static_cast<const uint64_t*>(wl->d_mem), wl->slots, wl->bc_len, wl->has_ones};
+}
+extern "C" int32_t ibu_abundance_add(ibu_ctx_t* ctx, ibu_abundance_t* ab, const void* d_records, const uint8_t* d_class, size_t n,
+                                     uint32_t class_mask, void* stream) {
+  int32_t rc = check_ctx(ctx);
+  if (rc) return rc;
+  rc = check_abundance(ctx, ab);
+  if (rc) return rc;
+  if (n == 0) return IBU_OK;
+  if (!d_records || !aligned8(d_records)) return err_arg("d_records must be non-NULL and 8-byte aligned");
+  if (n >= kAbundanceMax) return err_arg("abundance_add handles fewer than 2^40 records per call");
+  uint64_t seen = ab->offered.load();
+  do {
+    if (seen + n > kAbundanceMax)
+      return set_error(IBU_ERR_INVALID_ARG, seen, n, 0, "Invalid argument: %llu records offered so far and %llu more would pass 2^40 (reset the abundance)",
+                       (unsigned long long)seen, (unsigned long long)n);
+  } while (!ab->offered.compare_exchange_weak(seen, seen + n));
+  IBU_HIP(launch_abundance_add(ctx->cfg, table_of(ab->wl), d_records, d_class, n, class_mask & 0xFFu, ab->d_counters, pick_stream(ctx, stream)));
+  return IBU_OK;
+}
+extern "C" int32_t ibu_abundance_counts(ibu_ctx_t* ctx, const ibu_abundance_t* ab, const uint64_t* d_codes, size_t k, uint64_t* d_counts,
+                                        void* stream) {
+  int32_t rc = check_ctx(ctx);
+  if (rc) return rc;
+  rc = check_abundance(ctx, ab);
+  if (rc) return rc;
+  if (k == 0) return IBU_OK;
+  if (!d_codes || !aligned8(d_codes) || !d_counts || !aligned8(d_counts)) return err_arg("d_codes / d_counts must be non-NULL and 8-byte aligned");
+  if (k >= kAbundanceMax) return err_arg("abundance_counts handles fewer than 2^40 codes per call");
+  IBU_HIP(launch_abundance_counts(ctx->cfg, table_of(ab->wl), ab->d_counters, d_codes, k, d_counts, pick_stream(ctx, stream)));
+  return IBU_OK;
+}
+extern "C" int32_t ibu_resolve_barcodes(ibu_ctx_t* ctx, const ibu_whitelist_t* wl, const ibu_abundance_t* ab, void* d_records, size_t n,
+                                        uint64_t num, uint64_t den, uint8_t* d_class, ibu_resolve_counts_t* counts, void* stream) {
+  int32_t rc = check_ctx(ctx);
+  if (rc) return rc;
+  if (!wl) return err_arg("wl is NULL");
+  if (wl->ctx != ctx) return err_arg("the whitelist was created on another context");
+  rc = check_abundance(ctx, ab);
+  if (rc) return rc;
+  if (ab->wl != wl) return err_arg("the abundance belongs to another whitelist");
+  if (num < 1 || num > den || den >= (1ull << 24) || 2 * num <= den)
+    return err_arg("the share num / den must satisfy 1 <= num <= den < 2^24 and 2 * num > den");
+  if (counts) *counts = ibu_resolve_counts_t{0, 0, 0, 0};
+  if (n == 0) return IBU_OK;
+  if (!d_records || !aligned8(d_records)) return err_arg("d_records must be non-NULL and 8-byte aligned");
+  if (!d_class) return err_arg("d_class is NULL");
+  if (n >= (1ull << 40)) return err_arg("resolve_barcodes handles fewer than 2^40 records per call");
+  hipStream_t st = pick_stream(ctx, stream);
+  const WhitelistTable t = table_of(wl);
+  if (!counts) {   // nothing to bring back: the launch stays asynchronous and touches no per-call state
+    IBU_HIP(launch_resolve(ctx->cfg, t, ab->d_counters, d_records, n, num, den, d_class, nullptr, st));
+    return IBU_OK;
+  }
+  if (!ctx->d_resolve_acc) IBU_HIP(ctx_malloc(ctx, reinterpret_cast<void**>(&ctx->d_resolve_acc), kCorrectAccBytes));
+  IBU_HIP(hipMemsetAsync(ctx->d_resolve_acc, 0, kCorrectAccBytes, st));
+  IBU_HIP(launch_resolve(ctx->cfg, t, ab->d_counters, d_records, n, num, den, d_class, ctx->d_resolve_acc, st));
+  IBU_HIP(launch_correct_fold(ctx->d_resolve_acc, st));
+  IBU_HIP(hipMemcpyAsync(ctx->h_pinned, ctx->d_resolve_acc, 4 * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
+  IBU_HIP(hipStreamSynchronize(st));
+  counts->examined = ctx->h_pinned[0];
+  counts->resolved = ctx->h_pinned[1];
+  counts->below_share = ctx->h_pinned[2];
+  counts->unseen = ctx->h_pinned[3];
   return IBU_OK;
 }
 extern "C" int32_t ibu_select_records(ibu_ctx_t* ctx, const void* d_records, const uint8_t* d_class, size_t n, uint32_t keep_mask,

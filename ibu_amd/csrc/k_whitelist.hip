@@ -313,6 +313,184 @@ ibu_k_select_scatter(const u64* __restrict__ recs, const uint8_t* __restrict__ c
 }
 
 // =============================================================================================
+// abundance and resolve (ibu_abundance_add, ibu_abundance_counts, ibu_resolve_barcodes).  An abundance is one u64 counter
+// per table slot and one more, at index `slots`, for the all-ones key that never enters the table.  add counts the records
+// whose barcode is in the whitelist; resolve gives an ambiguous record (class 2) to the candidate that holds at least
+// num / den of its candidates' reads.
+// The adds are scattered 8-byte integer atomics: one per counted record on input in read order.  Their rate on this chip
+// is not measured anywhere (the guides price float atomics, as bytes of well-shaped rows): profiles/README.md r15_a.
+// =============================================================================================
+static constexpr u64 kNoSlot = ~0ull;
+
+// wl_lookup that says where: the key's slot, `slots` for the all-ones key, kNoSlot for a key that is not in the whitelist.
+__device__ __forceinline__ u64 wl_lookup_slot(const u64* __restrict__ table, u32 mask, u32 shift, u32 has_ones, u64 key) {
+  if (key == kEmpty) return has_ones ? (u64)mask + 1 : kNoSlot;
+  u32 s = wl_slot(key, shift) & mask;
+  for (;;) {
+    const u64 k = table[s];
+    if (k == key) return s;
+    if (k == kEmpty) return kNoSlot;
+    s = (s + 1) & mask;
+  }
+}
+__device__ __forceinline__ bool ab_counted(const uint8_t* __restrict__ cls, u64 i, u32 class_mask) {
+  if (!cls) return true;
+  const u32 c = cls[i];
+  return c < 8u && ((class_mask >> c) & 1u);
+}
+__device__ __forceinline__ void ab_add(u64* __restrict__ counters, u64 slot, u64 v) {   // no value comes back: a no-return atomic
+  (void)__hip_atomic_fetch_add(counters + slot, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
+// The shape of ibu_k_correct: lane L owns records 2L and 2L+1 of the wave's tile.  Grouped input (sorted records, a few hot
+// barcodes) would put the 128 adds of a tile on one address, so runs of equal slot inside the tile are merged first: a
+// record is a head where its slot differs from the record before it (across the lane seam by shuffle), a head's run ends at
+// the next head (from the two head ballots), and a head whose slot counts issues one atomic with the run's length.
+extern "C" __global__ void __launch_bounds__(kBlock, 8)
+ibu_k_abundance_add(const uint8_t* __restrict__ recs, u32 ntiles, const WlArgs a, const uint8_t* __restrict__ cls, u32 class_mask,
+                    u64* __restrict__ counters) {
+  __shared__ __attribute__((aligned(16))) uint8_t lds[kWavesPerBlock * kTileBytes];
+  const u32 lane = threadIdx.x & (kWave - 1), wib = threadIdx.x >> 6;
+  uint8_t* tile = lds + wib * kTileBytes;
+  const u64 m = mask2(a.bc_len);
+  const u64 above = ~((2ull << lane) - 1);           // the lanes above this one (none for lane 63: 2 << 63 wraps to 0)
+  sweep_tiles<CorRegs>(
+      tile_range(ntiles, wib),
+      [&](CorRegs& g, u32 t) {
+        const uint8_t* src = recs + (size_t)t * kTileBytes + 16 * lane;
+#pragma unroll
+        for (int k = 0; k < 3; ++k) g.v[k] = ld16(src + 1024 * k);
+      },
+      [&](const CorRegs& g, u32 t) {
+        wave_lds_fence();
+#pragma unroll
+        for (int k = 0; k < 3; ++k) *reinterpret_cast<u32x4*>(tile + 1024 * k + 16 * lane) = g.v[k];
+        wave_lds_fence();
+        u64 s[2];
+#pragma unroll
+        for (int h = 0; h < 2; ++h) {
+          const u64 bc = *reinterpret_cast<const u64*>(tile + (2 * lane + h) * 24);
+          s[h] = ab_counted(cls, (u64)t * kTileRecs + 2 * lane + h, class_mask) ? wl_lookup_slot(a.table, a.mask, a.shift, a.has_ones, bc & m)
+                                                                                : kNoSlot;
+        }
+        const u64 prev = shfl_up64(s[1], 1);
+        const bool head0 = lane == 0 || s[0] != prev, head1 = s[1] != s[0];
+        const u64 h0 = __ballot(head0) & above, h1 = __ballot(head1) & above;
+        const u32 n0 = h0 ? 2u * (u32)__builtin_ctzll(h0) : (u32)kTileRecs, n1 = h1 ? 2u * (u32)__builtin_ctzll(h1) + 1u : (u32)kTileRecs;
+        const u32 next = n0 < n1 ? n0 : n1;          // the first head behind this lane's two records, or the tile's end
+        if (head0 && s[0] != kNoSlot) ab_add(counters, s[0], head1 ? 1u : next - 2 * lane);
+        if (head1 && s[1] != kNoSlot) ab_add(counters, s[1], next - (2 * lane + 1));
+      });
+}
+
+// One thread per record: the peeled head and the n % 128 rest.
+extern "C" __global__ void __launch_bounds__(kBlock)
+ibu_k_abundance_add_tail(const u64* __restrict__ recs, u64 row0, u64 n, const WlArgs a, const uint8_t* __restrict__ cls, u32 class_mask,
+                         u64* __restrict__ counters) {
+  const u64 i = row0 + (u64)blockIdx.x * kBlock + threadIdx.x;
+  if (i >= n || !ab_counted(cls, i, class_mask)) return;
+  const u64 s = wl_lookup_slot(a.table, a.mask, a.shift, a.has_ones, recs[3 * i] & mask2(a.bc_len));
+  if (s != kNoSlot) ab_add(counters, s, 1);
+}
+
+// out[j] = the counter of codes[j]; 0 for a code that is not in the whitelist or has bits at or above 2*bc_len.
+extern "C" __global__ void __launch_bounds__(kBlock)
+ibu_k_abundance_counts(const u64* __restrict__ codes, u64 k, const WlArgs a, const u64* __restrict__ counters, u64* __restrict__ out) {
+  const u64 stride = (u64)gridDim.x * kBlock, m = mask2(a.bc_len);
+  for (u64 j = (u64)blockIdx.x * kBlock + threadIdx.x; j < k; j += stride) {
+    const u64 key = codes[j];
+    const u64 s = (key & ~m) ? kNoSlot : wl_lookup_slot(a.table, a.mask, a.shift, a.has_ones, key);
+    out[j] = s != kNoSlot ? counters[s] : 0;
+  }
+}
+
+struct OpMax { template <class T> __device__ __forceinline__ T operator()(T a, T b) const { return b > a ? b : a; } };
+
+// One round of resolve: every lane brings at most one class-2 record (`has`, row `idx`) and gathers its barcode; the wave
+// takes them one after the other, as wl_search_wave does: lane L probes neighbours L and L + 64 and loads their counters,
+// the reductions give total and best, the ballots of "hit and count == best" name the winner (one candidate only: best > 0
+// and best / total >= num / den > 1/2), and the record's own lane writes the 8 barcode bytes and the class byte.
+// cnt: examined, resolved, below the share, unseen.
+__device__ __forceinline__ void resolve_round(const WlArgs& a, const u64* __restrict__ counters, u64 num, u64 den, u64* recs, uint8_t* cls,
+                                              bool has, u64 idx, u32 lane, u32 cnt[4]) {
+  const u64 m = mask2(a.bc_len);
+  const u64 bc = has ? recs[3 * idx] : 0;
+  const u32 nn = 3 * a.bc_len;
+  u64 todo = __ballot(has);
+  while (todo) {                                     // wave-uniform
+    const u32 src = (u32)__builtin_ctzll(todo);
+    todo &= todo - 1;
+    const u64 low = (((u64)(u32)__builtin_amdgcn_readlane((u32)(bc >> 32), src) << 32) | (u64)(u32)__builtin_amdgcn_readlane((u32)bc, src)) & m;
+    u64 c0 = 0, c1 = 0;
+    bool hit0 = false, hit1 = false;
+    if (lane < nn) {
+      const u64 s = wl_lookup_slot(a.table, a.mask, a.shift, a.has_ones, wl_neighbour(low, lane));
+      hit0 = s != kNoSlot;
+      if (hit0) c0 = counters[s];
+    }
+    if (lane + 64 < nn) {
+      const u64 s = wl_lookup_slot(a.table, a.mask, a.shift, a.has_ones, wl_neighbour(low, lane + 64));
+      hit1 = s != kNoSlot;
+      if (hit1) c1 = counters[s];
+    }
+    const u64 total = wave_reduce(c0 + c1, OpAdd{});
+    const u64 best = wave_reduce(c0 > c1 ? c0 : c1, OpMax{});
+    const bool win = best > 0 && best * den >= num * total;   // counters sum to at most 2^40, den < 2^24: no overflow
+    const u64 b0 = __ballot(hit0 && c0 == best), b1 = __ballot(hit1 && c1 == best);
+    const u32 j = b0 ? (u32)__builtin_ctzll(b0) : 64u + (u32)__builtin_ctzll(b1 | (1ull << 63));
+    if (lane == src) {
+      ++cnt[0];
+      if (win) {
+        recs[3 * idx] = (bc & ~m) | wl_neighbour(low, j);
+        cls[idx] = 4;                                // IBU_BARCODE_RESOLVED
+        ++cnt[1];
+      } else if (total) ++cnt[2];
+      else ++cnt[3];
+    }
+  }
+}
+
+// The four-bit mask of the bytes of w that equal 2 (bit k: byte k).
+__device__ __forceinline__ u32 bytes_eq2(u32 w) {
+  const u32 x = w ^ 0x02020202u;
+  const u32 z = ~(((x & 0x7F7F7F7Fu) + 0x7F7F7F7Fu) | x | 0x7F7F7F7Fu);   // 0x80 in every byte of x that is zero, exactly
+  return (((z >> 7) * 0x00204081u) >> 21) & 0xFu;                          // bits 0, 8, 16, 24 -> bits 21..24 (no two terms meet)
+}
+
+// Driven by the class bytes (16-byte aligned here): a UNIT is 1024 of them, one 16-byte load per lane.  A record is touched
+// only where its class is 2.
+static constexpr u32 kResolveUnit = 16 * kWave;
+extern "C" __global__ void __launch_bounds__(kBlock, 8)
+ibu_k_resolve(u64* recs, uint8_t* cls, u32 nunits, const WlArgs a, const u64* __restrict__ counters, u64 num, u64 den, u64* __restrict__ acc) {
+  __shared__ u32 part[kWavesPerBlock][4];
+  const u32 lane = threadIdx.x & (kWave - 1), wib = threadIdx.x >> 6;
+  u32 cnt[4] = {0, 0, 0, 0};
+  const TileRange tr = tile_range(nunits, wib);
+  for (u32 t = tr.t; t < tr.end; t += tr.stride) {   // wave-uniform
+    const u64 base = (u64)t * kResolveUnit + 16 * lane;
+    const u32x4 v = *reinterpret_cast<const u32x4*>(cls + base);
+    u32 m16 = bytes_eq2(v.x) | (bytes_eq2(v.y) << 4) | (bytes_eq2(v.z) << 8) | (bytes_eq2(v.w) << 12);
+    while (__ballot(m16 != 0)) {                     // wave-uniform: every lane's next class-2 record
+      const bool has = m16 != 0;
+      resolve_round(a, counters, num, den, recs, cls, has, base + (has ? (u32)__builtin_ctz(m16) : 0u), lane, cnt);
+      m16 &= m16 - 1;
+    }
+  }
+  if (acc) wl_flush_totals(cnt, acc, part);          // uniform over the grid
+}
+
+// One class byte per lane: the bytes in front of the first 16-byte boundary of the class array and the rest behind the last unit.
+extern "C" __global__ void __launch_bounds__(kBlock)
+ibu_k_resolve_tail(u64* recs, uint8_t* cls, u64 row0, u64 row1, const WlArgs a, const u64* __restrict__ counters, u64 num, u64 den,
+                   u64* __restrict__ acc) {
+  __shared__ u32 part[kWavesPerBlock][4];
+  const u64 i = row0 + (u64)blockIdx.x * kBlock + threadIdx.x;
+  u32 cnt[4] = {0, 0, 0, 0};
+  resolve_round(a, counters, num, den, recs, cls, i < row1 && cls[i] == 2, i, threadIdx.x & (kWave - 1), cnt);
+  if (acc) wl_flush_totals(cnt, acc, part);
+}
+
+// =============================================================================================
 // Launchers
 // =============================================================================================
 size_t whitelist_slots(size_t w) {   // a power of two, at least 2 w (load factor at most 1/2) and at least 1024
@@ -363,6 +541,66 @@ hipError_t launch_correct(const LaunchCfg& cfg, const WhitelistTable& wl, void* 
 hipError_t launch_correct_fold(uint64_t* acc, hipStream_t st) {
   (void)hipGetLastError();
   hipLaunchKernelGGL(ibu_k_correct_fold, dim3(1), dim3(kReduceSlots), 0, st, (u64*)acc);
+  return hipGetLastError();
+}
+
+static inline WlArgs wl_args(const WhitelistTable& wl, uint32_t search) {
+  WlArgs a;
+  a.table = (const u64*)wl.table; a.mask = (u32)(wl.slots - 1); a.shift = 64u - log2_of(wl.slots); a.has_ones = wl.has_ones ? 1u : 0u;
+  a.bc_len = wl.bc_len; a.search = search;
+  return a;
+}
+hipError_t launch_abundance_add(const LaunchCfg& cfg, const WhitelistTable& wl, const void* recs, const uint8_t* d_class, size_t n,
+                                uint32_t class_mask, uint64_t* counters, hipStream_t st) {
+  (void)hipGetLastError();
+  if (n == 0) return hipSuccess;
+  if (n / kTileRecs > 0xFFFFFFFFull) return hipErrorInvalidValue;
+  const WlArgs a = wl_args(wl, 0);
+  const Span sp[1] = {{recs, 24}};
+  const RowSplit rs = split_rows(cfg, sp, 1, n, kTileRecs);   // an 8-B aligned base peels exactly one record
+  if (rs.head)
+    hipLaunchKernelGGL(ibu_k_abundance_add_tail, dim3(tail_grid(rs.head)), dim3(kBlock), 0, st, (const u64*)recs, (u64)0, (u64)rs.head, a, d_class,
+                       class_mask, (u64*)counters);
+  if (rs.main) {
+    const u32 ntiles = (u32)(rs.main / kTileRecs);
+    static std::atomic<int> occ;
+    hipLaunchKernelGGL(ibu_k_abundance_add, dim3(grid_for(ntiles, cfg.cus, resident_blocks<kBlock>(cfg, ibu_k_abundance_add, 0, &occ))),
+                       dim3(kBlock), 0, st, adv((const uint8_t*)recs, 24 * rs.head), ntiles, a, adv(d_class, rs.head), class_mask, (u64*)counters);
+  }
+  if (rs.head + rs.main < n)
+    hipLaunchKernelGGL(ibu_k_abundance_add_tail, dim3(tail_grid(n - rs.head - rs.main)), dim3(kBlock), 0, st, (const u64*)recs,
+                       (u64)(rs.head + rs.main), (u64)n, a, d_class, class_mask, (u64*)counters);
+  return hipGetLastError();
+}
+hipError_t launch_abundance_counts(const LaunchCfg& cfg, const WhitelistTable& wl, const uint64_t* counters, const uint64_t* codes, size_t k,
+                                   uint64_t* out, hipStream_t st) {
+  (void)hipGetLastError();
+  if (k == 0) return hipSuccess;
+  hipLaunchKernelGGL(ibu_k_abundance_counts, dim3(capped_grid(cfg, k, kBlock)), dim3(kBlock), 0, st, (const u64*)codes, (u64)k, wl_args(wl, 0),
+                     (const u64*)counters, (u64*)out);
+  return hipGetLastError();
+}
+hipError_t launch_resolve(const LaunchCfg& cfg, const WhitelistTable& wl, const uint64_t* counters, void* recs, size_t n, uint64_t num,
+                          uint64_t den, uint8_t* d_class, uint64_t* acc, hipStream_t st) {
+  (void)hipGetLastError();
+  if (n == 0) return hipSuccess;
+  const WlArgs a = wl_args(wl, 1);
+  size_t head = (size_t)((16 - (reinterpret_cast<uintptr_t>(d_class) & 15u)) & 15u);   // class bytes in front of the first 16-byte boundary
+  if (head > n) head = n;
+  const size_t main = ((n - head) / kResolveUnit) * kResolveUnit;
+  if (cfg.trace_rows) fprintf(stderr, "ibu rows: n=%zu head=%zu tiled=%zu rest=%zu tile=%u\n", n, head, main, n - head - main, kResolveUnit);
+  if (head)
+    hipLaunchKernelGGL(ibu_k_resolve_tail, dim3(tail_grid(head)), dim3(kBlock), 0, st, (u64*)recs, d_class, (u64)0, (u64)head, a,
+                       (const u64*)counters, (u64)num, (u64)den, (u64*)acc);
+  if (main) {
+    const u32 nunits = (u32)(main / kResolveUnit);   // n < 2^40: below 2^30
+    static std::atomic<int> occ;
+    hipLaunchKernelGGL(ibu_k_resolve, dim3(grid_for(nunits, cfg.cus, resident_blocks<kBlock>(cfg, ibu_k_resolve, 0, &occ))), dim3(kBlock), 0, st,
+                       adv((u64*)recs, 24 * head), d_class + head, nunits, a, (const u64*)counters, (u64)num, (u64)den, (u64*)acc);
+  }
+  if (head + main < n)
+    hipLaunchKernelGGL(ibu_k_resolve_tail, dim3(tail_grid(n - head - main)), dim3(kBlock), 0, st, (u64*)recs, d_class, (u64)(head + main), (u64)n, a,
+                       (const u64*)counters, (u64)num, (u64)den, (u64*)acc);
   return hipGetLastError();
 }
 

@@ -210,6 +210,16 @@ static constexpr size_t kCorrectAccBytes = (size_t)kReduceSlots * 4 * sizeof(uin
 hipError_t launch_correct(const LaunchCfg&, const WhitelistTable& wl, void* recs, size_t n, uint32_t max_mismatches, uint8_t* d_class,
                           uint64_t* acc, hipStream_t st);
 hipError_t launch_correct_fold(uint64_t* acc, hipStream_t st);
+// abundance and resolve (ibu_abundance_add, ibu_abundance_counts, ibu_resolve_barcodes).  counters: wl.slots + 1 u64, one per table
+// slot and the last for the all-ones key.  add: d_class nullable (every record counts), otherwise the records whose class c < 8 has
+// bit c of class_mask set.  resolve: d_class required; acc (nullable) as for launch_correct — examined, resolved, below the share,
+// unseen — folded by launch_correct_fold.
+hipError_t launch_abundance_add(const LaunchCfg&, const WhitelistTable& wl, const void* recs, const uint8_t* d_class, size_t n,
+                                uint32_t class_mask, uint64_t* counters, hipStream_t st);
+hipError_t launch_abundance_counts(const LaunchCfg&, const WhitelistTable& wl, const uint64_t* counters, const uint64_t* codes, size_t k,
+                                   uint64_t* out, hipStream_t st);
+hipError_t launch_resolve(const LaunchCfg&, const WhitelistTable& wl, const uint64_t* counters, void* recs, size_t n, uint64_t num,
+                          uint64_t den, uint8_t* d_class, uint64_t* acc, hipStream_t st);
 // select: count + scan leave the number of kept records in scratch[0] (u64) and every unit's offset behind it; scatter writes them.
 size_t select_scratch_bytes(size_t n);
 hipError_t launch_select_count(const LaunchCfg&, const uint8_t* d_class, size_t n, uint32_t keep_mask, void* scratch, size_t scratch_bytes,

@@ -363,6 +363,8 @@ class MmapReader {
 namespace device {
 class Whitelist;
 using CorrectCounts = ibu_correct_counts_t;
+class Abundance;
+using ResolveCounts = ibu_resolve_counts_t;
 using MoleculeCounts = ibu_molecule_counts_t;
 using CellCounts = ibu_cell_counts_t;
 using SaturationPoint = ibu_saturation_point_t;
@@ -453,6 +455,14 @@ class Context {
                                         void* st = nullptr);
   inline void correct_barcodes_async(const Whitelist& wl, void* d_recs, size_t n, uint32_t max_mismatches = 1, uint8_t* d_class = nullptr,
                                      void* st = nullptr);
+  // ambiguous barcodes (class 2 of correct_barcodes) to the candidate that holds at least num / den of the reads `ab` counted for the
+  // candidates, in place over records and class bytes (ibu_resolve_barcodes): a resolved record gets class IBU_BARCODE_RESOLVED;
+  // returns the four totals (synchronises).  resolve_barcodes_async: no totals, nothing synchronised.
+  // select_records(.., 0b10011, ..) then keeps exact, corrected and resolved records
+  inline ResolveCounts resolve_barcodes(const Whitelist& wl, const Abundance& ab, void* d_recs, size_t n, uint8_t* d_class, uint64_t num = 39,
+                                        uint64_t den = 40, void* st = nullptr);
+  inline void resolve_barcodes_async(const Whitelist& wl, const Abundance& ab, void* d_recs, size_t n, uint8_t* d_class, uint64_t num = 39,
+                                     uint64_t den = 40, void* st = nullptr);
   // one index per (barcode, umi) molecule of sorted records (ibu_classify_molecules): d_class (n bytes, or nullptr for the totals
   // only) gets IBU_MOLECULE_KEPT / _MINOR / _TIED per record; select_records(.., 1u << IBU_MOLECULE_KEPT, ..) drops the chimeric reads
   MoleculeCounts classify_molecules(const void* d_sorted, size_t n, uint8_t* d_class, bool tie_first = false, void* st = nullptr) {
@@ -590,6 +600,41 @@ class Whitelist {
  private:
   ibu_whitelist_t* w_ = nullptr;
 };
+// One read counter per entry of a whitelist (ibu_abundance_t), all zero at first.  Destroy it before its whitelist.
+class Abundance {
+ public:
+  Abundance(Context& ctx, const Whitelist& wl, void* st = nullptr) : ctx_(ctx.raw()) { check(ibu_abundance_create(ctx_, wl.raw(), st, &a_)); }
+  Abundance(Abundance&& o) noexcept : ctx_(o.ctx_), a_(o.a_) { o.a_ = nullptr; }
+  Abundance(const Abundance&) = delete;
+  Abundance& operator=(const Abundance&) = delete;
+  ~Abundance() { if (a_) ibu_abundance_destroy(a_); }
+  const ibu_abundance_t* raw() const { return a_; }
+  // counts the records whose barcode is in the whitelist (ibu_abundance_add): all of them with d_class == nullptr, else those whose
+  // class c < 8 has bit c of class_mask set.  Asynchronous; accumulates over calls
+  void add(const void* d_recs, size_t n, const uint8_t* d_class = nullptr, uint32_t class_mask = 1, void* st = nullptr) {
+    check(ibu_abundance_add(ctx_, a_, d_recs, d_class, n, class_mask, st));
+  }
+  // d_counts[j] = the counter of d_codes[j], 0 for a code that is not in the whitelist (ibu_abundance_counts); asynchronous
+  void counts(const uint64_t* d_codes, size_t k, uint64_t* d_counts, void* st = nullptr) const {
+    check(ibu_abundance_counts(ctx_, a_, d_codes, k, d_counts, st));
+  }
+  void reset(void* st = nullptr) { check(ibu_abundance_reset(a_, st)); }
+  size_t device_bytes() const { size_t n = 0; check(ibu_abundance_info(a_, &n)); return n; }
+
+ private:
+  ibu_ctx_t* ctx_ = nullptr;
+  ibu_abundance_t* a_ = nullptr;
+};
+inline ResolveCounts Context::resolve_barcodes(const Whitelist& wl, const Abundance& ab, void* d_recs, size_t n, uint8_t* d_class, uint64_t num,
+                                               uint64_t den, void* st) {
+  ResolveCounts c{};
+  check(ibu_resolve_barcodes(c_, wl.raw(), ab.raw(), d_recs, n, num, den, d_class, &c, st));
+  return c;
+}
+inline void Context::resolve_barcodes_async(const Whitelist& wl, const Abundance& ab, void* d_recs, size_t n, uint8_t* d_class, uint64_t num,
+                                            uint64_t den, void* st) {
+  check(ibu_resolve_barcodes(c_, wl.raw(), ab.raw(), d_recs, n, num, den, d_class, nullptr, st));
+}
 inline CorrectCounts Context::correct_barcodes(const Whitelist& wl, void* d_recs, size_t n, uint32_t max_mismatches, uint8_t* d_class, void* st) {
   CorrectCounts c{};
   check(ibu_correct_barcodes(c_, wl.raw(), d_recs, n, max_mismatches, d_class, &c, st));

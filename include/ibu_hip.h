@@ -800,6 +800,64 @@ int32_t ibu_correct_barcodes(ibu_ctx_t* ctx, const ibu_whitelist_t* wl, void* d_
  * context's sort scratch (8 bytes per 2048 records). */
 int32_t ibu_select_records(ibu_ctx_t* ctx, const void* d_records, const uint8_t* d_class, size_t n, uint32_t keep_mask,
                            void* d_out, size_t cap, size_t* n_out, void* stream);
+/* Whitelist abundance and the resolution of ambiguous barcodes, on the device (k_whitelist.hip): what recovers the records that
+ * ibu_correct_barcodes classes 2 (two or more whitelist entries one substitution away) with a prior, as Cell Ranger and STARsolo
+ * (1MM_multi) do — the candidate that carries nearly all of the exactly matching reads among the candidates wins.  Records carry no
+ * base qualities, so the prior is the whole posterior, in integers.  The reference has nothing like this; the semantics are this
+ * library's and are stated in full here.
+ * An ABUNDANCE belongs to one whitelist and one context.  It holds one uint64_t counter per slot of the whitelist's table and one for
+ * the all-ones key, which never enters the table: a counter for every whitelist entry.  All counters are zero after create and after
+ * reset.  Create is synchronous; reset is asynchronous on `stream`.  info: device_bytes (nullable) = what the counters take, 8 bytes
+ * per table slot + 8.  Destroy the abundance before its whitelist, and both before their context.  A NULL ctx on a host without a
+ * device: IBU_ERR_NO_DEVICE (ibu_abundance_create).  A whitelist, abundance or context that do not belong together:
+ * IBU_ERR_INVALID_ARG, in every call below.
+ *
+ * ibu_abundance_add: record i CONTRIBUTES when d_class == NULL, or when d_class[i] < 8 and bit d_class[i] of class_mask is set.  For
+ * such a record, low = barcode & mask(2*bc_len); if low is in the whitelist, its counter grows by one.  Records whose low is not in
+ * the whitelist are skipped silently: d_class == NULL on raw records counts the exact hits, class_mask = 0b0011 on the records and
+ * classes ibu_correct_barcodes left counts exact and corrected reads.  Asynchronous; reads only (records 8-byte aligned, class bytes
+ * at any alignment).  Counters accumulate over calls, and calls on several streams may add to one abundance at once: the adds are
+ * integer atomics, and the result does not depend on the order of the records or of the calls.  n == 0 is OK and touches nothing.
+ * n < 2^40 per call, and no counter ever exceeds 2^40: the library keeps, on the host, the running total of records OFFERED to add
+ * since create / reset (n per call, whatever contributes), and a call that would take it past 2^40 is refused with
+ * IBU_ERR_INVALID_ARG (detail.a = the total so far, detail.b = n) and adds nothing.
+ * Reads 24 B per record (+ 1 B of class) and a table line for each contributing barcode; one 8-byte atomic add per run of records
+ * with equal counter inside a 128-record tile — one per counted record on input in read order, one per tile and barcode on sorted
+ * input.
+ *
+ * ibu_abundance_counts: d_counts[j] = the counter of d_codes[j] (k codes and k counts in DEVICE memory, 8-byte aligned); 0 for a code
+ * that is not in the whitelist, and 0 for a code with bits at or above 2*bc_len.  Asynchronous.  k == 0 is OK.  The read-back for
+ * users and tests.
+ *
+ * ibu_resolve_barcodes: every record with d_class[i] == 2 (IBU ambiguous) is EXAMINED; no other record is read or written.  Its
+ * CANDIDATES are the neighbours of low that are in the whitelist — the neighbour set of ibu_correct_barcodes, recomputed here.
+ * total = the sum of the candidates' counters, best = the largest.  The record is RESOLVED iff best > 0 and best * den >= num * total
+ * (integers; equality passes, as in the set test of ibu_filter_barcodes).  1 <= num <= den < 2^24 and 2 * num > den are required
+ * (anything else: IBU_ERR_INVALID_ARG, whatever n is): a share above one half makes the winner unique, so there is no tie rule, and
+ * with counters of at most 2^40 no product overflows 64 bits.  A resolved record gets the winner in the low 2*bc_len bits of its
+ * barcode — the bits above, umi and index are untouched — and its class byte becomes IBU_BARCODE_RESOLVED (4).  Otherwise record and
+ * class byte stay as they are.  d_class is required (NULL with n > 0: IBU_ERR_INVALID_ARG), n bytes at any alignment.
+ * counts (nullable): examined; resolved; below_share = examined records with total > 0 that were not resolved; unseen = those with
+ * total == 0 (the three sum to examined).  Non-NULL synchronises `stream`, NULL leaves the call asynchronous; the totals pass through
+ * the context under the rule ibu_correct_barcodes states: of the calls in flight on one context, at most one may ask.
+ * n == 0 is OK and touches nothing (counts = 0).  n < 2^40.  A refused call touches nothing.
+ * ibu_select_records(..., keep_mask = 0b10011) then keeps exact, corrected and resolved records.  Resolve adds nothing to the
+ * abundance, so a second call finds no class-2 record it could resolve and changes nothing more.
+ * Reads 1 B of class per record, sixteen per lane and load where the alignment of d_class allows; gathers the 8 barcode bytes of the
+ * class-2 records only; a wave examines its class-2 records one after the other, 64 neighbours (probe and counter) at a time. */
+#define IBU_BARCODE_RESOLVED 4
+typedef struct ibu_abundance ibu_abundance_t;
+typedef struct ibu_resolve_counts { uint64_t examined, resolved, below_share, unseen; } ibu_resolve_counts_t;
+int32_t ibu_abundance_create(ibu_ctx_t* ctx, const ibu_whitelist_t* wl, void* stream, ibu_abundance_t** out);
+int32_t ibu_abundance_reset(ibu_abundance_t* ab, void* stream);
+int32_t ibu_abundance_info(const ibu_abundance_t* ab, size_t* device_bytes);
+void ibu_abundance_destroy(ibu_abundance_t* ab); /* before its whitelist is destroyed */
+int32_t ibu_abundance_add(ibu_ctx_t* ctx, ibu_abundance_t* ab, const void* d_records, const uint8_t* d_class, size_t n,
+                          uint32_t class_mask, void* stream);
+int32_t ibu_abundance_counts(ibu_ctx_t* ctx, const ibu_abundance_t* ab, const uint64_t* d_codes, size_t k, uint64_t* d_counts,
+                             void* stream);
+int32_t ibu_resolve_barcodes(ibu_ctx_t* ctx, const ibu_whitelist_t* wl, const ibu_abundance_t* ab, void* d_records, size_t n,
+                             uint64_t num, uint64_t den, uint8_t* d_class, ibu_resolve_counts_t* counts, void* stream);
 /* BGZF / DEFLATE on the device (k_inflate.hip).  A bgzip file — to niffler (src/io/reader.rs:345-352) a gzip stream of many
  * members — is a chain of independent deflate blocks of at most 64 KiB whose compressed and uncompressed sizes stand in their
  * headers and trailers: the blocks can be found without inflating them, their COMPRESSED bytes can cross the PCIe link (half the

@@ -5,7 +5,12 @@ ibu_select_records (classes 0 | 1) against ibu_device_copy of the bytes it keeps
   python tools/correctbench.py [--records 1e9] [--whitelists 1e5,1e6,6.9e6] [--errors 0,0.02,0.1] [--random 0.01] [--rounds 5]
 Barcodes of 16 bases drawn uniformly from the whitelist; `errors` of them get one substituted base, `random` of them (1 % unless
 told otherwise; 0 leaves the hit path alone) are uniform random.
-Times are HIP events on the stream the calls run on (the select call synchronises once inside: its time includes that)."""
+Times are HIP events on the stream the calls run on (the select call synchronises once inside: its time includes that).
+  python tools/correctbench.py --resolve [--records 1e9] [--whitelists 1e5,6.9e6] [--errors 0.02] [--rounds 5]
+A leg of its own (the lines above are not printed): the resolution of ambiguous barcodes.  Per configuration, in one process on one
+array: ibu_reduce (the plain 24-byte read), ibu_device_copy of the array, ibu_correct_barcodes, ibu_abundance_add over the class-0
+records in read order, the same add without class bytes in read order and on the same records SORTED (what run merging is for),
+and ibu_resolve_barcodes at 39/40."""
 import argparse
 import ctypes as C
 import json
@@ -24,6 +29,7 @@ def main():
     ap.add_argument("--errors", default="0,0.02,0.1")
     ap.add_argument("--rounds", type=int, default=5)
     ap.add_argument("--random", type=float, default=0.01, help="share of uniform random barcodes (they always take the miss path)")
+    ap.add_argument("--resolve", action="store_true", help="the abundance / resolve leg instead of the correct / select one")
     a = ap.parse_args()
     import torch                                             # before the library, as bench.py does
     torch.cuda.init()
@@ -83,6 +89,9 @@ def main():
             torch.cuda.synchronize()
             ctx.serialize(cols[0], cols[1], cols[2], n, orig)
             ctx.synchronize()
+            if a.resolve:
+                resolve_leg(ia, ctx, st, timed, stat, wl, d, orig, out, d_cls, n, asked, bc_len, len(codes), err, a)
+                continue
             t_red, t_cor, t_sel, t_cpy = [], [], [], []
             counts = kept = None
             k_out = C.c_size_t()
@@ -103,6 +112,52 @@ def main():
                               "select": sel, "copy_of_kept": cpy, "select_over_copy": round(sel["median_ms"] / cpy["median_ms"], 3)}), flush=True)
         wl.close()
     ctx.close()
+
+
+def resolve_leg(ia, ctx, st, timed, stat, wl, d, orig, out, d_cls, n, asked, bc_len, w, err, a):
+    t = {k: [] for k in ("reduce", "copy", "correct", "add_read_order", "add_read_order_no_class", "add_sorted_no_class", "resolve")}
+    ab = wl.abundance()
+    for _ in range(a.rounds + 1):
+        ctx.copy(d, orig, 24 * n, stream=st)
+        t["reduce"].append(timed(lambda: ctx.reduce(d, n, stream=st, reset=False, fetch=False)))
+        t["copy"].append(timed(lambda: ctx.copy(out, d, 24 * n, stream=st)))
+        t["correct"].append(timed(lambda: ctx.correct_barcodes(wl, d, n, 1, d_cls, counts=False, stream=st)))
+        ab.reset(stream=st)
+        t["add_read_order_no_class"].append(timed(lambda: ab.add(d, n, stream=st)))
+        ab.reset(stream=st)
+        t["add_read_order"].append(timed(lambda: ab.add(d, n, d_cls, 1, stream=st)))
+        t["resolve"].append(timed(lambda: ctx.resolve_barcodes(wl, ab, d, n, d_cls, counts=False, stream=st)))
+    ctx.copy(d, orig, 24 * n, stream=st)
+    counts = ctx.correct_barcodes(wl, d, n, 1, d_cls, stream=st)
+    ab.reset(stream=st)
+    ab.add(d, n, d_cls, 1, stream=st)
+    totals = ctx.resolve_barcodes(wl, ab, d, n, d_cls, stream=st)
+    ab.reset(stream=st)
+    ab.add(d, n, stream=st)                                  # what the sorted add must reproduce: the whitelist hits after correct and resolve
+    ctx.synchronize(st)
+    probe = ia.DeviceBuffer.wrap(ctx, d.ptr, 8 * 3 * min(n, 4096)).download("<u8")[::3] & ((1 << (2 * bc_len)) - 1)   # the first 4096 barcodes
+    before = ab.counts(probe, stream=st)
+    ctx.copy(out, d, 24 * n, stream=st)
+    ctx.sort_records(out, d, n, stream=st)                   # d is scratch from here on
+    for _ in range(a.rounds + 1):
+        ab.reset(stream=st)
+        t["add_sorted_no_class"].append(timed(lambda: ab.add(out, n, stream=st)))
+    same = bool((ab.counts(probe, stream=st) == before).all())
+    hits = counts["exact"] + counts["corrected"] + totals["resolved"]
+    s = {k: stat(v) for k, v in t.items()}
+    ms = {k: v["median_ms"] for k, v in s.items()}
+    print(json.dumps({"leg": "resolve", "n": n, "records_asked": asked, "bc_len": bc_len, "w": w, "table_MiB": round(wl.device_bytes / 2**20, 1),
+                      "counters_MiB": round(ab.device_bytes / 2**20, 1), "errors": err, "random": a.random, "counts": counts, "resolve_totals": totals,
+                      "share": [39, 40], **s,
+                      "add_over_correct": round(ms["add_read_order"] / ms["correct"], 3),
+                      "add_no_class_over_correct": round(ms["add_read_order_no_class"] / ms["correct"], 3),
+                      "add_sorted_over_correct": round(ms["add_sorted_no_class"] / ms["correct"], 3),
+                      "resolve_over_correct": round(ms["resolve"] / ms["correct"], 3),
+                      "correct_over_reduce": round(ms["correct"] / ms["reduce"], 3),
+                      "atomics_per_s_read_order": round(counts["exact"] / ms["add_read_order"] * 1e3),
+                      "atomics_per_s_read_order_no_class": round(hits / ms["add_read_order_no_class"] * 1e3),
+                      "sorted_counters_equal_read_order": same}), flush=True)
+    ab.close()
 
 
 if __name__ == "__main__":
