@@ -271,6 +271,10 @@ extern "C" {
                               d_counts: *mut u64, d_unique_umis: *mut u64, cap: usize, n_barcodes: *mut usize,
                               n_barcode_umi_pairs: *mut usize, stream: *mut c_void) -> i32;
     pub fn ibu_records_swap_umi_index(ctx: *mut ibu_ctx_t, d_src: *const c_void, d_dst: *mut c_void, n: usize, stream: *mut c_void) -> i32;
+    pub fn ibu_merge_sorted(ctx: *mut ibu_ctx_t, d_a: *const c_void, na: usize, d_b: *const c_void, nb: usize, d_out: *mut c_void,
+                            d_source: *mut u8, stream: *mut c_void) -> i32;
+    pub fn ibu_merge_sorted_runs(ctx: *mut ibu_ctx_t, d_records: *mut c_void, d_tmp: *mut c_void, run_lengths: *const usize, k: usize,
+                                 stream: *mut c_void) -> i32;
     pub fn ibu_pair_counts(ctx: *mut ibu_ctx_t, d_sorted_records: *const c_void, n: usize, d_first: *mut u64, d_second: *mut u64,
                            d_records_per_pair: *mut u64, d_distinct_third: *mut u64, cap: usize, n_pairs: *mut usize,
                            n_triples: *mut usize, stream: *mut c_void) -> i32;

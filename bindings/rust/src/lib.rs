@@ -537,6 +537,17 @@ pub mod device {
         pub fn sort_records(&self, recs: &DeviceBuf, tmp: &DeviceBuf, n: usize) -> Result<()> {
             check(unsafe { ffi::ibu_sort_records(self.raw, recs.ptr, tmp.ptr, n, std::ptr::null_mut()) })
         }
+        /// `ibu_merge_sorted`: the stable merge of the sorted `a[..na]` and `b[..nb]` into `out` (equal records: those of `a`
+        /// first).  `source`: one byte per output record, 0 = from `a`, 1 = from `b`.  `out` must overlap neither input.
+        pub fn merge_sorted(&self, a: &DeviceBuf, na: usize, b: &DeviceBuf, nb: usize, out: &DeviceBuf, source: Option<&DeviceBuf>) -> Result<()> {
+            let s = source.map_or(std::ptr::null_mut(), |d| d.ptr as *mut u8);
+            check(unsafe { ffi::ibu_merge_sorted(self.raw, a.ptr, na, b.ptr, nb, out.ptr, s, std::ptr::null_mut()) })
+        }
+        /// `ibu_merge_sorted_runs`: `recs` = consecutive sorted runs of these lengths -> all of them sorted, what `sort_records`
+        /// gives; `tmp` is as many bytes of scratch.
+        pub fn merge_sorted_runs(&self, recs: &DeviceBuf, tmp: &DeviceBuf, run_lengths: &[usize]) -> Result<()> {
+            check(unsafe { ffi::ibu_merge_sorted_runs(self.raw, recs.ptr, tmp.ptr, run_lengths.as_ptr(), run_lengths.len(), std::ptr::null_mut()) })
+        }
         /// The same order over several shards, one per context (= per GPU), in one call (`ibu_sort_records_contexts`): shard i
         /// ends up with the i-th range of the global order; returns the new record counts.  `shards[i]` = (records, tmp, n,
         /// capacity in records) on `ctxs[i]`'s device.  Leave headroom in `capacity` (up to 32 shards the owners are cut at the

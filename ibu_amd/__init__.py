@@ -945,6 +945,24 @@ class Context:
     def sort_records(self, d_records, d_tmp, n, stream=None):
         _check(lib.ibu_sort_records(self._c, _dptr(d_records), _dptr(d_tmp), n, stream))
 
+    def merge_sorted(self, d_a, na, d_b, nb, d_out=None, source=False, stream=None):
+        """ibu_merge_sorted: the stable merge of two sorted record arrays (equal records: those of d_a first) ->
+        (d_out, d_source | None).  d_out: (na + nb) * 24 bytes that overlap neither input, allocated when None; source:
+        True allocates, or a DeviceBuffer receives, one byte per output record (0 = from d_a, 1 = from d_b).
+        Asynchronous on `stream`."""
+        n = na + nb
+        if d_out is None:
+            d_out = self.alloc(max(24 * n, 1))
+        d_source = self.alloc(max(n, 1)) if source is True else (source or None)
+        _check(lib.ibu_merge_sorted(self._c, _dptr(d_a), na, _dptr(d_b), nb, _dptr(d_out), _dptr(d_source), stream))
+        return d_out, d_source
+
+    def merge_sorted_runs(self, d_records, d_tmp, run_lengths, stream=None):
+        """ibu_merge_sorted_runs: d_records = consecutive sorted runs of these lengths -> all of them sorted, in place
+        (what sort_records gives); d_tmp: as many bytes of scratch.  Asynchronous on `stream`."""
+        lengths = (C.c_size_t * max(len(run_lengths), 1))(*[int(x) for x in run_lengths])
+        _check(lib.ibu_merge_sorted_runs(self._c, _dptr(d_records), _dptr(d_tmp), lengths, len(run_lengths), stream))
+
     @staticmethod
     def sort_records_contexts(ctxs, shards):
         """The sort over several shards, one per context (= per GPU), in one call (ibu_sort_records_contexts): shards =

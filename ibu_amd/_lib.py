@@ -175,6 +175,8 @@ SIGNATURES = {
     "ibu_writer_write_ascii_batch": (i32, [vp, vp, vp, vp, vp, vp, u64, sz, u32, u32, vp]),
     "ibu_barcode_counts": (i32, [vp, vp, sz, vp, vp, vp, sz, P(sz), P(sz), vp]),
     "ibu_records_swap_umi_index": (i32, [vp, vp, vp, sz, vp]),
+    "ibu_merge_sorted": (i32, [vp, vp, sz, vp, sz, vp, vp, vp]),
+    "ibu_merge_sorted_runs": (i32, [vp, vp, vp, P(sz), sz, vp]),
     "ibu_pair_counts": (i32, [vp, vp, sz, vp, vp, vp, vp, sz, P(sz), P(sz), vp]),
     "ibu_count_matrix": (i32, [vp, vp, vp, sz, u32, vp, vp, vp, vp, sz, P(sz), P(sz), vp]),
     "ibu_whitelist_create": (i32, [vp, vp, sz, u32, vp, P(vp)]),

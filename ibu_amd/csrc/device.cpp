@@ -8,6 +8,8 @@
 #include <string.h>
 
 #include <chrono>
+#include <utility>
+#include <vector>
 
 #include <cstddef>
 #include "bgzf_plan.hpp"
@@ -1006,6 +1008,71 @@ extern "C" int32_t ibu_sort_records(ibu_ctx_t* ctx, void* d_records, void* d_tmp
   if (rc) return rc;
   IBU_HIP(launch_sort_records(ctx->cfg, d_records, d_tmp, n, ctx->d_sort_scratch, ctx->sort_scratch_bytes,
                               pick_stream(ctx, stream)));
+  return IBU_OK;
+}
+// ---- merge of sorted records (k_merge.hip).  The semantics are this library's: include/ibu_hip.h.
+// One two-way merge, arguments checked by the caller; an empty input is a copy of the other (and its source bytes a fill).
+static int32_t merge_two(ibu_ctx_t* ctx, const void* d_a, size_t na, const void* d_b, size_t nb, void* d_out, uint8_t* d_source, hipStream_t st) {
+  if (na == 0 || nb == 0) {
+    const size_t n = na + nb;
+    if (n == 0) return IBU_OK;
+    IBU_HIP(launch_copy(ctx->cfg, na ? d_a : d_b, d_out, 24 * n, st));
+    if (d_source) IBU_HIP(hipMemsetAsync(d_source, na ? 0 : 1, n, st));
+    return IBU_OK;
+  }
+  IBU_HIP(launch_merge(ctx->cfg, d_a, na, d_b, nb, d_out, d_source, ctx->d_sort_scratch, st));
+  return IBU_OK;
+}
+extern "C" int32_t ibu_merge_sorted(ibu_ctx_t* ctx, const void* d_a, size_t na, const void* d_b, size_t nb, void* d_out, uint8_t* d_source,
+                                    void* stream) {
+  int32_t rc = check_ctx(ctx);
+  if (rc) return rc;
+  if (na >= (1ull << 40) || nb >= (1ull << 40)) return err_arg("merge_sorted handles fewer than 2^40 records per input");
+  const size_t n = na + nb;
+  if (n == 0) return IBU_OK;
+  if ((na && (!d_a || !aligned8(d_a))) || (nb && (!d_b || !aligned8(d_b))) || !d_out || !aligned8(d_out))
+    return err_arg("d_a / d_b / d_out must be non-NULL and 8-byte aligned");
+  const uintptr_t o = reinterpret_cast<uintptr_t>(d_out), a = reinterpret_cast<uintptr_t>(d_a), b = reinterpret_cast<uintptr_t>(d_b);
+  if ((na && o < a + 24 * na && a < o + 24 * n) || (nb && o < b + 24 * nb && b < o + 24 * n)) return err_arg("d_out overlaps an input");
+  rc = ensure_sort_scratch(ctx, merge_scratch_bytes(n));
+  if (rc) return rc;
+  return merge_two(ctx, d_a, na, d_b, nb, d_out, d_source, pick_stream(ctx, stream));
+}
+extern "C" int32_t ibu_merge_sorted_runs(ibu_ctx_t* ctx, void* d_records, void* d_tmp, const size_t* run_lengths, size_t k, void* stream) {
+  int32_t rc = check_ctx(ctx);
+  if (rc) return rc;
+  if (k == 0) return IBU_OK;
+  if (!run_lengths) return err_arg("run_lengths is NULL");
+  size_t n = 0;
+  for (size_t i = 0; i < k; ++i) {
+    if (run_lengths[i] >= (1ull << 40)) return err_arg("merge_sorted_runs handles fewer than 2^40 records per call");
+    n += run_lengths[i];
+    if (n >= (1ull << 40)) return err_arg("merge_sorted_runs handles fewer than 2^40 records per call");
+  }
+  if (n == 0 || k == 1) return IBU_OK;
+  if (!d_records || !d_tmp || !aligned8(d_records) || !aligned8(d_tmp)) return err_arg("d_records / d_tmp must be non-NULL and 8-byte aligned");
+  const uintptr_t r = reinterpret_cast<uintptr_t>(d_records), t = reinterpret_cast<uintptr_t>(d_tmp);
+  if (r < t + 24 * n && t < r + 24 * n) return err_arg("d_tmp overlaps d_records");
+  rc = ensure_sort_scratch(ctx, merge_scratch_bytes(n));   // once, for the largest merge: nothing is allocated between the levels
+  if (rc) return rc;
+  hipStream_t st = pick_stream(ctx, stream);
+  std::vector<size_t> runs(run_lengths, run_lengths + k), next;
+  uint8_t* from = static_cast<uint8_t*>(d_records);
+  uint8_t* to = static_cast<uint8_t*>(d_tmp);
+  while (runs.size() > 1) {                                // one level: neighbouring runs pairwise, an unpaired last run copied
+    next.clear();
+    size_t at = 0;
+    for (size_t i = 0; i < runs.size(); i += 2) {
+      const size_t na = runs[i], nb = i + 1 < runs.size() ? runs[i + 1] : 0;
+      rc = merge_two(ctx, from + 24 * at, na, from + 24 * (at + na), nb, to + 24 * at, nullptr, st);
+      if (rc) return rc;
+      next.push_back(na + nb);
+      at += na + nb;
+    }
+    runs.swap(next);
+    std::swap(from, to);
+  }
+  if (from != d_records) IBU_HIP(launch_copy(ctx->cfg, from, d_records, 24 * n, st));   // an odd number of levels ended in d_tmp
   return IBU_OK;
 }
 // ---- count matrix: distinct UMIs and reads per (barcode, index) pair (k_records.hip: the field exchange; k_aggregate.hip: the

@@ -197,6 +197,13 @@ hipError_t launch_saturation(const LaunchCfg&, const void* recs, size_t n, uint6
                              size_t scratch_bytes, hipStream_t st);
 // record i of dst = {w0, w2, w1} of record i of src; dst == src (in place) or disjoint (k_records.hip)
 hipError_t launch_swap_fields(const LaunchCfg&, const void* src, void* dst, size_t n, hipStream_t st);
+// the stable two-way merge of sorted records (ibu_merge_sorted, ibu_merge_sorted_runs; k_merge.hip).  A wave merges one output tile of
+// kMergeTile records.  na, nb > 0 (an empty input is a copy: the caller's); `scratch`: merge_scratch_bytes(na + nb) bytes, 8-byte
+// aligned; src (nullable): one byte per output record, 0 = from a, 1 = from b.  out must not overlap a or b.
+static constexpr int kMergeTile = 256;
+size_t merge_scratch_bytes(size_t n);
+hipError_t launch_merge(const LaunchCfg&, const void* a, size_t na, const void* b, size_t nb, void* out, uint8_t* src, void* scratch,
+                        hipStream_t st);
 // barcode correction against a whitelist (k_whitelist.hip).  The table: `slots` 64-bit keys (a power of two, at least 2 w), all ones =
 // free; the all-ones key itself (a legal code at 32 bases) travels beside it as `has_ones`.
 struct WhitelistTable { const uint64_t* table; size_t slots; uint32_t bc_len; bool has_ones; };

@@ -417,6 +417,15 @@ class Context {
   }
   void copy(void* d_dst, const void* d_src, size_t bytes, void* st = nullptr) { check(ibu_device_copy(c_, d_dst, d_src, bytes, st)); }
   void sort_records(void* d_recs, void* d_tmp, size_t n, void* st = nullptr) { check(ibu_sort_records(c_, d_recs, d_tmp, n, st)); }
+  // the stable merge of two sorted record arrays into d_out (equal records: those of d_a first); d_source (nullable): one byte per
+  // output record, 0 = from d_a, 1 = from d_b (ibu_merge_sorted).  Asynchronous.
+  void merge_sorted(const void* d_a, size_t na, const void* d_b, size_t nb, void* d_out, uint8_t* d_source = nullptr, void* st = nullptr) {
+    check(ibu_merge_sorted(c_, d_a, na, d_b, nb, d_out, d_source, st));
+  }
+  // d_recs = consecutive sorted runs of these lengths -> all of them sorted, what sort_records gives (ibu_merge_sorted_runs)
+  void merge_sorted_runs(void* d_recs, void* d_tmp, const std::vector<size_t>& run_lengths, void* st = nullptr) {
+    check(ibu_merge_sorted_runs(c_, d_recs, d_tmp, run_lengths.data(), run_lengths.size(), st));
+  }
   // the sort over several shards, one per context (= per GPU), in one call: shard i ends up with the i-th range of the global
   // order and shards[i].n says how long it is (ibu_sort_records_contexts)
   static void sort_records_contexts(const std::vector<Context*>& ctxs, std::vector<ibu_sort_shard_t>& shards) {

@@ -433,6 +433,39 @@ int32_t ibu_device_copy(ibu_ctx_t* ctx, void* d_dst, const void* d_src, size_t b
  * varying bytes only and one finishing pass (option "sort_hybrid"); the result is the same bytes on every path. */
 int32_t ibu_sort_records(ibu_ctx_t* ctx, void* d_records, void* d_tmp, size_t n, void* stream);
 
+/* Merge of sorted records on the device (k_merge.hip): the way several sorted pieces — lanes, samples, shards, pulled batches that were
+ * each sorted — become one sorted array without being sorted again.  The reference has no merge; the semantics are this library's and
+ * are stated in full here.  Order is ibu_record_cmp: the three little-endian 64-bit words of a record in storage order, unsigned;
+ * records that went through ibu_records_swap_umi_index merge the same way.
+ *
+ * ibu_merge_sorted: d_out[0 .. na+nb) = the STABLE merge of the sorted inputs d_a[0 .. na) and d_b[0 .. nb): among equal records those
+ * of a come first, and within each input the order is kept.  Per record: a[i] lands at i + #{b < a[i]}, b[j] lands at j + #{a <= b[j]}.
+ * Per output prefix of length d: the number of a-records in it is the result of the binary search over i in
+ * [max(0, d - nb), min(d, na)] with the step `if a[mid] <= b[d-1-mid] then lo = mid + 1 else hi = mid` (the two statements are the
+ * same; the library partitions the output by the second and fills each part by the first).  d_source (nullable): d_source[p] = 0 or 1,
+ * the input output record p came from — equal records are the same 24 bytes, so stability shows only here; it is also the lane or
+ * sample tag of a two-way merge.
+ *   Arrays are 8-byte aligned.  Full 16-byte stores need d_out (and d_source, where given) 16-byte aligned; an output of 8-byte phase
+ *   runs on word stores.  d_a and d_b may have either 8-byte phase.  na, nb < 2^40, all index arithmetic in 64 bits (inputs of 2^32
+ *   records and more — about 100 GB — are UNTESTED).  na == 0 or nb == 0: a copy of the other input, d_source filled; both 0: OK,
+ *   nothing touched.  d_out overlapping either input: IBU_ERR_INVALID_ARG, nothing touched.  The two inputs may overlap each other or
+ *   be the same array.
+ *   Unsorted input yields an unspecified permutation of the input multiset (in fact a followed by b wherever the kernels notice), with
+ *   every write inside d_out[0, na+nb) and d_source[0, na+nb); nothing is ever read or written out of bounds.
+ *   Asynchronous on `stream`, no synchronisation; the only allocation is growth of the context's sort scratch (8 bytes per 256 output
+ *   records).  48 B per record: one read, one write.
+ *
+ * ibu_merge_sorted_runs: d_records holds k consecutive sorted runs of run_lengths[0 .. k) records (a host array; n = their sum); d_tmp
+ * is n*24 B of scratch, the contract of ibu_sort_records.  On return, in stream order, d_records holds all n records sorted: byte for
+ * byte what ibu_sort_records gives on the same input.  ceil(log2 k) levels of pairwise merges of neighbouring runs ping-pong between
+ * the two buffers, an unpaired last run of a level is copied, and when the last level lands in d_tmp (an odd number of levels) one
+ * more copy brings it back: (levels [+ 1]) x 48 B per record.  k == 0 or n == 0: OK; k == 1: nothing to do; runs of length 0 are
+ * allowed.  run_lengths is read before the call returns; asynchronous otherwise.  n >= 2^40, a NULL or misaligned pointer with n > 0
+ * and k > 1, or d_tmp overlapping d_records: IBU_ERR_INVALID_ARG. */
+int32_t ibu_merge_sorted(ibu_ctx_t* ctx, const void* d_a, size_t na, const void* d_b, size_t nb, void* d_out, uint8_t* d_source,
+                         void* stream);
+int32_t ibu_merge_sorted_runs(ibu_ctx_t* ctx, void* d_records, void* d_tmp, const size_t* run_lengths, size_t k, void* stream);
+
 /* The same order over SEVERAL shards, one per context (= per GPU), in one call — the multi-GPU form of the sort (SURVEY 8f-2:
  * sample sort with one device-to-device exchange), as ibu_mmap_process_contexts is the multi-GPU form of process_parallel.
  * EXPERIMENTAL: rehearsed with up to 16 contexts on one GPU, never run on two distinct GPUs (no such box in any round).

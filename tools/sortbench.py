@@ -1,7 +1,9 @@
 #!/usr/bin/env python3
 """Throughput of ibu_sort_records on device-resident records.
-  python tools/sortbench.py [--records 1e8,1e9] [--lens 16,12] [--rounds 3]"""
+  python tools/sortbench.py [--records 1e8,1e9] [--lens 16,12] [--rounds 3]
+  python tools/sortbench.py --merge [--records 1e9]   the merge of sorted records beside the copy, the field exchange and the sort"""
 import argparse
+import ctypes as C
 import json
 import os
 import statistics
@@ -47,9 +49,123 @@ def shards_main(a, ia, bc_len, umi_len):
             t.free()
 
 
+def merge_main(a):
+    """ibu_merge_sorted on two equal sorted halves of n resident records (three shapes) and ibu_merge_sorted_runs at k = 2, 8, 64,
+    beside the yardsticks on the same arrays in the same process: ibu_device_copy of n * 24 bytes, ibu_records_swap_umi_index out
+    of place and ibu_sort_records of the concatenation.  HIP-event times on one side stream; one warm-up and --rounds repeats each;
+    one JSON line."""
+    import torch
+    torch.cuda.init()
+    import ibu_amd as ia
+    from ibu_amd import _check, _dptr, lib
+
+    ctx = ia.Context(0)
+    side = torch.cuda.Stream()
+    st = side.cuda_stream
+    n = int(float((a.records or "1e9").split(",")[0])) // 128 * 128   # whole runs at every k
+    bc_len, umi_len = (int(x) for x in a.lens.split(","))
+    half = n // 2
+    orig, d, t = ctx.alloc(24 * n), ctx.alloc(24 * n), ctx.alloc(24 * n)
+    src = ctx.alloc(n)
+    at = lambda buf, first, count: ia.DeviceBuffer.wrap(ctx, buf.ptr + 24 * first, 24 * max(count, 1))
+
+    def timed(fn):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record(side)
+        fn()
+        e1.record(side)
+        e1.synchronize()
+        return e0.elapsed_time(e1)
+
+    def rounds(fn, before=None):
+        v = []
+        for _ in range(a.rounds + 1):
+            if before:
+                before()
+            torch.cuda.synchronize()
+            ctx.synchronize()
+            v.append(timed(fn))
+        v = v[1:]                                              # the first is the warm-up
+        return {"median_ms": round(statistics.median(v), 3), "min_ms": round(min(v), 3), "max_ms": round(max(v), 3)}
+
+    def restore():                                             # d = the records as `orig` holds them
+        ctx.copy(d, orig, 24 * n)
+        ctx.synchronize()
+
+    def sort_runs(k):                                          # orig = k sorted runs of n / k records
+        per = n // k
+        for j in range(k):
+            ctx.sort_records(at(orig, j * per, per), t, per)
+        ctx.synchronize()
+
+    def random_records():                                      # 16/12 keys, index = row number (below 2^32)
+        ctx.generate(0x1B0000A, 0, n, bc_len, umi_len, orig)
+        ctx.synchronize()
+
+    def whitelist_records(k=100_000):                          # barcodes from k distinct ones, skewed (rank ~ k u^3): long runs of equal barcode
+        g = torch.Generator(device="cuda").manual_seed(0x1B0000B)
+        cols = [ctx.alloc(8 * n) for _ in range(3)]
+        wl = _rand_bits(torch, g, 2 * bc_len, k)
+        bc, um, ix = (torch.as_tensor(c, device="cuda").view(torch.int64) for c in cols)
+        step = 1 << 26
+        for lo in range(0, n, step):
+            hi = min(n, lo + step)
+            u = torch.rand(hi - lo, generator=g, device="cuda", dtype=torch.float64)
+            bc[lo:hi] = wl[(u * u * u * k).to(torch.int64).clamp_(max=k - 1)]
+            um[lo:hi] = _rand_bits(torch, g, 2 * umi_len, hi - lo)
+            ix[lo:hi] = torch.arange(lo, hi, device="cuda", dtype=torch.int64)
+        del u, bc, um, ix
+        torch.cuda.synchronize()
+        ctx.serialize(cols[0], cols[1], cols[2], n, orig)
+        ctx.synchronize()
+        for c in cols:
+            c.free()
+
+    def two_way(shape):
+        if shape == "disjoint":                                # one sort of everything: the halves are disjoint key ranges
+            sort_runs(1)
+        else:
+            sort_runs(2)
+        a_, b_ = at(orig, 0, half), at(orig, half, n - half)
+        merge = lambda s: _check(lib.ibu_merge_sorted(ctx._c, _dptr(a_), half, _dptr(b_), n - half, _dptr(d), _dptr(s), st))
+        res = {"merge": rounds(lambda: merge(None)), "merge_with_source": rounds(lambda: merge(src)),
+               "copy": rounds(lambda: _check(lib.ibu_device_copy(ctx._c, _dptr(d), _dptr(orig), 24 * n, st))),
+               "swap_out_of_place": rounds(lambda: _check(lib.ibu_records_swap_umi_index(ctx._c, _dptr(orig), _dptr(d), n, st)))}
+        merge(None)
+        ctx.synchronize(st)
+        assert ctx.is_sorted(d, n)
+        res["sort_of_concatenation"] = rounds(lambda: _check(lib.ibu_sort_records(ctx._c, _dptr(d), _dptr(t), n, st)), before=restore)
+        res["merge_over_copy"] = round(res["merge"]["median_ms"] / res["copy"]["median_ms"], 3)
+        res["merge_over_sort"] = round(res["merge"]["median_ms"] / res["sort_of_concatenation"]["median_ms"], 3)
+        return res
+
+    out = {"n": n, "lens": [bc_len, umi_len], "rounds": a.rounds, "two_way": {}, "runs": {}}
+    random_records()
+    out["two_way"]["interleaved"] = two_way("interleaved")
+    out["two_way"]["disjoint"] = two_way("disjoint")
+    whitelist_records()
+    out["two_way"]["whitelist"] = two_way("whitelist")
+    for k in (2, 8, 64):
+        random_records()
+        sort_runs(k)
+        lengths = (C.c_size_t * k)(*[n // k] * k)
+        r = {"merge_runs": rounds(lambda: _check(lib.ibu_merge_sorted_runs(ctx._c, _dptr(d), _dptr(t), lengths, k, st)), before=restore)}
+        ctx.synchronize(st)
+        assert ctx.is_sorted(d, n)
+        r["sort_of_concatenation"] = rounds(lambda: _check(lib.ibu_sort_records(ctx._c, _dptr(d), _dptr(t), n, st)), before=restore)
+        r["levels"] = (k - 1).bit_length()
+        r["merge_runs_over_sort"] = round(r["merge_runs"]["median_ms"] / r["sort_of_concatenation"]["median_ms"], 3)
+        out["runs"][str(k)] = r
+    print(json.dumps(out), flush=True)
+    for b in (orig, d, t, src):
+        b.free()
+
+
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--records", default="1e8")
+    ap.add_argument("--records", default=None, help="comma list (default 1e8; with --merge one value, default 1e9)")
+    ap.add_argument("--merge", action="store_true",
+                    help="time ibu_merge_sorted / ibu_merge_sorted_runs beside the copy, the field exchange and the sort on the same arrays")
     ap.add_argument("--lens", default="16,12")
     ap.add_argument("--rounds", type=int, default=3)
     ap.add_argument("--random-index", action="store_true",
@@ -69,6 +185,9 @@ def main():
                          "multi-GPU sort: K local sorts, the device-to-device exchange, K sorts of what arrived), n / K records each")
     ap.add_argument("--presorted", action="store_true", help="also time ibu_sort_records on the SORTED result (the already-sorted fast exit: one read-only census)")
     a = ap.parse_args()
+    if a.merge:
+        return merge_main(a)
+    a.records = a.records or "1e8"
     if a.whitelist:
         import torch                                         # before the library, as bench.py does: its HIP runtime is the process's
         torch.cuda.init()
