@@ -1,0 +1,330 @@
+// api_analysis.cpp — the entry points of the C ABI (include/ibu_hip.h) that analyse sorted records: the run-length aggregations
+// (barcode and pair counts, the count matrix), molecules, cells, the per-barcode metrics and filter, subsampling and the saturation
+// curve.  Each is a count pass, its totals read back, and an emit pass on a scratch sized by them.
+#include <stddef.h>
+
+#include "ctx.hpp"
+
+using namespace ibu;
+
+// the emit scratch of the run-length aggregations (16 bytes per entry): grows only
+static int32_t ensure_runs_scratch(ibu_ctx* ctx, size_t need) {
+  if (need <= ctx->runs_scratch_bytes) return IBU_OK;
+  if (ctx->d_runs_scratch) IBU_HIP(hipFree(ctx->d_runs_scratch));
+  ctx->d_runs_scratch = nullptr;
+  ctx->runs_scratch_bytes = 0;
+  IBU_HIP(ctx_malloc(ctx, &ctx->d_runs_scratch, need));
+  ctx->runs_scratch_bytes = need;
+  return IBU_OK;
+}
+// The first half of every run-length aggregation: a count scratch of `need` bytes, the count pass, and its two totals (runs, ranked
+// heads) read back into ctx->h_pinned[0..1].  Synchronises the stream.
+static int32_t runs_count_totals(ibu_ctx* ctx, const void* d_sorted_records, size_t n, size_t need, RunsCount what, hipStream_t st) {
+  int32_t rc = ensure_sort_scratch(ctx, need);
+  if (rc) return rc;
+  IBU_HIP(launch_runs_count(ctx->cfg, d_sorted_records, n, ctx->d_sort_scratch, ctx->sort_scratch_bytes, what, st));
+  IBU_HIP(read_back<2>(ctx, ctx->d_sort_scratch, st));
+  return IBU_OK;
+}
+// BarcodeAnalyzer (parallel.rs:72-98) on sorted device records.
+extern "C" int32_t ibu_barcode_counts(ibu_ctx_t* ctx, const void* d_sorted_records, size_t n, uint64_t* d_barcodes,
+                                      uint64_t* d_counts, uint64_t* d_unique_umis, size_t cap, size_t* n_barcodes,
+                                      size_t* n_barcode_umi_pairs, void* stream) {
+  int32_t rc = check_ctx(ctx);
+  if (rc) return rc;
+  if (!n_barcodes) return err_arg("n_barcodes is NULL");
+  *n_barcodes = 0;
+  if (n_barcode_umi_pairs) *n_barcode_umi_pairs = 0;
+  if (n == 0) return IBU_OK;
+  if ((rc = check_u64_ptr(d_sorted_records, "d_sorted_records")) != 0) return rc;
+  if ((rc = check_below_2_40(n, "barcode_counts", "records")) != 0) return rc;
+  hipStream_t st = pick_stream(ctx, stream);
+  const bool size_query = !d_barcodes && !d_counts && cap == 0;
+  // (with outputs to fill, the count pass keeps every segment's first few run heads: the emit pass then reads the records again only
+  // where runs are short — k_aggregate.hip)
+  rc = runs_count_totals(ctx, d_sorted_records, n, runs_scratch_bytes(n), size_query ? RunsCount::Barcode : RunsCount::BarcodeStash, st);
+  if (rc) return rc;
+  const uint64_t runs = ctx->h_pinned[0], pairs = ctx->h_pinned[1];
+  *n_barcodes = runs;
+  if (n_barcode_umi_pairs) *n_barcode_umi_pairs = pairs;
+  if (size_query) return IBU_OK;
+  if (!d_barcodes || !d_counts) return err_arg("d_barcodes / d_counts are NULL");
+  if (runs > cap) return err_arg("output capacity is smaller than the number of distinct barcodes (see *n_barcodes)");
+  rc = ensure_runs_scratch(ctx, runs_emit_scratch_bytes(runs));
+  if (rc) return rc;
+  IBU_HIP(launch_runs_emit(ctx->cfg, d_sorted_records, n, ctx->d_sort_scratch, ctx->d_runs_scratch, runs, pairs, d_barcodes, nullptr,
+                           d_counts, d_unique_umis, st));
+  return IBU_OK;
+}
+// ---- count matrix: distinct UMIs and reads per (barcode, index) pair (k_records.hip: the field exchange; k_aggregate.hip: the
+// pair-level run walk).  The semantics are this library's: include/ibu_hip.h.
+extern "C" int32_t ibu_records_swap_umi_index(ibu_ctx_t* ctx, const void* d_src, void* d_dst, size_t n, void* stream) {
+  int32_t rc = check_ctx(ctx);
+  if (rc) return rc;
+  if (n == 0) return IBU_OK;
+  if ((rc = check_u64_ptrs({d_src, d_dst}, "d_src / d_dst")) != 0) return rc;
+  if ((rc = check_below_2_40(n, "records_swap_umi_index", "records")) != 0) return rc;
+  if (d_dst != d_src && ranges_overlap(d_dst, 24 * n, d_src, 24 * n))
+    return err_arg("d_dst overlaps d_src (only d_dst == d_src, in place, is allowed)");
+  IBU_HIP(launch_swap_fields(ctx->cfg, d_src, d_dst, n, pick_stream(ctx, stream)));
+  return IBU_OK;
+}
+extern "C" int32_t ibu_pair_counts(ibu_ctx_t* ctx, const void* d_sorted_records, size_t n, uint64_t* d_first, uint64_t* d_second,
+                                   uint64_t* d_records_per_pair, uint64_t* d_distinct_third, size_t cap, size_t* n_pairs,
+                                   size_t* n_triples, void* stream) {
+  int32_t rc = check_ctx(ctx);
+  if (rc) return rc;
+  if (!n_pairs) return err_arg("n_pairs is NULL");
+  *n_pairs = 0;
+  if (n_triples) *n_triples = 0;
+  if (n == 0) return IBU_OK;
+  if ((rc = check_u64_ptr(d_sorted_records, "d_sorted_records")) != 0) return rc;
+  if ((rc = check_below_2_40(n, "pair_counts", "records")) != 0) return rc;
+  hipStream_t st = pick_stream(ctx, stream);
+  rc = runs_count_totals(ctx, d_sorted_records, n, runs_scratch_bytes(n), RunsCount::Pair, st);
+  if (rc) return rc;
+  const bool size_query = !d_first && !d_second && !d_records_per_pair && cap == 0;
+  const uint64_t pairs = ctx->h_pinned[0], triples = ctx->h_pinned[1];
+  *n_pairs = pairs;
+  if (n_triples) *n_triples = triples;
+  if (size_query) return IBU_OK;
+  if (!d_first || !d_second || !d_records_per_pair) return err_arg("d_first / d_second / d_records_per_pair are NULL");
+  if (!aligned8(d_first) || !aligned8(d_second) || !aligned8(d_records_per_pair) || !aligned8(d_distinct_third))
+    return err_arg("the output arrays must be 8-byte aligned");
+  if (pairs > cap) return err_capacity(pairs, cap, "entries", "n_pairs");
+  rc = ensure_runs_scratch(ctx, runs_emit_scratch_bytes(pairs));
+  if (rc) return rc;
+  IBU_HIP(launch_runs_emit(ctx->cfg, d_sorted_records, n, ctx->d_sort_scratch, ctx->d_runs_scratch, pairs, triples, d_first, d_second,
+                           d_records_per_pair, d_distinct_third, st));
+  return IBU_OK;
+}
+// One index per (w0, w1) molecule: the candidate with strictly the most records (k_molecules.hip; the rule: include/ibu_hip.h).
+extern "C" int32_t ibu_classify_molecules(ibu_ctx_t* ctx, const void* d_sorted_records, size_t n, uint32_t flags, uint8_t* d_class,
+                                          ibu_molecule_counts_t* counts, void* stream) {
+  int32_t rc = check_ctx(ctx);
+  if (rc) return rc;
+  if (flags & ~(uint32_t)IBU_MOLECULES_TIE_FIRST) return err_arg("unknown bit in flags");
+  if (counts) *counts = ibu_molecule_counts_t{0, 0, 0, 0, 0, 0, 0, 0};
+  if (n == 0) return IBU_OK;
+  if ((rc = check_u64_ptr(d_sorted_records, "d_sorted_records")) != 0) return rc;
+  if ((rc = check_below_2_40(n, "classify_molecules", "records")) != 0) return rc;
+  hipStream_t st = pick_stream(ctx, stream);
+  rc = runs_count_totals(ctx, d_sorted_records, n, molecules_scratch_bytes(n), RunsCount::Pair, st);
+  if (rc) return rc;
+  const uint64_t molecules = ctx->h_pinned[0], candidates = ctx->h_pinned[1];
+  rc = ensure_runs_scratch(ctx, molecules_run_scratch_bytes(candidates));
+  if (rc) return rc;
+  IBU_HIP(launch_molecules_classify(ctx->cfg, d_sorted_records, n, ctx->d_sort_scratch, ctx->d_runs_scratch, candidates,
+                                    (flags & IBU_MOLECULES_TIE_FIRST) != 0, d_class, st));
+  if (!counts) return IBU_OK;
+  IBU_HIP(read_back<5>(ctx, ctx->d_runs_scratch, st));
+  counts->molecules = molecules;
+  counts->candidates = candidates;
+  counts->resolved = ctx->h_pinned[0];
+  counts->tied = ctx->h_pinned[1];
+  counts->reads_kept = ctx->h_pinned[2];
+  counts->reads_minor = ctx->h_pinned[3];
+  counts->reads_tied = ctx->h_pinned[4];
+  return IBU_OK;
+}
+// Which barcodes are cells: one threshold on the per-barcode UMI (or read) count (k_cells.hip; the rule: include/ibu_hip.h).
+extern "C" int32_t ibu_call_cells(ibu_ctx_t* ctx, const void* d_sorted_records, size_t n, uint32_t mode, uint64_t param, uint32_t flags,
+                                  uint8_t* d_class, ibu_cell_counts_t* counts, void* stream) {
+  int32_t rc = check_ctx(ctx);
+  if (rc) return rc;
+  if (mode > IBU_CELLS_ORDMAG) return err_arg("unknown mode");
+  if (flags & ~(uint32_t)IBU_CELLS_BY_READS) return err_arg("unknown bit in flags");
+  if (mode != IBU_CELLS_MIN && param == 0) return err_arg("param must be at least 1 in the TOP and ORDMAG modes");
+  if (n && (rc = check_u64_ptr(d_sorted_records, "d_sorted_records")) != 0) return rc;
+  if ((rc = check_below_2_40(n, "call_cells", "records")) != 0) return rc;
+  if (counts) {   // (behind the last argument check: a refused call leaves the totals alone)
+    *counts = ibu_cell_counts_t{0, 0, 0, 0, 0, 0, 0, 0};
+    if (mode == IBU_CELLS_MIN) counts->threshold = param;
+  }
+  if (n == 0) return IBU_OK;
+  hipStream_t st = pick_stream(ctx, stream);
+  rc = runs_count_totals(ctx, d_sorted_records, n, cells_scratch_bytes(n), RunsCount::Barcode, st);
+  if (rc) return rc;
+  const uint64_t barcodes = ctx->h_pinned[0], pairs = ctx->h_pinned[1];
+  rc = ensure_runs_scratch(ctx, cells_run_scratch_bytes(barcodes));
+  if (rc) return rc;
+  IBU_HIP(launch_cells_call(ctx->cfg, d_sorted_records, n, ctx->d_sort_scratch, ctx->d_runs_scratch, barcodes, pairs, mode, param,
+                            (flags & IBU_CELLS_BY_READS) != 0, d_class, st));
+  if (!counts) return IBU_OK;
+  IBU_HIP(read_back<7>(ctx, ctx->d_runs_scratch, st));
+  counts->barcodes = barcodes;
+  counts->cells = ctx->h_pinned[0];
+  counts->reads_cells = ctx->h_pinned[1];
+  counts->reads_background = ctx->h_pinned[2];
+  counts->umis_cells = ctx->h_pinned[3];
+  counts->umis_background = ctx->h_pinned[4];
+  counts->threshold = ctx->h_pinned[5];
+  counts->baseline = ctx->h_pinned[6];
+  return IBU_OK;
+}
+// ---- per-barcode QC metrics and the barcode filter (k_metrics.hip).  The semantics are this library's: include/ibu_hip.h.
+static_assert(sizeof(ibu_barcode_limits_t) == sizeof(MetricsLimits) && offsetof(ibu_barcode_limits_t, set_of) == offsetof(MetricsLimits, set_of) &&
+                  offsetof(ibu_barcode_limits_t, set_num) == offsetof(MetricsLimits, set_num) && sizeof(ibu_barcode_filter_counts_t) == 96,
+              "ibu_hip.h and kernels.h disagree");
+static int32_t check_feature_set(const uint64_t* d_set, uint64_t set_bits, uint32_t set_word) {
+  if (!metrics_set_ok(d_set, set_bits, set_word))
+    return err_arg("the feature set: set_word must be 1 or 2, set_bits at most 2^32, d_set 8-byte aligned and non-NULL unless set_bits is 0");
+  return IBU_OK;
+}
+// The first half of both: the count pass and its five totals read back into ctx->h_pinned[0..4].  Synchronises the stream.
+static int32_t metrics_count_totals(ibu_ctx* ctx, const void* d_records, size_t n, const uint64_t* d_set, uint64_t set_bits, uint32_t set_word,
+                                    hipStream_t st) {
+  int32_t rc = ensure_sort_scratch(ctx, metrics_scratch_bytes(n));
+  if (rc) return rc;
+  IBU_HIP(launch_metrics_count(ctx->cfg, d_records, n, d_set, set_bits, set_word, ctx->d_sort_scratch, ctx->sort_scratch_bytes, st));
+  IBU_HIP(read_back<5>(ctx, ctx->d_sort_scratch, st));
+  return IBU_OK;
+}
+extern "C" int32_t ibu_barcode_metrics(ibu_ctx_t* ctx, const void* d_records, size_t n, const uint64_t* d_set, uint64_t set_bits,
+                                       uint32_t set_word, uint64_t* d_barcodes, uint64_t* d_reads, uint64_t* d_pairs, uint64_t* d_triples,
+                                       uint64_t* d_set_reads, uint64_t* d_set_triples, size_t cap, size_t* n_barcodes, void* stream) {
+  int32_t rc = check_ctx(ctx);
+  if (rc) return rc;
+  if (!n_barcodes) return err_arg("n_barcodes is NULL");
+  if ((rc = check_feature_set(d_set, set_bits, set_word)) != 0) return rc;
+  if ((rc = check_below_2_40(n, "barcode_metrics", "records")) != 0) return rc;
+  if (n && (rc = check_u64_ptr(d_records, "d_records")) != 0) return rc;
+  if (n && (!aligned8(d_barcodes) || !aligned8(d_reads) || !aligned8(d_pairs) || !aligned8(d_triples) || !aligned8(d_set_reads) ||
+            !aligned8(d_set_triples)))
+    return err_arg("the output arrays must be 8-byte aligned");
+  *n_barcodes = 0;
+  if (n == 0) return IBU_OK;
+  hipStream_t st = pick_stream(ctx, stream);
+  rc = metrics_count_totals(ctx, d_records, n, d_set, set_bits, set_word, st);
+  if (rc) return rc;
+  const uint64_t barcodes = ctx->h_pinned[0];
+  *n_barcodes = barcodes;
+  const bool any_column = d_barcodes || d_reads || d_pairs || d_triples || d_set_reads || d_set_triples;
+  if (!any_column) return IBU_OK;   // the size query (cap == 0), or a cap and nothing to write
+  if (barcodes > cap) return err_capacity(barcodes, cap, "barcodes", "n_barcodes");
+  rc = ensure_runs_scratch(ctx, metrics_run_scratch_bytes(barcodes));
+  if (rc) return rc;
+  IBU_HIP(launch_metrics_table(ctx->cfg, d_records, n, d_set, set_bits, set_word, ctx->d_sort_scratch, ctx->d_runs_scratch, barcodes, d_barcodes,
+                               d_reads, d_pairs, d_triples, d_set_reads, d_set_triples, st));
+  return IBU_OK;
+}
+extern "C" int32_t ibu_filter_barcodes(ibu_ctx_t* ctx, const void* d_records, size_t n, const uint64_t* d_set, uint64_t set_bits,
+                                       uint32_t set_word, const ibu_barcode_limits_t* limits, uint8_t* d_class,
+                                       ibu_barcode_filter_counts_t* counts, void* stream) {
+  int32_t rc = check_ctx(ctx);
+  if (rc) return rc;
+  if ((rc = check_feature_set(d_set, set_bits, set_word)) != 0) return rc;
+  if (!limits) return err_arg("limits is NULL");
+  const MetricsLimits lim{limits->min_reads, limits->max_reads, limits->min_pairs, limits->max_pairs, limits->min_triples, limits->max_triples,
+                          limits->set_num, limits->set_den, limits->set_of, 0};
+  if (!metrics_limits_ok(lim)) return err_arg("limits: set_of must be 0 (reads) or 1 (triples), and set_num <= set_den < 2^24");
+  if (n && (rc = check_u64_ptr(d_records, "d_records")) != 0) return rc;
+  if ((rc = check_below_2_40(n, "filter_barcodes", "records")) != 0) return rc;
+  if (counts) *counts = ibu_barcode_filter_counts_t{};   // (behind the last argument check: a refused call leaves the totals alone)
+  if (n == 0) return IBU_OK;
+  hipStream_t st = pick_stream(ctx, stream);
+  rc = metrics_count_totals(ctx, d_records, n, d_set, set_bits, set_word, st);
+  if (rc) return rc;
+  const uint64_t barcodes = ctx->h_pinned[0];
+  rc = ensure_runs_scratch(ctx, metrics_run_scratch_bytes(barcodes));
+  if (rc) return rc;
+  IBU_HIP(launch_metrics_filter(ctx->cfg, d_records, n, d_set, set_bits, set_word, ctx->d_sort_scratch, ctx->d_runs_scratch, barcodes, lim, d_class, st));
+  if (!counts) return IBU_OK;
+  IBU_HIP(read_back<10>(ctx, ctx->d_runs_scratch, st));
+  counts->barcodes = barcodes;
+  for (int c = 0; c < 4; ++c) {
+    counts->barcodes_by_class[c] = ctx->h_pinned[c];
+    counts->reads_by_class[c] = ctx->h_pinned[4 + c];
+  }
+  counts->triples_passed = ctx->h_pinned[8];
+  counts->set_triples_passed = ctx->h_pinned[9];
+  return IBU_OK;
+}
+// ---- read subsampling and the saturation curve (k_saturation.hip).  The semantics are this library's: include/ibu_hip.h.
+extern "C" int32_t ibu_subsample_class(ibu_ctx_t* ctx, size_t n, uint64_t first_row, uint64_t seed, uint64_t threshold, uint8_t* d_class,
+                                       size_t* n_kept, void* stream) {
+  int32_t rc = check_ctx(ctx);
+  if (rc) return rc;
+  if (!d_class && !n_kept) return err_arg("d_class and n_kept are both NULL: nothing to do");
+  if ((rc = check_below_2_40(n, "subsample_class", "rows")) != 0) return rc;
+  if (n_kept) *n_kept = 0;
+  if (n == 0) return IBU_OK;
+  hipStream_t st = pick_stream(ctx, stream);
+  const uint64_t base = sample_base(seed, first_row);
+  if (!n_kept) {   // nothing to bring back: the launch stays asynchronous and touches no per-call state
+    IBU_HIP(launch_subsample(ctx->cfg, n, base, threshold, d_class, nullptr, st));
+    return IBU_OK;
+  }
+  rc = ensure_sort_scratch(ctx, kSubsampleAccBytes);
+  if (rc) return rc;
+  IBU_HIP(launch_subsample(ctx->cfg, n, base, threshold, d_class, static_cast<uint64_t*>(ctx->d_sort_scratch), st));
+  IBU_HIP(read_back<1>(ctx, ctx->d_sort_scratch, st));
+  *n_kept = ctx->h_pinned[0];
+  return IBU_OK;
+}
+extern "C" int32_t ibu_saturation_curve(ibu_ctx_t* ctx, const void* d_sorted_records, size_t n, uint64_t first_row, uint64_t seed,
+                                        const uint64_t* thresholds, uint32_t k, ibu_saturation_point_t* points, void* stream) {
+  int32_t rc = check_ctx(ctx);
+  if (rc) return rc;
+  if (k == 0 || k > IBU_SATURATION_MAX_POINTS) return err_arg("k must be 1..32");
+  if (!thresholds || !points) return err_arg("thresholds / points are NULL");
+  for (uint32_t j = 1; j < k; ++j)
+    if (thresholds[j] < thresholds[j - 1]) return err_arg("the thresholds must be non-decreasing");
+  if (n && (rc = check_u64_ptr(d_sorted_records, "d_sorted_records")) != 0) return rc;
+  if ((rc = check_below_2_40(n, "saturation_curve", "records")) != 0) return rc;
+  if (n == 0) {
+    for (uint32_t j = 0; j < k; ++j) points[j] = ibu_saturation_point_t{thresholds[j], 0, 0, 0};
+    return IBU_OK;
+  }
+  hipStream_t st = pick_stream(ctx, stream);
+  rc = ensure_sort_scratch(ctx, saturation_scratch_bytes(n));
+  if (rc) return rc;
+  IBU_HIP(launch_saturation(ctx->cfg, d_sorted_records, n, sample_base(seed, first_row), thresholds, k, ctx->d_sort_scratch,
+                            ctx->sort_scratch_bytes, st));
+  IBU_HIP(read_back<3 * kSaturationMaxPoints>(ctx, static_cast<const uint8_t*>(ctx->d_sort_scratch) + saturation_points_offset(), st));
+  for (uint32_t j = 0; j < k; ++j)
+    points[j] = ibu_saturation_point_t{thresholds[j], ctx->h_pinned[j], ctx->h_pinned[kSaturationMaxPoints + j],
+                                       ctx->h_pinned[2 * kSaturationMaxPoints + j]};
+  return IBU_OK;
+}
+// TEST HOOK, not part of the ABI (not declared in include/ibu_hip.h, no binding): the selection ibu_call_cells runs, on a caller's
+// array — *value = the rank-th largest (1 <= rank <= n) of n device values below 2^40.  Records cannot reach the digit passes above
+// bit 31 at any size a test can afford; tests/test_gpu_cells.py reaches them through this.  Synchronises.
+extern "C" int32_t ibu_test_rank_select(ibu_ctx_t* ctx, const uint64_t* d_values, size_t n, uint64_t rank, uint64_t* value, void* stream) {
+  int32_t rc = check_ctx(ctx);
+  if (rc) return rc;
+  if (!value) return err_arg("value is NULL");
+  if (n == 0 || rank == 0 || rank > n) return err_arg("rank must be in 1..n");
+  if ((rc = check_u64_ptr(d_values, "d_values")) != 0) return rc;
+  if ((rc = check_below_2_40(n, "rank_select", "values")) != 0) return rc;
+  hipStream_t st = pick_stream(ctx, stream);
+  rc = ensure_runs_scratch(ctx, rank_select_work_bytes());
+  if (rc) return rc;
+  IBU_HIP(launch_rank_select(ctx->cfg, d_values, n, rank, ctx->d_runs_scratch, st));
+  IBU_HIP(read_back<1>(ctx, ctx->d_runs_scratch, st));
+  *value = ctx->h_pinned[0];
+  return IBU_OK;
+}
+extern "C" int32_t ibu_count_matrix(ibu_ctx_t* ctx, void* d_records, void* d_tmp, size_t n, uint32_t flags, uint64_t* d_barcodes,
+                                    uint64_t* d_indices, uint64_t* d_reads, uint64_t* d_umis, size_t cap, size_t* n_entries,
+                                    size_t* n_molecules, void* stream) {
+  int32_t rc = check_ctx(ctx);
+  if (rc) return rc;
+  if (!n_entries) return err_arg("n_entries is NULL");
+  *n_entries = 0;
+  if (n_molecules) *n_molecules = 0;
+  if (flags & ~(uint32_t)IBU_COUNT_LEAVE_SWAPPED) return err_arg("unknown bit in flags");
+  if (n == 0) return IBU_OK;
+  if ((rc = check_u64_ptrs({d_records, d_tmp}, "d_records / d_tmp")) != 0) return rc;
+  if (!d_barcodes || !d_indices || !d_reads) return err_arg("d_barcodes / d_indices / d_reads are NULL");
+  if (!aligned8(d_barcodes) || !aligned8(d_indices) || !aligned8(d_reads) || !aligned8(d_umis))
+    return err_arg("the output arrays must be 8-byte aligned");
+  if ((rc = check_below_2_40(n, "count_matrix", "records")) != 0) return rc;
+  if ((rc = ibu_records_swap_umi_index(ctx, d_records, d_records, n, stream)) != 0) return rc;
+  if ((rc = ibu_sort_records(ctx, d_records, d_tmp, n, stream)) != 0) return rc;
+  // a capacity that is too small is reported once the records are back in the state the flags promise
+  const int32_t rc_counts = ibu_pair_counts(ctx, d_records, n, d_barcodes, d_indices, d_reads, d_umis, cap, n_entries, n_molecules, stream);
+  if (!(flags & IBU_COUNT_LEAVE_SWAPPED) && (rc_counts == IBU_OK || rc_counts == IBU_ERR_INVALID_ARG))
+    if ((rc = ibu_records_swap_umi_index(ctx, d_records, d_records, n, stream)) != 0) return rc;
+  return rc_counts;
+}

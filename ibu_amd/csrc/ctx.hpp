@@ -1,15 +1,18 @@
-// ctx.hpp — the device context behind ibu_ctx_t (shared by device.cpp and stream.cpp).
+// ctx.hpp — the device context behind ibu_ctx_t (shared by device.cpp, the api_*.cpp entry points and stream.cpp).
 #pragma once
 #include <hip/hip_runtime.h>
 
 #include <thread>
 #include <vector>
 
+#include "api_checks.hpp"
 #include "common.hpp"
 #include "kernels.h"
 #include "numa.hpp"
 
 namespace ibu {
+
+constexpr size_t kPinnedWords = 128;   // ibu_ctx::h_pinned
 
 inline int32_t hip_fail(hipError_t e, const char* what) {
   if (e == hipErrorNoDevice || e == hipErrorInvalidDevice)
@@ -56,9 +59,8 @@ struct ibu_ctx {
   uint64_t* d_status = nullptr;  // [first_bad_record, n_bad_records]
   uint64_t* d_acc = nullptr;     // [count, sum0..2, xor0..2, pad]
   uint32_t* d_flag = nullptr;    // sortedness flag
-  uint64_t* d_correct_acc = nullptr;  // the class totals of an ibu_correct_barcodes call that asks for them (kCorrectAccBytes, on first use)
-  uint64_t* d_resolve_acc = nullptr;  // the totals of an ibu_resolve_barcodes call that asks for them (kCorrectAccBytes, on first use)
-  uint64_t* h_pinned = nullptr;  // 128 x u64 of pinned host memory for small read-backs
+  uint64_t* d_class_acc = nullptr;  // the totals of an ibu_correct_barcodes / ibu_resolve_barcodes call that asks for them (kCorrectAccBytes, on first use; such a call synchronises, so two never share it)
+  uint64_t* h_pinned = nullptr;  // kPinnedWords x u64 of pinned host memory for small read-backs
   void* d_sort_scratch = nullptr;
   size_t sort_scratch_bytes = 0;
   void* d_runs_scratch = nullptr;  // per-run starts / pair ranks of ibu_barcode_counts (grows only)
@@ -124,5 +126,25 @@ inline const NumaPlace& feed_place(const ibu_ctx* ctx) {
 }
 inline hipStream_t pick_stream(const ibu_ctx* ctx, void* stream) {
   return stream ? static_cast<hipStream_t>(stream) : ctx->stream;
+}
+
+// ---- what the entry points of the C ABI share beside api_checks.hpp (device.cpp, api_*.cpp) ----
+inline int32_t check_ctx(const ibu_ctx* ctx) {
+  if (!ctx) return err_arg("ctx is NULL");
+  hipError_t e = hipSetDevice(ctx->device);
+  if (e != hipSuccess) return hip_fail(e, "hipSetDevice");
+  return IBU_OK;
+}
+inline int32_t check_lens(uint32_t bc_len, uint32_t umi_len) {  // header.rs:180-185
+  if (bc_len == 0 || bc_len > 32) return err_bc_len(bc_len);
+  if (umi_len == 0 || umi_len > 32) return err_umi_len(umi_len);
+  return IBU_OK;
+}
+// How a small result comes back: WORDS u64 from d_src into ctx->h_pinned[0 ..], and the stream synchronised.
+template <size_t WORDS>
+inline hipError_t read_back(ibu_ctx* ctx, const void* d_src, hipStream_t st) {
+  static_assert(WORDS <= kPinnedWords, "the words come back through h_pinned");
+  const hipError_t e = hipMemcpyAsync(ctx->h_pinned, d_src, WORDS * sizeof(uint64_t), hipMemcpyDeviceToHost, st);
+  return e != hipSuccess ? e : hipStreamSynchronize(st);
 }
 }  // namespace ibu

@@ -20,7 +20,7 @@
 // ibu_k_class_fill: the pass that turns the ballots a walk kept into class bytes, for the molecule classification (k_molecules.hip,
 // on the pair-level count pass) and cell calling (k_cells.hip, on the barcode-level one).
 //
-// Launchers: launch_runs_count, launch_runs_emit, launch_class_fill (kernels.h); C ABI: ibu_barcode_counts, ibu_pair_counts (device.cpp).
+// Launchers: launch_runs_count, launch_runs_emit, launch_class_fill (kernels.h); C ABI: ibu_barcode_counts, ibu_pair_counts (api_analysis.cpp).
 #include "runs_walk.hpp"
 
 namespace ibu {

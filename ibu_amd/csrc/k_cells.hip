@@ -16,7 +16,7 @@
 //            per block of a grid that is capped.
 //   fill     launch_class_fill of k_aggregate.hip: the ballots and the run heads' bases give each record's barcode number, the
 //            verdicts leave as class bytes.
-// Launchers: launch_cells_call, launch_rank_select (kernels.h); C ABI: ibu_call_cells (device.cpp; its test hook ibu_test_rank_select runs the selection alone).
+// Launchers: launch_cells_call, launch_rank_select (kernels.h); C ABI: ibu_call_cells (api_analysis.cpp; its test hook ibu_test_rank_select runs the selection alone).
 #include "runs_walk.hpp"
 
 namespace ibu {

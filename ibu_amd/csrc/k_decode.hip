@@ -200,23 +200,20 @@ hipError_t launch_decode(const LaunchCfg& cfg, const void* recs, size_t n, uint3
   if (n == 0) return hipSuccess;
   const Span sp[4] = {{recs, 24}, {bc, bc_len}, {umi, umi_len}, {idx, 8}};
   const size_t kDecRecs = (size_t)kDecRecsTable[mode_of_len(bc_len)][mode_of_len(umi_len)];
-  const RowSplit rs = split_rows(cfg, sp, 4, n, kDecRecs);   // peel rows until every array is 16-B aligned
-  if (rs.head)
-    hipLaunchKernelGGL(ibu_k_decode_tail, dim3(tail_grid(rs.head)), dim3(256), 0, st, (const u64*)recs, (u64)0,
-                       (u64)rs.head, bc_len, umi_len, cfg.base_order, bc, umi, (u64*)idx);
-  if (rs.main) {
-    const u32 ntiles = (u32)(rs.main / kDecRecs);
-    const int mb = mode_of_len(bc_len), mu = mode_of_len(umi_len);
-    const int mo = cfg.base_order ? 1 : 0;
-    const DecFn fn = kDecTable[mo][mb][mu];
-    static std::atomic<int> occ[2][kNumLenModes][kNumLenModes];
-    hipLaunchKernelGGL(fn, dim3(grid_for(ntiles, cfg.cus, resident_blocks<kBlock>(cfg, fn, 0, &occ[mo][mb][mu]))), dim3(kBlock), 0,
-                       st, adv((const uint8_t*)recs, 24 * rs.head), ntiles, bc_len, umi_len, adv(bc, rs.head * bc_len),
-                       adv(umi, rs.head * umi_len), adv((u64*)idx, 8 * rs.head));
-  }
-  if (rs.head + rs.main < n)
-    hipLaunchKernelGGL(ibu_k_decode_tail, dim3(tail_grid(n - rs.head - rs.main)), dim3(256), 0, st, (const u64*)recs,
-                       (u64)(rs.head + rs.main), (u64)n, bc_len, umi_len, cfg.base_order, bc, umi, (u64*)idx);
+  launch_rows(cfg, sp, 4, n, kDecRecs,   // peel rows until every array is 16-B aligned
+      [&](u64 row0, u64 row1) {
+        hipLaunchKernelGGL(ibu_k_decode_tail, dim3(tail_grid(row1 - row0)), dim3(256), 0, st, (const u64*)recs, row0, row1, bc_len,
+                           umi_len, cfg.base_order, bc, umi, (u64*)idx);
+      },
+      [&](size_t head, u32 ntiles) {
+        const int mb = mode_of_len(bc_len), mu = mode_of_len(umi_len);
+        const int mo = cfg.base_order ? 1 : 0;
+        const DecFn fn = kDecTable[mo][mb][mu];
+        static std::atomic<int> occ[2][kNumLenModes][kNumLenModes];
+        hipLaunchKernelGGL(fn, dim3(grid_for(ntiles, cfg.cus, resident_blocks<kBlock>(cfg, fn, 0, &occ[mo][mb][mu]))), dim3(kBlock), 0,
+                           st, adv((const uint8_t*)recs, 24 * head), ntiles, bc_len, umi_len, adv(bc, head * bc_len),
+                           adv(umi, head * umi_len), adv((u64*)idx, 8 * head));
+      });
   return hipGetLastError();
 }
 
@@ -231,20 +228,16 @@ hipError_t launch_unpack(const LaunchCfg& cfg, const uint64_t* codes, size_t n, 
   if (n == 0) return hipSuccess;
   const Span sp[2] = {{codes, 8}, {out, len}};
   const size_t tile_recs = (size_t)kTileRecs * unpack_nt(len_of_mode(mode_of_len(len)));
-  const RowSplit rs = split_rows(cfg, sp, 2, n, tile_recs);
-  if (rs.head)
-    hipLaunchKernelGGL(ibu_k_unpack_tail, dim3(tail_grid(rs.head)), dim3(256), 0, st, (const u64*)codes, (u64)0, (u64)rs.head,
-                       len, cfg.base_order, out);
-  if (rs.main) {
-    const u32 ntiles = (u32)(rs.main / tile_recs);
-    const int m = mode_of_len(len), mo = cfg.base_order ? 1 : 0;
-    static std::atomic<int> occ[2][kNumLenModes];
-    hipLaunchKernelGGL(kUnpTable[mo][m], dim3(grid_for(ntiles, cfg.cus, resident_blocks<kBlock>(cfg, kUnpTable[mo][m], 0, &occ[mo][m]))),
-                       dim3(kBlock), 0, st, adv((const u64*)codes, 8 * rs.head), ntiles, len, adv(out, rs.head * len));
-  }
-  if (rs.head + rs.main < n)
-    hipLaunchKernelGGL(ibu_k_unpack_tail, dim3(tail_grid(n - rs.head - rs.main)), dim3(256), 0, st, (const u64*)codes,
-                       (u64)(rs.head + rs.main), (u64)n, len, cfg.base_order, out);
+  launch_rows(cfg, sp, 2, n, tile_recs,
+      [&](u64 row0, u64 row1) {
+        hipLaunchKernelGGL(ibu_k_unpack_tail, dim3(tail_grid(row1 - row0)), dim3(256), 0, st, (const u64*)codes, row0, row1, len, cfg.base_order, out);
+      },
+      [&](size_t head, u32 ntiles) {
+        const int m = mode_of_len(len), mo = cfg.base_order ? 1 : 0;
+        static std::atomic<int> occ[2][kNumLenModes];
+        hipLaunchKernelGGL(kUnpTable[mo][m], dim3(grid_for(ntiles, cfg.cus, resident_blocks<kBlock>(cfg, kUnpTable[mo][m], 0, &occ[mo][m]))),
+                           dim3(kBlock), 0, st, adv((const u64*)codes, 8 * head), ntiles, len, adv(out, head * len));
+      });
   return hipGetLastError();
 }
 

@@ -270,26 +270,22 @@ hipError_t launch_encode(const LaunchCfg& cfg, const uint8_t* bc, const uint8_t*
   const int mb = mode_of_len(bc_len), mu = mode_of_len(umi_len);
   const u32 nt = (u32)kEncNtTable[mb][mu];
   const size_t tile_recs = (size_t)kTileRecs * nt;
-  const RowSplit rs = split_rows(cfg, sp, 4, n, tile_recs);   // peel rows until every array is 16-B aligned
-  if (rs.head)
-    hipLaunchKernelGGL(ibu_k_encode_tail, dim3(tail_grid(rs.head)), dim3(256), 0, st, bc, umi, (const u64*)idx, (u64)first_index,
-                       (u64)0, (u64)rs.head, bc_len, umi_len, cfg.base_order, (u64*)recs, (u64*)status);
-  if (rs.main) {
-    const u32 ntiles = (u32)(rs.main / tile_recs);
-    u32 wave_lds = (enc_field_lds(len_of_mode(mb), bc_len) + enc_field_lds(len_of_mode(mu), umi_len)) * nt;
-    if (wave_lds < (u32)kTileBytes * nt) wave_lds = kTileBytes * nt;
-    const int mo = cfg.base_order ? 1 : 0;
-    const EncFn fn = kEncTable[mo][mb][mu];
-    static std::atomic<int> occ[2][33][33];  // LDS depends on the actual lengths, not only on the mode
-    const int nb = resident_blocks<kBlock>(cfg, fn, wave_lds * kWavesPerBlock, &occ[mo][bc_len][umi_len]);
-    hipLaunchKernelGGL(fn, dim3(grid_for(ntiles, cfg.cus, nb)), dim3(kBlock), wave_lds * kWavesPerBlock, st,
-                       adv(bc, rs.head * bc_len), adv(umi, rs.head * umi_len), adv((const u64*)idx, 8 * rs.head),
-                       (u64)(first_index + rs.head), (u64)rs.head, ntiles, bc_len, umi_len, wave_lds,
-                       adv((uint8_t*)recs, 24 * rs.head), (u64*)status);
-  }
-  if (rs.head + rs.main < n)
-    hipLaunchKernelGGL(ibu_k_encode_tail, dim3(tail_grid(n - rs.head - rs.main)), dim3(256), 0, st, bc, umi, (const u64*)idx,
-                       (u64)first_index, (u64)(rs.head + rs.main), (u64)n, bc_len, umi_len, cfg.base_order, (u64*)recs, (u64*)status);
+  launch_rows(cfg, sp, 4, n, tile_recs,   // peel rows until every array is 16-B aligned
+      [&](u64 row0, u64 row1) {
+        hipLaunchKernelGGL(ibu_k_encode_tail, dim3(tail_grid(row1 - row0)), dim3(256), 0, st, bc, umi, (const u64*)idx, (u64)first_index,
+                           row0, row1, bc_len, umi_len, cfg.base_order, (u64*)recs, (u64*)status);
+      },
+      [&](size_t head, u32 ntiles) {
+        u32 wave_lds = (enc_field_lds(len_of_mode(mb), bc_len) + enc_field_lds(len_of_mode(mu), umi_len)) * nt;
+        if (wave_lds < (u32)kTileBytes * nt) wave_lds = kTileBytes * nt;
+        const int mo = cfg.base_order ? 1 : 0;
+        const EncFn fn = kEncTable[mo][mb][mu];
+        static std::atomic<int> occ[2][33][33];  // LDS depends on the actual lengths, not only on the mode
+        const int nb = resident_blocks<kBlock>(cfg, fn, wave_lds * kWavesPerBlock, &occ[mo][bc_len][umi_len]);
+        hipLaunchKernelGGL(fn, dim3(grid_for(ntiles, cfg.cus, nb)), dim3(kBlock), wave_lds * kWavesPerBlock, st, adv(bc, head * bc_len),
+                           adv(umi, head * umi_len), adv((const u64*)idx, 8 * head), (u64)(first_index + head), (u64)head, ntiles,
+                           bc_len, umi_len, wave_lds, adv((uint8_t*)recs, 24 * head), (u64*)status);
+      });
   return hipGetLastError();
 }
 
@@ -327,22 +323,17 @@ hipError_t launch_pack(const LaunchCfg& cfg, const uint8_t* in, size_t n, uint32
   const int m = mode_of_len(len), mo = cfg.base_order ? 1 : 0;
   const PackShape shape = m ? PackShape{pack_nt(len_of_mode(m)), 0} : pack_shape(len);
   const size_t tile_rows = (size_t)kTileRecs * shape.nt;
-  const RowSplit rs = split_rows(cfg, sp, 2, n, tile_rows);
-  if (rs.head)
-    hipLaunchKernelGGL(ibu_k_pack_tail, dim3(tail_grid(rs.head)), dim3(256), 0, st, in, (u64)0, (u64)rs.head, len, cfg.base_order,
-                       (u64*)codes, (u64*)status);
-  if (rs.main) {
-    const u32 ntiles = (u32)(rs.main / tile_rows);
-    const PackFn fn = m ? kPackTable[mo][m] : (mo ? pack_gen_entry<true>(shape.nt, shape.rounds) : pack_gen_entry<false>(shape.nt, shape.rounds));
-    static std::atomic<int> occ[2][kNumLenModes], occ_gen[2][33];
-    std::atomic<int>* oc = m ? &occ[mo][m] : &occ_gen[mo][len];
-    hipLaunchKernelGGL(fn, dim3(grid_for(ntiles, cfg.cus, resident_blocks<kBlock>(cfg, fn, 0, oc))),
-                       dim3(kBlock), 0, st, adv(in, rs.head * len), (u64)rs.head, ntiles, len, adv((u64*)codes, 8 * rs.head),
-                       (u64*)status);
-  }
-  if (rs.head + rs.main < n)
-    hipLaunchKernelGGL(ibu_k_pack_tail, dim3(tail_grid(n - rs.head - rs.main)), dim3(256), 0, st, in, (u64)(rs.head + rs.main),
-                       (u64)n, len, cfg.base_order, (u64*)codes, (u64*)status);
+  launch_rows(cfg, sp, 2, n, tile_rows,
+      [&](u64 row0, u64 row1) {
+        hipLaunchKernelGGL(ibu_k_pack_tail, dim3(tail_grid(row1 - row0)), dim3(256), 0, st, in, row0, row1, len, cfg.base_order, (u64*)codes, (u64*)status);
+      },
+      [&](size_t head, u32 ntiles) {
+        const PackFn fn = m ? kPackTable[mo][m] : (mo ? pack_gen_entry<true>(shape.nt, shape.rounds) : pack_gen_entry<false>(shape.nt, shape.rounds));
+        static std::atomic<int> occ[2][kNumLenModes], occ_gen[2][33];
+        std::atomic<int>* oc = m ? &occ[mo][m] : &occ_gen[mo][len];
+        hipLaunchKernelGGL(fn, dim3(grid_for(ntiles, cfg.cus, resident_blocks<kBlock>(cfg, fn, 0, oc))), dim3(kBlock), 0, st,
+                           adv(in, head * len), (u64)head, ntiles, len, adv((u64*)codes, 8 * head), (u64*)status);
+      });
   return hipGetLastError();
 }
 

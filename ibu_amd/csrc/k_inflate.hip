@@ -1,7 +1,7 @@
 // k_inflate.hip — DEFLATE blocks (RFC 1951) inflated ON THE DEVICE: the device half of BGZF ingest (the reference reads gzip through
 // niffler, src/io/reader.rs:345-352; a bgzip file is a chain of independent members of at most 64 KiB whose sizes stand in their
 // headers, so the COMPRESSED bytes can cross the PCIe link — half of them for a records file — and the blocks inflate side by side).
-// Launcher: launch_inflate_blocks (kernels.h); C ABI: ibu_inflate_blocks_device (device.cpp); the host walk over the block headers:
+// Launcher: launch_inflate_blocks (kernels.h); C ABI: ibu_inflate_blocks_device (api_records.cpp); the host walk over the block headers:
 // ibu_bgzf_scan (host_io.cpp); the library's user: ibu_load_bgzf_*_to_device (stream.cpp).  The host decoder with the same
 // acceptance rules: pgzip.cpp.
 //

@@ -16,7 +16,7 @@
 //            (ibu_filter_barcodes), then launch_class_fill of k_aggregate.hip.
 // The set test is a gather of one 64-bit word per record from the bitmap (60 000 features: 7.5 KB, resident in L2 and mostly in the
 // vector L1); a NULL set costs no load.  No atomic per record or per barcode, no LDS beyond the walk's tiles.
-// Launchers: launch_metrics_count, launch_metrics_table, launch_metrics_filter (kernels.h); C ABI: device.cpp.
+// Launchers: launch_metrics_count, launch_metrics_table, launch_metrics_filter (kernels.h); C ABI: api_analysis.cpp.
 #include "runs_walk.hpp"
 
 namespace ibu {

@@ -16,7 +16,7 @@
 //            molecule of any length costs a constant per candidate this way: 1e6 candidates are 977 blocks, one round here.
 //   fill     launch_class_fill of k_aggregate.hip: the ballots and the ranked heads' bases give each record's candidate number, the
 //            verdicts leave as class bytes.
-// Launcher: launch_molecules_classify (kernels.h); C ABI: ibu_classify_molecules (device.cpp).
+// Launcher: launch_molecules_classify (kernels.h); C ABI: ibu_classify_molecules (api_analysis.cpp).
 #include "runs_walk.hpp"
 
 namespace ibu {

@@ -1,5 +1,5 @@
 // k_records.hip — K1/K1' (AoS <-> u64 columns), the field exchange, K4 reduce, synthetic generator, sortedness check.
-// Design notes: kcommon.hpp.  Reference semantics are cited at the C-ABI entry points in device.cpp
+// Design notes: kcommon.hpp.  Reference semantics are cited at the C-ABI entry points in api_records.cpp
 // and include/ibu_hip.h (cast_slice of &[Record]: reader.rs:301, writer.rs:317, mmap.rs:268; the
 // in-repo processors: lib.rs:117-129, examples/parallel.rs:21-36, examples/roundtrip.rs:84-87).
 #include "kcommon.hpp"
@@ -390,21 +390,15 @@ hipError_t launch_deserialize(const LaunchCfg& cfg, const void* recs, size_t n, 
   (void)hipGetLastError();  // a stale error of an unrelated earlier call must not be blamed on this launch
   if (n == 0) return hipSuccess;
   const Span sp[4] = {{recs, 24}, {bc, 8}, {umi, 8}, {idx, 8}};
-  const RowSplit rs = split_rows(cfg, sp, 4, n, kRecTileRecs);   // peel rows until every array is 16-B aligned
-  if (rs.head)
-    hipLaunchKernelGGL(ibu_k_deserialize_tail, dim3(tail_grid(rs.head)), dim3(256), 0, st, (const u64*)recs, (u64)0, (u64)rs.head,
-                       (u64*)bc, (u64*)umi, (u64*)idx);
-  if (rs.main) {
-    u32 ntiles = (u32)(rs.main / kRecTileRecs);
-    static std::atomic<int> occ;
-    hipLaunchKernelGGL(ibu_k_deserialize,
-                       dim3(grid_for(ntiles, cfg.cus, resident_blocks<kBlock>(cfg, ibu_k_deserialize, 0, &occ))), dim3(kBlock), 0, st,
-                       adv((const uint8_t*)recs, 24 * rs.head), ntiles, adv((u64*)bc, 8 * rs.head), adv((u64*)umi, 8 * rs.head),
-                       adv((u64*)idx, 8 * rs.head));
-  }
-  if (rs.head + rs.main < n)
-    hipLaunchKernelGGL(ibu_k_deserialize_tail, dim3(tail_grid(n - rs.head - rs.main)), dim3(256), 0, st, (const u64*)recs,
-                       (u64)(rs.head + rs.main), (u64)n, (u64*)bc, (u64*)umi, (u64*)idx);
+  launch_rows(cfg, sp, 4, n, kRecTileRecs,   // peel rows until every array is 16-B aligned
+      [&](u64 row0, u64 row1) {
+        hipLaunchKernelGGL(ibu_k_deserialize_tail, dim3(tail_grid(row1 - row0)), dim3(256), 0, st, (const u64*)recs, row0, row1, (u64*)bc,
+                           (u64*)umi, (u64*)idx);
+      },
+      [&](size_t head, u32 ntiles) {
+        hipLaunchKernelGGL(ibu_k_deserialize, dim3(tiled_grid<ibu_k_deserialize>(cfg, ntiles)), dim3(kBlock), 0, st,
+                           adv((const uint8_t*)recs, 24 * head), ntiles, adv((u64*)bc, 8 * head), adv((u64*)umi, 8 * head), adv((u64*)idx, 8 * head));
+      });
   return hipGetLastError();
 }
 
@@ -413,20 +407,16 @@ hipError_t launch_serialize(const LaunchCfg& cfg, const uint64_t* bc, const uint
   (void)hipGetLastError();  // a stale error of an unrelated earlier call must not be blamed on this launch
   if (n == 0) return hipSuccess;
   const Span sp[4] = {{recs, 24}, {bc, 8}, {umi, 8}, {idx, 8}};
-  const RowSplit rs = split_rows(cfg, sp, 4, n, kRecTileRecs);
-  if (rs.head)
-    hipLaunchKernelGGL(ibu_k_serialize_tail, dim3(tail_grid(rs.head)), dim3(256), 0, st, (const u64*)bc, (const u64*)umi,
-                       (const u64*)idx, (u64)0, (u64)rs.head, (u64*)recs);
-  if (rs.main) {
-    u32 ntiles = (u32)(rs.main / kRecTileRecs);
-    static std::atomic<int> occ;
-    hipLaunchKernelGGL(ibu_k_serialize, dim3(grid_for(ntiles, cfg.cus, resident_blocks<kBlock>(cfg, ibu_k_serialize, 0, &occ))),
-                       dim3(kBlock), 0, st, adv((const u64*)bc, 8 * rs.head), adv((const u64*)umi, 8 * rs.head),
-                       adv((const u64*)idx, 8 * rs.head), ntiles, adv((uint8_t*)recs, 24 * rs.head));
-  }
-  if (rs.head + rs.main < n)
-    hipLaunchKernelGGL(ibu_k_serialize_tail, dim3(tail_grid(n - rs.head - rs.main)), dim3(256), 0, st, (const u64*)bc,
-                       (const u64*)umi, (const u64*)idx, (u64)(rs.head + rs.main), (u64)n, (u64*)recs);
+  launch_rows(cfg, sp, 4, n, kRecTileRecs,
+      [&](u64 row0, u64 row1) {
+        hipLaunchKernelGGL(ibu_k_serialize_tail, dim3(tail_grid(row1 - row0)), dim3(256), 0, st, (const u64*)bc, (const u64*)umi,
+                           (const u64*)idx, row0, row1, (u64*)recs);
+      },
+      [&](size_t head, u32 ntiles) {
+        hipLaunchKernelGGL(ibu_k_serialize, dim3(tiled_grid<ibu_k_serialize>(cfg, ntiles)), dim3(kBlock), 0, st,
+                           adv((const u64*)bc, 8 * head), adv((const u64*)umi, 8 * head), adv((const u64*)idx, 8 * head), ntiles,
+                           adv((uint8_t*)recs, 24 * head));
+      });
   return hipGetLastError();
 }
 
@@ -434,18 +424,14 @@ hipError_t launch_swap_fields(const LaunchCfg& cfg, const void* src, void* dst, 
   (void)hipGetLastError();
   if (n == 0) return hipSuccess;
   const Span sp[2] = {{src, 24}, {dst, 24}};
-  const RowSplit rs = split_rows(cfg, sp, 2, n, kTileRecs);   // an 8-B aligned base peels one record; bases of different phase: all rows take the tail kernel
-  if (rs.head)
-    hipLaunchKernelGGL(ibu_k_swap_fields_tail, dim3(tail_grid(rs.head)), dim3(256), 0, st, (const u64*)src, (u64)0, (u64)rs.head, (u64*)dst);
-  if (rs.main) {
-    const u32 ntiles = (u32)(rs.main / kTileRecs);
-    static std::atomic<int> occ;
-    hipLaunchKernelGGL(ibu_k_swap_fields, dim3(grid_for(ntiles, cfg.cus, resident_blocks<kBlock>(cfg, ibu_k_swap_fields, 0, &occ))), dim3(kBlock),
-                       0, st, adv((const uint8_t*)src, 24 * rs.head), ntiles, adv((uint8_t*)dst, 24 * rs.head));
-  }
-  if (rs.head + rs.main < n)
-    hipLaunchKernelGGL(ibu_k_swap_fields_tail, dim3(tail_grid(n - rs.head - rs.main)), dim3(256), 0, st, (const u64*)src,
-                       (u64)(rs.head + rs.main), (u64)n, (u64*)dst);
+  launch_rows(cfg, sp, 2, n, kTileRecs,   // an 8-B aligned base peels one record; bases of different phase: all rows take the tail kernel
+      [&](u64 row0, u64 row1) {
+        hipLaunchKernelGGL(ibu_k_swap_fields_tail, dim3(tail_grid(row1 - row0)), dim3(256), 0, st, (const u64*)src, row0, row1, (u64*)dst);
+      },
+      [&](size_t head, u32 ntiles) {
+        hipLaunchKernelGGL(ibu_k_swap_fields, dim3(tiled_grid<ibu_k_swap_fields>(cfg, ntiles)), dim3(kBlock), 0, st,
+                           adv((const uint8_t*)src, 24 * head), ntiles, adv((uint8_t*)dst, 24 * head));
+      });
   return hipGetLastError();
 }
 
@@ -453,18 +439,15 @@ hipError_t launch_reduce(const LaunchCfg& cfg, const void* recs, size_t n, uint6
   (void)hipGetLastError();  // a stale error of an unrelated earlier call must not be blamed on this launch
   if (n == 0) return hipSuccess;
   const Span sp[1] = {{recs, 24}};
-  const RowSplit rs = split_rows(cfg, sp, 1, n, kTileRecs);   // an 8-B aligned base peels exactly one record
-  if (rs.head)
-    hipLaunchKernelGGL(ibu_k_reduce_tail, dim3(tail_grid(rs.head)), dim3(256), 0, st, (const u64*)recs, (u64)0, (u64)rs.head,
-                       (u64*)acc);
-  u32 ntiles = (u32)(rs.main / kTileRecs);
-  // the main kernel also adds n to the count slot, so it always runs (ntiles may be 0)
-  static std::atomic<int> occ;
-  hipLaunchKernelGGL(ibu_k_reduce, dim3(grid_for(ntiles, cfg.cus, resident_blocks<kBlock>(cfg, ibu_k_reduce, 0, &occ))),
-                     dim3(kBlock), 0, st, adv((const uint8_t*)recs, 24 * rs.head), ntiles, (u64)n, (u64*)acc);
-  if (rs.head + rs.main < n)
-    hipLaunchKernelGGL(ibu_k_reduce_tail, dim3(tail_grid(n - rs.head - rs.main)), dim3(256), 0, st, (const u64*)recs,
-                       (u64)(rs.head + rs.main), (u64)n, (u64*)acc);
+  launch_rows(cfg, sp, 1, n, kTileRecs,   // an 8-B aligned base peels exactly one record
+      [&](u64 row0, u64 row1) {
+        hipLaunchKernelGGL(ibu_k_reduce_tail, dim3(tail_grid(row1 - row0)), dim3(256), 0, st, (const u64*)recs, row0, row1, (u64*)acc);
+      },
+      [&](size_t head, u32 ntiles) {
+        hipLaunchKernelGGL(ibu_k_reduce, dim3(tiled_grid<ibu_k_reduce>(cfg, ntiles)), dim3(kBlock), 0, st,
+                           adv((const uint8_t*)recs, 24 * head), ntiles, (u64)n, (u64*)acc);
+      },
+      true);   // the main kernel also adds n to the count slot, so it always runs (ntiles may be 0)
   return hipGetLastError();
 }
 
@@ -473,20 +456,15 @@ hipError_t launch_generate(const LaunchCfg& cfg, uint64_t seed, uint64_t first, 
   (void)hipGetLastError();  // a stale error of an unrelated earlier call must not be blamed on this launch
   if (n == 0) return hipSuccess;
   const Span sp[1] = {{recs, 24}};
-  const RowSplit rs = split_rows(cfg, sp, 1, n, kTileRecs);
-  if (rs.head)
-    hipLaunchKernelGGL(ibu_k_generate_tail, dim3(tail_grid(rs.head)), dim3(256), 0, st, (u64)seed, (u64)first, (u64)0, (u64)rs.head,
-                       bc_len, umi_len, (u64*)recs);
-  if (rs.main) {
-    const u32 ntiles = (u32)(rs.main / kTileRecs);
-    static std::atomic<int> occ;
-    hipLaunchKernelGGL(ibu_k_generate, dim3(grid_for(ntiles, cfg.cus, resident_blocks<kBlock>(cfg, ibu_k_generate, 0, &occ))),
-                       dim3(kBlock), 0, st, (u64)seed, (u64)(first + rs.head), ntiles, bc_len, umi_len,
-                       adv((uint8_t*)recs, 24 * rs.head));
-  }
-  if (rs.head + rs.main < n)
-    hipLaunchKernelGGL(ibu_k_generate_tail, dim3(tail_grid(n - rs.head - rs.main)), dim3(256), 0, st, (u64)seed, (u64)first,
-                       (u64)(rs.head + rs.main), (u64)n, bc_len, umi_len, (u64*)recs);
+  launch_rows(cfg, sp, 1, n, kTileRecs,
+      [&](u64 row0, u64 row1) {
+        hipLaunchKernelGGL(ibu_k_generate_tail, dim3(tail_grid(row1 - row0)), dim3(256), 0, st, (u64)seed, (u64)first, row0, row1, bc_len,
+                           umi_len, (u64*)recs);
+      },
+      [&](size_t head, u32 ntiles) {
+        hipLaunchKernelGGL(ibu_k_generate, dim3(tiled_grid<ibu_k_generate>(cfg, ntiles)), dim3(kBlock), 0, st, (u64)seed,
+                           (u64)(first + head), ntiles, bc_len, umi_len, adv((uint8_t*)recs, 24 * head));
+      });
   return hipGetLastError();
 }
 

@@ -18,7 +18,7 @@
 //   points   the 3 x K cumulative counts.
 // The subsample writes one class byte per row, sixteen rows per lane and dwordx4 store where the class array's alignment allows, bytes at
 // its two ends; the kept count goes through kReduceSlots slots, one atomic per workgroup.
-// Launchers: launch_subsample, launch_saturation (kernels.h); C ABI: ibu_subsample_class, ibu_saturation_curve (device.cpp).
+// Launchers: launch_subsample, launch_saturation (kernels.h); C ABI: ibu_subsample_class, ibu_saturation_curve (api_analysis.cpp).
 #include "runs_walk.hpp"
 
 namespace ibu {

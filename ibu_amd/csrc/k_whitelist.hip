@@ -515,27 +515,27 @@ hipError_t launch_whitelist_build(const LaunchCfg& cfg, const uint64_t* codes, s
   return hipGetLastError();
 }
 
+static inline WlArgs wl_args(const WhitelistTable& wl, uint32_t search) {
+  WlArgs a;
+  a.table = (const u64*)wl.table; a.mask = (u32)(wl.slots - 1); a.shift = 64u - log2_of(wl.slots); a.has_ones = wl.has_ones ? 1u : 0u;
+  a.bc_len = wl.bc_len; a.search = search;
+  return a;
+}
 hipError_t launch_correct(const LaunchCfg& cfg, const WhitelistTable& wl, void* recs, size_t n, uint32_t max_mismatches, uint8_t* d_class,
                           uint64_t* acc, hipStream_t st) {
   (void)hipGetLastError();
   if (n == 0) return hipSuccess;
   if (n / kTileRecs > 0xFFFFFFFFull) return hipErrorInvalidValue;
-  WlArgs a;
-  a.table = (const u64*)wl.table; a.mask = (u32)(wl.slots - 1); a.shift = 64u - log2_of(wl.slots); a.has_ones = wl.has_ones ? 1u : 0u;
-  a.bc_len = wl.bc_len; a.search = max_mismatches;
+  const WlArgs a = wl_args(wl, max_mismatches);
   const Span sp[1] = {{recs, 24}};
-  const RowSplit rs = split_rows(cfg, sp, 1, n, kTileRecs);   // an 8-B aligned base peels exactly one record
-  if (rs.head)
-    hipLaunchKernelGGL(ibu_k_correct_tail, dim3(tail_grid(rs.head)), dim3(kBlock), 0, st, (u64*)recs, (u64)0, (u64)rs.head, a, d_class, (u64*)acc);
-  if (rs.main) {
-    const u32 ntiles = (u32)(rs.main / kTileRecs);
-    static std::atomic<int> occ;
-    hipLaunchKernelGGL(ibu_k_correct, dim3(grid_for(ntiles, cfg.cus, resident_blocks<kBlock>(cfg, ibu_k_correct, 0, &occ))),
-                       dim3(kBlock), 0, st, adv((uint8_t*)recs, 24 * rs.head), ntiles, a, adv(d_class, rs.head), (u64*)acc);
-  }
-  if (rs.head + rs.main < n)
-    hipLaunchKernelGGL(ibu_k_correct_tail, dim3(tail_grid(n - rs.head - rs.main)), dim3(kBlock), 0, st, (u64*)recs, (u64)(rs.head + rs.main),
-                       (u64)n, a, d_class, (u64*)acc);
+  launch_rows(cfg, sp, 1, n, kTileRecs,   // an 8-B aligned base peels exactly one record
+      [&](u64 row0, u64 row1) {
+        hipLaunchKernelGGL(ibu_k_correct_tail, dim3(tail_grid(row1 - row0)), dim3(kBlock), 0, st, (u64*)recs, row0, row1, a, d_class, (u64*)acc);
+      },
+      [&](size_t head, u32 ntiles) {
+        hipLaunchKernelGGL(ibu_k_correct, dim3(tiled_grid<ibu_k_correct>(cfg, ntiles)), dim3(kBlock), 0, st, adv((uint8_t*)recs, 24 * head),
+                           ntiles, a, adv(d_class, head), (u64*)acc);
+      });
   return hipGetLastError();
 }
 hipError_t launch_correct_fold(uint64_t* acc, hipStream_t st) {
@@ -544,12 +544,6 @@ hipError_t launch_correct_fold(uint64_t* acc, hipStream_t st) {
   return hipGetLastError();
 }
 
-static inline WlArgs wl_args(const WhitelistTable& wl, uint32_t search) {
-  WlArgs a;
-  a.table = (const u64*)wl.table; a.mask = (u32)(wl.slots - 1); a.shift = 64u - log2_of(wl.slots); a.has_ones = wl.has_ones ? 1u : 0u;
-  a.bc_len = wl.bc_len; a.search = search;
-  return a;
-}
 hipError_t launch_abundance_add(const LaunchCfg& cfg, const WhitelistTable& wl, const void* recs, const uint8_t* d_class, size_t n,
                                 uint32_t class_mask, uint64_t* counters, hipStream_t st) {
   (void)hipGetLastError();
@@ -557,19 +551,15 @@ hipError_t launch_abundance_add(const LaunchCfg& cfg, const WhitelistTable& wl, 
   if (n / kTileRecs > 0xFFFFFFFFull) return hipErrorInvalidValue;
   const WlArgs a = wl_args(wl, 0);
   const Span sp[1] = {{recs, 24}};
-  const RowSplit rs = split_rows(cfg, sp, 1, n, kTileRecs);   // an 8-B aligned base peels exactly one record
-  if (rs.head)
-    hipLaunchKernelGGL(ibu_k_abundance_add_tail, dim3(tail_grid(rs.head)), dim3(kBlock), 0, st, (const u64*)recs, (u64)0, (u64)rs.head, a, d_class,
-                       class_mask, (u64*)counters);
-  if (rs.main) {
-    const u32 ntiles = (u32)(rs.main / kTileRecs);
-    static std::atomic<int> occ;
-    hipLaunchKernelGGL(ibu_k_abundance_add, dim3(grid_for(ntiles, cfg.cus, resident_blocks<kBlock>(cfg, ibu_k_abundance_add, 0, &occ))),
-                       dim3(kBlock), 0, st, adv((const uint8_t*)recs, 24 * rs.head), ntiles, a, adv(d_class, rs.head), class_mask, (u64*)counters);
-  }
-  if (rs.head + rs.main < n)
-    hipLaunchKernelGGL(ibu_k_abundance_add_tail, dim3(tail_grid(n - rs.head - rs.main)), dim3(kBlock), 0, st, (const u64*)recs,
-                       (u64)(rs.head + rs.main), (u64)n, a, d_class, class_mask, (u64*)counters);
+  launch_rows(cfg, sp, 1, n, kTileRecs,   // an 8-B aligned base peels exactly one record
+      [&](u64 row0, u64 row1) {
+        hipLaunchKernelGGL(ibu_k_abundance_add_tail, dim3(tail_grid(row1 - row0)), dim3(kBlock), 0, st, (const u64*)recs, row0, row1, a, d_class,
+                           class_mask, (u64*)counters);
+      },
+      [&](size_t head, u32 ntiles) {
+        hipLaunchKernelGGL(ibu_k_abundance_add, dim3(tiled_grid<ibu_k_abundance_add>(cfg, ntiles)), dim3(kBlock), 0, st,
+                           adv((const uint8_t*)recs, 24 * head), ntiles, a, adv(d_class, head), class_mask, (u64*)counters);
+      });
   return hipGetLastError();
 }
 hipError_t launch_abundance_counts(const LaunchCfg& cfg, const WhitelistTable& wl, const uint64_t* counters, const uint64_t* codes, size_t k,
@@ -585,22 +575,16 @@ hipError_t launch_resolve(const LaunchCfg& cfg, const WhitelistTable& wl, const 
   (void)hipGetLastError();
   if (n == 0) return hipSuccess;
   const WlArgs a = wl_args(wl, 1);
-  size_t head = (size_t)((16 - (reinterpret_cast<uintptr_t>(d_class) & 15u)) & 15u);   // class bytes in front of the first 16-byte boundary
-  if (head > n) head = n;
-  const size_t main = ((n - head) / kResolveUnit) * kResolveUnit;
-  if (cfg.trace_rows) fprintf(stderr, "ibu rows: n=%zu head=%zu tiled=%zu rest=%zu tile=%u\n", n, head, main, n - head - main, kResolveUnit);
-  if (head)
-    hipLaunchKernelGGL(ibu_k_resolve_tail, dim3(tail_grid(head)), dim3(kBlock), 0, st, (u64*)recs, d_class, (u64)0, (u64)head, a,
-                       (const u64*)counters, (u64)num, (u64)den, (u64*)acc);
-  if (main) {
-    const u32 nunits = (u32)(main / kResolveUnit);   // n < 2^40: below 2^30
-    static std::atomic<int> occ;
-    hipLaunchKernelGGL(ibu_k_resolve, dim3(grid_for(nunits, cfg.cus, resident_blocks<kBlock>(cfg, ibu_k_resolve, 0, &occ))), dim3(kBlock), 0, st,
-                       adv((u64*)recs, 24 * head), d_class + head, nunits, a, (const u64*)counters, (u64)num, (u64)den, (u64*)acc);
-  }
-  if (head + main < n)
-    hipLaunchKernelGGL(ibu_k_resolve_tail, dim3(tail_grid(n - head - main)), dim3(kBlock), 0, st, (u64*)recs, d_class, (u64)(head + main), (u64)n, a,
-                       (const u64*)counters, (u64)num, (u64)den, (u64*)acc);
+  const Span sp[1] = {{d_class, 1}};   // the split is the class bytes': those in front of the first 16-byte boundary are the head
+  launch_rows(cfg, sp, 1, n, kResolveUnit,
+      [&](u64 row0, u64 row1) {
+        hipLaunchKernelGGL(ibu_k_resolve_tail, dim3(tail_grid(row1 - row0)), dim3(kBlock), 0, st, (u64*)recs, d_class, row0, row1, a,
+                           (const u64*)counters, (u64)num, (u64)den, (u64*)acc);
+      },
+      [&](size_t head, u32 nunits) {   // n < 2^40: nunits below 2^30
+        hipLaunchKernelGGL(ibu_k_resolve, dim3(tiled_grid<ibu_k_resolve>(cfg, nunits)), dim3(kBlock), 0, st, adv((u64*)recs, 24 * head),
+                           d_class + head, nunits, a, (const u64*)counters, (u64)num, (u64)den, (u64*)acc);
+      });
   return hipGetLastError();
 }
 

@@ -525,6 +525,25 @@ template <class T> static inline T* adv(T* p, size_t bytes) {
   return p ? reinterpret_cast<T*>(reinterpret_cast<uintptr_t>(p) + bytes) : p;
 }
 static inline u32 tail_grid(u64 rows) { return (u32)((rows + 255) / 256); }
+// The split and its up to three launches, written once.  tail(row0, row1): the one-thread-per-row kernel over rows [row0, row1), on a
+// grid of tail_grid(row1 - row0); main(head, ntiles): the tiled kernel over `ntiles` tiles that begin at row `head`.  main gets the
+// head, not advanced pointers, because the callers differ in what they do with it: most adv() their columns, launch_generate adds
+// it to `first`, launch_census passes it as a row number.  main_always: the tiled kernel goes out even with no tile.
+template <class Tail, class Main>
+static inline void launch_rows(const LaunchCfg& cfg, const Span* s, int k, size_t n, size_t tile, Tail&& tail, Main&& main,
+                               bool main_always = false) {
+  const RowSplit rs = split_rows(cfg, s, k, n, tile);
+  if (rs.head) tail((u64)0, (u64)rs.head);
+  if (rs.main || main_always) main(rs.head, (u32)(rs.main / tile));
+  if (rs.head + rs.main < n) tail((u64)(rs.head + rs.main), (u64)n);
+}
+// The persistent grid of a tiled kernel of kBlock threads without dynamic LDS: exactly resident (kernels.h: resident_blocks), the
+// occupancy asked once per kernel — the static belongs to the instantiation, one per Kernel.
+template <auto Kernel>
+static inline u32 tiled_grid(const LaunchCfg& cfg, u32 ntiles) {
+  static std::atomic<int> occ;
+  return grid_for(ntiles, cfg.cus, resident_blocks<kBlock>(cfg, Kernel, 0, &occ));
+}
 // A grid-stride kernel over `items`: the workgroups that cover them once at per_block each, at most blocks_per_cu per CU, at least one.
 static inline u32 capped_grid(const LaunchCfg& cfg, u64 items, u64 per_block, u32 blocks_per_cu = 8) {
   u64 blocks = (items + per_block - 1) / per_block;

@@ -1,4 +1,4 @@
-// kernels.h — launch interface between the C-ABI layer (device.cpp) and the k_*.hip kernel files.
+// kernels.h — launch interface between the C-ABI layer (device.cpp, api_*.cpp) and the k_*.hip kernel files.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stddef.h>

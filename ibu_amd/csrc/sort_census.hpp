@@ -134,19 +134,14 @@ extern "C" __global__ void ibu_k_sort_census_tail(const u64* __restrict__ recs, 
 }
 static void launch_census(const LaunchCfg& cfg, const void* recs, size_t n, u64* census, u32* flag32, hipStream_t st) {
   const Span sp[1] = {{recs, 24}};
-  const RowSplit rs = split_rows(cfg, sp, 1, n, kTileRecs);   // an 8-B aligned base peels exactly one record
-  if (rs.head)
-    hipLaunchKernelGGL(ibu_k_sort_census_tail, dim3(tail_grid(rs.head)), dim3(256), 0, st, (const u64*)recs, (u64)0, (u64)rs.head,
-                       census, flag32);
-  if (rs.main) {
-    const u32 ntiles = (u32)(rs.main / kTileRecs);
-    static std::atomic<int> occ;
-    hipLaunchKernelGGL(ibu_k_sort_census, dim3(grid_for(ntiles, cfg.cus, resident_blocks<kBlock>(cfg, ibu_k_sort_census, 0, &occ))),
-                       dim3(kBlock), 0, st, (const u64*)recs, (u64)rs.head, ntiles, census, flag32);
-  }
-  if (rs.head + rs.main < n)
-    hipLaunchKernelGGL(ibu_k_sort_census_tail, dim3(tail_grid(n - rs.head - rs.main)), dim3(256), 0, st, (const u64*)recs,
-                       (u64)(rs.head + rs.main), (u64)n, census, flag32);
+  launch_rows(cfg, sp, 1, n, kTileRecs,   // an 8-B aligned base peels exactly one record
+      [&](u64 row0, u64 row1) {
+        hipLaunchKernelGGL(ibu_k_sort_census_tail, dim3(tail_grid(row1 - row0)), dim3(256), 0, st, (const u64*)recs, row0, row1, census, flag32);
+      },
+      [&](size_t head, u32 ntiles) {   // the tiled kernel takes the records' base and its first row
+        hipLaunchKernelGGL(ibu_k_sort_census, dim3(tiled_grid<ibu_k_sort_census>(cfg, ntiles)), dim3(kBlock), 0, st, (const u64*)recs, (u64)head,
+                           ntiles, census, flag32);
+      });
 }
 hipError_t launch_sorted_check(const LaunchCfg& cfg, const void* recs, size_t n, uint32_t* flag, hipStream_t st) {
   (void)hipGetLastError();  // a stale error of an unrelated earlier call must not be blamed on this launch
