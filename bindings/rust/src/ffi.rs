@@ -100,6 +100,23 @@ pub struct ibu_barcode_filter_counts_t {
 }
 #[repr(C)]
 #[derive(Default, Debug, Clone, Copy, PartialEq, Eq)]
+pub struct ibu_feature_limits_t {
+    pub min_reads: u64,
+    pub max_reads: u64,
+    pub min_umis: u64,
+    pub max_umis: u64,
+    pub min_cells: u64,
+    pub max_cells: u64,
+}
+#[repr(C)]
+#[derive(Default, Debug, Clone, Copy, PartialEq, Eq)]
+pub struct ibu_feature_filter_counts_t {
+    pub features_by_class: [u64; 3],
+    pub reads_by_class: [u64; 4],
+    pub reserved: u64,
+}
+#[repr(C)]
+#[derive(Default, Debug, Clone, Copy, PartialEq, Eq)]
 pub struct ibu_saturation_point_t {
     pub threshold: u64,
     pub reads: u64,
@@ -307,6 +324,11 @@ extern "C" {
     pub fn ibu_filter_barcodes(ctx: *mut ibu_ctx_t, d_records: *const c_void, n: usize, d_set: *const u64, set_bits: u64, set_word: u32,
                                limits: *const ibu_barcode_limits_t, d_class: *mut u8, counts: *mut ibu_barcode_filter_counts_t,
                                stream: *mut c_void) -> i32;
+    pub fn ibu_feature_metrics(ctx: *mut ibu_ctx_t, d_records: *const c_void, n: usize, feature_word: u32, n_features: u64, flags: u32,
+                               d_reads: *mut u64, d_umis: *mut u64, d_cells: *mut u64, totals: *mut u64, stream: *mut c_void) -> i32;
+    pub fn ibu_filter_features(ctx: *mut ibu_ctx_t, d_records: *const c_void, n: usize, feature_word: u32, n_features: u64,
+                               d_reads: *const u64, d_umis: *const u64, d_cells: *const u64, limits: *const ibu_feature_limits_t,
+                               d_class: *mut u8, d_verdict: *mut u8, counts: *mut ibu_feature_filter_counts_t, stream: *mut c_void) -> i32;
     pub fn ibu_subsample_class(ctx: *mut ibu_ctx_t, n: usize, first_row: u64, seed: u64, threshold: u64, d_class: *mut u8, n_kept: *mut usize,
                                stream: *mut c_void) -> i32;
     pub fn ibu_saturation_curve(ctx: *mut ibu_ctx_t, d_sorted_records: *const c_void, n: usize, first_row: u64, seed: u64, thresholds: *const u64,

@@ -745,6 +745,38 @@ pub mod device {
             check(unsafe { ffi::ibu_filter_barcodes(self.raw, recs.ptr, n, bits, nbits, set_word, limits, cls, &mut c, std::ptr::null_mut()) })?;
             Ok(c)
         }
+        /// `ibu_feature_metrics`: for every feature `f < n_features` (the value of a record's word `feature_word`, 1 or 2) its
+        /// reads, its (w0, w1, w2) triples (UMIs) and, with `feature_word = 1`, its (w0, w1) pairs (cells), added into the device
+        /// columns `reads`, `umis`, `cells` (each `None` or `n_features` u64; `cells` must be `None` with `feature_word = 2`).
+        /// The call zeroes the columns first unless `accumulate`.  Returns the totals of this call: reads, umis and cells in range,
+        /// and the reads whose feature is not below `n_features`.
+        pub fn feature_metrics(&self, recs: &DeviceBuf, n: usize, feature_word: u32, n_features: u64, accumulate: bool, reads: Option<&DeviceBuf>,
+                               umis: Option<&DeviceBuf>, cells: Option<&DeviceBuf>) -> Result<[u64; 4]> {
+            let col = |b: Option<&DeviceBuf>| b.map_or(std::ptr::null_mut(), |b| b.ptr as *mut u64);
+            let mut totals = [0u64; 4];
+            check(unsafe {
+                ffi::ibu_feature_metrics(self.raw, recs.ptr, n, feature_word, n_features, if accumulate { 1 } else { 0 }, col(reads), col(umis), col(cells),
+                                         totals.as_mut_ptr(), std::ptr::null_mut())
+            })?;
+            Ok(totals)
+        }
+        /// `ibu_filter_features`: the verdict of every feature from the columns `ibu_feature_metrics` made (on these records or on
+        /// others) — 0 pass, 1 a count below its minimum, 2 a count above its non-zero maximum — into `verdict` (`n_features`
+        /// bytes; optional), and one class byte per record into `class` (n bytes; `None`: totals only): the verdict of its feature,
+        /// 3 where the feature is not below `n_features`.  A column may be `None` while its two limits are 0.
+        /// `select_records(.., 1 << 0, ..)` then keeps the records of the kept features.
+        pub fn filter_features(&self, recs: &DeviceBuf, n: usize, feature_word: u32, n_features: u64, reads: Option<&DeviceBuf>, umis: Option<&DeviceBuf>,
+                               cells: Option<&DeviceBuf>, limits: &ffi::ibu_feature_limits_t, class: Option<&DeviceBuf>, verdict: Option<&DeviceBuf>)
+                               -> Result<ffi::ibu_feature_filter_counts_t> {
+            let col = |b: Option<&DeviceBuf>| b.map_or(std::ptr::null(), |b| b.ptr as *const u64);
+            let bytes = |b: Option<&DeviceBuf>| b.map_or(std::ptr::null_mut(), |b| b.ptr as *mut u8);
+            let mut c = ffi::ibu_feature_filter_counts_t::default();
+            check(unsafe {
+                ffi::ibu_filter_features(self.raw, recs.ptr, n, feature_word, n_features, col(reads), col(umis), col(cells), limits, bytes(class),
+                                         bytes(verdict), &mut c, std::ptr::null_mut())
+            })?;
+            Ok(c)
+        }
         /// `ibu_subsample_class`: a reproducible random subset of `n` rows — one class byte per row into `class` (n bytes; `None`:
         /// the count only), 0 where the row's number `splitmix64(splitmix64(seed) + first_row + row)` is below `threshold` (all
         /// ones keeps every row), 1 elsewhere.  No record is read, so the subset depends on the order of the records it is applied

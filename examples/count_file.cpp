@@ -29,6 +29,15 @@
 // ibu_select_records keeps the class IBU_BARCODE_PASS, and the matrix and its row lengths are counted from the kept records as they
 // stand (ibu_pair_counts, ibu_barcode_counts): no second sort.  The four class totals go to stderr.
 // --set=FILE (with --qc): the feature set, one index value per line (mitochondrial genes, spike-ins).
+//   count_file ... [--features=mincells:A[,minumi:B][,maxcells:C] --n-features=N] [--feature-table=FILE] IN [WHITELIST.txt]
+// --features: the matrix of the features that pass the per-feature filter — behind the cell steps above (--qc included), on the
+// records sorted by (barcode, index, umi), ibu_feature_metrics counts for every index value below N its reads, its UMIs and the cells
+// it was seen in, ibu_filter_features classes every record by its feature (mincells, maxcells: seen in too few or too many cells;
+// minumi: too few UMIs; an index value of N or more is unknown), ibu_select_records keeps the class IBU_FEATURE_PASS, and the matrix
+// is counted from the kept records as they stand.  The class totals go to stderr.
+// --feature-table=FILE (with --n-features=N): the per-feature table in front of that filter, one
+//   index<TAB>reads<TAB>umis<TAB>cells
+// line for every index value below N that has a read.
 #include <cerrno>
 #include <cstdio>
 #include <cstdlib>
@@ -116,6 +125,39 @@ static bool parse_qc(const char* s, ibu_barcode_limits_t* lim) {
   }
 }
 
+// "mincells:A[,minumi:B][,maxcells:C]" -> the limits of ibu_filter_features; every key at most once, mincells among them; false otherwise
+static bool parse_features(const char* s, ibu_feature_limits_t* lim) {
+  *lim = ibu_feature_limits_t{};
+  unsigned seen = 0;
+  for (;;) {
+    static const char* const keys[] = {"mincells:", "minumi:", "maxcells:"};
+    unsigned k = 0;
+    while (k < 3 && std::strncmp(s, keys[k], std::strlen(keys[k]))) ++k;
+    if (k == 3 || (seen >> k & 1)) return false;
+    seen |= 1u << k;
+    s += std::strlen(keys[k]);
+    char* end = nullptr;
+    if (*s < '0' || *s > '9') return false;
+    errno = 0;
+    const uint64_t v = std::strtoull(s, &end, 10);
+    if (errno == ERANGE) return false;                         // more than 64 bits
+    if (k == 0) lim->min_cells = v;
+    if (k == 1) lim->min_umis = v;
+    if (k == 2) lim->max_cells = v;
+    if (*end == 0) return (seen & 1u) != 0;
+    if (*end != ',') return false;
+    s = end + 1;
+  }
+}
+// "N" -> 1 .. 2^32 features; false otherwise
+static bool parse_n_features(const char* s, uint64_t* n) {
+  char* end = nullptr;
+  if (s[0] < '0' || s[0] > '9') return false;
+  errno = 0;
+  *n = std::strtoull(s, &end, 10);
+  return errno != ERANGE && *end == 0 && *n >= 1 && *n <= (1ull << 32);
+}
+
 // one index value per line -> the bitmap of ibu_filter_barcodes and its number of bits (the largest value + 1)
 static std::vector<uint64_t> read_set(const char* path, uint64_t* bits) {
   std::ifstream f(path);
@@ -141,9 +183,12 @@ static std::vector<uint64_t> read_set(const char* path, uint64_t* bits) {
 
 int main(int argc, char** argv) {
   int resolve = 0;                                              // 1: --resolve, 2: --resolve=first
-  bool cells = false, bad = false, subsample = false, qc = false;
+  bool cells = false, bad = false, subsample = false, qc = false, features = false;
   ibu_barcode_limits_t qc_limits{};
+  ibu_feature_limits_t feature_limits{};
+  uint64_t n_features = 0;
   const char* set_path = nullptr;
+  const char* table_path = nullptr;
   uint32_t cells_mode = 0, saturation = 0;
   uint64_t cells_param = 0, sample_seed = 0;
   double sample_fraction = 1;
@@ -155,12 +200,16 @@ int main(int argc, char** argv) {
     else if (!std::strncmp(argv[1], "--saturation=", 13) && parse_saturation(argv[1] + 13, &saturation)) {}
     else if (!std::strncmp(argv[1], "--qc=", 5) && parse_qc(argv[1] + 5, &qc_limits)) qc = true;
     else if (!std::strncmp(argv[1], "--set=", 6) && argv[1][6]) set_path = argv[1] + 6;
+    else if (!std::strncmp(argv[1], "--features=", 11) && parse_features(argv[1] + 11, &feature_limits)) features = true;
+    else if (!std::strncmp(argv[1], "--n-features=", 13) && parse_n_features(argv[1] + 13, &n_features)) {}
+    else if (!std::strncmp(argv[1], "--feature-table=", 16) && argv[1][16]) table_path = argv[1] + 16;
     else bad = true;
   }
-  if (argc < 2 || bad || (set_path && !qc)) {
+  if (argc < 2 || bad || (set_path && !qc) || ((features || table_path) != (n_features != 0))) {
     std::fprintf(stderr, "usage: count_file [--resolve | --resolve=first] [--cells=min:T|top:K|expected:E] [--subsample=F[:seed]] [--saturation=K] "
                  "IN [WHITELIST.txt]\n"
-                 "       further options: [--qc=minfeat:A[,maxfeat:B][,minumi:C][,maxset:NUM/DEN]] [--set=FILE] (FILE: one index value per line)\n");
+                 "       further options: [--qc=minfeat:A[,maxfeat:B][,minumi:C][,maxset:NUM/DEN]] [--set=FILE] (FILE: one index value per line)\n"
+                 "                        [--features=mincells:A[,minumi:B][,maxcells:C] --n-features=N] [--feature-table=FILE] (with --n-features=N)\n");
     return 2;
   }
   try {
@@ -267,10 +316,40 @@ int main(int argc, char** argv) {
                    (unsigned long long)c.barcodes_by_class[2], (unsigned long long)c.barcodes_by_class[3], (unsigned long long)c.reads_by_class[0],
                    (unsigned long long)c.reads_by_class[1], (unsigned long long)c.reads_by_class[2], (unsigned long long)c.reads_by_class[3]);
       std::swap(recs, scratch);
-      entries = ctx.pair_counts(recs, kept);
-    } else {
-      entries = ctx.count_matrix(recs, scratch, kept, 0, /*leave_swapped=*/true);
+    } else if (n_features) {                                    // the feature steps want the same order
+      ctx.swap_umi_index(recs, recs, kept);
+      if (kept) ctx.sort_records(recs, scratch, kept);
     }
+    if (n_features) {                                           // count every feature, class every record by its feature, keep the passing ones
+      device::DeviceBuffer d_reads(ctx, 8 * n_features), d_umis(ctx, 8 * n_features), d_cells(ctx, 8 * n_features);
+      const device::FeatureTotals t = ctx.feature_metrics(recs, kept, n_features, d_reads.as<uint64_t>(), d_umis.as<uint64_t>(), d_cells.as<uint64_t>());
+      std::fprintf(stderr, "%zu records: %llu features: reads %llu, umis %llu, cells %llu; reads of other index values %llu\n", kept,
+                   (unsigned long long)n_features, (unsigned long long)t.reads, (unsigned long long)t.umis, (unsigned long long)t.cells,
+                   (unsigned long long)t.reads_out_of_range);
+      if (table_path) {
+        const auto hr = d_reads.download<uint64_t>(n_features), hu = d_umis.download<uint64_t>(n_features), hc = d_cells.download<uint64_t>(n_features);
+        std::FILE* f = std::fopen(table_path, "w");
+        if (!f) throw std::runtime_error(std::string("cannot write ") + table_path);
+        for (uint64_t k = 0; k < n_features; ++k)
+          if (hr[k]) std::fprintf(f, "%llu\t%llu\t%llu\t%llu\n", (unsigned long long)k, (unsigned long long)hr[k], (unsigned long long)hu[k], (unsigned long long)hc[k]);
+        if (std::fclose(f)) throw std::runtime_error(std::string("cannot write ") + table_path);
+      }
+      if (features) {
+        device::DeviceBuffer d_class(ctx, kept ? kept : 1);
+        const size_t before = kept;
+        const device::FeatureFilterCounts c = ctx.filter_features(recs, before, n_features, d_reads.as<uint64_t>(), d_umis.as<uint64_t>(),
+                                                                  d_cells.as<uint64_t>(), feature_limits, d_class.as<uint8_t>());
+        if (before) kept = ctx.select_records(recs, d_class.as<uint8_t>(), before, 1u << IBU_FEATURE_PASS, scratch, before);
+        ctx.synchronize();
+        std::fprintf(stderr, "%zu records: features pass %llu, low %llu, high %llu; reads pass %llu, low %llu, high %llu, unknown %llu\n", before,
+                     (unsigned long long)c.features_by_class[0], (unsigned long long)c.features_by_class[1], (unsigned long long)c.features_by_class[2],
+                     (unsigned long long)c.reads_by_class[0], (unsigned long long)c.reads_by_class[1], (unsigned long long)c.reads_by_class[2],
+                     (unsigned long long)c.reads_by_class[3]);
+        std::swap(recs, scratch);
+      }
+    }
+    if (qc || n_features) entries = ctx.pair_counts(recs, kept);   // the records are sorted by (barcode, index, umi) already
+    else entries = ctx.count_matrix(recs, scratch, kept, 0, /*leave_swapped=*/true);
     for (const device::MatrixEntry& e : entries)
       std::printf("%s\t%llu\t%llu\t%llu\n", decode(e.first, h.bc_len).c_str(), (unsigned long long)e.second, (unsigned long long)e.distinct,
                   (unsigned long long)e.records);

@@ -9,7 +9,8 @@ package binds it and nothing else (no numpy/torch arithmetic stands in for a ker
 The device pipeline of a single-cell run, every step on resident records: load -> Context.correct_barcodes (-> Abundance.add ->
 Context.resolve_barcodes: ambiguous barcodes to the candidate with nearly all of the exact reads) -> select_records -> sort_records -> classify_molecules -> select_records -> call_cells -> select_records -> count_matrix(leave_swapped=True) ->
 filter_barcodes (the per-barcode QC filter: too few or too many features / UMIs, too large a share of a feature set built with
-Context.feature_bitmap; barcode_metrics returns the table itself) -> select_records -> pair_counts.
+Context.feature_bitmap; barcode_metrics returns the table itself) -> select_records -> feature_metrics -> filter_features (the
+other axis: features seen in too few cells) -> select_records -> pair_counts.
 """
 import copy
 import ctypes as C
@@ -19,7 +20,7 @@ from collections import namedtuple
 import numpy as np
 
 from . import _lib
-from ._lib import CAllocProbe, CBarcodeFilterCounts, CBarcodeLimits, CCellCounts, CCorrectCounts, CResolveCounts, CDecodeSink, CMoleculeCounts, CErrorDetail, CKeyPlan, CHeader, CNumaInfo, CProcessorVTable, CRecord, CReduceResult, CRingConfig, CSaturationPoint, CStreamStats
+from ._lib import CAllocProbe, CBarcodeFilterCounts, CBarcodeLimits, CFeatureFilterCounts, CFeatureLimits, CCellCounts, CCorrectCounts, CResolveCounts, CDecodeSink, CMoleculeCounts, CErrorDetail, CKeyPlan, CHeader, CNumaInfo, CProcessorVTable, CRecord, CReduceResult, CRingConfig, CSaturationPoint, CStreamStats
 
 lib = _lib.load()
 
@@ -44,6 +45,13 @@ BARCODE_RESOLVED = 4  # the class ibu_resolve_barcodes gives a record it resolve
 BarcodeMetrics = namedtuple("BarcodeMetrics", "barcodes reads pairs triples set_reads set_triples")
 #: the totals of one ibu_filter_barcodes call (ibu_barcode_filter_counts_t without its reserved word); the by_class fields are 4-tuples
 BarcodeFilterCounts = namedtuple("BarcodeFilterCounts", "barcodes barcodes_by_class reads_by_class triples_passed set_triples_passed")
+FEATURE_PASS, FEATURE_LOW, FEATURE_HIGH, FEATURE_UNKNOWN = 0, 1, 2, 3  # the classes of ibu_filter_features (IBU_FEATURE_*)
+FEATURE_ACCUMULATE = 1  # ibu_feature_metrics flags (IBU_FEATURE_ACCUMULATE)
+#: the table of ibu_feature_metrics: three DeviceBuffers of n_features u64 each (cells is None for feature_word 2), and the totals of
+#: the call that made it — (reads, umis, cells in range, reads out of range)
+FeatureTable = namedtuple("FeatureTable", "reads umis cells n_features totals")
+#: the totals of one ibu_filter_features call (ibu_feature_filter_counts_t without its reserved word): a 3-tuple and a 4-tuple
+FeatureFilterCounts = namedtuple("FeatureFilterCounts", "features_by_class reads_by_class")
 SAMPLE_KEPT, SAMPLE_DROPPED = 0, 1  # the classes of ibu_subsample_class (IBU_SAMPLE_KEPT, IBU_SAMPLE_DROPPED)
 SATURATION_MAX_POINTS = 32
 #: one point of ibu_saturation_curve (ibu_saturation_point_t)
@@ -1129,6 +1137,61 @@ class Context:
             return d_class, None
         return d_class, BarcodeFilterCounts(int(c.barcodes), tuple(int(x) for x in c.barcodes_by_class), tuple(int(x) for x in c.reads_by_class),
                                             int(c.triples_passed), int(c.set_triples_passed))
+
+    # per-feature metrics and the feature filter
+    def feature_metrics(self, d_records, n, n_features, feature_word=1, accumulate_into=None, totals=True, stream=None):
+        """ibu_feature_metrics over n device records: for every feature f < n_features (the value of a record's word feature_word)
+        its reads, its UMIs (runs of equal (w0, w1, w2)) and, with feature_word=1, the cells it was seen in (runs of equal (w0, w1))
+        -> FeatureTable(reads, umis, cells, n_features, totals): three DeviceBuffers of n_features u64 (cells is None with
+        feature_word=2, for ordinarily sorted records) and totals = (reads, umis, cells in range, reads with f >= n_features) of
+        this call.  feature_word=1 is for what count_matrix(leave_swapped=True) leaves.  accumulate_into: a FeatureTable of an
+        earlier call — the counts are added on top of its columns (shards cut where a barcode begins, or several samples) and the
+        same buffers come back.  totals=False returns None for the totals and leaves the call asynchronous."""
+        n_features = int(n_features)
+        if not 1 <= n_features <= 1 << 32:
+            raise ValueError("n_features must be in 1 .. 2^32")
+        if feature_word not in (1, 2):
+            raise ValueError("feature_word must be 1 or 2")
+        if accumulate_into is not None:
+            if accumulate_into.n_features != n_features or (accumulate_into.cells is None) != (feature_word == 2):
+                raise ValueError("accumulate_into is a table of another shape")
+            cols = list(accumulate_into[:3])
+        else:
+            cols = [self.alloc(max(8 * n_features, 16)) for _ in range(3 if feature_word == 1 else 2)] + [None] * (feature_word - 1)
+        t = (C.c_uint64 * 4)() if totals else None
+        _check(lib.ibu_feature_metrics(self._c, _dptr(d_records), n, feature_word, n_features, FEATURE_ACCUMULATE if accumulate_into is not None else 0,
+                                       *[_dptr(c) for c in cols], t, stream))
+        return FeatureTable(*cols, n_features, tuple(int(x) for x in t) if totals else None)
+
+    def filter_features(self, d_records, n, table, feature_word=1, *, min_reads=0, max_reads=0, min_umis=0, max_umis=0, min_cells=0,
+                        max_cells=0, d_class=None, d_verdict=None, counts=True, stream=None):
+        """ibu_filter_features over n device records with the columns of `table` (a FeatureTable, made on these records or on
+        others — the called cells, say): feature f is FEATURE_LOW where its reads, umis or cells are below their minimum, else
+        FEATURE_HIGH where one is above its maximum (0: no maximum), else FEATURE_PASS; every record gets the class of its
+        feature, FEATURE_UNKNOWN where it is not below table.n_features.  -> (d_class, FeatureFilterCounts).  d_class: n bytes of
+        device memory; None allocates them, False asks for the totals only (and returns None in its place).  d_verdict: a
+        DeviceBuffer of n_features bytes that receives the per-feature verdicts.  counts=False returns None for the totals and does
+        not wait for them.  select_records(d_records, d_class, n, keep_mask=1 << FEATURE_PASS) then keeps the kept features."""
+        given = {"reads": (min_reads, max_reads), "umis": (min_umis, max_umis), "cells": (min_cells, max_cells)}
+        for name, (lo, hi) in given.items():
+            _u64_arg("min_" + name, lo), _u64_arg("max_" + name, hi)
+            if hi and lo > hi:
+                raise ValueError(f"min_{name} is above max_{name}")
+            if getattr(table, name) is None and (lo or hi):
+                raise ValueError(f"a limit on {name}, and the table has no such column")
+        if feature_word not in (1, 2):
+            raise ValueError("feature_word must be 1 or 2")
+        lim = CFeatureLimits(min_reads, max_reads, min_umis, max_umis, min_cells, max_cells)
+        if d_class is None:
+            d_class = self.alloc(max(n, 16))
+        elif d_class is False:
+            d_class = None
+        c = CFeatureFilterCounts() if counts else None
+        _check(lib.ibu_filter_features(self._c, _dptr(d_records), n, feature_word, table.n_features, _dptr(table.reads), _dptr(table.umis),
+                                       _dptr(table.cells), C.byref(lim), _dptr(d_class), _dptr(d_verdict), C.byref(c) if counts else None, stream))
+        if not counts:
+            return d_class, None
+        return d_class, FeatureFilterCounts(tuple(int(x) for x in c.features_by_class), tuple(int(x) for x in c.reads_by_class))
 
     # read subsampling and the saturation curve
     def subsample_class(self, n, d_class=None, *, fraction=None, threshold=None, seed=0, first_row=0, count=True, stream=None):

@@ -58,6 +58,14 @@ class CBarcodeFilterCounts(C.Structure):  # ibu_barcode_filter_counts_t
                 ("set_triples_passed", u64), ("reserved", u64)]
 
 
+class CFeatureLimits(C.Structure):  # ibu_feature_limits_t
+    _fields_ = [("min_reads", u64), ("max_reads", u64), ("min_umis", u64), ("max_umis", u64), ("min_cells", u64), ("max_cells", u64)]
+
+
+class CFeatureFilterCounts(C.Structure):  # ibu_feature_filter_counts_t
+    _fields_ = [("features_by_class", u64 * 3), ("reads_by_class", u64 * 4), ("reserved", u64)]
+
+
 class CSaturationPoint(C.Structure):  # ibu_saturation_point_t
     _fields_ = [("threshold", u64), ("reads", u64), ("barcodes", u64), ("molecules", u64)]
 
@@ -187,6 +195,8 @@ SIGNATURES = {
     "ibu_subsample_class": (i32, [vp, sz, u64, u64, u64, vp, P(sz), vp]),
     "ibu_barcode_metrics": (i32, [vp, vp, sz, vp, u64, u32, vp, vp, vp, vp, vp, vp, sz, P(sz), vp]),
     "ibu_filter_barcodes": (i32, [vp, vp, sz, vp, u64, u32, P(CBarcodeLimits), vp, P(CBarcodeFilterCounts), vp]),
+    "ibu_feature_metrics": (i32, [vp, vp, sz, u32, u64, u32, vp, vp, vp, P(u64), vp]),
+    "ibu_filter_features": (i32, [vp, vp, sz, u32, u64, vp, vp, vp, P(CFeatureLimits), vp, vp, P(CFeatureFilterCounts), vp]),
     "ibu_saturation_curve": (i32, [vp, vp, sz, u64, u64, P(u64), u32, P(CSaturationPoint), vp]),
     "ibu_correct_barcodes": (i32, [vp, vp, vp, sz, u32, vp, P(CCorrectCounts), vp]),
     "ibu_select_records": (i32, [vp, vp, vp, sz, u32, vp, sz, P(sz), vp]),

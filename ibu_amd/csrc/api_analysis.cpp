@@ -1,6 +1,6 @@
 // api_analysis.cpp — the entry points of the C ABI (include/ibu_hip.h) that analyse sorted records: the run-length aggregations
-// (barcode and pair counts, the count matrix), molecules, cells, the per-barcode metrics and filter, subsampling and the saturation
-// curve.  Each is a count pass, its totals read back, and an emit pass on a scratch sized by them.
+// (barcode and pair counts, the count matrix), molecules, cells, the per-barcode and per-feature metrics and filters, subsampling and the
+// saturation curve.  Most are a count pass, its totals read back, and an emit pass on a scratch sized by them.
 #include <stddef.h>
 
 #include "ctx.hpp"
@@ -238,6 +238,65 @@ extern "C" int32_t ibu_filter_barcodes(ibu_ctx_t* ctx, const void* d_records, si
   }
   counts->triples_passed = ctx->h_pinned[8];
   counts->set_triples_passed = ctx->h_pinned[9];
+  return IBU_OK;
+}
+// ---- per-feature metrics and the feature filter (k_features.hip).  The semantics are this library's: include/ibu_hip.h.
+static_assert(sizeof(ibu_feature_limits_t) == sizeof(FeatureLimits) && offsetof(ibu_feature_limits_t, min_cells) == offsetof(FeatureLimits, min_cells) &&
+                  sizeof(ibu_feature_filter_counts_t) == 64,
+              "ibu_hip.h and kernels.h disagree");
+// what both calls check first: the feature word, the table size, the columns' alignment, the records
+static int32_t check_feature_call(const char* fn, const void* d_records, size_t n, uint32_t feature_word, uint64_t n_features,
+                                  const uint64_t* d_reads, const uint64_t* d_umis, const uint64_t* d_cells) {
+  if (!feature_args_ok(feature_word, n_features)) return err_arg("feature_word must be 1 or 2 and n_features in 1 .. 2^32");
+  if (!aligned8(d_reads) || !aligned8(d_umis) || !aligned8(d_cells)) return err_arg("the columns must be 8-byte aligned");
+  int32_t rc = check_below_2_40(n, fn, "records");
+  if (rc) return rc;
+  return n ? check_u64_ptr(d_records, "d_records") : IBU_OK;
+}
+extern "C" int32_t ibu_feature_metrics(ibu_ctx_t* ctx, const void* d_records, size_t n, uint32_t feature_word, uint64_t n_features,
+                                       uint32_t flags, uint64_t* d_reads, uint64_t* d_umis, uint64_t* d_cells, uint64_t totals[4], void* stream) {
+  int32_t rc = check_ctx(ctx);
+  if (rc) return rc;
+  if ((rc = check_feature_call("feature_metrics", d_records, n, feature_word, n_features, d_reads, d_umis, d_cells)) != 0) return rc;
+  if (flags & ~(uint32_t)IBU_FEATURE_ACCUMULATE) return err_arg("unknown bit in flags");
+  if (feature_word == 2 && d_cells) return err_arg("d_cells needs feature_word 1: cells are not available on records sorted by (barcode, umi, index)");
+  hipStream_t st = pick_stream(ctx, stream);
+  rc = ensure_runs_scratch(ctx, feature_run_scratch_bytes(0));
+  if (rc) return rc;
+  if (!(flags & IBU_FEATURE_ACCUMULATE))
+    for (uint64_t* col : {d_reads, d_umis, d_cells})
+      if (col) IBU_HIP(hipMemsetAsync(col, 0, sizeof(uint64_t) * n_features, st));
+  uint64_t* acc = static_cast<uint64_t*>(ctx->d_runs_scratch);
+  IBU_HIP(launch_feature_count(ctx->cfg, d_records, n, feature_word, n_features, d_reads, d_umis, d_cells, acc, st));
+  if (!totals) return IBU_OK;
+  IBU_HIP(read_back<4>(ctx, acc, st));
+  for (int k = 0; k < 4; ++k) totals[k] = ctx->h_pinned[k];
+  return IBU_OK;
+}
+extern "C" int32_t ibu_filter_features(ibu_ctx_t* ctx, const void* d_records, size_t n, uint32_t feature_word, uint64_t n_features,
+                                       const uint64_t* d_reads, const uint64_t* d_umis, const uint64_t* d_cells,
+                                       const ibu_feature_limits_t* limits, uint8_t* d_class, uint8_t* d_verdict,
+                                       ibu_feature_filter_counts_t* counts, void* stream) {
+  int32_t rc = check_ctx(ctx);
+  if (rc) return rc;
+  if ((rc = check_feature_call("filter_features", d_records, n, feature_word, n_features, d_reads, d_umis, d_cells)) != 0) return rc;
+  if (!limits) return err_arg("limits is NULL");
+  if ((!d_reads && (limits->min_reads || limits->max_reads)) || (!d_umis && (limits->min_umis || limits->max_umis)) ||
+      (!d_cells && (limits->min_cells || limits->max_cells)))
+    return err_arg("a column with a non-zero limit is NULL");
+  const FeatureLimits lim{limits->min_reads, limits->max_reads, limits->min_umis, limits->max_umis, limits->min_cells, limits->max_cells};
+  hipStream_t st = pick_stream(ctx, stream);
+  rc = ensure_runs_scratch(ctx, feature_run_scratch_bytes(d_verdict ? 0 : n_features));
+  if (rc) return rc;
+  uint64_t* acc = static_cast<uint64_t*>(ctx->d_runs_scratch);
+  uint8_t* verdict = d_verdict ? d_verdict : static_cast<uint8_t*>(ctx->d_runs_scratch) + kFeatureAccBytes;
+  IBU_HIP(launch_feature_filter(ctx->cfg, d_records, n, feature_word, n_features, d_reads, d_umis, d_cells, lim, verdict, d_class, counts != nullptr,
+                                acc, st));
+  if (!counts) return IBU_OK;
+  IBU_HIP(read_back<8>(ctx, acc, st));
+  *counts = ibu_feature_filter_counts_t{};
+  for (int v = 0; v < 3; ++v) counts->features_by_class[v] = ctx->h_pinned[v];
+  for (int c = 0; c < 4; ++c) counts->reads_by_class[c] = ctx->h_pinned[4 + c];
   return IBU_OK;
 }
 // ---- read subsampling and the saturation curve (k_saturation.hip).  The semantics are this library's: include/ibu_hip.h.

@@ -180,6 +180,23 @@ hipError_t launch_metrics_table(const LaunchCfg&, const void* recs, size_t n, co
 hipError_t launch_metrics_filter(const LaunchCfg&, const void* recs, size_t n, const uint64_t* set, uint64_t set_bits, uint32_t set_word,
                                  void* scratch, void* run_scratch, uint64_t barcodes, const MetricsLimits& limits, uint8_t* d_class,
                                  hipStream_t st);
+// per-feature metrics and the feature filter (ibu_feature_metrics, ibu_filter_features, k_features.hip).  The feature of a record is
+// the value of its word feature_word (1 or 2); 1 <= n_features <= 2^32.  `acc`: kFeatureAccBytes of device memory, 8-byte aligned,
+// zeroed by the launcher.  launch_feature_count ADDS into the columns (each nullable, n_features u64; d_cells only with
+// feature_word 1) and leaves u64[4] in acc: reads, umis and cells in range, reads out of range.  launch_feature_filter writes the
+// n_features verdict bytes, one class byte per record into d_class (nullable), and leaves in acc the features per verdict [0 .. 2]
+// and, with class_totals, the records per class [4 .. 7].
+struct FeatureLimits {   // = ibu_feature_limits_t (ibu_hip.h)
+  uint64_t min_reads, max_reads, min_umis, max_umis, min_cells, max_cells;
+};
+static constexpr size_t kFeatureAccBytes = 128;
+bool feature_args_ok(uint32_t feature_word, uint64_t n_features);
+size_t feature_run_scratch_bytes(uint64_t verdict_bytes);   // acc | a verdict table of that many bytes
+hipError_t launch_feature_count(const LaunchCfg&, const void* recs, size_t n, uint32_t feature_word, uint64_t n_features, uint64_t* d_reads,
+                                uint64_t* d_umis, uint64_t* d_cells, uint64_t* acc, hipStream_t st);
+hipError_t launch_feature_filter(const LaunchCfg&, const void* recs, size_t n, uint32_t feature_word, uint64_t n_features,
+                                 const uint64_t* d_reads, const uint64_t* d_umis, const uint64_t* d_cells, const FeatureLimits& limits,
+                                 uint8_t* verdict, uint8_t* d_class, bool class_totals, uint64_t* acc, hipStream_t st);
 // read subsampling and the saturation curve (ibu_subsample_class, ibu_saturation_curve, k_saturation.hip).  The number of a read is
 // splitmix64(base + row) with base = sample_base(seed, first_row); kept at a threshold: ibu_hip.h.
 uint64_t sample_base(uint64_t seed, uint64_t first_row);

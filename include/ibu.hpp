@@ -370,6 +370,10 @@ using CellCounts = ibu_cell_counts_t;
 using SaturationPoint = ibu_saturation_point_t;
 using BarcodeLimits = ibu_barcode_limits_t;
 using BarcodeFilterCounts = ibu_barcode_filter_counts_t;
+using FeatureLimits = ibu_feature_limits_t;
+using FeatureFilterCounts = ibu_feature_filter_counts_t;
+// the totals of one ibu_feature_metrics call: reads, umis and cells of the features below n_features, and the records that are not
+struct FeatureTotals { uint64_t reads, umis, cells, reads_out_of_range; };
 // one row of ibu_barcode_metrics: a barcode, its records, the (w0, w1) pairs and (w0, w1, w2) triples that begin in it, and its
 // records / triples in the feature set
 struct BarcodeMetrics { uint64_t barcode, reads, pairs, triples, set_reads, set_triples; };
@@ -497,6 +501,27 @@ class Context {
                                       uint8_t* d_class, void* st = nullptr) {
     BarcodeFilterCounts c{};
     check(ibu_filter_barcodes(c_, d_recs, n, set.d_bits, set.bits, set_word, &limits, d_class, &c, st));
+    return c;
+  }
+  // the per-feature columns (ibu_feature_metrics): for every feature f < n_features (the value of a record's word feature_word, 1
+  // or 2) its reads, its triples (UMIs) and, with feature_word = 1, its pairs (cells) — device columns of n_features u64, each
+  // nullable, zeroed by the call unless flags has IBU_FEATURE_ACCUMULATE; d_cells must be nullptr with feature_word = 2.
+  // Synchronises once, for the totals
+  FeatureTotals feature_metrics(const void* d_recs, size_t n, uint64_t n_features, uint64_t* d_reads, uint64_t* d_umis, uint64_t* d_cells,
+                                uint32_t feature_word = 1, uint32_t flags = 0, void* st = nullptr) {
+    uint64_t t[4] = {0, 0, 0, 0};
+    check(ibu_feature_metrics(c_, d_recs, n, feature_word, n_features, flags, d_reads, d_umis, d_cells, t, st));
+    return FeatureTotals{t[0], t[1], t[2], t[3]};
+  }
+  // the feature filter made from those columns (ibu_filter_features), which may come from other records than the ones classed:
+  // d_class (n bytes, or nullptr for the totals only) gets the verdict of the record's feature — IBU_FEATURE_PASS / _LOW / _HIGH,
+  // and IBU_FEATURE_UNKNOWN where it is not below n_features; d_verdict (n_features bytes, nullable) the verdicts themselves;
+  // select_records(.., 1u << IBU_FEATURE_PASS, ..) keeps the records of the kept features
+  FeatureFilterCounts filter_features(const void* d_recs, size_t n, uint64_t n_features, const uint64_t* d_reads, const uint64_t* d_umis,
+                                      const uint64_t* d_cells, const FeatureLimits& limits, uint8_t* d_class, uint8_t* d_verdict = nullptr,
+                                      uint32_t feature_word = 1, void* st = nullptr) {
+    FeatureFilterCounts c{};
+    check(ibu_filter_features(c_, d_recs, n, feature_word, n_features, d_reads, d_umis, d_cells, &limits, d_class, d_verdict, &c, st));
     return c;
   }
   // a reproducible random subset of n rows (ibu_subsample_class): d_class (n bytes, or nullptr for the count only) gets

@@ -743,6 +743,78 @@ int32_t ibu_barcode_metrics(ibu_ctx_t* ctx, const void* d_records, size_t n, con
                             uint64_t* d_set_triples, size_t cap, size_t* n_barcodes, void* stream);
 int32_t ibu_filter_barcodes(ibu_ctx_t* ctx, const void* d_records, size_t n, const uint64_t* d_set, uint64_t set_bits, uint32_t set_word,
                             const ibu_barcode_limits_t* limits, uint8_t* d_class, ibu_barcode_filter_counts_t* counts, void* stream);
+/* Per-feature metrics and the feature filter, on the device (k_features.hip) — the other axis of the count matrix: for every feature
+ * (the index word: gene, antibody, guide) the reads and UMIs it received and the cells it was seen in, and the filter that drops the
+ * features seen in too few cells (scanpy's filter_genes(min_cells = 3), Seurat's min.cells).  The reference has no such function;
+ * the semantics are this library's and are stated in full here.  PAIRS and TRIPLES are those of the per-barcode block above: a pair
+ * is a maximal run of consecutive records with equal (w0, w1), a triple one with equal (w0, w1, w2).  THE FEATURE of a record is the
+ * value f of its word feature_word, which is 1 or 2.  1 <= n_features <= 2^32.
+ *
+ * ibu_feature_metrics.  feature_word == 1 is for records that went through ibu_records_swap_umi_index and the sort (what
+ * IBU_COUNT_LEAVE_SWAPPED leaves: sorted by (barcode, index, umi)).  For every f < n_features:
+ *   reads[f] = the records whose feature is f;
+ *   umis[f]  = the triples whose feature is f (all records of a triple agree in every word);
+ *   cells[f] = the pairs whose feature is f (all records of a pair agree in w1).  A record that begins a barcode begins a pair even
+ *              where it leaves w1 unchanged: two neighbouring barcodes with the same feature count two cells.
+ * feature_word == 2 is for ordinarily sorted records (barcode, umi, index): reads and umis are defined the same way; cells are not
+ * available in that order, a non-NULL d_cells is IBU_ERR_INVALID_ARG and totals[2] is 0.
+ * A record with f >= n_features enters no column — a value of 2^32 and more whose low bits name a valid feature included.
+ * totals (nullable, host) = {the sum of reads, the sum of umis, the sum of cells, the records with f >= n_features}: the first and
+ * the last add up to n.  Unsorted input gives the same computation on the runs as they stand (a pair that is interrupted and returns
+ * is two cells).  The records are never written.
+ * Each column is nullable on its own and holds n_features uint64_t, 8-byte aligned.  The call zeroes the columns it is given; with
+ * flags bit 0, IBU_FEATURE_ACCUMULATE, it does not and adds on top of their contents — shards cut at barcode boundaries, or several
+ * samples into one table.  A pair (or triple) that the boundary between two such calls cuts counts once in each call: cut shards
+ * where a barcode begins.  totals are always those of this call alone.
+ * n == 0 is OK: the columns are zeroed unless accumulating, and the totals are 0.  Asynchronous on `stream`; with totals != NULL
+ * the call waits once, for them.  The results are sums of integers: two runs give the same columns.
+ * IBU_ERR_INVALID_ARG, with nothing touched: feature_word outside {1, 2}, n_features outside 1 .. 2^32, an unknown bit in flags, a
+ * misaligned column, d_cells with feature_word == 2, n >= 2^40, and, with n > 0, a NULL or misaligned d_records.  A NULL context
+ * is an error.
+ *
+ * ibu_filter_features.  The three columns are INPUTS here: what ibu_feature_metrics made, possibly on other records (the called
+ * cells) than the ones that are classed (all records) — which is why these are two calls.  The verdict of feature f < n_features is
+ * the first that applies:
+ *   IBU_FEATURE_LOW  1   reads[f] < min_reads, umis[f] < min_umis or cells[f] < min_cells
+ *   IBU_FEATURE_HIGH 2   reads[f] > max_reads, umis[f] > max_umis or cells[f] > max_cells, for the maxima that are not 0
+ *   IBU_FEATURE_PASS 0   otherwise
+ * A maximum of 0 means no maximum: a zeroed limits struct passes every feature.  A feature without reads is LOW as soon as one
+ * minimum is positive.  A column may be NULL when its two limits are both 0; otherwise IBU_ERR_INVALID_ARG.
+ * Every record gets the verdict of its feature in d_class (nullable: totals only; n bytes at any alignment), and
+ * IBU_FEATURE_UNKNOWN 3 where f >= n_features.  d_verdict (nullable) receives the n_features verdict bytes.  counts (nullable,
+ * host): features_by_class[v] = the table entries of verdict v (they sum to n_features), reads_by_class[c] = the records of class c
+ * (they sum to n), reserved = 0.  With n == 0 the verdicts and features_by_class are still produced and no record is touched.
+ * ibu_select_records(..., keep_mask = 1 << IBU_FEATURE_PASS) then keeps the records of the kept features in input order, still
+ * sorted, and ibu_pair_counts on them is the filtered matrix with no second sort.
+ * IBU_ERR_INVALID_ARG, with nothing touched (`counts` included): feature_word outside {1, 2}, n_features outside 1 .. 2^32, a NULL
+ * limits, a misaligned column, a NULL column with a non-zero limit, n >= 2^40, and, with n > 0, a NULL or misaligned d_records.
+ * A NULL context is an error.  Asynchronous on `stream`; with counts != NULL the call waits once, for them.
+ *
+ * Traffic: the metrics read the records once and issue at most three 8-byte integer atomics per group — a pair (feature_word 1) or
+ * a triple (2), cut where a step of 128 records ends — into columns of 8 B per feature that stay in L2; the filter reads the columns
+ * once, the records once, gathers one verdict byte per record and writes one class byte per record.  Scratch: 128 B of the
+ * context's run scratch, and n_features bytes more when d_verdict is NULL. */
+#define IBU_FEATURE_PASS 0
+#define IBU_FEATURE_LOW 1
+#define IBU_FEATURE_HIGH 2
+#define IBU_FEATURE_UNKNOWN 3
+#define IBU_FEATURE_ACCUMULATE 1u     /* flags bit 0 */
+int32_t ibu_feature_metrics(ibu_ctx_t* ctx, const void* d_records, size_t n, uint32_t feature_word, uint64_t n_features, uint32_t flags,
+                            uint64_t* d_reads, uint64_t* d_umis, uint64_t* d_cells, uint64_t totals[4] /*nullable, host*/, void* stream);
+typedef struct ibu_feature_limits {
+  uint64_t min_reads, max_reads;       /* a maximum of 0: none */
+  uint64_t min_umis, max_umis;
+  uint64_t min_cells, max_cells;
+} ibu_feature_limits_t;
+typedef struct ibu_feature_filter_counts {
+  uint64_t features_by_class[3];       /* their sum is n_features */
+  uint64_t reads_by_class[4];          /* their sum is n */
+  uint64_t reserved;                   /* 0 */
+} ibu_feature_filter_counts_t;
+int32_t ibu_filter_features(ibu_ctx_t* ctx, const void* d_records, size_t n, uint32_t feature_word, uint64_t n_features,
+                            const uint64_t* d_reads, const uint64_t* d_umis, const uint64_t* d_cells, const ibu_feature_limits_t* limits,
+                            uint8_t* d_class /*nullable*/, uint8_t* d_verdict /*nullable, n_features bytes*/,
+                            ibu_feature_filter_counts_t* counts /*nullable, host*/, void* stream);
 /* Read subsampling and the saturation curve, on the device (k_saturation.hip): a reproducible random subset of the reads — what
  * brings samples of different depth to a common depth — and the number every single-cell summary reports first: how many distinct
  * molecules and barcodes would have been seen at a fraction of the reads.  The reference has nothing like this; the semantics are

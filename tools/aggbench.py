@@ -8,6 +8,7 @@ into preallocated device arrays, no download.
   python tools/aggbench.py --cells [--records 1e9] [--reads-per-molecule 4]     ibu_call_cells (cell_legs below)
   python tools/aggbench.py --saturation [--records 1e9] [--reads-per-molecule 4]     ibu_saturation_curve, ibu_subsample_class (saturation_legs below)
   python tools/aggbench.py --metrics [--records 1e9] [--reads-per-molecule 4]     ibu_barcode_metrics, ibu_filter_barcodes (metrics_legs below)
+  python tools/aggbench.py --features [--records 1e9] [--reads-per-molecule 4]     ibu_feature_metrics, ibu_filter_features (feature_legs below)
 bc_len 10 gives 2^20 distinct barcodes (a single-cell whitelist's order of magnitude); 16 gives ~n runs of length one."""
 import argparse
 import ctypes as C
@@ -428,6 +429,121 @@ def metrics_legs(a):
     assert [int((cls == c).sum()) for c in range(4)] == list(fcounts.reads_by_class)
 
 
+def feature_legs(a):
+    """--features: ibu_feature_metrics (all three columns; reads only) and ibu_filter_features (the class pass alone; with its
+    totals; metrics and filter together) on the resident {barcode, index, umi} array of --metrics — the knee of --cells with four
+    molecules per feature, feature numbers spread over 0 .. 60 000 — with n_features = 60 000, so that a few records are out of
+    range; timed with events on a side stream (the first round is the warm-up).  In the same run and on the same array: the
+    ibu_pair_counts size query (the same walk, once), ibu_reduce (the plain read) and ibu_call_cells with classes.  Then a second
+    leg on the same array with a tenth of all pairs given to ONE feature (pairs picked by a hash, so the array is no longer sorted
+    inside a barcode, which the metrics do not need): the hot counter every real sample has."""
+    import numpy as np
+    import torch                                             # before the library, as bench.py does
+    torch.cuda.init()
+    import ibu_amd as ia
+    from ibu_amd import _dptr, _check, lib, _lib
+
+    ctx = ia.Context(0)
+    side = torch.cuda.Stream()
+    st = side.cuda_stream
+    n = int(float(a.records.split(",")[0]))
+    rpm = a.reads_per_molecule
+    nf, hot = 60_000, 7
+    umis, starts, ends, n_cells, n_bg = knee_layout(torch, n, rpm, "cuda")
+    cols = [ctx.alloc(8 * n) for _ in range(3)]
+    bc, feat, um = (torch.as_tensor(c, device="cuda").view(torch.int64) for c in cols)
+
+    def fill(hot_share):
+        for lo in range(0, n, 1 << 26):
+            hi = min(n, lo + (1 << 26))
+            i = torch.arange(lo, hi, device="cuda", dtype=torch.int64)
+            b, m = knee_fill(torch, i, starts, ends, rpm)
+            bc[lo:hi], um[lo:hi] = b, m
+            f = ((m // 4) * 100 + b % 100).clamp_(max=nf + 99)   # ascending inside a barcode; a few at and above n_features
+            if hot_share:
+                h = (((b * 0x9E3779B1 + m // 4) * 0x1E3779B97F4A7C15) >> 20) & 0xFFFFF   # 20 pseudo-random bits per pair
+                f = torch.where(h % hot_share == 0, torch.full_like(f, hot), f)
+            feat[lo:hi] = f
+        torch.cuda.synchronize()
+        ctx.serialize(cols[0], cols[1], cols[2], n, d)       # w1 = the feature, w2 = the umi: what the swap and the sort leave
+        ctx.synchronize()
+
+    d, d_class = ctx.alloc(24 * n), ctx.alloc(n)
+    table = [ctx.alloc(8 * nf) for _ in range(3)]
+    fill(0)
+    assert ctx.is_sorted(d, n)
+
+    def timed(fn):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record(side)
+        fn()
+        e1.record(side)
+        e1.synchronize()
+        return e0.elapsed_time(e1)
+
+    def rounds(fn):
+        v = [timed(fn) for _ in range(a.rounds + 1)][1:]
+        return {"median_ms": round(statistics.median(v), 3), "min_ms": round(min(v), 3), "max_ms": round(max(v), 3)}
+
+    npairs, ntriples = C.c_size_t(), C.c_size_t()
+    totals = (C.c_uint64 * 4)()
+    ccounts, fcounts = _lib.CCellCounts(), _lib.CFeatureFilterCounts()
+    lim = _lib.CFeatureLimits(0, 0, 0, 0, 3, 0)                  # min_cells = 3
+    metrics = lambda given, t: _check(lib.ibu_feature_metrics(ctx._c, _dptr(d), n, 1, nf, 0, *[_dptr(x) for x in given], t, st))
+    filt = lambda cls, cnt: _check(lib.ibu_filter_features(ctx._c, _dptr(d), n, 1, nf, *[_dptr(x) for x in table], C.byref(lim),
+                                                           _dptr(d_class) if cls else None, None, C.byref(fcounts) if cnt else None, st))
+    pairs = lambda: _check(lib.ibu_pair_counts(ctx._c, _dptr(d), n, None, None, None, None, 0, C.byref(npairs), C.byref(ntriples), st))
+
+    def leg():
+        r = {}
+        r["reduce"] = rounds(lambda: _check(lib.ibu_reduce(ctx._c, _dptr(d), n, st)))
+        r["pair_counts_size_query"] = rounds(pairs)
+        r["call_cells_with_classes"] = rounds(lambda: _check(lib.ibu_call_cells(ctx._c, _dptr(d), n, ia.CELLS_MIN, 200, 0, _dptr(d_class), C.byref(ccounts), st)))
+        r["metrics_three_columns"] = rounds(lambda: metrics(table, totals))
+        r["metrics_reads_only"] = rounds(lambda: metrics([table[0], None, None], totals))
+        r["metrics_three_columns_no_totals"] = rounds(lambda: metrics(table, None))
+        r["pair_counts_size_query_again"] = rounds(pairs)
+        r["metrics_three_columns_again"] = rounds(lambda: metrics(table, totals))
+        r["filter_class_pass"] = rounds(lambda: filt(True, False))
+        r["filter_with_classes_and_totals"] = rounds(lambda: filt(True, True))
+        r["filter_totals_only"] = rounds(lambda: filt(False, True))
+        r["metrics_and_filter"] = rounds(lambda: (metrics(table, None), filt(True, True)))
+        pq = min(r["pair_counts_size_query"]["median_ms"], r["pair_counts_size_query_again"]["median_ms"])
+        m3 = min(r["metrics_three_columns"]["median_ms"], r["metrics_three_columns_again"]["median_ms"])
+        for k in ("metrics_reads_only", "filter_class_pass", "filter_with_classes_and_totals", "metrics_and_filter"):
+            r[k + "_vs_size_query"] = round(r[k]["median_ms"] / pq, 3)
+            r[k + "_vs_reduce"] = round(r[k]["median_ms"] / r["reduce"]["median_ms"], 3)
+            r[k + "_vs_call_cells"] = round(r[k]["median_ms"] / r["call_cells_with_classes"]["median_ms"], 3)
+        r["metrics_three_columns_vs_size_query"] = round(m3 / pq, 3)
+        r["metrics_three_columns_vs_reduce"] = round(m3 / r["reduce"]["median_ms"], 3)
+        r["metrics_three_columns_vs_call_cells"] = round(m3 / r["call_cells_with_classes"]["median_ms"], 3)
+        r.update({"pairs": npairs.value, "triples": ntriples.value, "totals": list(totals), "features_by_class": list(fcounts.features_by_class),
+                  "reads_by_class": list(fcounts.reads_by_class)})
+        return r, m3
+
+    def checks():
+        got = [t.download(np.uint64, nf) for t in table]
+        assert totals[0] + totals[3] == n == sum(fcounts.reads_by_class) and int(got[0].sum()) == totals[0]
+        assert int(got[1].sum()) == totals[1] <= ntriples.value and int(got[2].sum()) == totals[2] <= npairs.value
+        assert sum(fcounts.features_by_class) == nf and fcounts.features_by_class[1] == int((got[2] < 3).sum())
+        cls = torch.as_tensor(d_class, device="cuda").view(torch.uint8)[:n]
+        assert [int((cls == c).sum()) for c in range(4)] == list(fcounts.reads_by_class) and fcounts.reads_by_class[3] == totals[3]
+        return got
+
+    res = {"leg": "feature_metrics", "n": n, "reads_per_molecule": rpm, "cells_laid": n_cells, "background_laid": n_bg, "n_features": nf}
+    res["uniform"], m3_uniform = leg()
+    print(json.dumps(res), flush=True)                       # (before the checks: a run that fails one still leaves its times)
+    got = checks()
+    assert int(umis.sum()) == ntriples.value, "every molecule that was laid"
+    fill(10)
+    res["hot"], m3_hot = leg()
+    res["hot_vs_uniform_three_columns"] = round(m3_hot / m3_uniform, 3)
+    res["hot_vs_uniform_reads_only"] = round(res["hot"]["metrics_reads_only"]["median_ms"] / res["uniform"]["metrics_reads_only"]["median_ms"], 3)
+    got = checks()
+    res["hot_feature_share_of_pairs"] = round(int(got[2][hot]) / max(1, npairs.value), 4)
+    print(json.dumps(res), flush=True)
+
+
 def saturation_legs(a):
     """--saturation: the ten-point ibu_saturation_curve, and ibu_subsample_class + ibu_select_records at fraction 0.5, on resident
     sorted 16/12 records (the array --molecules lays), timed with events on a side stream (the first round is the warm-up).  In the
@@ -523,6 +639,7 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--saturation", action="store_true", help="the ibu_saturation_curve / ibu_subsample_class legs instead of the barcode leg")
     ap.add_argument("--metrics", action="store_true", help="the ibu_barcode_metrics / ibu_filter_barcodes legs instead of the barcode leg")
+    ap.add_argument("--features", action="store_true", help="the ibu_feature_metrics / ibu_filter_features legs instead of the barcode leg")
     ap.add_argument("--cells", action="store_true", help="the ibu_call_cells legs instead of the barcode leg")
     ap.add_argument("--molecules", action="store_true", help="the ibu_classify_molecules legs instead of the barcode leg")
     ap.add_argument("--reads-per-molecule", type=int, default=4)
@@ -537,6 +654,8 @@ def main():
         return saturation_legs(a)
     if a.metrics:
         return metrics_legs(a)
+    if a.features:
+        return feature_legs(a)
     if a.molecules:
         return molecule_legs(a)
     if a.cells:
