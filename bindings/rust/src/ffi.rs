@@ -298,6 +298,11 @@ extern "C" {
     pub fn ibu_count_matrix(ctx: *mut ibu_ctx_t, d_records: *mut c_void, d_tmp: *mut c_void, n: usize, flags: u32, d_barcodes: *mut u64,
                             d_indices: *mut u64, d_reads: *mut u64, d_umis: *mut u64, cap: usize, n_entries: *mut usize,
                             n_molecules: *mut usize, stream: *mut c_void) -> i32;
+    pub fn ibu_matrix_rows(ctx: *mut ibu_ctx_t, d_first: *const u64, n_entries: usize, d_row_of_entry: *mut u64, d_row_keys: *mut u64,
+                           d_row_ptr: *mut u64, cap: usize, n_rows: *mut usize, stream: *mut c_void) -> i32;
+    pub fn ibu_matrix_market_body(ctx: *mut ibu_ctx_t, d_a: *const u64, d_b: *const u64, d_c: *const u64, n_entries: usize, add_a: u64,
+                                  add_b: u64, d_text: *mut c_char, cap_bytes: usize, n_bytes: *mut usize, maxima: *mut u64,
+                                  stream: *mut c_void) -> i32;
     pub fn ibu_whitelist_create(ctx: *mut ibu_ctx_t, d_codes: *const u64, w: usize, bc_len: u32, stream: *mut c_void,
                                 out: *mut *mut ibu_whitelist_t) -> i32;
     pub fn ibu_whitelist_info(wl: *const ibu_whitelist_t, bc_len: *mut u32, n_distinct: *mut usize, device_bytes: *mut usize) -> i32;

@@ -672,6 +672,52 @@ pub mod device {
             let host = self.download_columns(&[&a, &b, &c, &d], ne)?;
             Ok((0..ne).map(|k| (host[k], host[ne + k], host[2 * ne + k], host[3 * ne + k])).collect())
         }
+        /// `ibu_matrix_rows`: the row structure of the device column `first` (`n_entries` u64, e.g. the barcodes of the entry
+        /// table) — a row is a maximal run of equal values.  Returns `(row_of_entry, row_keys, row_ptr)` as host vectors: the
+        /// 0-based row of every entry, the value of every row, and the CSR `indptr` (`n_rows + 1` words, the last `n_entries`).
+        pub fn matrix_rows(&self, first: &DeviceBuf, n_entries: usize) -> Result<(Vec<u64>, Vec<u64>, Vec<u64>)> {
+            let mut nr = 0usize;
+            check(unsafe {
+                ffi::ibu_matrix_rows(self.raw, first.ptr as *const u64, n_entries, std::ptr::null_mut(), std::ptr::null_mut(), std::ptr::null_mut(), 0,
+                                     &mut nr, std::ptr::null_mut())
+            })?;
+            if nr == 0 {
+                return Ok((Vec::new(), Vec::new(), vec![0u64]));
+            }
+            let (ord, keys, ptr) = (self.alloc(8 * n_entries)?, self.alloc(8 * nr)?, self.alloc(8 * (nr + 1))?);
+            check(unsafe {
+                ffi::ibu_matrix_rows(self.raw, first.ptr as *const u64, n_entries, ord.ptr as *mut u64, keys.ptr as *mut u64, ptr.ptr as *mut u64, nr,
+                                     &mut nr, std::ptr::null_mut())
+            })?;
+            let o = self.download_columns(&[&ord], n_entries)?;
+            let k = self.download_columns(&[&keys], nr)?;
+            let p = self.download_columns(&[&ptr], nr + 1)?;
+            Ok((o, k, p))
+        }
+        /// `ibu_matrix_market_body`: the device columns `a`, `b`, `c` (`n_entries` u64 each) as decimal text, line k =
+        /// `a[k] + add_a`, `b[k] + add_b`, `c[k]` separated by blanks and ended by a newline.  Returns the text and the largest
+        /// printed value of each column.
+        pub fn matrix_market_body(&self, a: &DeviceBuf, b: &DeviceBuf, c: &DeviceBuf, n_entries: usize, add_a: u64, add_b: u64)
+                                  -> Result<(Vec<u8>, [u64; 3])> {
+            let col = |d: &DeviceBuf| d.ptr as *const u64;
+            let (mut nb, mut maxima) = (0usize, [0u64; 3]);
+            check(unsafe {
+                ffi::ibu_matrix_market_body(self.raw, col(a), col(b), col(c), n_entries, add_a, add_b, std::ptr::null_mut(), 0, &mut nb,
+                                            maxima.as_mut_ptr(), std::ptr::null_mut())
+            })?;
+            if nb == 0 {
+                return Ok((Vec::new(), maxima));
+            }
+            let text = self.alloc(nb)?;
+            check(unsafe {
+                ffi::ibu_matrix_market_body(self.raw, col(a), col(b), col(c), n_entries, add_a, add_b, text.ptr as *mut std::os::raw::c_char, nb,
+                                            &mut nb, maxima.as_mut_ptr(), std::ptr::null_mut())
+            })?;
+            let mut host = vec![0u8; nb];
+            check(unsafe { ffi::ibu_memcpy_d2h(self.raw, host.as_mut_ptr() as *mut c_void, text.ptr, nb, std::ptr::null_mut()) })?;
+            check(unsafe { ffi::ibu_ctx_synchronize(self.raw, std::ptr::null_mut()) })?;
+            Ok((host, maxima))
+        }
         /// Barcode correction against a whitelist, in place over `n` device records (`ibu_correct_barcodes`): exact hits stay, a
         /// barcode with exactly one whitelist entry one substitution away moves onto it.  `class` (optional): `n` bytes, one
         /// class per record (0 exact, 1 corrected, 2 ambiguous, 3 unmatched).  Synchronises and returns the four totals.

@@ -38,6 +38,13 @@
 // --feature-table=FILE (with --n-features=N): the per-feature table in front of that filter, one
 //   index<TAB>reads<TAB>umis<TAB>cells
 // line for every index value below N that has a read.
+//   count_file ... [--mtx=DIR --n-features=N] IN [WHITELIST.txt]
+// --mtx=DIR: the matrix at the end of whatever chain the other options selected, as the directory scanpy's read_10x_mtx and Seurat's
+// Read10X read, beside the lines on stdout: DIR/matrix.mtx (MatrixMarket coordinate, features x barcodes, 1-based, the UMI counts),
+// DIR/barcodes.tsv and DIR/features.tsv (N lines, the index value as id and name).  The entry table stays on the device:
+// ibu_pair_counts into device columns, ibu_matrix_rows numbers the barcodes, ibu_matrix_market_body formats the lines there, and
+// the text comes down in pieces.  An index value of N or more is an error, and nothing is written.
+#include <algorithm>
 #include <cerrno>
 #include <cstdio>
 #include <cstdlib>
@@ -181,6 +188,56 @@ static std::vector<uint64_t> read_set(const char* path, uint64_t* bits) {
   return words;
 }
 
+// --mtx: the 10x directory of the {barcode, index, umi} records as they stand; the entry table never leaves the device as numbers
+static void write_mtx(ibu::device::Context& ctx, const void* recs, size_t n, uint32_t bc_len, uint64_t n_features, const std::string& dir) {
+  using namespace ibu;
+  size_t nnz = 0, rows = 0, bytes = 0;
+  check(ibu_pair_counts(ctx.raw(), recs, n, nullptr, nullptr, nullptr, nullptr, 0, &nnz, nullptr, nullptr));
+  device::DeviceBuffer d_bc(ctx, 8 * nnz), d_idx(ctx, 8 * nnz), d_reads(ctx, 8 * nnz), d_umis(ctx, 8 * nnz), d_ord(ctx, 8 * nnz);
+  check(ibu_pair_counts(ctx.raw(), recs, n, d_bc.as<uint64_t>(), d_idx.as<uint64_t>(), d_reads.as<uint64_t>(), d_umis.as<uint64_t>(), nnz, &nnz,
+                        nullptr, nullptr));
+  rows = ctx.matrix_rows(d_bc.as<uint64_t>(), nnz, nullptr, nullptr, nullptr, 0);
+  device::DeviceBuffer d_keys(ctx, 8 * rows), d_ascii(ctx, (size_t)bc_len * rows);
+  ctx.matrix_rows(d_bc.as<uint64_t>(), nnz, d_ord.as<uint64_t>(), d_keys.as<uint64_t>(), nullptr, rows);
+  // the size query on the values as they stand says what the largest index is; adding one lengthens a line by at most two bytes
+  uint64_t maxima[3] = {0, 0, 0};
+  bytes = ctx.matrix_market_body(d_idx.as<uint64_t>(), d_ord.as<uint64_t>(), d_umis.as<uint64_t>(), nnz, nullptr, 0, 0, 0, maxima);
+  if (nnz && maxima[0] >= n_features)
+    throw std::runtime_error("--mtx: the records hold index " + std::to_string(maxima[0]) + ", which is not below --n-features");
+  const size_t cap = bytes + 2 * nnz;
+  device::DeviceBuffer d_text(ctx, cap);
+  bytes = ctx.matrix_market_body(d_idx.as<uint64_t>(), d_ord.as<uint64_t>(), d_umis.as<uint64_t>(), nnz, d_text.as<char>(), cap, 1, 1);
+  ctx.unpack_2bit(d_keys.as<uint64_t>(), rows, bc_len, d_ascii.as<uint8_t>());
+  ctx.synchronize();
+  const auto open = [&](const char* name) {
+    std::FILE* f = std::fopen((dir + "/" + name).c_str(), "wb");
+    if (!f) throw std::runtime_error("cannot write " + dir + "/" + name + " (the directory must exist)");
+    return f;
+  };
+  const auto close = [&](std::FILE* f, const char* name) {
+    if (std::fclose(f)) throw std::runtime_error("cannot write " + dir + "/" + name);
+  };
+  std::FILE* f = open("matrix.mtx");
+  std::fprintf(f, "%%%%MatrixMarket matrix coordinate integer general\n%llu %zu %zu\n", (unsigned long long)n_features, rows, nnz);
+  std::vector<char> piece(std::min<size_t>(bytes, (size_t)64 << 20));
+  for (size_t off = 0; off < bytes; off += piece.size()) {
+    const size_t k = std::min(piece.size(), bytes - off);
+    ctx.download(piece.data(), d_text.as<char>() + off, k);
+    std::fwrite(piece.data(), 1, k, f);
+  }
+  close(f, "matrix.mtx");
+  f = open("barcodes.tsv");
+  const std::vector<uint8_t> ascii = d_ascii.download<uint8_t>((size_t)bc_len * rows);
+  for (size_t r = 0; r < rows; ++r) {
+    std::fwrite(ascii.data() + r * bc_len, 1, bc_len, f);
+    std::fputc('\n', f);
+  }
+  close(f, "barcodes.tsv");
+  f = open("features.tsv");
+  for (uint64_t j = 0; j < n_features; ++j) std::fprintf(f, "%llu\t%llu\tGene Expression\n", (unsigned long long)j, (unsigned long long)j);
+  close(f, "features.tsv");
+}
+
 int main(int argc, char** argv) {
   int resolve = 0;                                              // 1: --resolve, 2: --resolve=first
   bool cells = false, bad = false, subsample = false, qc = false, features = false;
@@ -189,6 +246,7 @@ int main(int argc, char** argv) {
   uint64_t n_features = 0;
   const char* set_path = nullptr;
   const char* table_path = nullptr;
+  const char* mtx_dir = nullptr;
   uint32_t cells_mode = 0, saturation = 0;
   uint64_t cells_param = 0, sample_seed = 0;
   double sample_fraction = 1;
@@ -203,13 +261,16 @@ int main(int argc, char** argv) {
     else if (!std::strncmp(argv[1], "--features=", 11) && parse_features(argv[1] + 11, &feature_limits)) features = true;
     else if (!std::strncmp(argv[1], "--n-features=", 13) && parse_n_features(argv[1] + 13, &n_features)) {}
     else if (!std::strncmp(argv[1], "--feature-table=", 16) && argv[1][16]) table_path = argv[1] + 16;
+    else if (!std::strncmp(argv[1], "--mtx=", 6) && argv[1][6]) mtx_dir = argv[1] + 6;
     else bad = true;
   }
-  if (argc < 2 || bad || (set_path && !qc) || ((features || table_path) != (n_features != 0))) {
+  const bool feature_steps = features || table_path;            // --mtx wants N as well, and none of the feature steps
+  if (argc < 2 || bad || (set_path && !qc) || ((feature_steps || mtx_dir) != (n_features != 0))) {
     std::fprintf(stderr, "usage: count_file [--resolve | --resolve=first] [--cells=min:T|top:K|expected:E] [--subsample=F[:seed]] [--saturation=K] "
                  "IN [WHITELIST.txt]\n"
                  "       further options: [--qc=minfeat:A[,maxfeat:B][,minumi:C][,maxset:NUM/DEN]] [--set=FILE] (FILE: one index value per line)\n"
-                 "                        [--features=mincells:A[,minumi:B][,maxcells:C] --n-features=N] [--feature-table=FILE] (with --n-features=N)\n");
+                 "                        [--features=mincells:A[,minumi:B][,maxcells:C] --n-features=N] [--feature-table=FILE] (with --n-features=N)\n"
+                 "                        [--mtx=DIR --n-features=N] (matrix.mtx, barcodes.tsv, features.tsv)\n");
     return 2;
   }
   try {
@@ -316,11 +377,11 @@ int main(int argc, char** argv) {
                    (unsigned long long)c.barcodes_by_class[2], (unsigned long long)c.barcodes_by_class[3], (unsigned long long)c.reads_by_class[0],
                    (unsigned long long)c.reads_by_class[1], (unsigned long long)c.reads_by_class[2], (unsigned long long)c.reads_by_class[3]);
       std::swap(recs, scratch);
-    } else if (n_features) {                                    // the feature steps want the same order
+    } else if (feature_steps) {                                 // the feature steps want the same order
       ctx.swap_umi_index(recs, recs, kept);
       if (kept) ctx.sort_records(recs, scratch, kept);
     }
-    if (n_features) {                                           // count every feature, class every record by its feature, keep the passing ones
+    if (feature_steps) {                                        // count every feature, class every record by its feature, keep the passing ones
       device::DeviceBuffer d_reads(ctx, 8 * n_features), d_umis(ctx, 8 * n_features), d_cells(ctx, 8 * n_features);
       const device::FeatureTotals t = ctx.feature_metrics(recs, kept, n_features, d_reads.as<uint64_t>(), d_umis.as<uint64_t>(), d_cells.as<uint64_t>());
       std::fprintf(stderr, "%zu records: %llu features: reads %llu, umis %llu, cells %llu; reads of other index values %llu\n", kept,
@@ -348,7 +409,7 @@ int main(int argc, char** argv) {
         std::swap(recs, scratch);
       }
     }
-    if (qc || n_features) entries = ctx.pair_counts(recs, kept);   // the records are sorted by (barcode, index, umi) already
+    if (qc || feature_steps) entries = ctx.pair_counts(recs, kept);   // the records are sorted by (barcode, index, umi) already
     else entries = ctx.count_matrix(recs, scratch, kept, 0, /*leave_swapped=*/true);
     for (const device::MatrixEntry& e : entries)
       std::printf("%s\t%llu\t%llu\t%llu\n", decode(e.first, h.bc_len).c_str(), (unsigned long long)e.second, (unsigned long long)e.distinct,
@@ -359,6 +420,7 @@ int main(int argc, char** argv) {
       total += n_entries;
     }
     if (total != entries.size()) throw std::runtime_error("the row lengths do not add up to the number of entries");
+    if (mtx_dir) write_mtx(ctx, recs, kept, h.bc_len, n_features, mtx_dir);
     ctx.free(d_recs);
   } catch (const std::exception& e) {
     std::fprintf(stderr, "error: %s\n", e.what());

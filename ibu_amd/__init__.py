@@ -10,7 +10,8 @@ The device pipeline of a single-cell run, every step on resident records: load -
 Context.resolve_barcodes: ambiguous barcodes to the candidate with nearly all of the exact reads) -> select_records -> sort_records -> classify_molecules -> select_records -> call_cells -> select_records -> count_matrix(leave_swapped=True) ->
 filter_barcodes (the per-barcode QC filter: too few or too many features / UMIs, too large a share of a feature set built with
 Context.feature_bitmap; barcode_metrics returns the table itself) -> select_records -> feature_metrics -> filter_features (the
-other axis: features seen in too few cells) -> select_records -> pair_counts.
+other axis: features seen in too few cells) -> select_records -> pair_counts, or, in the forms other tools read, matrix_csr (a CSR
+triple on the device) and write_matrix_market (the 10x directory, its text formatted on the device).
 """
 import copy
 import ctypes as C
@@ -52,6 +53,10 @@ FEATURE_ACCUMULATE = 1  # ibu_feature_metrics flags (IBU_FEATURE_ACCUMULATE)
 FeatureTable = namedtuple("FeatureTable", "reads umis cells n_features totals")
 #: the totals of one ibu_filter_features call (ibu_feature_filter_counts_t without its reserved word): a 3-tuple and a 4-tuple
 FeatureFilterCounts = namedtuple("FeatureFilterCounts", "features_by_class reads_by_class")
+#: what ibu_matrix_rows leaves: the number of rows and three DeviceBuffers of u64 — the value of every row (n_rows words), the CSR
+#: indptr (n_rows + 1 words) and the 0-based row of every entry (None where not asked for)
+MatrixRows = namedtuple("MatrixRows", "n_rows d_keys d_ptr d_row_of_entry")
+MTX_BANNER = "%%MatrixMarket matrix coordinate integer general"
 SAMPLE_KEPT, SAMPLE_DROPPED = 0, 1  # the classes of ibu_subsample_class (IBU_SAMPLE_KEPT, IBU_SAMPLE_DROPPED)
 SATURATION_MAX_POINTS = 32
 #: one point of ibu_saturation_curve (ibu_saturation_point_t)
@@ -682,6 +687,29 @@ class DeviceBuffer:
     __del__ = free
 
 
+class CsrMatrix:
+    """The cell x feature count matrix in CSR form, on the device (Context.matrix_csr): DeviceBuffers of u64 — `barcodes` (n_rows
+    codes, row r's barcode), `indptr` (n_rows + 1), `indices` and `data` (nnz each; the feature number and the count of every
+    entry).  The buffers speak the CUDA array interface as flat bytes, so torch.as_tensor(buf, device=...).view(torch.int64) wraps
+    one without a copy."""
+
+    def __init__(self, barcodes, indptr, indices, data, n_rows, nnz):
+        self.barcodes, self.indptr, self.indices, self.data, self.n_rows, self.nnz = barcodes, indptr, indices, data, n_rows, nnz
+
+    def download(self):
+        """-> (barcodes, indptr, indices, data) as numpy u64 arrays."""
+        e = np.empty(0, np.uint64)
+        if self.nnz == 0:
+            return e, np.zeros(1, np.uint64), e.copy(), e.copy()
+        return (self.barcodes.download(np.uint64, self.n_rows), self.indptr.download(np.uint64, self.n_rows + 1),
+                self.indices.download(np.uint64, self.nnz), self.data.download(np.uint64, self.nnz))
+
+    def free(self):
+        for b in (self.barcodes, self.indptr, self.indices, self.data):
+            if b is not None:
+                b.free()
+
+
 class DeviceBatch:
     """One device-resident batch of a DeviceStream: `n` AoS records at device pointer `ptr` (a ring slot), the first of them
     record number `first_index` of the stream.  release() (or leaving the `with` block) gives the slot back: it is refilled once
@@ -1041,6 +1069,109 @@ class Context:
                                     *[_dptr(o) for o in outs], cap, C.byref(ne), C.byref(nm), stream))
         self.synchronize(stream)
         return tuple(o.download(np.uint64, count=ne.value) for o in outs)
+
+    # matrix export: CSR row structure and Matrix Market text from the entry table
+    def matrix_rows(self, d_first, n_entries, ordinals=True, stream=None):
+        """ibu_matrix_rows over a device column of n_entries u64 (the barcodes of the entry table): a row is a maximal run of equal
+        values -> MatrixRows(n_rows, d_keys, d_ptr, d_row_of_entry), DeviceBuffers of u64: the value of every row, the CSR indptr
+        (n_rows + 1 words, the last n_entries) and, with ordinals, the 0-based row of every entry.  Synchronises once."""
+        nr = C.c_size_t()
+        _check(lib.ibu_matrix_rows(self._c, _dptr(d_first), n_entries, None, None, None, 0, C.byref(nr), stream))
+        r = nr.value
+        d_keys, d_ptr = self.alloc(max(8 * r, 16)), self.alloc(8 * (r + 1) + 8)
+        d_ord = self.alloc(max(8 * n_entries, 16)) if ordinals else None
+        if n_entries == 0:
+            d_ptr.upload(np.zeros(1, np.uint64))                 # the call touches nothing: indptr of no rows is [0]
+        _check(lib.ibu_matrix_rows(self._c, _dptr(d_first), n_entries, _dptr(d_ord), _dptr(d_keys), _dptr(d_ptr), r, C.byref(nr), stream))
+        return MatrixRows(r, d_keys, d_ptr, d_ord)
+
+    def matrix_market_body(self, d_a, d_b, d_c, n_entries, add=(1, 1), stream=None):
+        """ibu_matrix_market_body: three device columns of n_entries u64 as decimal text, line k = "a[k]+add[0] b[k]+add[1] c[k]\\n"
+        (sums modulo 2^64) -> (DeviceBuffer holding the text, n_bytes, maxima): maxima = the largest printed value of each column.
+        Two calls, the size query and the write: the columns are read three times.  Synchronises."""
+        add_a, add_b = (_u64_arg("add", v) for v in add)
+        cols = [_dptr(d_a), _dptr(d_b), _dptr(d_c)]
+        nb, mx = C.c_size_t(), (C.c_uint64 * 3)()
+        _check(lib.ibu_matrix_market_body(self._c, *cols, n_entries, add_a, add_b, None, 0, C.byref(nb), mx, stream))
+        d_text = self.alloc(max(nb.value, 16))
+        _check(lib.ibu_matrix_market_body(self._c, *cols, n_entries, add_a, add_b, _dptr(d_text), nb.value, C.byref(nb), mx, stream))
+        return d_text, nb.value, tuple(int(x) for x in mx)
+
+    def _entry_columns(self, d_records, n, stream):
+        """ibu_pair_counts into device columns -> ([first, second, records_per_pair, distinct_third], entries)."""
+        npairs = C.c_size_t()
+        _check(lib.ibu_pair_counts(self._c, _dptr(d_records), n, None, None, None, None, 0, C.byref(npairs), None, stream))
+        u = npairs.value
+        cols = [self.alloc(max(8 * u, 16)) for _ in range(4)]
+        _check(lib.ibu_pair_counts(self._c, _dptr(d_records), n, *[_dptr(c) for c in cols], u, C.byref(npairs), None, stream))
+        return cols, u
+
+    @staticmethod
+    def _values_column(values):
+        if values not in ("umis", "reads"):
+            raise ValueError('values must be "umis" or "reads"')
+        return 3 if values == "umis" else 2
+
+    def matrix_csr(self, d_records, n, values="umis", stream=None):
+        """The count matrix of the {barcode, index, umi} records count_matrix(leave_swapped=True) leaves (or what a chain of filters
+        and select_records kept of them), as a CsrMatrix on the device: ibu_pair_counts into device columns, then ibu_matrix_rows.
+        values: "umis" (distinct UMIs per entry) or "reads".  Nothing is downloaded; CsrMatrix.download() gives numpy arrays."""
+        which = self._values_column(values)
+        cols, nnz = self._entry_columns(d_records, n, stream)
+        rows = self.matrix_rows(cols[0], nnz, ordinals=False, stream=stream)
+        self.synchronize(stream)
+        for k in (0, 5 - which):
+            cols[k].free()
+        return CsrMatrix(rows.d_keys, rows.d_ptr, cols[1], cols[which], rows.n_rows, nnz)
+
+    def write_matrix_market(self, directory, d_records, n, n_features, bc_len, values="umis", barcode_suffix="", feature_names=None,
+                            stream=None, piece_bytes=64 << 20):
+        """The 10x directory of the same records: matrix.mtx (features x barcodes, 1-based, the body formatted on the device by
+        ibu_matrix_market_body), barcodes.tsv (ibu_unpack_2bit of the row keys, each followed by barcode_suffix) and features.tsv
+        ("id\\tname\\tGene Expression": the decimal feature number for both unless feature_names gives n_features names) — what
+        scanpy.read_10x_mtx and Seurat's Read10X read.  An index that is not below n_features raises ValueError before any file is
+        created.  The text comes down in pieces of piece_bytes.  -> (n_rows, nnz).  Synchronises."""
+        import os
+        which = self._values_column(values)
+        n_features = _u64_arg("n_features", n_features)
+        if not 1 <= bc_len <= 32:
+            raise ValueError("bc_len must be in 1 .. 32")
+        if feature_names is not None and len(feature_names) != n_features:
+            raise ValueError("feature_names must hold n_features names")
+        cols, nnz = self._entry_columns(d_records, n, stream)
+        rows = self.matrix_rows(cols[0], nnz, stream=stream)
+        trio = [_dptr(cols[1]), _dptr(rows.d_row_of_entry), _dptr(cols[which])]
+        # the size query on the values as they stand: the largest index comes back unwrapped, and adding one to the first two
+        # columns lengthens a line by at most two bytes
+        nb, mx = C.c_size_t(), (C.c_uint64 * 3)()
+        _check(lib.ibu_matrix_market_body(self._c, *trio, nnz, 0, 0, None, 0, C.byref(nb), mx, stream))
+        if nnz and int(mx[0]) >= n_features:
+            raise ValueError(f"the records hold index {int(mx[0])}, which is not below n_features = {n_features}")
+        cap = nb.value + 2 * nnz
+        d_text = self.alloc(max(cap, 16))
+        _check(lib.ibu_matrix_market_body(self._c, *trio, nnz, 1, 1, _dptr(d_text), cap, C.byref(nb), None, stream))
+        d_ascii = self.alloc(max(rows.n_rows * bc_len, 16))
+        self.unpack_2bit(rows.d_keys, rows.n_rows, bc_len, d_ascii, stream)
+        self.synchronize(stream)
+        os.makedirs(directory, exist_ok=True)
+        with open(os.path.join(directory, "matrix.mtx"), "wb") as f:
+            f.write(f"{MTX_BANNER}\n{n_features} {rows.n_rows} {nnz}\n".encode())
+            for off in range(0, nb.value, piece_bytes):
+                f.write(d_text.download(np.uint8, min(piece_bytes, nb.value - off), off).tobytes())
+        tail = np.frombuffer(barcode_suffix.encode() + b"\n", np.uint8)
+        per = max(1, piece_bytes // (bc_len + len(tail)))
+        with open(os.path.join(directory, "barcodes.tsv"), "wb") as f:
+            for r0 in range(0, rows.n_rows, per):
+                k = min(per, rows.n_rows - r0)
+                text = d_ascii.download(np.uint8, k * bc_len, r0 * bc_len).reshape(k, bc_len)
+                f.write(np.concatenate([text, np.broadcast_to(tail, (k, len(tail)))], axis=1).tobytes())
+        with open(os.path.join(directory, "features.tsv"), "w") as f:
+            for j in range(n_features):
+                name = str(j) if feature_names is None else str(feature_names[j])
+                f.write(f"{name}\t{name}\tGene Expression\n")
+        for b in (*cols, rows.d_keys, rows.d_ptr, rows.d_row_of_entry, d_text, d_ascii):
+            b.free()
+        return rows.n_rows, nnz
 
     def classify_molecules(self, d_sorted_records, n, d_class=None, tie_first=False, counts=True, stream=None):
         """ibu_classify_molecules over n device records sorted by (barcode, umi, index): one class byte per record — MOLECULE_KEPT

@@ -187,6 +187,8 @@ SIGNATURES = {
     "ibu_merge_sorted_runs": (i32, [vp, vp, vp, P(sz), sz, vp]),
     "ibu_pair_counts": (i32, [vp, vp, sz, vp, vp, vp, vp, sz, P(sz), P(sz), vp]),
     "ibu_count_matrix": (i32, [vp, vp, vp, sz, u32, vp, vp, vp, vp, sz, P(sz), P(sz), vp]),
+    "ibu_matrix_rows": (i32, [vp, vp, sz, vp, vp, vp, sz, P(sz), vp]),
+    "ibu_matrix_market_body": (i32, [vp, vp, vp, vp, sz, u64, u64, vp, sz, P(sz), P(u64), vp]),
     "ibu_whitelist_create": (i32, [vp, vp, sz, u32, vp, P(vp)]),
     "ibu_whitelist_info": (i32, [vp, P(u32), P(sz), P(sz)]),
     "ibu_whitelist_destroy": (None, [vp]),

@@ -387,3 +387,54 @@ extern "C" int32_t ibu_count_matrix(ibu_ctx_t* ctx, void* d_records, void* d_tmp
     if ((rc = ibu_records_swap_umi_index(ctx, d_records, d_records, n, stream)) != 0) return rc;
   return rc_counts;
 }
+// ---- the matrix export (k_matrix.hip): the row structure of a column of the entry table, and three columns as decimal text.  The
+// semantics are this library's: include/ibu_hip.h.  Both are a count pass and its scan on the context's sort scratch, the totals read
+// back, and a scatter pass.
+extern "C" int32_t ibu_matrix_rows(ibu_ctx_t* ctx, const uint64_t* d_first, size_t n_entries, uint64_t* d_row_of_entry, uint64_t* d_row_keys,
+                                   uint64_t* d_row_ptr, size_t cap, size_t* n_rows, void* stream) {
+  int32_t rc = check_ctx(ctx);
+  if (rc) return rc;
+  if (!n_rows) return err_arg("n_rows is NULL");
+  *n_rows = 0;
+  if (n_entries == 0) return IBU_OK;
+  if ((rc = check_u64_ptr(d_first, "d_first")) != 0) return rc;
+  if ((rc = check_below_2_40(n_entries, "matrix_rows", "entries")) != 0) return rc;
+  if (!aligned8(d_row_of_entry) || !aligned8(d_row_keys) || !aligned8(d_row_ptr)) return err_arg("the output arrays must be 8-byte aligned");
+  hipStream_t st = pick_stream(ctx, stream);
+  if ((rc = ensure_sort_scratch(ctx, matrix_scratch_bytes(n_entries))) != 0) return rc;
+  IBU_HIP(launch_matrix_rows_count(ctx->cfg, d_first, n_entries, ctx->d_sort_scratch, ctx->sort_scratch_bytes, st));
+  IBU_HIP(read_back<1>(ctx, static_cast<const uint64_t*>(ctx->d_sort_scratch) + kMatrixTotalWord, st));
+  const uint64_t rows = ctx->h_pinned[0];
+  *n_rows = rows;
+  if (!d_row_of_entry && !d_row_keys && !d_row_ptr) return IBU_OK;   // the size query (cap == 0), or nothing asked for
+  if (rows > cap) return err_capacity(rows, cap, "rows", "n_rows");
+  IBU_HIP(launch_matrix_rows_scatter(ctx->cfg, d_first, n_entries, ctx->d_sort_scratch, d_row_of_entry, d_row_keys, d_row_ptr, st));
+  return IBU_OK;
+}
+extern "C" int32_t ibu_matrix_market_body(ibu_ctx_t* ctx, const uint64_t* d_a, const uint64_t* d_b, const uint64_t* d_c, size_t n_entries,
+                                          uint64_t add_a, uint64_t add_b, char* d_text, size_t cap_bytes, size_t* n_bytes, uint64_t maxima[3],
+                                          void* stream) {
+  int32_t rc = check_ctx(ctx);
+  if (rc) return rc;
+  if (!n_bytes) return err_arg("n_bytes is NULL");
+  *n_bytes = 0;
+  if (maxima) maxima[0] = maxima[1] = maxima[2] = 0;
+  if (n_entries == 0) return IBU_OK;
+  if ((rc = check_u64_ptrs({d_a, d_b, d_c}, "d_a / d_b / d_c")) != 0) return rc;
+  if ((rc = check_below_2_40(n_entries, "matrix_market_body", "entries")) != 0) return rc;
+  hipStream_t st = pick_stream(ctx, stream);
+  if ((rc = ensure_sort_scratch(ctx, matrix_scratch_bytes(n_entries))) != 0) return rc;
+  IBU_HIP(launch_matrix_text_count(ctx->cfg, d_a, d_b, d_c, n_entries, add_a, add_b, ctx->d_sort_scratch, ctx->sort_scratch_bytes, st));
+  IBU_HIP(read_back<kMatrixTotalWord + 1>(ctx, ctx->d_sort_scratch, st));
+  const uint64_t bytes = ctx->h_pinned[kMatrixTotalWord];
+  *n_bytes = bytes;
+  if (maxima)
+    for (int k = 0; k < 3; ++k) maxima[k] = ctx->h_pinned[k];
+  if (!d_text && cap_bytes == 0) return IBU_OK;   // the size query
+  if (!d_text) return err_arg("d_text is NULL");
+  if (bytes > cap_bytes) return err_capacity(bytes, cap_bytes, "bytes of text", "n_bytes");
+  for (const uint64_t* col : {d_a, d_b, d_c})
+    if (ranges_overlap(d_text, bytes, col, 8 * n_entries)) return err_arg("d_text overlaps an input column");
+  IBU_HIP(launch_matrix_text_write(ctx->cfg, d_a, d_b, d_c, n_entries, add_a, add_b, ctx->d_sort_scratch, d_text, st));
+  return IBU_OK;
+}

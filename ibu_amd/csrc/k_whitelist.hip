@@ -254,38 +254,10 @@ ibu_k_select_count(const uint8_t* __restrict__ cls, u64 n, u32 nunits, u32 keep_
   }
 }
 
-// One workgroup of 1024 threads, 16 units per thread and iteration.
-static constexpr u32 kScanBlock = 1024, kScanPer = 16;
+// One workgroup of kScanBlock threads: kcommon.hpp, scan_units_in_place (shared with the matrix export, k_matrix.hip).
 extern "C" __global__ void __launch_bounds__(kScanBlock)
 ibu_k_select_scan(u64* __restrict__ units, u32 nunits) {
-  __shared__ u64 wsum[kScanBlock / kWave];
-  const u32 lane = threadIdx.x & (kWave - 1), wib = threadIdx.x >> 6;
-  u64 carry = 0;
-  for (u32 base = 0; base < nunits; base += kScanBlock * kScanPer) {   // uniform over the workgroup
-    const u32 first = base + threadIdx.x * kScanPer;
-    u64 sum = 0;
-    for (u32 k = 0; k < kScanPer; ++k)
-      if (first + k < nunits) sum += units[1 + first + k];
-    const u64 inc = wave_scan(sum, OpAdd{});
-    if (lane == kWave - 1) wsum[wib] = inc;
-    __syncthreads();
-    u64 off = carry, tot = 0;
-    for (u32 k = 0; k < kScanBlock / kWave; ++k) {
-      const u64 s = wsum[k];
-      if (k < wib) off += s;
-      tot += s;
-    }
-    __syncthreads();
-    u64 run = off + inc - sum;
-    for (u32 k = 0; k < kScanPer; ++k)
-      if (first + k < nunits) {
-        const u64 v = units[1 + first + k];
-        units[1 + first + k] = run;
-        run += v;
-      }
-    carry += tot;
-  }
-  if (threadIdx.x == 0) units[0] = carry;
+  scan_units_in_place(units, nunits);
 }
 
 extern "C" __global__ void __launch_bounds__(kBlock, 8)
@@ -403,8 +375,6 @@ ibu_k_abundance_counts(const u64* __restrict__ codes, u64 k, const WlArgs a, con
     out[j] = s != kNoSlot ? counters[s] : 0;
   }
 }
-
-struct OpMax { template <class T> __device__ __forceinline__ T operator()(T a, T b) const { return b > a ? b : a; } };
 
 // One round of resolve: every lane brings at most one class-2 record (`has`, row `idx`) and gathers its barcode; the wave
 // takes them one after the other, as wl_search_wave does: lane L probes neighbours L and L + 64 and loads their counters,

@@ -571,6 +571,7 @@ __device__ __forceinline__ u32 shfl_up_lanes(u32 v, int d) { return __shfl_up(v,
 __device__ __forceinline__ u64 shfl_up_lanes(u64 v, int d) { return shfl_up64(v, d); }
 struct OpAdd { template <class T> __device__ __forceinline__ T operator()(T a, T b) const { return a + b; } };
 struct OpMin { template <class T> __device__ __forceinline__ T operator()(T a, T b) const { return b < a ? b : a; } };
+struct OpMax { template <class T> __device__ __forceinline__ T operator()(T a, T b) const { return b > a ? b : a; } };
 // op over the 64 lanes (u32 or u64), the result in every lane; the array form reduces K values side by side.
 template <class T, class Op>
 __device__ __forceinline__ T wave_reduce(T v, Op op) {
@@ -614,6 +615,41 @@ __device__ __forceinline__ u32 block_exclusive_scan(u32 v, u32* wsum /*[4] share
   __syncthreads();  // wsum may be reused by the caller's next scan
   *total = tot;
   return off + inc - v;
+}
+
+// The middle step of a count -> scan -> scatter chain over UNITS (select in k_whitelist.hip, the matrix export in k_matrix.hip): the
+// exclusive prefix sum of units[1 .. nunits] in place, their total left in units[0].  One workgroup of kScanBlock threads, every
+// thread of it must call; kScanPer units per thread and iteration of the outer loop.
+static constexpr u32 kScanBlock = 1024, kScanPer = 16;
+__device__ __forceinline__ void scan_units_in_place(u64* __restrict__ units, u32 nunits) {
+  __shared__ u64 wsum[kScanBlock / kWave];
+  const u32 lane = threadIdx.x & (kWave - 1), wib = threadIdx.x >> 6;
+  u64 carry = 0;
+  for (u32 base = 0; base < nunits; base += kScanBlock * kScanPer) {   // uniform over the workgroup
+    const u32 first = base + threadIdx.x * kScanPer;
+    u64 sum = 0;
+    for (u32 k = 0; k < kScanPer; ++k)
+      if (first + k < nunits) sum += units[1 + first + k];
+    const u64 inc = wave_scan(sum, OpAdd{});
+    if (lane == kWave - 1) wsum[wib] = inc;
+    __syncthreads();
+    u64 off = carry, tot = 0;
+    for (u32 k = 0; k < kScanBlock / kWave; ++k) {
+      const u64 s = wsum[k];
+      if (k < wib) off += s;
+      tot += s;
+    }
+    __syncthreads();
+    u64 run = off + inc - sum;
+    for (u32 k = 0; k < kScanPer; ++k)
+      if (first + k < nunits) {
+        const u64 v = units[1 + first + k];
+        units[1 + first + k] = run;
+        run += v;
+      }
+    carry += tot;
+  }
+  if (threadIdx.x == 0) units[0] = carry;
 }
 
 }  // namespace ibu

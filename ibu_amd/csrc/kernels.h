@@ -250,6 +250,20 @@ hipError_t launch_select_count(const LaunchCfg&, const uint8_t* d_class, size_t 
                                hipStream_t st);
 hipError_t launch_select_scatter(const LaunchCfg&, const void* recs, const uint8_t* d_class, size_t n, uint32_t keep_mask,
                                  const void* scratch, void* out, hipStream_t st);
+// the matrix export (ibu_matrix_rows, ibu_matrix_market_body; k_matrix.hip), on u64 columns of n entries.  `scratch`:
+// matrix_scratch_bytes(n) bytes, 8-byte aligned.  A count launcher (count + scan) leaves u64[4] at its front for the caller to read
+// back — [0 .. 2] the largest printed value of each column (text only), [3] the total: rows, or bytes of text — and every unit's
+// offset behind them; the scatter / write launcher takes the same scratch.  rows: each output is nullable; row_ptr gets total + 1
+// words.  text: `text` at any byte alignment, exactly `total` bytes are written.
+size_t matrix_scratch_bytes(size_t n);
+static constexpr int kMatrixTotalWord = 3;
+hipError_t launch_matrix_rows_count(const LaunchCfg&, const uint64_t* first, size_t n, void* scratch, size_t scratch_bytes, hipStream_t st);
+hipError_t launch_matrix_rows_scatter(const LaunchCfg&, const uint64_t* first, size_t n, const void* scratch, uint64_t* row_of_entry,
+                                      uint64_t* row_keys, uint64_t* row_ptr, hipStream_t st);
+hipError_t launch_matrix_text_count(const LaunchCfg&, const uint64_t* a, const uint64_t* b, const uint64_t* c, size_t n, uint64_t add_a,
+                                    uint64_t add_b, void* scratch, size_t scratch_bytes, hipStream_t st);
+hipError_t launch_matrix_text_write(const LaunchCfg&, const uint64_t* a, const uint64_t* b, const uint64_t* c, size_t n, uint64_t add_a,
+                                    uint64_t add_b, const void* scratch, char* text, hipStream_t st);
 
 // DEFLATE blocks inflated on the device, one wave per block (k_inflate.hip).  The compressed bytes must be readable 2 KiB past the
 // last block (kInflatePad); block i's output goes to d_out_base + ooff (signed: a block that begins in front of the window a batch

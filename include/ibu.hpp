@@ -524,6 +524,25 @@ class Context {
     check(ibu_filter_features(c_, d_recs, n, feature_word, n_features, d_reads, d_umis, d_cells, &limits, d_class, d_verdict, &c, st));
     return c;
   }
+  // the row structure of a column of the entry table (ibu_matrix_rows): a row is a maximal run of equal d_first[k].  Each output is
+  // nullable: d_row_of_entry (n_entries words) the 0-based row of every entry, d_row_keys (cap words) the value of every row,
+  // d_row_ptr (cap + 1 words) the CSR indptr.  All three nullptr and cap = 0: the size query.  Returns the number of rows
+  // (synchronises once, for it)
+  size_t matrix_rows(const uint64_t* d_first, size_t n_entries, uint64_t* d_row_of_entry, uint64_t* d_row_keys, uint64_t* d_row_ptr, size_t cap,
+                     void* st = nullptr) {
+    size_t rows = 0;
+    check(ibu_matrix_rows(c_, d_first, n_entries, d_row_of_entry, d_row_keys, d_row_ptr, cap, &rows, st));
+    return rows;
+  }
+  // three u64 columns as decimal text (ibu_matrix_market_body): line k = d_a[k] + add_a, d_b[k] + add_b, d_c[k], separated by blanks
+  // and ended by '\n'.  d_text (any alignment) holds cap_bytes; nullptr and 0: the size query.  Returns the bytes of the text;
+  // maxima (nullable) receives the largest printed value of each column.  Synchronises once, for both
+  size_t matrix_market_body(const uint64_t* d_a, const uint64_t* d_b, const uint64_t* d_c, size_t n_entries, char* d_text, size_t cap_bytes,
+                            uint64_t add_a = 1, uint64_t add_b = 1, uint64_t maxima[3] = nullptr, void* st = nullptr) {
+    size_t bytes = 0;
+    check(ibu_matrix_market_body(c_, d_a, d_b, d_c, n_entries, add_a, add_b, d_text, cap_bytes, &bytes, maxima, st));
+    return bytes;
+  }
   // a reproducible random subset of n rows (ibu_subsample_class): d_class (n bytes, or nullptr for the count only) gets
   // IBU_SAMPLE_KEPT where the row's number splitmix64(splitmix64(seed) + first_row + row) is below `threshold` (all ones keeps every
   // row) and IBU_SAMPLE_DROPPED elsewhere; no record is read.  Returns the number kept (synchronises).  subsample_class_async: no

@@ -547,8 +547,8 @@ int32_t ibu_records_swap_umi_index(ibu_ctx_t* ctx, const void* d_src, void* d_ds
  *     (barcode, index);
  *   on ordinarily sorted records, entries are (barcode, umi) molecules with their reads and the number of distinct indices — the
  *     molecules with more than one are the chimeric ones a caller may want to drop.
- * Row pointers for a CSR view need nothing new: ibu_barcode_counts on the swapped-and-sorted records returns each barcode and, as
- * unique_umis, its number of entries (examples/count_file.cpp).
+ * Row pointers, row ordinals and the barcode of every row for a CSR view: ibu_matrix_rows on d_first (below).  The row LENGTHS alone
+ * also come from ibu_barcode_counts on the swapped-and-sorted records, as unique_umis (examples/count_file.cpp).
  * Unsorted input yields the run-length encoding described above, as ibu_barcode_counts documents for itself.  Size query: d_first =
  * d_second = d_records_per_pair = NULL and cap = 0.  cap too small: IBU_ERR_INVALID_ARG with *n_pairs (and *n_triples) set and
  * nothing written (detail.a = entries, detail.b = cap).  n == 0: OK, both totals 0.  n < 2^40; 8-byte aligned arrays.  Synchronises
@@ -572,6 +572,46 @@ int32_t ibu_pair_counts(ibu_ctx_t* ctx, const void* d_sorted_records, size_t n, 
 int32_t ibu_count_matrix(ibu_ctx_t* ctx, void* d_records, void* d_tmp, size_t n, uint32_t flags, uint64_t* d_barcodes,
                          uint64_t* d_indices, uint64_t* d_reads, uint64_t* d_umis, size_t cap, size_t* n_entries, size_t* n_molecules,
                          void* stream);
+/* Matrix export, on the device (k_matrix.hip): the two steps between the entry table above and what readers of a single-cell matrix
+ * take — a CSR triple with rows numbered from 0, or the 10x directory (matrix.mtx, barcodes.tsv, features.tsv) that scanpy's
+ * read_10x_mtx and Seurat's Read10X read.  Both calls work on the ENTRY TABLE, the device columns ibu_pair_counts / ibu_count_matrix
+ * produce, not on the records, so they follow any chain of filters.  The reference has no such function; the semantics are this
+ * library's and are stated in full here.  The input columns are never written.
+ *
+ * ibu_matrix_rows: the row structure of a column.  A ROW is a maximal run of consecutive entries with equal d_first[k]; equal values
+ * in runs that are not adjacent are different rows (A, B, A is three rows), as every run-level call here documents for itself.  Each
+ * of the three outputs is nullable on its own:
+ *   d_row_of_entry[k]  the 0-based number of the row entry k lies in; n_entries words;
+ *   d_row_keys[r]      the value of row r;
+ *   d_row_ptr[r]       the index of row r's first entry for r < *n_rows, and d_row_ptr[*n_rows] = n_entries — the CSR indptr.  The
+ *                      array holds cap + 1 words; exactly *n_rows + 1 are written.
+ * With d_first = the barcodes of the entry table, d_row_ptr / d_second / the counts are the CSR triple (indptr, indices, data) of
+ * the cell x feature matrix and d_row_keys its barcodes.  *n_rows = the number of rows.  Size query: the three outputs NULL and
+ * cap = 0 (with the outputs NULL any cap gives the count alone).  cap < *n_rows with any output given: IBU_ERR_INVALID_ARG with
+ * *n_rows set and nothing written (detail.a = rows, detail.b = cap).  n_entries == 0: OK, *n_rows = 0, nothing touched — not even
+ * d_row_ptr[0].  n_entries < 2^40; 8-byte aligned arrays; the outputs must not overlap d_first or each other.  Synchronises
+ * `stream` once (the number of rows comes back); the writes may still be queued on return.  Reads the column twice (once for the size
+ * query) and writes 8 B per entry and 16 B per row.  Scratch: 8 B per 2048 entries of the context's sort scratch, grown on demand.
+ *
+ * ibu_matrix_market_body: three u64 columns as decimal text.  Line k is
+ *   dec(d_a[k] + add_a) ' ' dec(d_b[k] + add_b) ' ' dec(d_c[k]) '\n'
+ * with the sums taken modulo 2^64 (2^64 - 1 with an addend of 1 prints 0) and dec(v) the shortest decimal form of v: "0" for zero, no
+ * sign, no padding.  A line is 6 to 63 bytes.  The text is the concatenation of the lines in entry order — every line ends in its
+ * '\n', and nothing (no NUL) follows the last.  *n_bytes = its length.  maxima (nullable, host) = the largest PRINTED value of each
+ * column (after the addition), all zero when n_entries == 0: a caller checks the dimensions it writes in a header against them
+ * without downloading a column.  d_text may have ANY byte alignment; no byte in front of d_text and none from d_text + *n_bytes on
+ * is written, not even with the value it already holds.  The three columns may be one and the same array.  With d_a = the indices,
+ * add_a = 1, d_b = d_row_of_entry, add_b = 1 and d_c = a count column this is the body of a MatrixMarket coordinate file, features x
+ * barcodes, 1-based, as 10x writes it.  Size query: d_text = NULL and cap_bytes = 0.  cap_bytes < *n_bytes: IBU_ERR_INVALID_ARG with
+ * *n_bytes (and maxima) set and nothing written (detail.a = bytes, detail.b = cap_bytes).  n_entries == 0: OK, *n_bytes = 0, nothing
+ * touched.  n_entries < 2^40; 8-byte aligned columns; d_text must not overlap a column.  Synchronises `stream` once (the length
+ * and the maxima come back); the write pass may still be queued on return.  Reads the columns twice (once for the size query).
+ * Scratch: as ibu_matrix_rows. */
+int32_t ibu_matrix_rows(ibu_ctx_t* ctx, const uint64_t* d_first, size_t n_entries, uint64_t* d_row_of_entry, uint64_t* d_row_keys,
+                        uint64_t* d_row_ptr, size_t cap, size_t* n_rows, void* stream);
+int32_t ibu_matrix_market_body(ibu_ctx_t* ctx, const uint64_t* d_a, const uint64_t* d_b, const uint64_t* d_c, size_t n_entries,
+                               uint64_t add_a, uint64_t add_b, char* d_text, size_t cap_bytes, size_t* n_bytes,
+                               uint64_t maxima[3] /* host, nullable */, void* stream);
 /* One index per molecule, on the device (k_molecules.hip) — the step between ibu_sort_records and the count matrix that drops
  * chimeric reads: a (barcode, umi) seen with two or more index values (PCR chimeras, index hopping, multi-mapped reads) would
  * otherwise be counted once under every one of them.  The reference has no such function; the semantics are this library's and are

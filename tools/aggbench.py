@@ -9,6 +9,7 @@ into preallocated device arrays, no download.
   python tools/aggbench.py --saturation [--records 1e9] [--reads-per-molecule 4]     ibu_saturation_curve, ibu_subsample_class (saturation_legs below)
   python tools/aggbench.py --metrics [--records 1e9] [--reads-per-molecule 4]     ibu_barcode_metrics, ibu_filter_barcodes (metrics_legs below)
   python tools/aggbench.py --features [--records 1e9] [--reads-per-molecule 4]     ibu_feature_metrics, ibu_filter_features (feature_legs below)
+  python tools/aggbench.py --mtx [--records 1e8] [--host-entries 1e7]     ibu_matrix_rows, ibu_matrix_market_body (mtx_legs below; --records counts entries)
 bc_len 10 gives 2^20 distinct barcodes (a single-cell whitelist's order of magnitude); 16 gives ~n runs of length one."""
 import argparse
 import ctypes as C
@@ -635,8 +636,138 @@ def saturation_legs(a):
     print(json.dumps(res), flush=True)
 
 
+MTX_ROW, MTX_BC_LEN = 1999, 16                                  # --mtx: entries per barcode (no multiple of a unit of 2048), bases per barcode
+
+
+def mtx_fill(torch, i):
+    """--mtx: entry i of the synthetic entry table -> (barcode, index, umis, reads) as int64 tensors, a pure function of i (replayed
+    on the CPU by tests/test_mtx_tools.py).  Rows of MTX_ROW entries; the barcode of row r is r scattered over 32 bits by an odd
+    multiplier, so neighbouring rows differ; the index ascends inside a row in steps of 17 (up to five digits); the UMI count is
+    1 .. 20 with one entry in 1024 in the thousands, the reads three times that and one."""
+    row = i // MTX_ROW
+    bc = (row * 0x9E3779B1) & 0xFFFFFFFF
+    idx = (i % MTX_ROW) * 17
+    h = ((i * 0x9E3779B1) >> 7) & 0xFFFFF
+    umis = 1 + h % 20 + torch.where(h % 1024 == 0, h // 64, torch.zeros_like(h))
+    return bc, idx, umis, 3 * umis + 1
+
+
+def mtx_layout(n):
+    """-> (rows, n_features) of the table mtx_fill lays for n entries."""
+    return (n + MTX_ROW - 1) // MTX_ROW, (MTX_ROW - 1) * 17 + 1
+
+
+def mtx_traffic(n, text_bytes):
+    """The bytes ibu_matrix_market_body moves for n entries and text_bytes of text: the three columns read twice and the text written
+    once — and the size of the ibu_device_copy (read + write of every byte) that moves as many."""
+    total = 2 * 3 * 8 * n + text_bytes
+    return total, total // 2
+
+
+def mtx_legs(a):
+    """--mtx: the matrix export on a resident entry table of --records entries (mtx_fill), one run on one set of arrays, timed with
+    events on a side stream (the first round is the warm-up): ibu_matrix_rows (size query; all three outputs), ibu_matrix_market_body
+    (the size query = the length pass; the full call = length pass + write pass, the write pass being the difference), against
+    ibu_device_copy of as many bytes as the body moves (mtx_traffic) and ibu_reduce over the three columns (one plain read of 24 B
+    per entry); then the wall time of the host loop examples/count_file.cpp prints with (tools/mtx_host_loop.cpp, one printf per entry
+    to /dev/null) on the same columns, downloaded.  Before anything is timed the row structure is checked against what was laid."""
+    import subprocess
+    import tempfile
+    import numpy as np
+    import torch                                             # before the library, as bench.py does
+    torch.cuda.init()
+    import ibu_amd as ia
+    from ibu_amd import _dptr, _check, lib
+
+    ctx = ia.Context(0)
+    side = torch.cuda.Stream()
+    st = side.cuda_stream
+    n = int(float(a.records.split(",")[0]))
+    rows_laid, nf = mtx_layout(n)
+    assert n >= MTX_ROW, "--mtx wants at least one full row"
+    three = ctx.alloc(24 * n)                                # index | row ordinal | umis, back to back: ibu_reduce reads them as n records
+    d_idx, d_ord, d_umis = (ia.DeviceBuffer.wrap(ctx, three.ptr + 8 * n * k, 8 * n) for k in range(3))
+    d_bc, d_reads = ctx.alloc(8 * n), ctx.alloc(8 * n)
+    views = [torch.as_tensor(b, device="cuda").view(torch.int64) for b in (d_bc, d_idx, d_umis, d_reads)]
+    for lo in range(0, n, 1 << 26):
+        hi = min(n, lo + (1 << 26))
+        for v, x in zip(views, mtx_fill(torch, torch.arange(lo, hi, device="cuda", dtype=torch.int64))):
+            v[lo:hi] = x
+    torch.cuda.synchronize()
+    d_keys, d_ptr = ctx.alloc(8 * rows_laid), ctx.alloc(8 * (rows_laid + 1))
+
+    def timed(fn):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record(side)
+        fn()
+        e1.record(side)
+        e1.synchronize()
+        return e0.elapsed_time(e1)
+
+    def rounds(fn):
+        v = [timed(fn) for _ in range(a.rounds + 1)][1:]
+        return {"median_ms": round(statistics.median(v), 3), "min_ms": round(min(v), 3), "max_ms": round(max(v), 3)}
+
+    nr, nb, mx = C.c_size_t(), C.c_size_t(), (C.c_uint64 * 3)()
+    rows = lambda outs, cap: _check(lib.ibu_matrix_rows(ctx._c, _dptr(d_bc), n, *[_dptr(o) for o in outs], cap, C.byref(nr), st))
+    body = lambda text, cap: _check(lib.ibu_matrix_market_body(ctx._c, _dptr(d_idx), _dptr(d_ord), _dptr(d_umis), n, 1, 1, _dptr(text), cap,
+                                                               C.byref(nb), mx, st))
+    # the check, before anything is timed
+    rows([d_ord, d_keys, d_ptr], rows_laid)
+    ctx.synchronize()
+    assert nr.value == rows_laid, (nr.value, rows_laid)
+    ptr = torch.as_tensor(d_ptr, device="cuda").view(torch.int64)[:rows_laid + 1]
+    assert bool((ptr == torch.clamp(torch.arange(rows_laid + 1, device="cuda", dtype=torch.int64) * MTX_ROW, max=n)).all())
+    body(None, 0)
+    text_bytes = nb.value
+    assert tuple(mx) == (nf, rows_laid, int(views[2].max())), (tuple(mx), nf, rows_laid)
+    d_text = ctx.alloc(text_bytes + 1)
+    body(ia.DeviceBuffer.wrap(ctx, d_text.ptr + 1, text_bytes), text_bytes)   # an odd address
+    ctx.synchronize()
+    head = d_text.download(np.uint8, 64, 1).tobytes().split(b"\n")[0]
+    assert head == b"1 1 %d" % int(views[2][0]), head
+    total, copy_bytes = mtx_traffic(n, text_bytes)
+    src, dst = ctx.alloc(copy_bytes), ctx.alloc(copy_bytes)
+    res = {"leg": "mtx", "n": n, "rows": rows_laid, "n_features": nf, "text_bytes": text_bytes, "bytes_per_line": round(text_bytes / n, 2),
+           "body_traffic_bytes": total, "copy_bytes": copy_bytes}
+    res["device_copy"] = rounds(lambda: _check(lib.ibu_device_copy(ctx._c, _dptr(dst), _dptr(src), copy_bytes, st)))
+    res["reduce_three_columns"] = rounds(lambda: _check(lib.ibu_reduce(ctx._c, _dptr(three), n, st)))
+    res["matrix_rows_size_query"] = rounds(lambda: rows([None] * 3, 0))
+    res["matrix_rows_all_outputs"] = rounds(lambda: rows([d_ord, d_keys, d_ptr], rows_laid))
+    res["body_size_query"] = rounds(lambda: body(None, 0))
+    res["body_full_call"] = rounds(lambda: body(d_text, text_bytes))
+    res["device_copy_again"] = rounds(lambda: _check(lib.ibu_device_copy(ctx._c, _dptr(dst), _dptr(src), copy_bytes, st)))
+    cp = min(res["device_copy"]["median_ms"], res["device_copy_again"]["median_ms"])
+    res["body_write_pass_ms"] = round(res["body_full_call"]["median_ms"] - res["body_size_query"]["median_ms"], 3)   # a difference, not a timing
+    res["body_full_call_vs_copy"] = round(res["body_full_call"]["median_ms"] / cp, 3)
+    res["body_size_query_vs_reduce"] = round(res["body_size_query"]["median_ms"] / res["reduce_three_columns"]["median_ms"], 3)
+    res["matrix_rows_all_outputs_vs_reduce"] = round(res["matrix_rows_all_outputs"]["median_ms"] / res["reduce_three_columns"]["median_ms"], 3)
+    print(json.dumps(res), flush=True)                       # (before the host loop: a run that is cut short there still leaves its times)
+    host_n = min(n, int(float(a.host_entries))) if a.host_entries else n
+    with tempfile.TemporaryDirectory() as td:
+        so = os.path.join(td, "mtx_host_loop.so")
+        subprocess.check_call(["g++", "-O2", "-std=c++17", "-shared", "-fPIC", os.path.join(ROOT, "tools", "mtx_host_loop.cpp"), "-o", so])
+        loop = C.CDLL(so).mtx_host_loop
+        loop.restype, loop.argtypes = C.c_double, [C.c_void_p] * 4 + [C.c_size_t, C.c_uint32, C.c_char_p]
+        t0 = time.perf_counter()
+        cols = [b.download(np.uint64, host_n) for b in (d_bc, d_idx, d_umis, d_reads)]
+        res["download_four_columns_s"] = round(time.perf_counter() - t0, 3)
+        s = loop(*[c.ctypes.data for c in cols], host_n, MTX_BC_LEN, b"/dev/null")
+        assert s >= 0
+    res["host_loop_entries"] = host_n
+    res["host_loop_s"] = round(s, 3)
+    res["host_loop_s_per_1e8"] = round(s * 1e8 / host_n, 3)
+    t0 = time.perf_counter()
+    got = d_text.download(np.uint8, text_bytes)
+    res["download_text_s"] = round(time.perf_counter() - t0, 3)
+    assert got[-1] == 10 and int((got == 10).sum()) == n
+    print(json.dumps(res), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--mtx", action="store_true", help="the ibu_matrix_rows / ibu_matrix_market_body legs instead of the barcode leg")
+    ap.add_argument("--host-entries", default="", help="--mtx: the host loop runs over this many entries (default: all)")
     ap.add_argument("--saturation", action="store_true", help="the ibu_saturation_curve / ibu_subsample_class legs instead of the barcode leg")
     ap.add_argument("--metrics", action="store_true", help="the ibu_barcode_metrics / ibu_filter_barcodes legs instead of the barcode leg")
     ap.add_argument("--features", action="store_true", help="the ibu_feature_metrics / ibu_filter_features legs instead of the barcode leg")
@@ -650,6 +781,8 @@ def main():
     ap.add_argument("--rounds", type=int, default=5)
     ap.add_argument("--whitelist", type=int, default=0, help="K > 0: barcodes drawn from K distinct ones, skewed (rank ~ K u^3), as tools/sortbench.py --whitelist")
     a = ap.parse_args()
+    if a.mtx:
+        return mtx_legs(a)
     if a.saturation:
         return saturation_legs(a)
     if a.metrics:
