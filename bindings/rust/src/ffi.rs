@@ -115,6 +115,25 @@ pub struct ibu_feature_filter_counts_t {
     pub reads_by_class: [u64; 4],
     pub reserved: u64,
 }
+pub const IBU_NO_KEY: u64 = u64::MAX;
+pub const IBU_ROW_ASSIGNED: u8 = 0;
+pub const IBU_ROW_NONE: u8 = 1;
+pub const IBU_ROW_MIXED: u8 = 2;
+#[repr(C)]
+#[derive(Default, Debug, Clone, Copy, PartialEq, Eq)]
+pub struct ibu_assign_rule_t {
+    pub min_value: u64,
+    pub num: u64,
+    pub den: u64,
+}
+#[repr(C)]
+#[derive(Default, Debug, Clone, Copy, PartialEq, Eq)]
+pub struct ibu_assign_counts_t {
+    pub rows: u64,
+    pub assigned: u64,
+    pub none: u64,
+    pub mixed: u64,
+}
 #[repr(C)]
 #[derive(Default, Debug, Clone, Copy, PartialEq, Eq)]
 pub struct ibu_saturation_point_t {
@@ -303,6 +322,11 @@ extern "C" {
     pub fn ibu_matrix_market_body(ctx: *mut ibu_ctx_t, d_a: *const u64, d_b: *const u64, d_c: *const u64, n_entries: usize, add_a: u64,
                                   add_b: u64, d_text: *mut c_char, cap_bytes: usize, n_bytes: *mut usize, maxima: *mut u64,
                                   stream: *mut c_void) -> i32;
+    pub fn ibu_matrix_row_top(ctx: *mut ibu_ctx_t, d_first: *const u64, d_second: *const u64, d_values: *const u64, n_entries: usize,
+                              d_set: *const u64, set_bits: u64, d_top_key: *mut u64, d_top_value: *mut u64, d_next_value: *mut u64,
+                              d_row_sum: *mut u64, d_row_entries: *mut u64, cap: usize, n_rows: *mut usize, stream: *mut c_void) -> i32;
+    pub fn ibu_assign_rows(ctx: *mut ibu_ctx_t, d_top_value: *const u64, d_next_value: *const u64, d_row_sum: *const u64, n_rows: usize,
+                           rule: *const ibu_assign_rule_t, d_row_class: *mut u8, counts: *mut ibu_assign_counts_t, stream: *mut c_void) -> i32;
     pub fn ibu_whitelist_create(ctx: *mut ibu_ctx_t, d_codes: *const u64, w: usize, bc_len: u32, stream: *mut c_void,
                                 out: *mut *mut ibu_whitelist_t) -> i32;
     pub fn ibu_whitelist_info(wl: *const ibu_whitelist_t, bc_len: *mut u32, n_distinct: *mut usize, device_bytes: *mut usize) -> i32;

@@ -718,6 +718,45 @@ pub mod device {
             check(unsafe { ffi::ibu_ctx_synchronize(self.raw, std::ptr::null_mut()) })?;
             Ok((host, maxima))
         }
+        /// `ibu_matrix_row_top`: per row of the entry table (a row is a maximal run of equal `first`) the largest of `values`, the
+        /// `second` of the first entry that holds it, the largest value among the other entries, the sum modulo 2^64 and the number
+        /// of entries — over the entries whose `second` is in `set` (`(bitmap, bits)`; `None`: all entries).  Returns the five
+        /// device columns `[top_key, top_value, next_value, row_sum, row_entries]` and the number of rows.  A row in which no entry
+        /// takes part has `IBU_NO_KEY, 0, 0, 0, 0`.
+        pub fn matrix_row_top(&self, first: &DeviceBuf, second: &DeviceBuf, values: &DeviceBuf, n_entries: usize, set: Option<(&DeviceBuf, u64)>)
+                              -> Result<(Vec<DeviceBuf>, usize)> {
+            let col = |d: &DeviceBuf| d.ptr as *const u64;
+            let (d_set, bits) = set.map_or((std::ptr::null(), 0u64), |(b, n)| (b.ptr as *const u64, n));
+            let mut nr = 0usize;
+            check(unsafe {
+                ffi::ibu_matrix_row_top(self.raw, col(first), col(second), col(values), n_entries, d_set, bits, std::ptr::null_mut(), std::ptr::null_mut(),
+                                        std::ptr::null_mut(), std::ptr::null_mut(), std::ptr::null_mut(), 0, &mut nr, std::ptr::null_mut())
+            })?;
+            let mut outs = Vec::new();
+            for _ in 0..5 {
+                outs.push(self.alloc(8 * nr.max(2))?);
+            }
+            let out = |k: usize| outs[k].ptr as *mut u64;
+            check(unsafe {
+                ffi::ibu_matrix_row_top(self.raw, col(first), col(second), col(values), n_entries, d_set, bits, out(0), out(1), out(2), out(3), out(4), nr,
+                                        &mut nr, std::ptr::null_mut())
+            })?;
+            Ok((outs, nr))
+        }
+        /// `ibu_assign_rows`: the class of every row from the columns `matrix_row_top` returned — `IBU_ROW_NONE` where the top value
+        /// is below `max(rule.min_value, 1)`, else `IBU_ROW_ASSIGNED` where it is above the runner-up and `top * den >= num * sum`
+        /// (exact; `num == 0`: no share test), else `IBU_ROW_MIXED`.  `class` (optional): `n_rows` bytes.  Synchronises and returns
+        /// the totals.
+        pub fn assign_rows(&self, top_value: &DeviceBuf, next_value: &DeviceBuf, row_sum: &DeviceBuf, n_rows: usize, rule: &ffi::ibu_assign_rule_t,
+                           class: Option<&DeviceBuf>) -> Result<ffi::ibu_assign_counts_t> {
+            let col = |d: &DeviceBuf| d.ptr as *const u64;
+            let mut c = ffi::ibu_assign_counts_t::default();
+            check(unsafe {
+                ffi::ibu_assign_rows(self.raw, col(top_value), col(next_value), col(row_sum), n_rows, rule, class.map_or(std::ptr::null_mut(), |b| b.ptr as *mut u8),
+                                     &mut c, std::ptr::null_mut())
+            })?;
+            Ok(c)
+        }
         /// Barcode correction against a whitelist, in place over `n` device records (`ibu_correct_barcodes`): exact hits stay, a
         /// barcode with exactly one whitelist entry one substitution away moves onto it.  `class` (optional): `n` bytes, one
         /// class per record (0 exact, 1 corrected, 2 ambiguous, 3 unmatched).  Synchronises and returns the four totals.

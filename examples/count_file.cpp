@@ -44,6 +44,15 @@
 // DIR/barcodes.tsv and DIR/features.tsv (N lines, the index value as id and name).  The entry table stays on the device:
 // ibu_pair_counts into device columns, ibu_matrix_rows numbers the barcodes, ibu_matrix_market_body formats the lines there, and
 // the text comes down in pieces.  An index value of N or more is an error, and nothing is written.
+//   count_file ... [--assign=min:A[,share:NUM/DEN]] [--set=FILE] IN [WHITELIST.txt]
+// --assign: the dominant feature of every barcode — which hashtag, antibody or guide a cell carries — behind whatever chain the other
+// options selected, behind the matrix and its rows as one
+//   #assign<TAB>barcode<TAB>top_feature<TAB>top<TAB>next<TAB>total<TAB>class
+// line per barcode: over the features of --set=FILE (without it: all features) the index value with the most UMIs (the smallest one
+// among tied ones; - when the barcode has none of them), its UMIs, the UMIs of the runner-up, the UMIs of all of them, and the class —
+// none (fewer than max(A, 1) UMIs at the top), assigned (the top is alone there and holds at least NUM/DEN of the total; without
+// share: no such test) or mixed.  ibu_pair_counts into device columns, ibu_matrix_row_top, ibu_assign_rows: the entry table stays on
+// the device and 41 bytes per barcode come down.  The four totals go to stderr.
 #include <algorithm>
 #include <cerrno>
 #include <cstdio>
@@ -165,6 +174,22 @@ static bool parse_n_features(const char* s, uint64_t* n) {
   return errno != ERANGE && *end == 0 && *n >= 1 && *n <= (1ull << 32);
 }
 
+// "min:A[,share:NUM/DEN]" -> the rule of ibu_assign_rows; false otherwise
+static bool parse_assign(const char* s, ibu_assign_rule_t* rule) {
+  *rule = ibu_assign_rule_t{0, 0, 1};
+  char* end = nullptr;
+  if (std::strncmp(s, "min:", 4) || s[4] < '0' || s[4] > '9') return false;
+  errno = 0;
+  rule->min_value = std::strtoull(s + 4, &end, 10);
+  if (errno == ERANGE) return false;
+  if (*end == 0) return true;
+  if (std::strncmp(end, ",share:", 7) || end[7] < '0' || end[7] > '9') return false;
+  rule->num = std::strtoull(end + 7, &end, 10);
+  if (*end != '/' || end[1] < '0' || end[1] > '9') return false;
+  rule->den = std::strtoull(end + 1, &end, 10);
+  return errno != ERANGE && *end == 0 && rule->den >= 1 && rule->num <= rule->den;
+}
+
 // one index value per line -> the bitmap of ibu_filter_barcodes and its number of bits (the largest value + 1)
 static std::vector<uint64_t> read_set(const char* path, uint64_t* bits) {
   std::ifstream f(path);
@@ -238,9 +263,44 @@ static void write_mtx(ibu::device::Context& ctx, const void* recs, size_t n, uin
   close(f, "features.tsv");
 }
 
+// --assign: one line per barcode of the {barcode, index, umi} records as they stand, and the totals
+static void print_assignment(ibu::device::Context& ctx, const void* recs, size_t n, uint32_t bc_len, const ibu_assign_rule_t& rule,
+                             const char* set_path) {
+  using namespace ibu;
+  uint64_t set_bits = 0;
+  std::vector<uint64_t> words(1, 0);
+  if (set_path) words = read_set(set_path, &set_bits);
+  device::DeviceBuffer d_set(ctx, 8 * words.size());
+  d_set.upload(words);
+  const uint64_t* set = set_path ? d_set.as<uint64_t>() : nullptr;   // an empty file is the empty set, not "all features"
+  size_t nnz = 0;
+  check(ibu_pair_counts(ctx.raw(), recs, n, nullptr, nullptr, nullptr, nullptr, 0, &nnz, nullptr, nullptr));
+  device::DeviceBuffer d_bc(ctx, 8 * nnz), d_idx(ctx, 8 * nnz), d_reads(ctx, 8 * nnz), d_umis(ctx, 8 * nnz);
+  check(ibu_pair_counts(ctx.raw(), recs, n, d_bc.as<uint64_t>(), d_idx.as<uint64_t>(), d_reads.as<uint64_t>(), d_umis.as<uint64_t>(), nnz, &nnz,
+                        nullptr, nullptr));
+  const size_t rows = ctx.matrix_rows(d_bc.as<uint64_t>(), nnz, nullptr, nullptr, nullptr, 0);
+  device::DeviceBuffer d_keys(ctx, 8 * rows), d_key(ctx, 8 * rows), d_top(ctx, 8 * rows), d_next(ctx, 8 * rows), d_sum(ctx, 8 * rows), d_class(ctx, rows);
+  ctx.matrix_rows(d_bc.as<uint64_t>(), nnz, nullptr, d_keys.as<uint64_t>(), nullptr, rows);
+  ctx.matrix_row_top(d_bc.as<uint64_t>(), d_idx.as<uint64_t>(), d_umis.as<uint64_t>(), nnz,
+                     {d_key.as<uint64_t>(), d_top.as<uint64_t>(), d_next.as<uint64_t>(), d_sum.as<uint64_t>(), nullptr}, rows, set, set_bits);
+  const device::AssignCounts c = ctx.assign_rows(d_top.as<uint64_t>(), d_next.as<uint64_t>(), d_sum.as<uint64_t>(), rows, rule, d_class.as<uint8_t>());
+  const auto bc = d_keys.download<uint64_t>(rows), key = d_key.download<uint64_t>(rows), top = d_top.download<uint64_t>(rows),
+             next = d_next.download<uint64_t>(rows), sum = d_sum.download<uint64_t>(rows);
+  const auto cls = d_class.download<uint8_t>(rows);
+  static const char* const names[] = {"assigned", "none", "mixed"};
+  for (size_t r = 0; r < rows; ++r) {
+    const std::string feature = key[r] == IBU_NO_KEY ? "-" : std::to_string(key[r]);
+    std::printf("#assign\t%s\t%s\t%llu\t%llu\t%llu\t%s\n", decode(bc[r], bc_len).c_str(), feature.c_str(), (unsigned long long)top[r],
+                (unsigned long long)next[r], (unsigned long long)sum[r], cls[r] < 3 ? names[cls[r]] : "?");
+  }
+  std::fprintf(stderr, "%zu barcodes: assigned %llu, none %llu, mixed %llu\n", (size_t)c.rows, (unsigned long long)c.assigned,
+               (unsigned long long)c.none, (unsigned long long)c.mixed);
+}
+
 int main(int argc, char** argv) {
   int resolve = 0;                                              // 1: --resolve, 2: --resolve=first
-  bool cells = false, bad = false, subsample = false, qc = false, features = false;
+  bool cells = false, bad = false, subsample = false, qc = false, features = false, assign = false;
+  ibu_assign_rule_t assign_rule{0, 0, 1};
   ibu_barcode_limits_t qc_limits{};
   ibu_feature_limits_t feature_limits{};
   uint64_t n_features = 0;
@@ -262,15 +322,17 @@ int main(int argc, char** argv) {
     else if (!std::strncmp(argv[1], "--n-features=", 13) && parse_n_features(argv[1] + 13, &n_features)) {}
     else if (!std::strncmp(argv[1], "--feature-table=", 16) && argv[1][16]) table_path = argv[1] + 16;
     else if (!std::strncmp(argv[1], "--mtx=", 6) && argv[1][6]) mtx_dir = argv[1] + 6;
+    else if (!std::strncmp(argv[1], "--assign=", 9) && parse_assign(argv[1] + 9, &assign_rule)) assign = true;
     else bad = true;
   }
   const bool feature_steps = features || table_path;            // --mtx wants N as well, and none of the feature steps
-  if (argc < 2 || bad || (set_path && !qc) || ((feature_steps || mtx_dir) != (n_features != 0))) {
+  if (argc < 2 || bad || (set_path && !qc && !assign) || ((feature_steps || mtx_dir) != (n_features != 0))) {
     std::fprintf(stderr, "usage: count_file [--resolve | --resolve=first] [--cells=min:T|top:K|expected:E] [--subsample=F[:seed]] [--saturation=K] "
                  "IN [WHITELIST.txt]\n"
                  "       further options: [--qc=minfeat:A[,maxfeat:B][,minumi:C][,maxset:NUM/DEN]] [--set=FILE] (FILE: one index value per line)\n"
                  "                        [--features=mincells:A[,minumi:B][,maxcells:C] --n-features=N] [--feature-table=FILE] (with --n-features=N)\n"
-                 "                        [--mtx=DIR --n-features=N] (matrix.mtx, barcodes.tsv, features.tsv)\n");
+                 "                        [--mtx=DIR --n-features=N] (matrix.mtx, barcodes.tsv, features.tsv)\n"
+                 "                        [--assign=min:A[,share:NUM/DEN]] [--set=FILE] (the dominant feature of every barcode, over the set)\n");
     return 2;
   }
   try {
@@ -421,6 +483,7 @@ int main(int argc, char** argv) {
     }
     if (total != entries.size()) throw std::runtime_error("the row lengths do not add up to the number of entries");
     if (mtx_dir) write_mtx(ctx, recs, kept, h.bc_len, n_features, mtx_dir);
+    if (assign) print_assignment(ctx, recs, kept, h.bc_len, assign_rule, set_path);
     ctx.free(d_recs);
   } catch (const std::exception& e) {
     std::fprintf(stderr, "error: %s\n", e.what());

@@ -11,7 +11,9 @@ Context.resolve_barcodes: ambiguous barcodes to the candidate with nearly all of
 filter_barcodes (the per-barcode QC filter: too few or too many features / UMIs, too large a share of a feature set built with
 Context.feature_bitmap; barcode_metrics returns the table itself) -> select_records -> feature_metrics -> filter_features (the
 other axis: features seen in too few cells) -> select_records -> pair_counts, or, in the forms other tools read, matrix_csr (a CSR
-triple on the device) and write_matrix_market (the 10x directory, its text formatted on the device).
+triple on the device) and write_matrix_market (the 10x directory, its text formatted on the device); for hashtag, antibody and guide
+libraries assign_features (one line per cell: its dominant feature, the runner-up, the row total and a class, from matrix_row_top
+and assign_rows over the entry table).
 """
 import copy
 import ctypes as C
@@ -21,7 +23,7 @@ from collections import namedtuple
 import numpy as np
 
 from . import _lib
-from ._lib import CAllocProbe, CBarcodeFilterCounts, CBarcodeLimits, CFeatureFilterCounts, CFeatureLimits, CCellCounts, CCorrectCounts, CResolveCounts, CDecodeSink, CMoleculeCounts, CErrorDetail, CKeyPlan, CHeader, CNumaInfo, CProcessorVTable, CRecord, CReduceResult, CRingConfig, CSaturationPoint, CStreamStats
+from ._lib import CAllocProbe, CAssignCounts, CAssignRule, CBarcodeFilterCounts, CBarcodeLimits, CFeatureFilterCounts, CFeatureLimits, CCellCounts, CCorrectCounts, CResolveCounts, CDecodeSink, CMoleculeCounts, CErrorDetail, CKeyPlan, CHeader, CNumaInfo, CProcessorVTable, CRecord, CReduceResult, CRingConfig, CSaturationPoint, CStreamStats
 
 lib = _lib.load()
 
@@ -56,6 +58,10 @@ FeatureFilterCounts = namedtuple("FeatureFilterCounts", "features_by_class reads
 #: what ibu_matrix_rows leaves: the number of rows and three DeviceBuffers of u64 — the value of every row (n_rows words), the CSR
 #: indptr (n_rows + 1 words) and the 0-based row of every entry (None where not asked for)
 MatrixRows = namedtuple("MatrixRows", "n_rows d_keys d_ptr d_row_of_entry")
+NO_KEY = (1 << 64) - 1  # the top key of a row in which no entry took part (IBU_NO_KEY)
+ROW_ASSIGNED, ROW_NONE, ROW_MIXED = 0, 1, 2  # the classes of ibu_assign_rows (IBU_ROW_*)
+#: the totals of one ibu_assign_rows call (ibu_assign_counts_t)
+AssignCounts = namedtuple("AssignCounts", "rows assigned none mixed")
 MTX_BANNER = "%%MatrixMarket matrix coordinate integer general"
 SAMPLE_KEPT, SAMPLE_DROPPED = 0, 1  # the classes of ibu_subsample_class (IBU_SAMPLE_KEPT, IBU_SAMPLE_DROPPED)
 SATURATION_MAX_POINTS = 32
@@ -710,6 +716,30 @@ class CsrMatrix:
                 b.free()
 
 
+class RowTop:
+    """What ibu_matrix_row_top leaves, on the device (Context.matrix_row_top): five DeviceBuffers of n_rows u64 — per row of the
+    entry table `top_key` (the feature of the first entry with the largest value; NO_KEY where no entry took part), `top_value`,
+    `next_value` (the largest value among the other entries), `row_sum` (modulo 2^64) and `row_entries`."""
+
+    def __init__(self, top_key, top_value, next_value, row_sum, row_entries, n_rows):
+        self.top_key, self.top_value, self.next_value, self.row_sum, self.row_entries, self.n_rows = (
+            top_key, top_value, next_value, row_sum, row_entries, n_rows)
+
+    def _buffers(self):
+        return self.top_key, self.top_value, self.next_value, self.row_sum, self.row_entries
+
+    def download(self):
+        """-> (top_key, top_value, next_value, row_sum, row_entries) as numpy u64 arrays."""
+        if self.n_rows == 0:
+            return tuple(np.empty(0, np.uint64) for _ in range(5))
+        return tuple(b.download(np.uint64, self.n_rows) for b in self._buffers())
+
+    def free(self):
+        for b in self._buffers():
+            if b is not None:
+                b.free()
+
+
 class DeviceBatch:
     """One device-resident batch of a DeviceStream: `n` AoS records at device pointer `ptr` (a ring slot), the first of them
     record number `first_index` of the stream.  release() (or leaving the `with` block) gives the slot back: it is refilled once
@@ -1123,6 +1153,58 @@ class Context:
         for k in (0, 5 - which):
             cols[k].free()
         return CsrMatrix(rows.d_keys, rows.d_ptr, cols[1], cols[which], rows.n_rows, nnz)
+
+    # the dominant feature of every row: per-row top-2 of the entry table, and the class made from it
+    def matrix_row_top(self, d_first, d_second, d_values, n_entries, feature_set=None, stream=None):
+        """ibu_matrix_row_top over three device columns of n_entries u64 (the barcodes, the feature numbers and a count column of
+        the entry table): per row — a maximal run of equal d_first — the largest value, the feature of the first entry that holds
+        it, the largest value among the other entries, the sum modulo 2^64 and the number of entries, over the entries whose
+        feature is in feature_set (what feature_bitmap returned; None: all entries) -> RowTop, on the device.  A row in which
+        nothing takes part has NO_KEY, 0, 0, 0, 0.  Two calls, the size query and the write; synchronises once each."""
+        d_set, bits = _feature_set(feature_set)
+        cols = [_dptr(d_first), _dptr(d_second), _dptr(d_values)]
+        nr = C.c_size_t()
+        _check(lib.ibu_matrix_row_top(self._c, *cols, n_entries, d_set, bits, None, None, None, None, None, 0, C.byref(nr), stream))
+        r = nr.value
+        outs = [self.alloc(max(8 * r, 16)) for _ in range(5)]
+        _check(lib.ibu_matrix_row_top(self._c, *cols, n_entries, d_set, bits, *[_dptr(o) for o in outs], r, C.byref(nr), stream))
+        return RowTop(*outs, r)
+
+    def assign_rows(self, row_top, min_value=1, min_share=(0, 1), d_class=None, counts=True, stream=None):
+        """ibu_assign_rows over the columns of a RowTop: one class byte per row — ROW_NONE where the top value is below
+        max(min_value, 1), else ROW_ASSIGNED where it is above the runner-up and holds at least min_share = (num, den) of the row
+        sum (top * den >= num * sum in exact integers, equality passes; num = 0: no share test), else ROW_MIXED.
+        -> (d_class, AssignCounts).  d_class: n_rows bytes of device memory; None allocates them, False asks for the totals only
+        (and returns None in its place).  counts=False returns None for the totals and does not wait for them."""
+        num, den = min_share
+        rule = CAssignRule(_u64_arg("min_value", min_value), _u64_arg("min_share", num), _u64_arg("min_share", den))
+        if d_class is None:
+            d_class = self.alloc(max(row_top.n_rows, 16))
+        elif d_class is False:
+            d_class = None
+        c = CAssignCounts() if counts else None
+        _check(lib.ibu_assign_rows(self._c, _dptr(row_top.top_value), _dptr(row_top.next_value), _dptr(row_top.row_sum), row_top.n_rows,
+                                   C.byref(rule), _dptr(d_class), C.byref(c) if counts else None, stream))
+        return d_class, (AssignCounts(*[int(getattr(c, f)) for f in AssignCounts._fields]) if counts else None)
+
+    def assign_features(self, d_records, n, feature_set=None, values="umis", stream=None, **rule):
+        """The dominant feature of every barcode of the {barcode, index, umi} records count_matrix(leave_swapped=True) leaves (or
+        what a chain of filters and select_records kept of them): ibu_pair_counts into device columns, the row barcodes
+        (ibu_matrix_rows, keys only), matrix_row_top over the features in feature_set, assign_rows with **rule (min_value,
+        min_share) -> (d_barcodes, RowTop, d_class, AssignCounts): row r is barcode d_barcodes[r] (a DeviceBuffer of n_rows u64).
+        values: "umis" (distinct UMIs per entry) or "reads".  Nothing but the totals is downloaded."""
+        which = self._values_column(values)
+        cols, nnz = self._entry_columns(d_records, n, stream)
+        nr = C.c_size_t()
+        _check(lib.ibu_matrix_rows(self._c, _dptr(cols[0]), nnz, None, None, None, 0, C.byref(nr), stream))
+        d_keys = self.alloc(max(8 * nr.value, 16))
+        _check(lib.ibu_matrix_rows(self._c, _dptr(cols[0]), nnz, None, _dptr(d_keys), None, nr.value, C.byref(nr), stream))
+        top = self.matrix_row_top(cols[0], cols[1], cols[which], nnz, feature_set, stream)
+        d_class, counts = self.assign_rows(top, stream=stream, **rule)
+        self.synchronize(stream)
+        for c in cols:
+            c.free()
+        return d_keys, top, d_class, counts
 
     def write_matrix_market(self, directory, d_records, n, n_features, bc_len, values="umis", barcode_suffix="", feature_names=None,
                             stream=None, piece_bytes=64 << 20):

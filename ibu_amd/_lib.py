@@ -66,6 +66,14 @@ class CFeatureFilterCounts(C.Structure):  # ibu_feature_filter_counts_t
     _fields_ = [("features_by_class", u64 * 3), ("reads_by_class", u64 * 4), ("reserved", u64)]
 
 
+class CAssignRule(C.Structure):  # ibu_assign_rule_t
+    _fields_ = [("min_value", u64), ("num", u64), ("den", u64)]
+
+
+class CAssignCounts(C.Structure):  # ibu_assign_counts_t
+    _fields_ = [("rows", u64), ("assigned", u64), ("none", u64), ("mixed", u64)]
+
+
 class CSaturationPoint(C.Structure):  # ibu_saturation_point_t
     _fields_ = [("threshold", u64), ("reads", u64), ("barcodes", u64), ("molecules", u64)]
 
@@ -189,6 +197,8 @@ SIGNATURES = {
     "ibu_count_matrix": (i32, [vp, vp, vp, sz, u32, vp, vp, vp, vp, sz, P(sz), P(sz), vp]),
     "ibu_matrix_rows": (i32, [vp, vp, sz, vp, vp, vp, sz, P(sz), vp]),
     "ibu_matrix_market_body": (i32, [vp, vp, vp, vp, sz, u64, u64, vp, sz, P(sz), P(u64), vp]),
+    "ibu_matrix_row_top": (i32, [vp, vp, vp, vp, sz, vp, u64, vp, vp, vp, vp, vp, sz, P(sz), vp]),
+    "ibu_assign_rows": (i32, [vp, vp, vp, vp, sz, P(CAssignRule), vp, P(CAssignCounts), vp]),
     "ibu_whitelist_create": (i32, [vp, vp, sz, u32, vp, P(vp)]),
     "ibu_whitelist_info": (i32, [vp, P(u32), P(sz), P(sz)]),
     "ibu_whitelist_destroy": (None, [vp]),

@@ -438,3 +438,68 @@ extern "C" int32_t ibu_matrix_market_body(ibu_ctx_t* ctx, const uint64_t* d_a, c
   IBU_HIP(launch_matrix_text_write(ctx->cfg, d_a, d_b, d_c, n_entries, add_a, add_b, ctx->d_sort_scratch, d_text, st));
   return IBU_OK;
 }
+// ---- the per-row top-2 and the class of a row (k_matrix.hip).  The semantics are this library's: include/ibu_hip.h.  The count pass
+// and scan of ibu_matrix_rows give the row ordinals, the row total comes back, then a reduce pass and a finishing pass.
+extern "C" int32_t ibu_matrix_row_top(ibu_ctx_t* ctx, const uint64_t* d_first, const uint64_t* d_second, const uint64_t* d_values,
+                                      size_t n_entries, const uint64_t* d_set, uint64_t set_bits, uint64_t* d_top_key, uint64_t* d_top_value,
+                                      uint64_t* d_next_value, uint64_t* d_row_sum, uint64_t* d_row_entries, size_t cap, size_t* n_rows,
+                                      void* stream) {
+  int32_t rc = check_ctx(ctx);
+  if (rc) return rc;
+  if (!n_rows) return err_arg("n_rows is NULL");
+  if (!d_set && set_bits) return err_arg("d_set is NULL and set_bits is not 0");
+  if (set_bits > (1ull << 32) || !aligned8(d_set)) return err_arg("the feature set: set_bits at most 2^32, d_set 8-byte aligned");
+  *n_rows = 0;
+  if (n_entries == 0) return IBU_OK;
+  if ((rc = check_u64_ptrs({d_first, d_second, d_values}, "d_first / d_second / d_values")) != 0) return rc;
+  if ((rc = check_below_2_40(n_entries, "matrix_row_top", "entries")) != 0) return rc;
+  uint64_t* const outs[5] = {d_top_key, d_top_value, d_next_value, d_row_sum, d_row_entries};
+  for (const uint64_t* o : outs)
+    if (!aligned8(o)) return err_arg("the output arrays must be 8-byte aligned");
+  hipStream_t st = pick_stream(ctx, stream);
+  if ((rc = ensure_sort_scratch(ctx, row_top_scratch_bytes(n_entries))) != 0) return rc;
+  IBU_HIP(launch_matrix_rows_count(ctx->cfg, d_first, n_entries, ctx->d_sort_scratch, ctx->sort_scratch_bytes, st));
+  IBU_HIP(read_back<1>(ctx, static_cast<const uint64_t*>(ctx->d_sort_scratch) + kMatrixTotalWord, st));
+  const uint64_t rows = ctx->h_pinned[0];
+  *n_rows = rows;
+  if (!d_top_key && !d_top_value && !d_next_value && !d_row_sum && !d_row_entries) return IBU_OK;   // the size query, whatever cap says
+  if (rows > cap) return err_capacity(rows, cap, "rows", "n_rows");
+  for (int a = 0; a < 5; ++a) {
+    if (!outs[a]) continue;
+    for (const uint64_t* col : {d_first, d_second, d_values})
+      if (ranges_overlap(outs[a], 8 * rows, col, 8 * n_entries)) return err_arg("an output overlaps an input column");
+    for (int b = a + 1; b < 5; ++b)
+      if (outs[b] && ranges_overlap(outs[a], 8 * rows, outs[b], 8 * rows)) return err_arg("two outputs overlap");
+  }
+  IBU_HIP(launch_matrix_row_top(ctx->cfg, d_first, d_second, d_values, n_entries, d_set, set_bits, ctx->d_sort_scratch,
+                                ctx->sort_scratch_bytes, d_top_key, d_top_value, d_next_value, d_row_sum, d_row_entries, st));
+  return IBU_OK;
+}
+extern "C" int32_t ibu_assign_rows(ibu_ctx_t* ctx, const uint64_t* d_top_value, const uint64_t* d_next_value, const uint64_t* d_row_sum,
+                                   size_t n_rows, const ibu_assign_rule_t* rule, uint8_t* d_row_class, ibu_assign_counts_t* counts,
+                                   void* stream) {
+  int32_t rc = check_ctx(ctx);
+  if (rc) return rc;
+  if (!rule) return err_arg("rule is NULL");
+  if (rule->den == 0 || rule->num > rule->den) return err_arg("rule: den must be at least 1 and num at most den");
+  if (!d_row_class && !counts) return err_arg("d_row_class and counts are both NULL: nothing to do");
+  if ((rc = check_below_2_40(n_rows, "assign_rows", "rows")) != 0) return rc;
+  if (n_rows && (rc = check_u64_ptrs({d_top_value, d_next_value, d_row_sum}, "d_top_value / d_next_value / d_row_sum")) != 0) return rc;
+  if (counts) *counts = ibu_assign_counts_t{0, 0, 0, 0};   // (behind the last argument check: a refused call leaves the totals alone)
+  if (n_rows == 0) return IBU_OK;
+  hipStream_t st = pick_stream(ctx, stream);
+  uint64_t* acc = nullptr;
+  if (counts) {
+    if ((rc = ensure_sort_scratch(ctx, kAssignAccBytes)) != 0) return rc;
+    acc = static_cast<uint64_t*>(ctx->d_sort_scratch);
+  }
+  IBU_HIP(launch_matrix_assign(ctx->cfg, d_top_value, d_next_value, d_row_sum, n_rows, rule->min_value, rule->num, rule->den, d_row_class,
+                               acc, st));
+  if (!counts) return IBU_OK;
+  IBU_HIP(read_back<3>(ctx, acc, st));
+  counts->rows = n_rows;
+  counts->assigned = ctx->h_pinned[IBU_ROW_ASSIGNED];
+  counts->none = ctx->h_pinned[IBU_ROW_NONE];
+  counts->mixed = ctx->h_pinned[IBU_ROW_MIXED];
+  return IBU_OK;
+}

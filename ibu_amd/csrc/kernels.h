@@ -264,6 +264,19 @@ hipError_t launch_matrix_text_count(const LaunchCfg&, const uint64_t* a, const u
                                     uint64_t add_b, void* scratch, size_t scratch_bytes, hipStream_t st);
 hipError_t launch_matrix_text_write(const LaunchCfg&, const uint64_t* a, const uint64_t* b, const uint64_t* c, size_t n, uint64_t add_a,
                                     uint64_t add_b, const void* scratch, char* text, hipStream_t st);
+// the per-row top-2 and the class of a row (ibu_matrix_row_top, ibu_assign_rows; k_matrix.hip).  launch_matrix_row_top runs behind
+// launch_matrix_rows_count on the same `scratch`, row_top_scratch_bytes(n) bytes (the scan array, then 88 B per 2048 entries of
+// partial tuples): a reduce pass and a finishing pass for the rows that cross a unit seam; each output is nullable and gets one word
+// per row; `set` (nullable, then set_bits == 0): the bitmap of ibu_barcode_metrics over the values of `second`.
+// launch_matrix_assign: one class byte per row (nullable) and, in acc (nullable, kAssignAccBytes, zeroed by the launcher), u64[3] = the
+// rows of class 0, 1, 2; den >= 1 and num <= den.
+size_t row_top_scratch_bytes(size_t n);
+static constexpr size_t kAssignAccBytes = 32;
+hipError_t launch_matrix_row_top(const LaunchCfg&, const uint64_t* first, const uint64_t* second, const uint64_t* values, size_t n,
+                                 const uint64_t* set, uint64_t set_bits, void* scratch, size_t scratch_bytes, uint64_t* top_key,
+                                 uint64_t* top_value, uint64_t* next_value, uint64_t* row_sum, uint64_t* row_entries, hipStream_t st);
+hipError_t launch_matrix_assign(const LaunchCfg&, const uint64_t* top_value, const uint64_t* next_value, const uint64_t* row_sum, size_t rows,
+                                uint64_t min_value, uint64_t num, uint64_t den, uint8_t* d_class, uint64_t* acc, hipStream_t st);
 
 // DEFLATE blocks inflated on the device, one wave per block (k_inflate.hip).  The compressed bytes must be readable 2 KiB past the
 // last block (kInflatePad); block i's output goes to d_out_base + ooff (signed: a block that begins in front of the window a batch

@@ -372,6 +372,10 @@ using BarcodeLimits = ibu_barcode_limits_t;
 using BarcodeFilterCounts = ibu_barcode_filter_counts_t;
 using FeatureLimits = ibu_feature_limits_t;
 using FeatureFilterCounts = ibu_feature_filter_counts_t;
+using AssignRule = ibu_assign_rule_t;       // ibu_assign_rows: {min_value, num, den}
+using AssignCounts = ibu_assign_counts_t;
+// the five per-row columns of ibu_matrix_row_top, device arrays of one u64 per row, each nullable
+struct RowTopColumns { uint64_t* top_key; uint64_t* top_value; uint64_t* next_value; uint64_t* row_sum; uint64_t* row_entries; };
 // the totals of one ibu_feature_metrics call: reads, umis and cells of the features below n_features, and the records that are not
 struct FeatureTotals { uint64_t reads, umis, cells, reads_out_of_range; };
 // one row of ibu_barcode_metrics: a barcode, its records, the (w0, w1) pairs and (w0, w1, w2) triples that begin in it, and its
@@ -542,6 +546,32 @@ class Context {
     size_t bytes = 0;
     check(ibu_matrix_market_body(c_, d_a, d_b, d_c, n_entries, add_a, add_b, d_text, cap_bytes, &bytes, maxima, st));
     return bytes;
+  }
+  // the dominant entry of every row of the entry table (ibu_matrix_row_top): per row — a maximal run of equal d_first[k] — the largest
+  // d_values[k], the d_second[k] of the first entry that holds it, the largest value among the other entries, the sum modulo 2^64 and
+  // the number of entries, over the entries whose d_second[k] is in the bitmap d_set of set_bits bits (nullptr and 0: all entries).
+  // A row in which nothing takes part gets IBU_NO_KEY, 0, 0, 0, 0.  All five columns nullptr: the size query.  Returns the number of
+  // rows (synchronises once, for it)
+  size_t matrix_row_top(const uint64_t* d_first, const uint64_t* d_second, const uint64_t* d_values, size_t n_entries, const RowTopColumns& out,
+                        size_t cap, const uint64_t* d_set = nullptr, uint64_t set_bits = 0, void* st = nullptr) {
+    size_t rows = 0;
+    check(ibu_matrix_row_top(c_, d_first, d_second, d_values, n_entries, d_set, set_bits, out.top_key, out.top_value, out.next_value, out.row_sum,
+                             out.row_entries, cap, &rows, st));
+    return rows;
+  }
+  // the class of every row from three of those columns (ibu_assign_rows): IBU_ROW_NONE where the top is below max(rule.min_value, 1),
+  // else IBU_ROW_ASSIGNED where it is above the runner-up and top * den >= num * sum (exact; num = 0: no share test), else
+  // IBU_ROW_MIXED.  d_row_class: n_rows bytes, or nullptr for the totals only.  Synchronises, for the totals; assign_rows_async: no
+  // totals, nothing synchronised
+  AssignCounts assign_rows(const uint64_t* d_top_value, const uint64_t* d_next_value, const uint64_t* d_row_sum, size_t n_rows,
+                           const AssignRule& rule, uint8_t* d_row_class, void* st = nullptr) {
+    AssignCounts c{};
+    check(ibu_assign_rows(c_, d_top_value, d_next_value, d_row_sum, n_rows, &rule, d_row_class, &c, st));
+    return c;
+  }
+  void assign_rows_async(const uint64_t* d_top_value, const uint64_t* d_next_value, const uint64_t* d_row_sum, size_t n_rows, const AssignRule& rule,
+                         uint8_t* d_row_class, void* st = nullptr) {
+    check(ibu_assign_rows(c_, d_top_value, d_next_value, d_row_sum, n_rows, &rule, d_row_class, nullptr, st));
   }
   // a reproducible random subset of n rows (ibu_subsample_class): d_class (n bytes, or nullptr for the count only) gets
   // IBU_SAMPLE_KEPT where the row's number splitmix64(splitmix64(seed) + first_row + row) is below `threshold` (all ones keeps every

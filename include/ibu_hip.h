@@ -612,6 +612,61 @@ int32_t ibu_matrix_rows(ibu_ctx_t* ctx, const uint64_t* d_first, size_t n_entrie
 int32_t ibu_matrix_market_body(ibu_ctx_t* ctx, const uint64_t* d_a, const uint64_t* d_b, const uint64_t* d_c, size_t n_entries,
                                uint64_t add_a, uint64_t add_b, char* d_text, size_t cap_bytes, size_t* n_bytes,
                                uint64_t maxima[3] /* host, nullable */, void* stream);
+/* One line per row of the entry table, on the device (k_matrix.hip): the dominant feature of every cell — which hashtag, antibody or
+ * guide a cell carries, with how many UMIs, how far ahead of the runner-up, and whether the call is clean.  Both calls work on the
+ * ENTRY TABLE (the device columns ibu_pair_counts / ibu_count_matrix produce), so they follow any chain of filters.  The reference has
+ * no such function; the semantics are this library's and are stated in full here.  The input columns are never written.
+ *
+ * ibu_matrix_row_top: a ROW is a maximal run of consecutive entries with equal d_first[k] — the rows of ibu_matrix_rows (A, B, A is
+ * three rows), and row r here is row r there.  Entry k TAKES PART iff d_set == NULL, or d_second[k] < set_bits and bit d_second[k] of
+ * the bitmap d_set is set — the bitmap has the layout ibu_barcode_metrics takes (bit v is bit v & 63 of u64 word v >> 6; set_bits at
+ * most 2^32; 8-byte aligned).  A key of set_bits or more never takes part, however its low bits read: 2^32 + j is not bit j.
+ * d_set == NULL requires set_bits == 0 (IBU_ERR_INVALID_ARG otherwise).  Per row r, over the entries of the row that take part — each
+ * output nullable on its own, one u64 per row:
+ *   d_top_value[r]    the largest d_values[k];
+ *   d_top_key[r]      d_second[k] of the FIRST entry, in entry order, that holds the largest value — on sorted input the smallest
+ *                     feature number among the tied ones;
+ *   d_next_value[r]   the largest value among the OTHER entries that take part: equal to d_top_value[r] when the top is tied, 0 when
+ *                     fewer than two entries take part;
+ *   d_row_sum[r]      the sum of the values modulo 2^64;
+ *   d_row_entries[r]  how many entries take part.
+ * A row with no entry taking part gets IBU_NO_KEY, 0, 0, 0, 0.  *n_rows = the number of rows.  Size query: the five outputs NULL (any
+ * cap gives the count alone).  cap < *n_rows with any output given: IBU_ERR_INVALID_ARG with *n_rows set and nothing written
+ * (detail.a = rows, detail.b = cap).  n_entries == 0: OK, *n_rows = 0, nothing touched.  n_entries < 2^40; 8-byte aligned arrays; the
+ * outputs must not overlap an input column or each other (IBU_ERR_INVALID_ARG, nothing written); the three input columns may be one
+ * and the same array.  Synchronises `stream` once (the number of rows comes back); the writes may still be queued on return.
+ * Traffic: d_first is read twice (once for the size query), d_second and d_values once, one gathered bitmap word per entry with a set;
+ * 40 B per row are written.  A row that crosses the seams of the 2048-entry units the kernels work in is put together from 40-byte
+ * partial results, one per unit, by one wave, 64 units per step: a row of m entries adds m / 2048 such reads and ceil(m / 131072)
+ * dependent steps — rows are not walked entry by entry by one thread, however long.  Scratch: 96 B per 2048 entries of the context's
+ * sort scratch (8 for the row ordinals, 88 for the partial results and a flag), grown on demand.
+ *
+ * ibu_assign_rows: one class byte per row from three of those columns.  The class of row r is the first that applies:
+ *   IBU_ROW_NONE      d_top_value[r] < max(rule->min_value, 1);
+ *   IBU_ROW_ASSIGNED  d_top_value[r] > d_next_value[r] and d_top_value[r] * den >= num * d_row_sum[r];
+ *   IBU_ROW_MIXED     otherwise.
+ * The products are exact (128 bits), as every share test of this library is in integers; equality passes.  num == 0 switches the
+ * share test off.  The strict top > next makes the winner unique whatever the share.  den >= 1 and num <= den are required and rule
+ * must not be NULL (IBU_ERR_INVALID_ARG, nothing touched).  d_row_class (nullable): n_rows bytes.  counts (nullable, host): rows =
+ * n_rows and the rows of each class.  The two may not both be NULL.  n_rows == 0 is OK: all counts are 0.  n_rows < 2^40; 8-byte
+ * aligned columns.  Asynchronous on `stream`; it synchronises only when counts is given.  24 B per row read, 1 B written. */
+#define IBU_NO_KEY UINT64_MAX
+int32_t ibu_matrix_row_top(ibu_ctx_t* ctx, const uint64_t* d_first, const uint64_t* d_second, const uint64_t* d_values, size_t n_entries,
+                           const uint64_t* d_set /*nullable*/, uint64_t set_bits, uint64_t* d_top_key, uint64_t* d_top_value,
+                           uint64_t* d_next_value, uint64_t* d_row_sum, uint64_t* d_row_entries, size_t cap, size_t* n_rows, void* stream);
+#define IBU_ROW_ASSIGNED 0
+#define IBU_ROW_NONE 1
+#define IBU_ROW_MIXED 2
+typedef struct ibu_assign_rule {
+  uint64_t min_value; /* a top value below max(min_value, 1) is no call */
+  uint64_t num, den;  /* the least share of the row sum the top must hold: num <= den, den >= 1; num == 0: no share test */
+} ibu_assign_rule_t;
+typedef struct ibu_assign_counts {
+  uint64_t rows, assigned, none, mixed; /* rows = assigned + none + mixed */
+} ibu_assign_counts_t;
+int32_t ibu_assign_rows(ibu_ctx_t* ctx, const uint64_t* d_top_value, const uint64_t* d_next_value, const uint64_t* d_row_sum, size_t n_rows,
+                        const ibu_assign_rule_t* rule, uint8_t* d_row_class /*nullable*/, ibu_assign_counts_t* counts /*nullable, host*/,
+                        void* stream);
 /* One index per molecule, on the device (k_molecules.hip) — the step between ibu_sort_records and the count matrix that drops
  * chimeric reads: a (barcode, umi) seen with two or more index values (PCR chimeras, index hopping, multi-mapped reads) would
  * otherwise be counted once under every one of them.  The reference has no such function; the semantics are this library's and are

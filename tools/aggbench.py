@@ -10,6 +10,7 @@ into preallocated device arrays, no download.
   python tools/aggbench.py --metrics [--records 1e9] [--reads-per-molecule 4]     ibu_barcode_metrics, ibu_filter_barcodes (metrics_legs below)
   python tools/aggbench.py --features [--records 1e9] [--reads-per-molecule 4]     ibu_feature_metrics, ibu_filter_features (feature_legs below)
   python tools/aggbench.py --mtx [--records 1e8] [--host-entries 1e7]     ibu_matrix_rows, ibu_matrix_market_body (mtx_legs below; --records counts entries)
+  python tools/aggbench.py --rowtop [--records 1e8]     ibu_matrix_row_top, ibu_assign_rows on the same entry table (rowtop_legs below)
 bc_len 10 gives 2^20 distinct barcodes (a single-cell whitelist's order of magnitude); 16 gives ~n runs of length one."""
 import argparse
 import ctypes as C
@@ -664,6 +665,106 @@ def mtx_traffic(n, text_bytes):
     return total, total // 2
 
 
+def mtx_table(torch, ia, ctx, n):
+    """The resident entry table of --mtx and --rowtop, laid by mtx_fill -> (three, d_idx, d_ord, d_umis, d_bc, d_reads, views): `three` holds
+    index | row ordinal | umis back to back (ibu_reduce reads them as n records), views are int64 tensors over bc, idx, umis, reads."""
+    three = ctx.alloc(24 * n)
+    d_idx, d_ord, d_umis = (ia.DeviceBuffer.wrap(ctx, three.ptr + 8 * n * k, 8 * n) for k in range(3))
+    d_bc, d_reads = ctx.alloc(8 * n), ctx.alloc(8 * n)
+    views = [torch.as_tensor(b, device="cuda").view(torch.int64) for b in (d_bc, d_idx, d_umis, d_reads)]
+    for lo in range(0, n, 1 << 26):
+        hi = min(n, lo + (1 << 26))
+        for v, x in zip(views, mtx_fill(torch, torch.arange(lo, hi, device="cuda", dtype=torch.int64))):
+            v[lo:hi] = x
+    torch.cuda.synchronize()
+    return three, d_idx, d_ord, d_umis, d_bc, d_reads, views
+
+
+ROWTOP_SET_EVERY = 3                                             # --rowtop: the set holds every third feature number
+
+
+def rowtop_legs(a):
+    """--rowtop: the per-row top-2 on the resident entry table of --mtx (mtx_table: the same arrays, one run), timed with events on a
+    side stream (the first round is the warm-up): ibu_matrix_row_top with all five outputs, without a set and with one (every third
+    feature number: one gathered bitmap word per entry), its size query, and ibu_assign_rows on the columns it left (classes and
+    totals) — against ibu_matrix_rows with all three outputs and ibu_reduce over the three columns (one plain read of 24 B per
+    entry) on the same arrays.  Before anything is timed the result is checked against what was laid: the rows, and per row the
+    largest UMI count, its feature, the runner-up, the sum and the entries, computed with torch from the same columns."""
+    import torch                                             # before the library, as bench.py does
+    torch.cuda.init()
+    import ibu_amd as ia
+    from ibu_amd import _dptr, _check, lib, _lib
+
+    ctx = ia.Context(0)
+    side = torch.cuda.Stream()
+    st = side.cuda_stream
+    n = int(float(a.records.split(",")[0]))
+    rows_laid, nf = mtx_layout(n)
+    assert n >= MTX_ROW, "--rowtop wants at least one full row"
+    three, d_idx, d_ord, d_umis, d_bc, d_reads, views = mtx_table(torch, ia, ctx, n)
+    d_keys, d_ptr = ctx.alloc(8 * rows_laid), ctx.alloc(8 * (rows_laid + 1))
+    outs = [ctx.alloc(8 * rows_laid) for _ in range(5)]
+    d_class = ctx.alloc(rows_laid)
+    fset = ctx.feature_bitmap(range(0, nf, ROWTOP_SET_EVERY), nf)
+
+    def timed(fn):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record(side)
+        fn()
+        e1.record(side)
+        e1.synchronize()
+        return e0.elapsed_time(e1)
+
+    def rounds(fn):
+        v = [timed(fn) for _ in range(a.rounds + 1)][1:]
+        return {"median_ms": round(statistics.median(v), 3), "min_ms": round(min(v), 3), "max_ms": round(max(v), 3)}
+
+    nr = C.c_size_t()
+    rows = lambda o, cap: _check(lib.ibu_matrix_rows(ctx._c, _dptr(d_bc), n, *[_dptr(x) for x in o], cap, C.byref(nr), st))
+    top = lambda s, o, cap: _check(lib.ibu_matrix_row_top(ctx._c, _dptr(d_bc), _dptr(d_idx), _dptr(d_umis), n, _dptr(s[0]) if s else None,
+                                                         s[1] if s else 0, *[_dptr(x) for x in o], cap, C.byref(nr), st))
+    rule, counts = _lib.CAssignRule(2, 1, 2), _lib.CAssignCounts()
+    assign = lambda: _check(lib.ibu_assign_rows(ctx._c, _dptr(outs[1]), _dptr(outs[2]), _dptr(outs[3]), rows_laid, C.byref(rule), _dptr(d_class),
+                                                C.byref(counts), st))
+    # the check, before anything is timed: a row is MTX_ROW consecutive entries (the last one shorter)
+    got = [torch.as_tensor(o, device="cuda").view(torch.int64)[:rows_laid] for o in outs]
+    pad = rows_laid * MTX_ROW - n
+    for s in (None, fset):
+        top(s, outs, rows_laid)
+        ctx.synchronize()
+        assert nr.value == rows_laid, (nr.value, rows_laid)
+        part = torch.ones(n, dtype=torch.bool, device="cuda") if s is None else views[1] % ROWTOP_SET_EVERY == 0
+        v = torch.nn.functional.pad(torch.where(part, views[2], torch.zeros_like(views[2])), (0, pad)).view(rows_laid, MTX_ROW)
+        k = torch.nn.functional.pad(part.to(torch.int64), (0, pad)).view(rows_laid, MTX_ROW)
+        best, at = v.max(dim=1)                                  # torch does not promise the FIRST maximum: the key is checked through its value
+        assert bool((got[1] == best).all()) and bool((got[3] == v.sum(dim=1)).all()) and bool((got[4] == k.sum(dim=1)).all())
+        key_at = got[0] // 17                                    # idx = 17 x the position in the row
+        assert bool((v.gather(1, key_at.view(-1, 1)).view(-1) == best).all())
+        pos = torch.arange(MTX_ROW, device="cuda", dtype=torch.int64).view(1, -1)
+        first_at = torch.where(v == best.view(-1, 1), pos, torch.full_like(pos, MTX_ROW)).min(dim=1).values
+        assert bool((key_at == first_at).all())
+        others = v.clone()
+        others.scatter_(1, first_at.view(-1, 1), 0)
+        assert bool((got[2] == others.max(dim=1).values).all())
+        del v, k, others
+    res = {"leg": "rowtop", "n": n, "rows": rows_laid, "n_features": nf, "set_every": ROWTOP_SET_EVERY}
+    res["reduce_three_columns"] = rounds(lambda: _check(lib.ibu_reduce(ctx._c, _dptr(three), n, st)))
+    res["matrix_rows_all_outputs"] = rounds(lambda: rows([d_ord, d_keys, d_ptr], rows_laid))
+    res["row_top_size_query"] = rounds(lambda: top(None, [None] * 5, 0))
+    res["row_top_all_outputs"] = rounds(lambda: top(None, outs, rows_laid))
+    res["row_top_all_outputs_with_set"] = rounds(lambda: top(fset, outs, rows_laid))
+    res["assign_rows"] = rounds(assign)
+    res["reduce_three_columns_again"] = rounds(lambda: _check(lib.ibu_reduce(ctx._c, _dptr(three), n, st)))
+    rd = min(res["reduce_three_columns"]["median_ms"], res["reduce_three_columns_again"]["median_ms"])
+    assert counts.rows == rows_laid == counts.assigned + counts.none + counts.mixed
+    res["assign_counts"] = [int(counts.assigned), int(counts.none), int(counts.mixed)]
+    for leg in ("row_top_size_query", "row_top_all_outputs", "row_top_all_outputs_with_set", "matrix_rows_all_outputs"):
+        res[leg + "_vs_reduce"] = round(res[leg]["median_ms"] / rd, 3)
+    for leg in ("row_top_all_outputs", "row_top_all_outputs_with_set"):
+        res[leg + "_vs_matrix_rows"] = round(res[leg]["median_ms"] / res["matrix_rows_all_outputs"]["median_ms"], 3)
+    print(json.dumps(res), flush=True)
+
+
 def mtx_legs(a):
     """--mtx: the matrix export on a resident entry table of --records entries (mtx_fill), one run on one set of arrays, timed with
     events on a side stream (the first round is the warm-up): ibu_matrix_rows (size query; all three outputs), ibu_matrix_market_body
@@ -685,15 +786,7 @@ def mtx_legs(a):
     n = int(float(a.records.split(",")[0]))
     rows_laid, nf = mtx_layout(n)
     assert n >= MTX_ROW, "--mtx wants at least one full row"
-    three = ctx.alloc(24 * n)                                # index | row ordinal | umis, back to back: ibu_reduce reads them as n records
-    d_idx, d_ord, d_umis = (ia.DeviceBuffer.wrap(ctx, three.ptr + 8 * n * k, 8 * n) for k in range(3))
-    d_bc, d_reads = ctx.alloc(8 * n), ctx.alloc(8 * n)
-    views = [torch.as_tensor(b, device="cuda").view(torch.int64) for b in (d_bc, d_idx, d_umis, d_reads)]
-    for lo in range(0, n, 1 << 26):
-        hi = min(n, lo + (1 << 26))
-        for v, x in zip(views, mtx_fill(torch, torch.arange(lo, hi, device="cuda", dtype=torch.int64))):
-            v[lo:hi] = x
-    torch.cuda.synchronize()
+    three, d_idx, d_ord, d_umis, d_bc, d_reads, views = mtx_table(torch, ia, ctx, n)
     d_keys, d_ptr = ctx.alloc(8 * rows_laid), ctx.alloc(8 * (rows_laid + 1))
 
     def timed(fn):
@@ -780,7 +873,10 @@ def main():
     ap.add_argument("--lens", default="10,12;16,12")
     ap.add_argument("--rounds", type=int, default=5)
     ap.add_argument("--whitelist", type=int, default=0, help="K > 0: barcodes drawn from K distinct ones, skewed (rank ~ K u^3), as tools/sortbench.py --whitelist")
+    ap.add_argument("--rowtop", action="store_true", help="the ibu_matrix_row_top / ibu_assign_rows legs on the entry table of --mtx instead of the barcode leg")
     a = ap.parse_args()
+    if a.rowtop:
+        return rowtop_legs(a)
     if a.mtx:
         return mtx_legs(a)
     if a.saturation:
