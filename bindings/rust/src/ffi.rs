@@ -119,6 +119,11 @@ pub const IBU_NO_KEY: u64 = u64::MAX;
 pub const IBU_ROW_ASSIGNED: u8 = 0;
 pub const IBU_ROW_NONE: u8 = 1;
 pub const IBU_ROW_MIXED: u8 = 2;
+pub const IBU_LABEL_MATCH: u32 = 1;
+pub const IBU_LABEL_IS: u8 = 0;
+pub const IBU_LABEL_OTHER: u8 = 1;
+pub const IBU_LABEL_MISSING: u8 = 2;
+pub const IBU_LABEL_BINS: usize = 257;
 #[repr(C)]
 #[derive(Default, Debug, Clone, Copy, PartialEq, Eq)]
 pub struct ibu_assign_rule_t {
@@ -238,6 +243,7 @@ pub enum ibu_ctx_t {}
 pub enum ibu_stream_t {}
 pub enum ibu_whitelist_t {}
 pub enum ibu_abundance_t {}
+pub enum ibu_labels_t {}
 pub type ibu_write_fn = unsafe extern "C" fn(*mut c_void, *const u8, usize) -> i32;
 pub type ibu_flush_fn = unsafe extern "C" fn(*mut c_void) -> i32;
 pub type ibu_read_fn = unsafe extern "C" fn(*mut c_void, *mut u8, usize, *mut usize) -> i32;
@@ -343,6 +349,15 @@ extern "C" {
                                 stream: *mut c_void) -> i32;
     pub fn ibu_resolve_barcodes(ctx: *mut ibu_ctx_t, wl: *const ibu_whitelist_t, ab: *const ibu_abundance_t, d_records: *mut c_void, n: usize,
                                 num: u64, den: u64, d_class: *mut u8, counts: *mut ibu_resolve_counts_t, stream: *mut c_void) -> i32;
+    pub fn ibu_labels_create(ctx: *mut ibu_ctx_t, wl: *const ibu_whitelist_t, fill: u32, stream: *mut c_void, out: *mut *mut ibu_labels_t) -> i32;
+    pub fn ibu_labels_info(lb: *const ibu_labels_t, device_bytes: *mut usize) -> i32;
+    pub fn ibu_labels_destroy(lb: *mut ibu_labels_t);
+    pub fn ibu_labels_set(ctx: *mut ibu_ctx_t, lb: *mut ibu_labels_t, d_codes: *const u64, d_labels: *const u8, k: usize, n_skipped: *mut usize,
+                          stream: *mut c_void) -> i32;
+    pub fn ibu_labels_get(ctx: *mut ibu_ctx_t, lb: *const ibu_labels_t, d_codes: *const u64, k: usize, missing: u32, d_labels_out: *mut u8,
+                          stream: *mut c_void) -> i32;
+    pub fn ibu_label_records(ctx: *mut ibu_ctx_t, lb: *const ibu_labels_t, d_records: *const c_void, n: usize, flags: u32, r#match: u32,
+                             missing_class: u32, d_class: *mut u8, hist: *mut u64, stream: *mut c_void) -> i32;
     pub fn ibu_classify_molecules(ctx: *mut ibu_ctx_t, d_sorted_records: *const c_void, n: usize, flags: u32, d_class: *mut u8,
                                   counts: *mut ibu_molecule_counts_t, stream: *mut c_void) -> i32;
     pub fn ibu_call_cells(ctx: *mut ibu_ctx_t, d_sorted_records: *const c_void, n: usize, mode: u32, param: u64, flags: u32, d_class: *mut u8,

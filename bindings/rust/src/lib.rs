@@ -777,6 +777,21 @@ pub mod device {
             check(unsafe { ffi::ibu_resolve_barcodes(self.raw, wl.raw, ab.raw, recs.ptr, n, num, den, class.ptr as *mut u8, &mut c, std::ptr::null_mut()) })?;
             Ok(c)
         }
+        /// `ibu_label_records` over `n` device records (never written): a record is found when its barcode is an entry of the
+        /// whitelist `labels` belongs to, and its label is that entry's byte.  `class` (optional): `n` bytes — with `match_label`
+        /// `None` the label, or `missing_class` where not found; with `Some(l)` the classes `IBU_LABEL_IS` (found, label == l),
+        /// `IBU_LABEL_OTHER` and `IBU_LABEL_MISSING`, so that `select_records(.., 1 << 0, ..)` extracts the records of label `l`.
+        /// `hist`: `true` synchronises and returns the reads per label and, last, the reads not found (257 counts); `false`
+        /// leaves the call asynchronous and returns `None`.
+        pub fn label_records(&self, labels: &Labels, recs: &DeviceBuf, n: usize, match_label: Option<u8>, missing_class: u8, class: Option<&DeviceBuf>,
+                             hist: bool) -> Result<Option<Vec<u64>>> {
+            let cls = class.map_or(std::ptr::null_mut(), |b| b.ptr as *mut u8);
+            let mut h = vec![0u64; ffi::IBU_LABEL_BINS];
+            let hp = if hist { h.as_mut_ptr() } else { std::ptr::null_mut() };
+            let (flags, m) = match match_label { Some(l) => (ffi::IBU_LABEL_MATCH, l as u32), None => (0, 0) };
+            check(unsafe { ffi::ibu_label_records(self.raw, labels.raw, recs.ptr, n, flags, m, missing_class as u32, cls, hp, std::ptr::null_mut()) })?;
+            Ok(if hist { Some(h) } else { None })
+        }
         /// `ibu_classify_molecules` over records sorted by (barcode, umi, index): one class byte per record into `class` (n bytes;
         /// `None`: totals only) — 0 for the index its (barcode, umi) molecule was seen with strictly most often, 1 for the molecule's
         /// other reads, 2 for every read of a molecule whose top is shared (`tie_first`: the first index at the top is kept, the
@@ -979,6 +994,43 @@ pub mod device {
     impl Drop for Abundance<'_> {
         fn drop(&mut self) {
             unsafe { ffi::ibu_abundance_destroy(self.raw) }
+        }
+    }
+    /// `ibu_labels_t`: one label byte per entry of a whitelist, all `fill` at first.  Borrows its whitelist (and through it the
+    /// context), so it cannot outlive either.
+    pub struct Labels<'w> {
+        pub(crate) raw: *mut ffi::ibu_labels_t,
+        ctx: *mut ffi::ibu_ctx_t,
+        _p: PhantomData<&'w ()>,
+    }
+    impl<'w> Labels<'w> {
+        pub fn new<'c: 'w>(ctx: &'c Context, wl: &'w Whitelist<'c>, fill: u8) -> Result<Self> {
+            let mut raw = std::ptr::null_mut();
+            check(unsafe { ffi::ibu_labels_create(ctx.raw, wl.raw, fill as u32, std::ptr::null_mut(), &mut raw) })?;
+            Ok(Self { raw, ctx: ctx.raw, _p: PhantomData })
+        }
+        /// `ibu_labels_set`: the label of `codes[j]` becomes `labels[j]` (`k` u64 codes and `k` bytes, device memory).  Returns the
+        /// number of codes skipped: not in the whitelist, or with bits at or above `2 * bc_len`.  Synchronises.
+        pub fn set(&self, codes: &DeviceBuf, labels: &DeviceBuf, k: usize) -> Result<usize> {
+            let mut skipped = 0usize;
+            check(unsafe { ffi::ibu_labels_set(self.ctx, self.raw, codes.ptr as *const u64, labels.ptr as *const u8, k, &mut skipped, std::ptr::null_mut()) })?;
+            Ok(skipped)
+        }
+        /// `ibu_labels_get`: `out[j]` = the label of `codes[j]`, `missing` for a code that is not an entry.  Asynchronous on the
+        /// context's stream.
+        pub fn get(&self, codes: &DeviceBuf, k: usize, missing: u8, out: &DeviceBuf) -> Result<()> {
+            check(unsafe { ffi::ibu_labels_get(self.ctx, self.raw, codes.ptr as *const u64, k, missing as u32, out.ptr as *mut u8, std::ptr::null_mut()) })
+        }
+        /// Bytes of device memory the labels take.
+        pub fn device_bytes(&self) -> Result<usize> {
+            let mut bytes = 0usize;
+            check(unsafe { ffi::ibu_labels_info(self.raw, &mut bytes) })?;
+            Ok(bytes)
+        }
+    }
+    impl Drop for Labels<'_> {
+        fn drop(&mut self) {
+            unsafe { ffi::ibu_labels_destroy(self.raw) }
         }
     }
     /// `ibu_stream_t`: iterate to pull one device-resident batch at a time.  An `Err` item is the source's error

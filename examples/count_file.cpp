@@ -53,6 +53,15 @@
 // none (fewer than max(A, 1) UMIs at the top), assigned (the top is alone there and holds at least NUM/DEN of the total; without
 // share: no such test) or mixed.  ibu_pair_counts into device columns, ibu_matrix_row_top, ibu_assign_rows: the entry table stays on
 // the device and 41 bytes per barcode come down.  The four totals go to stderr.
+//   count_file ... [--labels=FILE [--keep-label=L] [--label-hist]] IN [WHITELIST.txt]
+// --labels=FILE: a per-barcode label table, one "barcode label" line per barcode (label: 0 .. 255) — the hashtag a cell was assigned in
+// another library, a cluster id, a QC verdict.  The barcodes become a whitelist of their own and the labels an ibu_labels_t on it.
+// --keep-label=L: the matrix of the records whose barcode has label L — ibu_label_records in match mode, ibu_select_records of the
+// class IBU_LABEL_IS — behind the whitelist step (the labels then meet corrected barcodes) and in front of whatever chain the other
+// options select; the count goes to stderr.
+// --label-hist: the reads per label of the records in front of that step (ibu_label_records without class bytes), in front of the matrix as
+//   #label<TAB>label<TAB>reads
+// one line per label that has a read, and a last one with - for the reads whose barcode is not in FILE.
 #include <algorithm>
 #include <cerrno>
 #include <cstdio>
@@ -190,6 +199,32 @@ static bool parse_assign(const char* s, ibu_assign_rule_t* rule) {
   return errno != ERANGE && *end == 0 && rule->den >= 1 && rule->num <= rule->den;
 }
 
+// "L" -> a label 0 .. 255; false otherwise
+static bool parse_label(const char* s, uint32_t* label) {
+  char* end = nullptr;
+  if (s[0] < '0' || s[0] > '9') return false;
+  const unsigned long long v = std::strtoull(s, &end, 10);
+  *label = (uint32_t)v;
+  return *end == 0 && v <= 255;
+}
+// "barcode label" lines -> the barcodes' text back to back and their labels
+static void read_labels(const char* path, uint32_t bc_len, std::vector<uint8_t>* ascii, std::vector<uint8_t>* labels) {
+  std::ifstream f(path);
+  if (!f) throw std::runtime_error(std::string("cannot open ") + path);
+  std::string line;
+  while (std::getline(f, line)) {
+    while (!line.empty() && (line.back() == '\r' || line.back() == ' ' || line.back() == '\t')) line.pop_back();
+    if (line.empty()) continue;
+    const size_t gap = line.find_first_of(" \t");
+    uint32_t label = 0;
+    if (gap != bc_len || !parse_label(line.c_str() + line.find_first_not_of(" \t", gap), &label))
+      throw std::runtime_error("the labels file has a line that is not a " + std::to_string(bc_len) + "-base barcode and a label 0 .. 255: " + line);
+    ascii->insert(ascii->end(), line.begin(), line.begin() + bc_len);
+    labels->push_back((uint8_t)label);
+  }
+  if (labels->empty()) throw std::runtime_error("the labels file is empty");
+}
+
 // one index value per line -> the bitmap of ibu_filter_barcodes and its number of bits (the largest value + 1)
 static std::vector<uint64_t> read_set(const char* path, uint64_t* bits) {
   std::ifstream f(path);
@@ -299,7 +334,9 @@ static void print_assignment(ibu::device::Context& ctx, const void* recs, size_t
 
 int main(int argc, char** argv) {
   int resolve = 0;                                              // 1: --resolve, 2: --resolve=first
-  bool cells = false, bad = false, subsample = false, qc = false, features = false, assign = false;
+  bool cells = false, bad = false, subsample = false, qc = false, features = false, assign = false, keep_label = false, label_hist = false;
+  const char* labels_path = nullptr;
+  uint32_t kept_label = 0;
   ibu_assign_rule_t assign_rule{0, 0, 1};
   ibu_barcode_limits_t qc_limits{};
   ibu_feature_limits_t feature_limits{};
@@ -323,16 +360,21 @@ int main(int argc, char** argv) {
     else if (!std::strncmp(argv[1], "--feature-table=", 16) && argv[1][16]) table_path = argv[1] + 16;
     else if (!std::strncmp(argv[1], "--mtx=", 6) && argv[1][6]) mtx_dir = argv[1] + 6;
     else if (!std::strncmp(argv[1], "--assign=", 9) && parse_assign(argv[1] + 9, &assign_rule)) assign = true;
+    else if (!std::strncmp(argv[1], "--labels=", 9) && argv[1][9]) labels_path = argv[1] + 9;
+    else if (!std::strncmp(argv[1], "--keep-label=", 13) && parse_label(argv[1] + 13, &kept_label)) keep_label = true;
+    else if (!std::strcmp(argv[1], "--label-hist")) label_hist = true;
     else bad = true;
   }
   const bool feature_steps = features || table_path;            // --mtx wants N as well, and none of the feature steps
-  if (argc < 2 || bad || (set_path && !qc && !assign) || ((feature_steps || mtx_dir) != (n_features != 0))) {
+  if (argc < 2 || bad || (set_path && !qc && !assign) || ((feature_steps || mtx_dir) != (n_features != 0)) ||
+      ((keep_label || label_hist) && !labels_path)) {
     std::fprintf(stderr, "usage: count_file [--resolve | --resolve=first] [--cells=min:T|top:K|expected:E] [--subsample=F[:seed]] [--saturation=K] "
                  "IN [WHITELIST.txt]\n"
                  "       further options: [--qc=minfeat:A[,maxfeat:B][,minumi:C][,maxset:NUM/DEN]] [--set=FILE] (FILE: one index value per line)\n"
                  "                        [--features=mincells:A[,minumi:B][,maxcells:C] --n-features=N] [--feature-table=FILE] (with --n-features=N)\n"
                  "                        [--mtx=DIR --n-features=N] (matrix.mtx, barcodes.tsv, features.tsv)\n"
-                 "                        [--assign=min:A[,share:NUM/DEN]] [--set=FILE] (the dominant feature of every barcode, over the set)\n");
+                 "                        [--assign=min:A[,share:NUM/DEN]] [--set=FILE] (the dominant feature of every barcode, over the set)\n"
+                 "                        [--labels=FILE [--keep-label=L] [--label-hist]] (FILE: one \"barcode label\" line per barcode, label 0 .. 255)\n");
     return 2;
   }
   try {
@@ -369,6 +411,36 @@ int main(int argc, char** argv) {
                    (unsigned long long)c.corrected, (unsigned long long)c.ambiguous, (unsigned long long)c.unmatched, kept);
       recs = tmp.ptr();                                         // the kept records live in tmp; the input array is scratch from here on
       scratch = d_recs;
+    }
+    if (labels_path && !kept && label_hist) std::printf("#label\t-\t0\n");   // no record: no label has a read, and none is missing
+    if (labels_path && kept) {                                  // a label per barcode -> reads per label, and the records of one label
+      std::vector<uint8_t> ascii, labels;
+      read_labels(labels_path, h.bc_len, &ascii, &labels);
+      const size_t w = labels.size();
+      device::DeviceBuffer d_ascii(ctx, ascii.size()), d_codes(ctx, 8 * w), d_labels(ctx, w);
+      d_ascii.upload(ascii);
+      d_labels.upload(labels);
+      ctx.pack_2bit(d_ascii.as<uint8_t>(), w, h.bc_len, d_codes.as<uint64_t>());
+      ctx.codec_status();                                       // throws InvalidBase on a letter outside ACGTacgt
+      device::Whitelist cells_wl(ctx, d_codes.as<uint64_t>(), w, h.bc_len);
+      device::Labels lb(ctx, cells_wl);
+      lb.set(d_codes.as<uint64_t>(), d_labels.as<uint8_t>(), w);
+      if (label_hist) {
+        uint64_t hist[IBU_LABEL_BINS];
+        ctx.label_records(lb, recs, kept, nullptr, hist);
+        for (uint32_t l = 0; l < 256; ++l)
+          if (hist[l]) std::printf("#label\t%u\t%llu\n", l, (unsigned long long)hist[l]);
+        std::printf("#label\t-\t%llu\n", (unsigned long long)hist[256]);
+      }
+      if (keep_label) {
+        device::DeviceBuffer d_class(ctx, kept);
+        const size_t before = kept;
+        ctx.label_records_match(lb, recs, before, kept_label, d_class.as<uint8_t>());
+        kept = ctx.select_records(recs, d_class.as<uint8_t>(), before, 1u << IBU_LABEL_IS, scratch, before);
+        ctx.synchronize();
+        std::fprintf(stderr, "%zu records: label %u; kept %zu\n", before, kept_label, kept);
+        std::swap(recs, scratch);
+      }
     }
     if (resolve && kept) {                                      // sort -> classify -> keep class 0: one index per molecule
       ctx.sort_records(recs, scratch, kept);

@@ -13,7 +13,8 @@ Context.feature_bitmap; barcode_metrics returns the table itself) -> select_reco
 other axis: features seen in too few cells) -> select_records -> pair_counts, or, in the forms other tools read, matrix_csr (a CSR
 triple on the device) and write_matrix_market (the 10x directory, its text formatted on the device); for hashtag, antibody and guide
 libraries assign_features (one line per cell: its dominant feature, the runner-up, the row total and a class, from matrix_row_top
-and assign_rows over the entry table).
+and assign_rows over the entry table), and, to carry such a per-barcode verdict onto the records of any library with the same
+barcodes, labels_from_assignment -> label_records (-> select_records: one sample of a multiplexed library).
 """
 import copy
 import ctypes as C
@@ -44,6 +45,9 @@ CELLS_MIN, CELLS_TOP, CELLS_ORDMAG = 0, 1, 2  # its modes (IBU_CELLS_*)
 CELLS_BY_READS = 1  # its flag (IBU_CELLS_BY_READS)
 BARCODE_PASS, BARCODE_LOW, BARCODE_HIGH, BARCODE_SET = 0, 1, 2, 3  # the classes of ibu_filter_barcodes (IBU_BARCODE_*)
 BARCODE_RESOLVED = 4  # the class ibu_resolve_barcodes gives a record it resolves (IBU_BARCODE_RESOLVED), beside 0..3 of ibu_correct_barcodes
+LABEL_MATCH = 1  # ibu_label_records flags (IBU_LABEL_MATCH)
+LABEL_IS, LABEL_OTHER, LABEL_MISSING = 0, 1, 2  # its classes in match mode (IBU_LABEL_*)
+LABEL_BINS = 257  # its histogram: the labels 0 .. 255, then the records not found (IBU_LABEL_BINS)
 #: the table of ibu_barcode_metrics: one numpy u64 column each, a row per barcode in input order
 BarcodeMetrics = namedtuple("BarcodeMetrics", "barcodes reads pairs triples set_reads set_triples")
 #: the totals of one ibu_filter_barcodes call (ibu_barcode_filter_counts_t without its reserved word); the by_class fields are 4-tuples
@@ -889,6 +893,12 @@ def _u64_arg(name, v):
     return int(v)
 
 
+def _u32_arg(name, v):
+    if not 0 <= v < 1 << 32:
+        raise ValueError(f"{name} must fit an unsigned 32-bit integer")
+    return int(v)
+
+
 def _one_threshold(fraction, threshold):
     if (fraction is None) == (threshold is None):
         raise ValueError("exactly one of fraction and threshold must be given")
@@ -1476,6 +1486,73 @@ class Context:
             return None
         return {"examined": c.examined, "resolved": c.resolved, "below_share": c.below_share, "unseen": c.unseen}
 
+    # per-barcode labels onto records
+    def label_records(self, labels, d_records, n, d_class=None, match=None, missing_class=255, hist=False, stream=None):
+        """ibu_label_records over n device records (never written): a record is found when its barcode (the low 2*bc_len bits) is
+        an entry of the whitelist `labels` belongs to, and its label is that entry's byte.  d_class (optional): n bytes — with
+        match=None the label, or missing_class where not found; with match=L the classes LABEL_IS (found, label == L), LABEL_OTHER
+        and LABEL_MISSING, so that select_records(..., keep_mask=1 << LABEL_IS) extracts the records of label L.  hist=True
+        synchronises and returns a numpy u64[257]: reads per label, then the reads not found (d_class=None with hist=True is the
+        "reads per label" query and writes nothing per record); hist=False leaves the call asynchronous and returns None."""
+        h = (C.c_uint64 * LABEL_BINS)() if hist else None
+        _check(lib.ibu_label_records(self._c, getattr(labels, "_c", None), _dptr(d_records), n, 0 if match is None else LABEL_MATCH,
+                                     _u32_arg("match", 0 if match is None else match), _u32_arg("missing_class", missing_class),
+                                     _dptr(d_class), h, stream))
+        return np.array(h, dtype=np.uint64) if hist else None
+
+    def labels_from_assignment(self, row_barcodes, row_top, row_class, features, bc_len, mixed=254, none=253, stream=None):
+        """A Whitelist and a Labels table from what assign_features returned (its d_barcodes, RowTop and d_class) -> (Whitelist,
+        Labels): the whitelist holds the row barcodes (their low 2*bc_len bits), and the label of a ROW_ASSIGNED row is the
+        position of its top feature in `features`, of a ROW_MIXED row `mixed`, of a ROW_NONE row — and of an assigned row whose top
+        feature is not in `features` — `none`.  `features` may therefore hold at most 253 positions; more raise ValueError, and so do
+        rows whose barcodes differ only in bits at or above 2*bc_len (they would be one entry with two labels).
+        label_records(labels, ...) then carries the verdict onto the records of any library with these barcodes.
+        The byte column is composed on the HOST in numpy, from one download per column of the per-barcode table (barcodes, top
+        features, classes): that table has one row per barcode, far fewer than there are records, and nothing per record leaves the
+        device.  Close the labels and the whitelist (in that order, or the whitelist alone) when done.  Synchronises."""
+        feats = [int(f) for f in features]
+        if len(feats) > 253:
+            raise ValueError(f"features holds {len(feats)} positions; a label byte has room for 253 beside `mixed` and `none`")
+        if len(set(feats)) != len(feats):
+            raise ValueError("features must be distinct")
+        for name, v in (("mixed", mixed), ("none", none)):
+            if not len(feats) <= v <= 255:
+                raise ValueError(f"{name} must be a byte that is no position of `features`")
+        r = row_top.n_rows
+        if r == 0:
+            raise ValueError("no rows: a whitelist needs at least one barcode")
+        if not 1 <= bc_len <= 32:
+            raise ValueError("bc_len must be in 1 .. 32")
+        self.synchronize(stream)
+        keys = row_barcodes.download(np.uint64, r)
+        top = row_top.top_key.download(np.uint64, r)
+        cls = row_class.download(np.uint8, r)
+        if bc_len < 32:
+            keys = keys & np.uint64((1 << (2 * bc_len)) - 1)
+        if len(np.unique(keys)) != r:                            # one label per barcode: two rows of one barcode would leave it either's
+            raise ValueError("row barcodes that differ only in bits at or above 2*bc_len are one barcode: mask the records' barcodes "
+                             "before they are counted")
+        order = np.argsort(np.array(feats, np.uint64), kind="stable") if feats else np.empty(0, np.int64)
+        sorted_feats = np.array(feats, np.uint64)[order]
+        pos = np.minimum(np.searchsorted(sorted_feats, top), max(len(feats) - 1, 0))
+        known = (sorted_feats[pos] == top) if feats else np.zeros(r, bool)
+        lab = np.full(r, none, np.uint8)
+        on = (cls == ROW_ASSIGNED) & known
+        lab[on] = order[pos[on]].astype(np.uint8)
+        lab[cls == ROW_MIXED] = mixed
+        d_keys = self.upload(keys)
+        try:
+            wl = Whitelist(self, d_keys, r, bc_len, stream)
+        finally:
+            d_keys.free()
+        try:
+            labels = wl.labels(fill=none, stream=stream)
+            labels.set(keys, lab, stream=stream)
+        except BaseException:
+            wl.close()                                           # (closes the labels on it as well)
+            raise
+        return wl, labels
+
     def select_records(self, d_records, d_class, n, keep_mask=0b0011, stream=None):
         """ibu_select_records: the records whose class has its bit set in keep_mask (default: exact and corrected), in
         input order -> (DeviceBuffer, n_out).  One call, so one count pass and one synchronisation: the buffer has room for
@@ -1608,7 +1685,7 @@ class Whitelist:
         h = C.c_void_p()
         _check(lib.ibu_whitelist_create(getattr(ctx, "_c", None), _dptr(d_codes), w, bc_len, stream, C.byref(h)))
         self._c, self.ctx = h, ctx
-        self._abundances = weakref.WeakSet()   # live Abundances on it
+        self._abundances = weakref.WeakSet()   # live Abundances and Labels on it
         ctx._whitelists.add(self)   # a context that closes first destroys what was built on it (Context.close)
         b, nd, db = C.c_uint32(), C.c_size_t(), C.c_size_t()
         _check(lib.ibu_whitelist_info(self._c, C.byref(b), C.byref(nd), C.byref(db)))
@@ -1641,9 +1718,13 @@ class Whitelist:
         """A new Abundance on this whitelist: one read counter per entry, all zero."""
         return Abundance(self.ctx, self, stream)
 
+    def labels(self, fill=255, stream=None):
+        """A new Labels table on this whitelist: one label byte per entry, all `fill`."""
+        return Labels(self.ctx, self, fill, stream)
+
     def close(self):
         if getattr(self, "_c", None):
-            for a in list(getattr(self, "_abundances", ())):   # an abundance goes before its whitelist
+            for a in list(getattr(self, "_abundances", ())):   # an abundance or a label table goes before its whitelist
                 a.close()
             lib.ibu_whitelist_destroy(self._c)
             self._c = None
@@ -1710,7 +1791,69 @@ class Abundance:
         self.close()
 
 
-__all__ = ["Whitelist", "Abundance", "Header", "Record", "HEADER_SIZE", "MAGIC", "RECORD_SIZE", "VERSION", "IbuError", "load_to_vec",
+class Labels:
+    """ibu_labels_t: one label byte per entry of a Whitelist, on the device (Whitelist.labels()).  set() writes labels by barcode,
+    Context.label_records carries them onto records.  Belongs to its whitelist and that whitelist's context; close it before them
+    (a whitelist that closes first closes it)."""
+
+    def __init__(self, ctx, wl, fill=255, stream=None):
+        h = C.c_void_p()
+        _check(lib.ibu_labels_create(getattr(ctx, "_c", None), getattr(wl, "_c", None), _u32_arg("fill", fill), stream, C.byref(h)))
+        self._c, self.ctx, self.wl = h, ctx, wl
+        wl._abundances.add(self)
+        db = C.c_size_t()
+        _check(lib.ibu_labels_info(self._c, C.byref(db)))
+        self.device_bytes = db.value
+
+    def set(self, codes, labels, stream=None):
+        """ibu_labels_set: the label of codes[j] (host u64 values) becomes labels[j] (host bytes, one per code).  -> the number of
+        codes skipped: not in the whitelist, or with bits at or above 2*bc_len.  Synchronises."""
+        a = np.ascontiguousarray(codes, dtype=np.uint64).reshape(-1)
+        v = np.ascontiguousarray(labels, dtype=np.uint8).reshape(-1)
+        if len(a) != len(v):
+            raise ValueError("one label per code")
+        if len(a) == 0:
+            return 0
+        d_codes, d_vals = self.ctx.upload(a), self.ctx.upload(v)
+        try:
+            k = C.c_size_t()
+            _check(lib.ibu_labels_set(self.ctx._c, self._c, d_codes.ptr, d_vals.ptr, len(a), C.byref(k), stream))
+            return k.value
+        finally:
+            d_codes.free()
+            d_vals.free()
+
+    def get(self, codes, missing=255, stream=None):
+        """ibu_labels_get: the labels of `codes` (host u64 values) as a numpy u8 array; `missing` for a code that is not an entry.
+        Synchronises."""
+        a = np.ascontiguousarray(codes, dtype=np.uint64).reshape(-1)
+        missing = _u32_arg("missing", missing)
+        if len(a) == 0:
+            return np.empty(0, np.uint8)
+        d_codes, d_out = self.ctx.upload(a), self.ctx.alloc(max(len(a), 16))
+        try:
+            _check(lib.ibu_labels_get(self.ctx._c, self._c, d_codes.ptr, len(a), missing, d_out.ptr, stream))
+            self.ctx.synchronize(stream)
+            return d_out.download(np.uint8, len(a))
+        finally:
+            d_codes.free()
+            d_out.free()
+
+    def close(self):
+        if getattr(self, "_c", None):
+            lib.ibu_labels_destroy(self._c)
+            self._c = None
+
+    __del__ = close
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
+
+
+__all__ = ["Whitelist", "Abundance", "Labels", "Header", "Record", "HEADER_SIZE", "MAGIC", "RECORD_SIZE", "VERSION", "IbuError", "load_to_vec",
            "MmapReader", "Reader", "Writer", "ParallelProcessor", "ProcessError", "shard_range", "Context",
            "DeviceBuffer", "DeviceStream", "DeviceBatch", "numa_of_pci", "records_array", "key_plan", "REC_DTYPE", "device_count", "PROC_REDUCE", "PROC_DECODE",
            "DEFAULT_BUFFER_SIZE", "BATCH_SIZE"]

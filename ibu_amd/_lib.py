@@ -219,6 +219,12 @@ SIGNATURES = {
     "ibu_abundance_add": (i32, [vp, vp, vp, vp, sz, u32, vp]),
     "ibu_abundance_counts": (i32, [vp, vp, vp, sz, vp, vp]),
     "ibu_resolve_barcodes": (i32, [vp, vp, vp, vp, sz, u64, u64, vp, P(CResolveCounts), vp]),
+    "ibu_labels_create": (i32, [vp, vp, u32, vp, P(vp)]),
+    "ibu_labels_info": (i32, [vp, P(sz)]),
+    "ibu_labels_destroy": (None, [vp]),
+    "ibu_labels_set": (i32, [vp, vp, vp, vp, sz, P(sz), vp]),
+    "ibu_labels_get": (i32, [vp, vp, vp, sz, u32, vp, vp]),
+    "ibu_label_records": (i32, [vp, vp, vp, sz, u32, u32, u32, vp, P(u64), vp]),
     "ibu_bgzf_scan": (i32, [vp, sz, i32, P(CInflateBlock), sz, P(sz), P(sz), P(C.c_uint64)]),
     "ibu_inflate_blocks_device": (i32, [vp, vp, vp, sz, vp, vp, vp, vp]),
     "ibu_device_alloc": (i32, [vp, sz, P(vp)]),

@@ -30,6 +30,12 @@ inline int32_t check_below_2_40(uint64_t n, const char* fn, const char* what) {
   return set_error(IBU_ERR_INVALID_ARG, 0, 0, 0, "Invalid argument: %s handles fewer than 2^40 %s per call", fn, what);
 }
 
+// An argument that stands for one byte (a label, a class): a = the value.  `what`: fill, match, missing_class, missing.
+inline int32_t check_byte(uint32_t v, const char* what) {
+  if (v <= 255u) return IBU_OK;
+  return set_error(IBU_ERR_INVALID_ARG, v, 0, 0, "Invalid argument: %s must be at most 255 (it stands for one byte)", what);
+}
+
 // Do [a, a + a_bytes) and [b, b + b_bytes) share a byte?  An empty range shares none.  Compares distances, never an end: a range
 // that ends at the top of the address space does not wrap.
 inline bool ranges_overlap(const void* a, size_t a_bytes, const void* b, size_t b_bytes) {

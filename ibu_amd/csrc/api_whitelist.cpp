@@ -1,5 +1,8 @@
 // api_whitelist.cpp — the entry points of the C ABI (include/ibu_hip.h) around a barcode whitelist: the table, correction, the
-// abundance counters and the resolution of ambiguous barcodes, and the selection of records by class (k_whitelist.hip).
+// abundance counters and the resolution of ambiguous barcodes, the per-barcode labels, and the selection of records by class
+// (k_whitelist.hip).
+#include <string.h>
+
 #include <atomic>
 
 #include "ctx.hpp"
@@ -226,6 +229,124 @@ extern "C" int32_t ibu_resolve_barcodes(ibu_ctx_t* ctx, const ibu_whitelist_t* w
   counts->resolved = ctx->h_pinned[1];
   counts->below_share = ctx->h_pinned[2];
   counts->unseen = ctx->h_pinned[3];
+  return IBU_OK;
+}
+// ---- per-barcode labels onto records (k_whitelist.hip) --------------------------------------------------------------------
+struct ibu_labels {
+  ibu_ctx* ctx = nullptr;
+  const ibu_whitelist* wl = nullptr;
+  uint8_t* d_labels = nullptr;             // slots + 1: one per table slot, the last for the all-ones key
+  size_t device_bytes = 0;
+};
+static int32_t check_labels(const ibu_ctx* ctx, const ibu_labels* lb) {
+  if (!lb) return err_arg("lb is NULL");
+  if (lb->ctx != ctx) return err_arg("the labels were created on another context");
+  return IBU_OK;
+}
+extern "C" int32_t ibu_labels_create(ibu_ctx_t* ctx, const ibu_whitelist_t* wl, uint32_t fill, void* stream, ibu_labels_t** out) {
+  if (!ctx) return no_ctx_error("a label table");
+  int32_t rc = check_ctx(ctx);
+  if (rc) return rc;
+  if (!out) return err_arg("out is NULL");
+  *out = nullptr;
+  if (!wl) return err_arg("wl is NULL");
+  if (wl->ctx != ctx) return err_arg("the whitelist was created on another context");
+  if ((rc = check_byte(fill, "fill")) != 0) return rc;
+  hipStream_t st = pick_stream(ctx, stream);
+  ibu_labels* lb = new ibu_labels;
+  lb->ctx = ctx;
+  lb->wl = wl;
+  lb->device_bytes = wl->slots + 1;
+  hipError_t e = ctx_malloc(ctx, reinterpret_cast<void**>(&lb->d_labels), lb->device_bytes);
+  if (e == hipSuccess) e = hipMemsetAsync(lb->d_labels, (int)fill, lb->device_bytes, st);
+  if (e == hipSuccess) e = hipStreamSynchronize(st);
+  if (e != hipSuccess) {
+    ibu_labels_destroy(lb);
+    return hip_fail(e, "ibu_labels_create");
+  }
+  *out = lb;
+  return IBU_OK;
+}
+extern "C" int32_t ibu_labels_info(const ibu_labels_t* lb, size_t* device_bytes) {
+  if (!lb) return err_arg("lb is NULL");
+  if (device_bytes) *device_bytes = lb->device_bytes;
+  return IBU_OK;
+}
+extern "C" void ibu_labels_destroy(ibu_labels_t* lb) {
+  if (!lb) return;
+  if (lb->d_labels) {
+    (void)hipSetDevice(lb->ctx->device);
+    (void)hipFree(lb->d_labels);   // (waits for launches that still write or read the labels)
+  }
+  delete lb;
+}
+extern "C" int32_t ibu_labels_set(ibu_ctx_t* ctx, ibu_labels_t* lb, const uint64_t* d_codes, const uint8_t* d_labels, size_t k,
+                                  size_t* n_skipped, void* stream) {
+  int32_t rc = check_ctx(ctx);
+  if (rc) return rc;
+  if ((rc = check_labels(ctx, lb)) != 0) return rc;
+  if (k > 0) {
+    if ((rc = check_u64_ptr(d_codes, "d_codes")) != 0) return rc;
+    if (!d_labels) return err_arg("d_labels is NULL");
+    if ((rc = check_below_2_40(k, "labels_set", "codes")) != 0) return rc;
+  }
+  if (n_skipped) *n_skipped = 0;
+  if (k == 0) return IBU_OK;
+  hipStream_t st = pick_stream(ctx, stream);
+  if (!n_skipped) {   // nothing to bring back: the launch stays asynchronous and touches no per-call state
+    IBU_HIP(launch_labels_set(ctx->cfg, table_of(lb->wl), lb->d_labels, d_codes, d_labels, k, nullptr, st));
+    return IBU_OK;
+  }
+  if (!ctx->d_class_acc) IBU_HIP(ctx_malloc(ctx, reinterpret_cast<void**>(&ctx->d_class_acc), kCorrectAccBytes));
+  IBU_HIP(hipMemsetAsync(ctx->d_class_acc, 0, sizeof(uint64_t), st));
+  IBU_HIP(launch_labels_set(ctx->cfg, table_of(lb->wl), lb->d_labels, d_codes, d_labels, k, ctx->d_class_acc, st));
+  IBU_HIP(read_back<1>(ctx, ctx->d_class_acc, st));
+  *n_skipped = ctx->h_pinned[0];
+  return IBU_OK;
+}
+extern "C" int32_t ibu_labels_get(ibu_ctx_t* ctx, const ibu_labels_t* lb, const uint64_t* d_codes, size_t k, uint32_t missing,
+                                  uint8_t* d_labels_out, void* stream) {
+  int32_t rc = check_ctx(ctx);
+  if (rc) return rc;
+  if ((rc = check_labels(ctx, lb)) != 0) return rc;
+  if ((rc = check_byte(missing, "missing")) != 0) return rc;
+  if (k == 0) return IBU_OK;
+  if ((rc = check_u64_ptr(d_codes, "d_codes")) != 0) return rc;
+  if (!d_labels_out) return err_arg("d_labels_out is NULL");
+  if ((rc = check_below_2_40(k, "labels_get", "codes")) != 0) return rc;
+  IBU_HIP(launch_labels_get(ctx->cfg, table_of(lb->wl), lb->d_labels, d_codes, k, missing, d_labels_out, pick_stream(ctx, stream)));
+  return IBU_OK;
+}
+extern "C" int32_t ibu_label_records(ibu_ctx_t* ctx, const ibu_labels_t* lb, const void* d_records, size_t n, uint32_t flags, uint32_t match,
+                                     uint32_t missing_class, uint8_t* d_class, uint64_t* hist, void* stream) {
+  if (!ctx) return no_ctx_error("labelling");   // there is no host form to fall back to
+  int32_t rc = check_ctx(ctx);
+  if (rc) return rc;
+  if ((rc = check_labels(ctx, lb)) != 0) return rc;
+  if (flags & ~(uint32_t)IBU_LABEL_MATCH) return err_arg("unknown flag bit (label_records knows IBU_LABEL_MATCH)");
+  if ((rc = check_byte(match, "match")) != 0) return rc;
+  if ((rc = check_byte(missing_class, "missing_class")) != 0) return rc;
+  if (n > 0) {
+    if ((rc = check_u64_ptr(d_records, "d_records")) != 0) return rc;
+    if ((rc = check_below_2_40(n, "label_records", "records")) != 0) return rc;
+  }
+  if (hist) memset(hist, 0, 257 * sizeof(uint64_t));
+  if (n == 0) return IBU_OK;
+  hipStream_t st = pick_stream(ctx, stream);
+  const auto label = [&](uint64_t* acc) {
+    return launch_label_records(ctx->cfg, table_of(lb->wl), lb->d_labels, d_records, n, (flags & IBU_LABEL_MATCH) != 0, match, missing_class,
+                                d_class, acc, st);
+  };
+  if (!hist) {   // nothing to bring back: the launch stays asynchronous and touches no per-call state
+    IBU_HIP(label(nullptr));
+    return IBU_OK;
+  }
+  if (!ctx->d_label_acc) IBU_HIP(ctx_malloc(ctx, reinterpret_cast<void**>(&ctx->d_label_acc), kLabelAccBytes));
+  IBU_HIP(hipMemsetAsync(ctx->d_label_acc, 0, kLabelAccBytes, st));
+  IBU_HIP(label(ctx->d_label_acc));
+  IBU_HIP(launch_label_fold(ctx->d_label_acc, st));
+  IBU_HIP(hipMemcpyAsync(hist, ctx->d_label_acc, 257 * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
+  IBU_HIP(hipStreamSynchronize(st));
   return IBU_OK;
 }
 extern "C" int32_t ibu_select_records(ibu_ctx_t* ctx, const void* d_records, const uint8_t* d_class, size_t n, uint32_t keep_mask,

@@ -60,6 +60,7 @@ struct ibu_ctx {
   uint64_t* d_acc = nullptr;     // [count, sum0..2, xor0..2, pad]
   uint32_t* d_flag = nullptr;    // sortedness flag
   uint64_t* d_class_acc = nullptr;  // the totals of an ibu_correct_barcodes / ibu_resolve_barcodes call that asks for them (kCorrectAccBytes, on first use; such a call synchronises, so two never share it)
+  uint64_t* d_label_acc = nullptr;  // the histogram slots of an ibu_label_records call that asks for `hist` (kLabelAccBytes, on first use; under the same rule)
   uint64_t* h_pinned = nullptr;  // kPinnedWords x u64 of pinned host memory for small read-backs
   void* d_sort_scratch = nullptr;
   size_t sort_scratch_bytes = 0;

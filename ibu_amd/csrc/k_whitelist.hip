@@ -1,5 +1,6 @@
 // k_whitelist.hip — barcode correction against a whitelist: table build, correct, select (include/ibu_hip.h:
-// ibu_whitelist_create, ibu_correct_barcodes, ibu_select_records).  Design notes: kcommon.hpp, DESIGN.md "Whitelist".
+// ibu_whitelist_create, ibu_correct_barcodes, ibu_select_records), and what else probes the table: the abundance, resolve and
+// the per-barcode labels (ibu_label_records).  Design notes: kcommon.hpp, DESIGN.md "Whitelist".
 //
 // The table: open addressing with linear probing over 64-bit keys, a power of two of slots, at most half of them
 // taken, so a successful search looks at 1.5 slots on average and an unsuccessful one at 2.5 (linear probing at load
@@ -461,6 +462,145 @@ ibu_k_resolve_tail(u64* recs, uint8_t* cls, u64 row0, u64 row1, const WlArgs a, 
 }
 
 // =============================================================================================
+// labels (ibu_labels_set, ibu_labels_get, ibu_label_records).  A label table is the abundance's shape with one BYTE per table
+// slot and one more, at index `slots`, for the all-ones key.  Labelling is one probe and one gathered byte per record; a record
+// whose barcode is not an entry has bin kLabelMissing.  The histogram (257 bins) costs no global atomic per record: runs of equal
+// bin inside a tile are merged as ibu_k_abundance_add merges runs of equal slot, a run's length goes into the workgroup's LDS
+// histogram, and the workgroup flushes its non-zero bins once, when its sweep is over, into slot blockIdx % kReduceSlots of `acc`
+// (kReduceSlots x kLabelBins u64, folded by ibu_k_label_fold).  The LDS bins are u64: no sweep length can overflow them.
+// =============================================================================================
+static constexpr u32 kLabelMissing = 256, kLabelBins = 257;
+
+struct LabelArgs {
+  const uint8_t* labels;
+  u32 match_mode;   // 0: class = label, or `missing` where not found; 1: 0 label == match, 1 another label, 2 not found
+  u32 match, missing;
+};
+__device__ __forceinline__ u32 label_bin(const WlArgs& a, const LabelArgs& l, u64 low) {
+  const u64 s = wl_lookup_slot(a.table, a.mask, a.shift, a.has_ones, low);
+  return s != kNoSlot ? (u32)l.labels[s] : kLabelMissing;
+}
+__device__ __forceinline__ u32 label_class(const LabelArgs& l, u32 bin) {
+  if (l.match_mode) return bin == kLabelMissing ? 2u : bin == l.match ? 0u : 1u;
+  return bin == kLabelMissing ? l.missing : bin;
+}
+__device__ __forceinline__ void label_hist_add(u64* hist, u32 bin, u32 v) {   // no value comes back: a no-return LDS atomic
+  (void)__hip_atomic_fetch_add(hist + bin, (u64)v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+}
+__device__ __forceinline__ void label_hist_clear(u64* hist) {   // every thread of the workgroup calls
+  for (u32 b = threadIdx.x; b < kLabelBins; b += blockDim.x) hist[b] = 0;
+  __syncthreads();
+}
+__device__ __forceinline__ void label_hist_flush(const u64* hist, u64* __restrict__ acc) {   // every thread of the workgroup calls
+  __syncthreads();
+  u64* slot = acc + (size_t)kLabelBins * (blockIdx.x & (kReduceSlots - 1));
+  for (u32 b = threadIdx.x; b < kLabelBins; b += blockDim.x) {
+    const u64 v = hist[b];
+    if (v) atomicAdd(&slot[b], v);
+  }
+}
+
+// The shape of ibu_k_abundance_add and the class store of ibu_k_correct.  HIST: the call asked for the histogram (acc != NULL).
+template <bool HIST>
+__global__ void __launch_bounds__(kBlock, 8)
+ibu_k_label(const uint8_t* __restrict__ recs, u32 ntiles, const WlArgs a, const LabelArgs l, uint8_t* __restrict__ cls_out, u64* __restrict__ acc) {
+  __shared__ __attribute__((aligned(16))) uint8_t lds[kWavesPerBlock * kTileBytes];
+  __shared__ u64 hist[HIST ? kLabelBins : 1];
+  const u32 lane = threadIdx.x & (kWave - 1), wib = threadIdx.x >> 6;
+  uint8_t* tile = lds + wib * kTileBytes;
+  const u64 m = mask2(a.bc_len);
+  const bool cls16 = (reinterpret_cast<uintptr_t>(cls_out) & 1u) == 0;   // wave-uniform: two class bytes as one 16-bit store
+  const u64 above = ~((2ull << lane) - 1);           // the lanes above this one (none for lane 63: 2 << 63 wraps to 0)
+  if constexpr (HIST) label_hist_clear(hist);
+  sweep_tiles<CorRegs>(
+      tile_range(ntiles, wib),
+      [&](CorRegs& g, u32 t) {
+        const uint8_t* src = recs + (size_t)t * kTileBytes + 16 * lane;
+#pragma unroll
+        for (int k = 0; k < 3; ++k) g.v[k] = ld16(src + 1024 * k);
+      },
+      [&](const CorRegs& g, u32 t) {
+        wave_lds_fence();
+#pragma unroll
+        for (int k = 0; k < 3; ++k) *reinterpret_cast<u32x4*>(tile + 1024 * k + 16 * lane) = g.v[k];
+        wave_lds_fence();
+        u32 b[2];
+#pragma unroll
+        for (int h = 0; h < 2; ++h) b[h] = label_bin(a, l, *reinterpret_cast<const u64*>(tile + (2 * lane + h) * 24) & m);
+        if (cls_out) {                               // wave-uniform
+          const u32 c0 = label_class(l, b[0]), c1 = label_class(l, b[1]);
+          uint8_t* q = cls_out + (size_t)t * kTileRecs + 2 * lane;
+          if (cls16) *reinterpret_cast<uint16_t*>(q) = (uint16_t)(c0 | (c1 << 8));
+          else { q[0] = (uint8_t)c0; q[1] = (uint8_t)c1; }
+        }
+        if constexpr (HIST) {
+          const u32 prev = __shfl_up(b[1], 1);
+          const bool head0 = lane == 0 || b[0] != prev, head1 = b[1] != b[0];
+          const u64 h0 = __ballot(head0) & above, h1 = __ballot(head1) & above;
+          const u32 n0 = h0 ? 2u * (u32)__builtin_ctzll(h0) : (u32)kTileRecs, n1 = h1 ? 2u * (u32)__builtin_ctzll(h1) + 1u : (u32)kTileRecs;
+          const u32 next = n0 < n1 ? n0 : n1;        // the first head behind this lane's two records, or the tile's end
+          if (head0) label_hist_add(hist, b[0], head1 ? 1u : next - 2 * lane);
+          if (head1) label_hist_add(hist, b[1], next - (2 * lane + 1));
+        }
+      });
+  if constexpr (HIST) label_hist_flush(hist, acc);
+}
+
+// One thread per record: the peeled head and the n % 128 rest.  acc (nullable) is uniform over the grid.
+extern "C" __global__ void __launch_bounds__(kBlock)
+ibu_k_label_tail(const u64* __restrict__ recs, u64 row0, u64 n, const WlArgs a, const LabelArgs l, uint8_t* __restrict__ cls_out,
+                 u64* __restrict__ acc) {
+  __shared__ u64 hist[kLabelBins];
+  const u64 i = row0 + (u64)blockIdx.x * kBlock + threadIdx.x;
+  if (acc) label_hist_clear(hist);
+  if (i < n) {
+    const u32 b = label_bin(a, l, recs[3 * i] & mask2(a.bc_len));
+    if (cls_out) cls_out[i] = (uint8_t)label_class(l, b);
+    if (acc) label_hist_add(hist, b, 1);
+  }
+  if (acc) label_hist_flush(hist, acc);
+}
+
+// slots -> slot 0: thread b sums bin b of every slot (it alone reads and writes bin b of slot 0)
+extern "C" __global__ void ibu_k_label_fold(u64* acc) {
+  const u32 b = threadIdx.x;
+  if (b >= kLabelBins) return;
+  u64 v = 0;
+  for (u32 s = 0; s < (u32)kReduceSlots; ++s) v += acc[(size_t)kLabelBins * s + b];
+  acc[b] = v;
+}
+
+// The label of codes[j] becomes vals[j] (byte stores only); a code that is not in the whitelist or has bits at or above 2*bc_len
+// is skipped and, with skipped != NULL, counted there.
+extern "C" __global__ void __launch_bounds__(kBlock)
+ibu_k_labels_set(const u64* __restrict__ codes, const uint8_t* __restrict__ vals, u64 k, const WlArgs a, uint8_t* __restrict__ labels,
+                 u64* __restrict__ skipped) {
+  const u64 stride = (u64)gridDim.x * kBlock, m = mask2(a.bc_len);
+  u32 miss = 0;
+  for (u64 j = (u64)blockIdx.x * kBlock + threadIdx.x; j < k; j += stride) {
+    const u64 key = codes[j];
+    const u64 s = (key & ~m) ? kNoSlot : wl_lookup_slot(a.table, a.mask, a.shift, a.has_ones, key);
+    if (s != kNoSlot) labels[s] = vals[j];
+    else ++miss;
+  }
+  if (skipped) {                                     // uniform over the grid
+    miss = wave_reduce(miss, OpAdd{});
+    if ((threadIdx.x & (kWave - 1)) == 0 && miss) atomicAdd(skipped, (u64)miss);
+  }
+}
+
+// out[j] = the label of codes[j]; `missing` for a code that is not in the whitelist or has bits at or above 2*bc_len.
+extern "C" __global__ void __launch_bounds__(kBlock)
+ibu_k_labels_get(const u64* __restrict__ codes, u64 k, const WlArgs a, const uint8_t* __restrict__ labels, u32 missing, uint8_t* __restrict__ out) {
+  const u64 stride = (u64)gridDim.x * kBlock, m = mask2(a.bc_len);
+  for (u64 j = (u64)blockIdx.x * kBlock + threadIdx.x; j < k; j += stride) {
+    const u64 key = codes[j];
+    const u64 s = (key & ~m) ? kNoSlot : wl_lookup_slot(a.table, a.mask, a.shift, a.has_ones, key);
+    out[j] = s != kNoSlot ? labels[s] : (uint8_t)missing;
+  }
+}
+
+// =============================================================================================
 // Launchers
 // =============================================================================================
 size_t whitelist_slots(size_t w) {   // a power of two, at least 2 w (load factor at most 1/2) and at least 1024
@@ -555,6 +695,53 @@ hipError_t launch_resolve(const LaunchCfg& cfg, const WhitelistTable& wl, const 
         hipLaunchKernelGGL(ibu_k_resolve, dim3(tiled_grid<ibu_k_resolve>(cfg, nunits)), dim3(kBlock), 0, st, adv((u64*)recs, 24 * head),
                            d_class + head, nunits, a, (const u64*)counters, (u64)num, (u64)den, (u64*)acc);
       });
+  return hipGetLastError();
+}
+
+static_assert(kLabelAccBytes == (size_t)kReduceSlots * kLabelBins * sizeof(u64), "kernels.h sizes the histogram slots");
+hipError_t launch_labels_set(const LaunchCfg& cfg, const WhitelistTable& wl, uint8_t* labels, const uint64_t* codes, const uint8_t* vals, size_t k,
+                             uint64_t* skipped, hipStream_t st) {
+  (void)hipGetLastError();
+  if (k == 0) return hipSuccess;
+  hipLaunchKernelGGL(ibu_k_labels_set, dim3(capped_grid(cfg, k, kBlock)), dim3(kBlock), 0, st, (const u64*)codes, vals, (u64)k, wl_args(wl, 0),
+                     labels, (u64*)skipped);
+  return hipGetLastError();
+}
+hipError_t launch_labels_get(const LaunchCfg& cfg, const WhitelistTable& wl, const uint8_t* labels, const uint64_t* codes, size_t k,
+                             uint32_t missing, uint8_t* out, hipStream_t st) {
+  (void)hipGetLastError();
+  if (k == 0) return hipSuccess;
+  hipLaunchKernelGGL(ibu_k_labels_get, dim3(capped_grid(cfg, k, kBlock)), dim3(kBlock), 0, st, (const u64*)codes, (u64)k, wl_args(wl, 0), labels,
+                     missing, out);
+  return hipGetLastError();
+}
+hipError_t launch_label_records(const LaunchCfg& cfg, const WhitelistTable& wl, const uint8_t* labels, const void* recs, size_t n, bool match_mode,
+                                uint32_t match, uint32_t missing_class, uint8_t* d_class, uint64_t* acc, hipStream_t st) {
+  (void)hipGetLastError();
+  if (n == 0 || (!d_class && !acc)) return hipSuccess;
+  if (n / kTileRecs > 0xFFFFFFFFull) return hipErrorInvalidValue;
+  const WlArgs a = wl_args(wl, 0);
+  const LabelArgs l{labels, match_mode ? 1u : 0u, match, missing_class};
+  const Span sp[1] = {{recs, 24}};
+  launch_rows(cfg, sp, 1, n, kTileRecs,   // an 8-B aligned base peels exactly one record
+      [&](u64 row0, u64 row1) {
+        hipLaunchKernelGGL(ibu_k_label_tail, dim3(tail_grid(row1 - row0)), dim3(kBlock), 0, st, (const u64*)recs, row0, row1, a, l, d_class,
+                           (u64*)acc);
+      },
+      [&](size_t head, u32 ntiles) {
+        const uint8_t* r = adv((const uint8_t*)recs, 24 * head);
+        if (acc)
+          hipLaunchKernelGGL(ibu_k_label<true>, dim3(tiled_grid<ibu_k_label<true>>(cfg, ntiles)), dim3(kBlock), 0, st, r, ntiles, a, l,
+                             adv(d_class, head), (u64*)acc);
+        else
+          hipLaunchKernelGGL(ibu_k_label<false>, dim3(tiled_grid<ibu_k_label<false>>(cfg, ntiles)), dim3(kBlock), 0, st, r, ntiles, a, l,
+                             adv(d_class, head), (u64*)nullptr);
+      });
+  return hipGetLastError();
+}
+hipError_t launch_label_fold(uint64_t* acc, hipStream_t st) {
+  (void)hipGetLastError();
+  hipLaunchKernelGGL(ibu_k_label_fold, dim3(1), dim3(320), 0, st, (u64*)acc);   // five waves: a thread per bin
   return hipGetLastError();
 }
 

@@ -244,6 +244,18 @@ hipError_t launch_abundance_counts(const LaunchCfg&, const WhitelistTable& wl, c
                                    uint64_t* out, hipStream_t st);
 hipError_t launch_resolve(const LaunchCfg&, const WhitelistTable& wl, const uint64_t* counters, void* recs, size_t n, uint64_t num,
                           uint64_t den, uint8_t* d_class, uint64_t* acc, hipStream_t st);
+// labels (ibu_labels_set, ibu_labels_get, ibu_label_records).  labels: wl.slots + 1 bytes, one per table slot and the last for the
+// all-ones key.  set: skipped (nullable) = a device u64, zeroed by the caller, that gets the number of codes skipped.  label_records:
+// d_class nullable; acc (nullable): kLabelAccBytes, zeroed by the caller — kReduceSlots x 257 u64, launch_label_fold leaves the 257
+// bins (the labels 0 .. 255, then the records not found) in its first 257 words.
+static constexpr size_t kLabelAccBytes = (size_t)kReduceSlots * 257 * sizeof(uint64_t);
+hipError_t launch_labels_set(const LaunchCfg&, const WhitelistTable& wl, uint8_t* labels, const uint64_t* codes, const uint8_t* vals, size_t k,
+                             uint64_t* skipped, hipStream_t st);
+hipError_t launch_labels_get(const LaunchCfg&, const WhitelistTable& wl, const uint8_t* labels, const uint64_t* codes, size_t k,
+                             uint32_t missing, uint8_t* out, hipStream_t st);
+hipError_t launch_label_records(const LaunchCfg&, const WhitelistTable& wl, const uint8_t* labels, const void* recs, size_t n, bool match_mode,
+                                uint32_t match, uint32_t missing_class, uint8_t* d_class, uint64_t* acc, hipStream_t st);
+hipError_t launch_label_fold(uint64_t* acc, hipStream_t st);
 // select: count + scan leave the number of kept records in scratch[0] (u64) and every unit's offset behind it; scatter writes them.
 size_t select_scratch_bytes(size_t n);
 hipError_t launch_select_count(const LaunchCfg&, const uint8_t* d_class, size_t n, uint32_t keep_mask, void* scratch, size_t scratch_bytes,

@@ -364,6 +364,7 @@ namespace device {
 class Whitelist;
 using CorrectCounts = ibu_correct_counts_t;
 class Abundance;
+class Labels;
 using ResolveCounts = ibu_resolve_counts_t;
 using MoleculeCounts = ibu_molecule_counts_t;
 using CellCounts = ibu_cell_counts_t;
@@ -480,6 +481,14 @@ class Context {
                                         uint64_t den = 40, void* st = nullptr);
   inline void resolve_barcodes_async(const Whitelist& wl, const Abundance& ab, void* d_recs, size_t n, uint8_t* d_class, uint64_t num = 39,
                                      uint64_t den = 40, void* st = nullptr);
+  // per-barcode labels onto records (ibu_label_records): a record is found when its barcode is an entry of the whitelist `lb` belongs
+  // to.  Plain mode: d_class[i] = the entry's label, or missing_class where not found.  label_records_match: IBU_LABEL_IS / _OTHER /
+  // _MISSING against `match`, so that select_records(.., 1u << IBU_LABEL_IS, ..) extracts one of up to 256 labels.  d_class (n bytes)
+  // and hist (host, uint64_t[IBU_LABEL_BINS]: reads per label, then the reads not found) are each nullable; a non-null hist synchronises
+  inline void label_records(const Labels& lb, const void* d_recs, size_t n, uint8_t* d_class, uint64_t* hist = nullptr, uint32_t missing_class = 255,
+                            void* st = nullptr);
+  inline void label_records_match(const Labels& lb, const void* d_recs, size_t n, uint32_t match, uint8_t* d_class, uint64_t* hist = nullptr,
+                                  void* st = nullptr);
   // one index per (barcode, umi) molecule of sorted records (ibu_classify_molecules): d_class (n bytes, or nullptr for the totals
   // only) gets IBU_MOLECULE_KEPT / _MINOR / _TIED per record; select_records(.., 1u << IBU_MOLECULE_KEPT, ..) drops the chimeric reads
   MoleculeCounts classify_molecules(const void* d_sorted, size_t n, uint8_t* d_class, bool tie_first = false, void* st = nullptr) {
@@ -708,6 +717,43 @@ class Abundance {
   ibu_ctx_t* ctx_ = nullptr;
   ibu_abundance_t* a_ = nullptr;
 };
+// One label byte per entry of a whitelist (ibu_labels_t), all `fill` at first.  Destroy it before its whitelist.
+class Labels {
+ public:
+  Labels(Context& ctx, const Whitelist& wl, uint32_t fill = 255, void* st = nullptr) : ctx_(ctx.raw()) {
+    check(ibu_labels_create(ctx_, wl.raw(), fill, st, &l_));
+  }
+  Labels(Labels&& o) noexcept : ctx_(o.ctx_), l_(o.l_) { o.l_ = nullptr; }
+  Labels(const Labels&) = delete;
+  Labels& operator=(const Labels&) = delete;
+  ~Labels() { if (l_) ibu_labels_destroy(l_); }
+  const ibu_labels_t* raw() const { return l_; }
+  // the label of d_codes[j] becomes d_labels[j] (ibu_labels_set; device arrays); returns the number of codes skipped — not in the
+  // whitelist, or with bits at or above 2*bc_len (synchronises).  set_async: no count, nothing synchronised
+  size_t set(const uint64_t* d_codes, const uint8_t* d_labels, size_t k, void* st = nullptr) {
+    size_t skipped = 0;
+    check(ibu_labels_set(ctx_, l_, d_codes, d_labels, k, &skipped, st));
+    return skipped;
+  }
+  void set_async(const uint64_t* d_codes, const uint8_t* d_labels, size_t k, void* st = nullptr) {
+    check(ibu_labels_set(ctx_, l_, d_codes, d_labels, k, nullptr, st));
+  }
+  // d_labels_out[j] = the label of d_codes[j], `missing` for a code that is not an entry (ibu_labels_get); asynchronous
+  void get(const uint64_t* d_codes, size_t k, uint8_t* d_labels_out, uint32_t missing = 255, void* st = nullptr) const {
+    check(ibu_labels_get(ctx_, l_, d_codes, k, missing, d_labels_out, st));
+  }
+  size_t device_bytes() const { size_t n = 0; check(ibu_labels_info(l_, &n)); return n; }
+
+ private:
+  ibu_ctx_t* ctx_ = nullptr;
+  ibu_labels_t* l_ = nullptr;
+};
+inline void Context::label_records(const Labels& lb, const void* d_recs, size_t n, uint8_t* d_class, uint64_t* hist, uint32_t missing_class, void* st) {
+  check(ibu_label_records(c_, lb.raw(), d_recs, n, 0, 0, missing_class, d_class, hist, st));
+}
+inline void Context::label_records_match(const Labels& lb, const void* d_recs, size_t n, uint32_t match, uint8_t* d_class, uint64_t* hist, void* st) {
+  check(ibu_label_records(c_, lb.raw(), d_recs, n, IBU_LABEL_MATCH, match, 255, d_class, hist, st));
+}
 inline ResolveCounts Context::resolve_barcodes(const Whitelist& wl, const Abundance& ab, void* d_recs, size_t n, uint8_t* d_class, uint64_t num,
                                                uint64_t den, void* st) {
   ResolveCounts c{};

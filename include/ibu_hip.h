@@ -1058,6 +1058,64 @@ int32_t ibu_abundance_counts(ibu_ctx_t* ctx, const ibu_abundance_t* ab, const ui
                              void* stream);
 int32_t ibu_resolve_barcodes(ibu_ctx_t* ctx, const ibu_whitelist_t* wl, const ibu_abundance_t* ab, void* d_records, size_t n,
                              uint64_t num, uint64_t den, uint8_t* d_class, ibu_resolve_counts_t* counts, void* stream);
+/* Per-barcode labels onto records, on the device (k_whitelist.hip): what carries a verdict that exists per BARCODE — the hashtag a
+ * cell was assigned (ibu_assign_rows), a cluster id, a doublet flag, a QC verdict — onto the records of ANY library that shares the
+ * barcodes, in any order, so that ibu_select_records can split a library into its samples and a lane can report its reads per sample.
+ * Every other class byte this library writes comes from a walk over the same records; this one comes from a table keyed by barcode.
+ * The reference has nothing like this; the semantics are this library's and are stated in full here.
+ * A LABEL TABLE (ibu_labels_t) belongs to one whitelist and one context, as an abundance does.  It holds one byte per slot of the
+ * whitelist's table and one for the all-ones key, which never enters the table: a label for every whitelist entry.
+ *
+ * ibu_labels_create: every entry's label starts as `fill` (at most 255).  Synchronous.  A NULL ctx on a host without a device:
+ * IBU_ERR_NO_DEVICE.  info: device_bytes (nullable) = what the labels take, one byte per table slot + 1.  Destroy the labels before
+ * their whitelist, and both before their context.  Labels or a whitelist created on another context: IBU_ERR_INVALID_ARG, in every
+ * call below.  (No call takes labels and a whitelist together: labels always act through the whitelist they were created on.)
+ *
+ * ibu_labels_set: the label of d_codes[j] becomes d_labels[j], for j in [0, k) (DEVICE memory: the codes 8-byte aligned, the label
+ * bytes at any alignment).  A code with bits at or above 2*bc_len, or a code that is not in the whitelist, is SKIPPED: nothing is
+ * written for it, and *n_skipped (host, nullable) counts such codes.  A non-NULL n_skipped synchronises `stream` (the count passes
+ * through the context under the rule ibu_correct_barcodes states for `counts`); NULL leaves the call asynchronous.  The codes are
+ * meant to be distinct: if one code occurs twice in a call with different labels the entry ends as one of them, as a whole byte.  A
+ * later call overrides an earlier one, in stream order.  k == 0 is OK.  k < 2^40.
+ *
+ * ibu_labels_get: d_labels_out[j] = the label of d_codes[j]; `missing` (at most 255) for a code that is not an entry — not in the
+ * whitelist, or with bits at or above 2*bc_len.  Asynchronous.  k == 0 is OK.  The read-back for users and tests.
+ *
+ * ibu_label_records: for record i, low = barcode & mask(2*bc_len); the record is FOUND when low is a whitelist entry, and its label
+ * is that entry's byte.
+ *   flags == 0 (plain mode): d_class[i] = the label when found, otherwise missing_class, which may be any byte.
+ *   flags == IBU_LABEL_MATCH (match mode): d_class[i] = IBU_LABEL_IS (0) when the record is found and its label equals `match`,
+ *     IBU_LABEL_OTHER (1) when it is found with another label, IBU_LABEL_MISSING (2) when it is not found.
+ *     ibu_select_records(..., keep_mask = 1 << IBU_LABEL_IS) then extracts the records of any one of up to 256 labels;
+ *     ibu_select_records never keeps class bytes above 7, so match mode is the only way to reach labels 8 and above.
+ * hist (host, uint64_t[257], nullable): hist[l] = the number of found records with label l, hist[256] = the number of records not
+ * found — in either mode, whatever `match` is; the 257 entries sum to n.  A non-NULL hist synchronises `stream`, NULL leaves the
+ * call asynchronous; the totals pass through the context under the rule ibu_correct_barcodes states: of the calls in flight on one
+ * context, at most one may ask for totals.  d_class (nullable): n bytes at any alignment.  d_class == NULL with hist != NULL is the
+ * "reads per label" query: it reads 24 B per record and writes nothing per record.  (Both NULL: the call checks its arguments and
+ * does nothing.)  The records (8-byte aligned) are never written.  n == 0 is OK and touches nothing (hist = 0).  n < 2^40.
+ * IBU_ERR_INVALID_ARG: labels of another context, a flag bit other than IBU_LABEL_MATCH, match or missing_class above 255 (in either
+ * mode), a NULL or misaligned d_records with n > 0.  A refused call touches nothing, hist included.  A NULL ctx on a host without a
+ * device: IBU_ERR_NO_DEVICE, as for create — there is no host form to fall back to.
+ * Reads 24 B per record, a table line for its barcode and one gathered label byte; writes 1 B of class.  The histogram costs no
+ * global atomic per record: runs of equal label inside a 128-record tile are merged, run lengths go into a per-workgroup histogram
+ * in LDS, and every workgroup adds its non-zero bins to the totals once, at the end of its sweep; a call without hist runs a kernel
+ * that has none of it. */
+#define IBU_LABEL_MATCH 1u
+#define IBU_LABEL_IS 0
+#define IBU_LABEL_OTHER 1
+#define IBU_LABEL_MISSING 2
+#define IBU_LABEL_BINS 257u
+typedef struct ibu_labels ibu_labels_t;
+int32_t ibu_labels_create(ibu_ctx_t* ctx, const ibu_whitelist_t* wl, uint32_t fill, void* stream, ibu_labels_t** out);
+int32_t ibu_labels_info(const ibu_labels_t* lb, size_t* device_bytes);
+void ibu_labels_destroy(ibu_labels_t* lb); /* before its whitelist is destroyed */
+int32_t ibu_labels_set(ibu_ctx_t* ctx, ibu_labels_t* lb, const uint64_t* d_codes, const uint8_t* d_labels, size_t k, size_t* n_skipped,
+                       void* stream);
+int32_t ibu_labels_get(ibu_ctx_t* ctx, const ibu_labels_t* lb, const uint64_t* d_codes, size_t k, uint32_t missing,
+                       uint8_t* d_labels_out, void* stream);
+int32_t ibu_label_records(ibu_ctx_t* ctx, const ibu_labels_t* lb, const void* d_records, size_t n, uint32_t flags, uint32_t match,
+                          uint32_t missing_class, uint8_t* d_class, uint64_t* hist, void* stream);
 /* BGZF / DEFLATE on the device (k_inflate.hip).  A bgzip file — to niffler (src/io/reader.rs:345-352) a gzip stream of many
  * members — is a chain of independent deflate blocks of at most 64 KiB whose compressed and uncompressed sizes stand in their
  * headers and trailers: the blocks can be found without inflating them, their COMPRESSED bytes can cross the PCIe link (half the

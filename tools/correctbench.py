@@ -10,7 +10,12 @@ Times are HIP events on the stream the calls run on (the select call synchronise
 A leg of its own (the lines above are not printed): the resolution of ambiguous barcodes.  Per configuration, in one process on one
 array: ibu_reduce (the plain 24-byte read), ibu_device_copy of the array, ibu_correct_barcodes, ibu_abundance_add over the class-0
 records in read order, the same add without class bytes in read order and on the same records SORTED (what run merging is for),
-and ibu_resolve_barcodes at 39/40."""
+and ibu_resolve_barcodes at 39/40.
+  python tools/correctbench.py --labels [--records 1e9] [--whitelists 1e5] [--errors 0.02] [--rounds 5]
+A leg of its own on the same arrays: per-barcode labels onto records.  Per configuration, in one process on one array and one
+whitelist (entry of rank r labelled r % 256), in read order and then on the same records SORTED: ibu_reduce (the plain 24-byte read),
+ibu_correct_barcodes(max_mismatches=0) with class bytes — the yardstick: the same read, one probe and a 1-byte write — and
+ibu_label_records with class bytes, with class bytes and the histogram, and with the histogram alone."""
 import argparse
 import ctypes as C
 import json
@@ -30,6 +35,7 @@ def main():
     ap.add_argument("--rounds", type=int, default=5)
     ap.add_argument("--random", type=float, default=0.01, help="share of uniform random barcodes (they always take the miss path)")
     ap.add_argument("--resolve", action="store_true", help="the abundance / resolve leg instead of the correct / select one")
+    ap.add_argument("--labels", action="store_true", help="the label leg instead of the correct / select one")
     a = ap.parse_args()
     import torch                                             # before the library, as bench.py does
     torch.cuda.init()
@@ -91,6 +97,9 @@ def main():
             ctx.synchronize()
             if a.resolve:
                 resolve_leg(ia, ctx, st, timed, stat, wl, d, orig, out, d_cls, n, asked, bc_len, len(codes), err, a)
+                continue
+            if a.labels:
+                labels_leg(ia, ctx, torch, st, timed, stat, wl, codes, d, orig, out, d_cls, n, asked, bc_len, err, a)
                 continue
             t_red, t_cor, t_sel, t_cpy = [], [], [], []
             counts = kept = None
@@ -158,6 +167,45 @@ def resolve_leg(ia, ctx, st, timed, stat, wl, d, orig, out, d_cls, n, asked, bc_
                       "atomics_per_s_read_order_no_class": round(hits / ms["add_read_order_no_class"] * 1e3),
                       "sorted_counters_equal_read_order": same}), flush=True)
     ab.close()
+
+
+def labels_leg(ia, ctx, torch, st, timed, stat, wl, codes, d, orig, out, d_cls, n, asked, bc_len, err, a):
+    calls = ("reduce", "correct0", "label_class", "label_class_hist", "label_hist")
+    w = len(codes)
+    unsigned = codes ^ torch.iinfo(torch.int64).min          # int64 order of this = unsigned order of the codes (32 bases set the top bit)
+    labs = (torch.argsort(torch.argsort(unsigned)) % 256).to(torch.uint8).contiguous()   # rank % 256
+    torch.cuda.synchronize()
+    lb = wl.labels(fill=255)
+    ia._check(ia.lib.ibu_labels_set(ctx._c, lb._c, codes.data_ptr(), labs.data_ptr(), w, None, None))
+    ctx.synchronize()
+    result = {"leg": "labels", "n": n, "records_asked": asked, "bc_len": bc_len, "w": w, "table_MiB": round(wl.device_bytes / 2**20, 1),
+              "labels_MiB": round(lb.device_bytes / 2**20, 2), "errors": err, "random": a.random}
+    hists = {}
+    for order in ("read_order", "sorted"):
+        if order == "read_order":
+            ctx.copy(d, orig, 24 * n, stream=st)
+            recs = d
+        else:
+            ctx.copy(out, orig, 24 * n, stream=st)
+            ctx.sort_records(out, d, n, stream=st)               # d is scratch from here on
+            recs = out
+        t = {k: [] for k in calls}
+        for _ in range(a.rounds + 1):
+            t["reduce"].append(timed(lambda: ctx.reduce(recs, n, stream=st, reset=False, fetch=False)))
+            t["correct0"].append(timed(lambda: ctx.correct_barcodes(wl, recs, n, 0, d_cls, counts=False, stream=st)))
+            t["label_class"].append(timed(lambda: ctx.label_records(lb, recs, n, d_class=d_cls, stream=st)))
+            t["label_class_hist"].append(timed(lambda: ctx.label_records(lb, recs, n, d_class=d_cls, hist=True, stream=st)))
+            t["label_hist"].append(timed(lambda: ctx.label_records(lb, recs, n, hist=True, stream=st)))
+        hists[order] = ctx.label_records(lb, recs, n, hist=True, stream=st)
+        s = {k: stat(v) for k, v in t.items()}
+        ms = {k: v["median_ms"] for k, v in s.items()}
+        result[order] = {**s, "correct0_over_reduce": round(ms["correct0"] / ms["reduce"], 3),
+                         **{k + "_over_correct0": round(ms[k] / ms["correct0"], 3) for k in calls[2:]}}
+    result["found"] = int(hists["read_order"][:256].sum())
+    result["not_found"] = int(hists["read_order"][256])
+    result["sorted_histogram_equals_read_order"] = bool((hists["read_order"] == hists["sorted"]).all()) and int(hists["sorted"].sum()) == n
+    print(json.dumps(result), flush=True)
+    lb.close()
 
 
 if __name__ == "__main__":
