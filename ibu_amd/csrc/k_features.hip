@@ -3,16 +3,15 @@
 // the features seen in too few cells — include/ibu_hip.h has the rules in full.  Three kernels:
 //   count    the D = 2 walk of runs_walk.hpp with FeatureSink on NoSink::words.  Inside a step the records of a GROUP are adjacent
 //            (feature_word 1: a pair; 2: a triple; and whatever the step's first record continues), so the lane that holds a group's
-//            first record takes the group's extent and its triple heads from the step's head ballots — as ibu_k_abundance_add merges
-//            the runs of a tile — and issues at most three 8-byte integer atomics into the columns: reads += records, umis += triple
-//            heads, cells += 1 where the group begins with a real pair head.  The adds commute: nothing is carried from step to
+//            first record takes the group's extent and its triple heads from the step's head ballots — kcommon.hpp, next_head,
+//            as ibu_k_abundance_add merges the runs of a tile — and issues at most three 8-byte integer atomics into the
+//            columns: reads += records, umis += triple heads, cells += 1 where the group begins with a real pair head.  The adds commute: nothing is carried from step to
 //            step, and the sums are integers, so two runs give the same columns.  The columns are 8 B per feature and live in L2.
 //            Records with f >= n_features enter no column; they and the in-range sums go to per-lane totals and block_accumulate.
 //   verdict  a grid-stride loop over the features: the verdict byte from the three columns and the limits, features per class
 //            through block_accumulate.
-//   class    a tiled streaming kernel in the shape of ibu_k_correct: three 16-byte loads per lane, the LDS re-tile, one gathered
-//            verdict byte per record (the table is n_features bytes and cache resident), coalesced class bytes at any alignment,
-//            reads per class per wave and workgroup; a thread-per-record kernel for the peeled record and the n % 128 rest.
+//   class    a per-record pass (kcommon.hpp: sweep_records, store_class_pair, launch_record_pass): one gathered verdict byte per
+//            record (the table is n_features bytes and cache resident), reads per class per wave and workgroup.
 // No LDS beyond the tiles and block_accumulate's, no scratch memory.  Launchers: launch_feature_count, launch_feature_filter
 // (kernels.h); C ABI: api_analysis.cpp.
 #include "runs_walk.hpp"
@@ -33,7 +32,6 @@ struct FeatureCols { u64* reads; u64* umis; u64* cells; u64 nf; u32 word; };   /
 struct FeatureSink : NoSink {
   FeatureCols c;
   u32 lane;
-  u64 above;                                                  // the lanes above this one (none for lane 63: 2 << 63 wraps to 0)
   mutable u64 t_reads, t_umis, t_cells, t_out;                // per lane: in-range reads, umis, cells; reads out of range
   // the group of feature f over positions [pos, next): te / to = the step's ballots of triple heads at even / odd positions
   __device__ __forceinline__ void group(u64 f, u32 pos, u32 next, bool pair, bool pair_head, u64 te, u64 to) const {
@@ -57,9 +55,7 @@ struct FeatureSink : NoSink {
     const bool gb = pair && (c.word == 1 ? b1 : b2);
     const u64 ge = __ballot(ga), go = __ballot(gb), te = __ballot(a2), to = __ballot(b2);
     const u32 end = 2u * (u32)__popcll(__ballot(va));         // the valid lanes are the first ones
-    const u64 he = ge & above, ho = go & above;
-    const u32 n0 = he ? 2u * (u32)__builtin_ctzll(he) : end, n1 = ho ? 2u * (u32)__builtin_ctzll(ho) + 1u : end;
-    const u32 next = n0 < n1 ? n0 : n1;                       // the first group head behind this lane's records, or the step's end
+    const u32 next = next_head(ge, go, lane, end);            // the first group head behind this lane's records, or the step's end
     if (ga) group(c.word == 1 ? a.w1 : a.w2, 2 * lane, gb ? 2 * lane + 1 : next, pair, a1, te, to);
     if (gb) group(c.word == 1 ? b.w1 : b.w2, 2 * lane + 1, next, pair, b1, te, to);
   }
@@ -72,7 +68,7 @@ ibu_k_feature_count(const u64* __restrict__ recs, SegPlan sp, FeatureCols cols, 
   __shared__ u64 accl[kSortWaves * 4];
   const u32 lane = threadIdx.x & (kWave - 1), wib = threadIdx.x >> 6;
   const u32 seg = wave_segment();
-  const FeatureSink sink{{}, cols, lane, ~((2ull << lane) - 1), 0, 0, 0, 0};
+  const FeatureSink sink{{}, cols, lane, 0, 0, 0, 0};
   if (seg < sp.nseg) {                                        // wave-uniform; no return: every thread reaches the barrier below
     u64 c1, c2;
     runs_segment<2>(recs, sp, seg, lds + wib * kTileBytes, lane, 0, 0, c1, c2, sink);
@@ -103,60 +99,42 @@ ibu_k_feature_verdict(const u64* __restrict__ reads, const u64* __restrict__ umi
 
 __device__ __forceinline__ u32 feature_class(const uint8_t* __restrict__ verdict, u64 nf, u64 f) { return f < nf ? (u32)verdict[f] : 3u; }
 
-struct ClsRegs { u32x4 v[3]; };
+// acc (nullable, uniform over the grid; block_accumulate): [0 .. 3] records per class
+struct FeatureClassArgs { const uint8_t* verdict; u64 nf; u32 word; u64* acc; };
 
-// acc (nullable; block_accumulate): [0 .. 3] records per class
 extern "C" __global__ void __launch_bounds__(kBlock, 8)
-ibu_k_feature_class(const uint8_t* __restrict__ recs, u32 ntiles, const uint8_t* __restrict__ verdict, u64 nf, u32 word,
-                    uint8_t* __restrict__ cls_out /*nullable*/, u64* __restrict__ acc) {
+ibu_k_feature_class(const uint8_t* __restrict__ recs, u32 ntiles, uint8_t* __restrict__ cls_out /*nullable*/, const FeatureClassArgs fa) {
   __shared__ __attribute__((aligned(16))) uint8_t lds[kWavesPerBlock * kTileBytes];
   __shared__ u64 accl[kSortWaves * 4];
   const u32 lane = threadIdx.x & (kWave - 1), wib = threadIdx.x >> 6;
   uint8_t* tile = lds + wib * kTileBytes;
-  const bool cls16 = (reinterpret_cast<uintptr_t>(cls_out) & 1u) == 0;   // wave-uniform: two class bytes as one 16-bit store
   u64 t[4] = {0, 0, 0, 0};
-  sweep_tiles<ClsRegs>(
-      tile_range(ntiles, wib),
-      [&](ClsRegs& g, u32 k) {
-        const uint8_t* src = recs + (size_t)k * kTileBytes + 16 * lane;
+  sweep_records(recs, ntiles, tile, lane, wib, [&](u32 k) {
+    u32 c[2];
 #pragma unroll
-        for (int j = 0; j < 3; ++j) g.v[j] = ld16(src + 1024 * j);
-      },
-      [&](const ClsRegs& g, u32 k) {
-        wave_lds_fence();
+    for (int h = 0; h < 2; ++h) {
+      c[h] = feature_class(fa.verdict, fa.nf, rec_word(tile, lane, h, fa.word));
 #pragma unroll
-        for (int j = 0; j < 3; ++j) *reinterpret_cast<u32x4*>(tile + 1024 * j + 16 * lane) = g.v[j];
-        wave_lds_fence();
-        u32 c[2];
-#pragma unroll
-        for (int h = 0; h < 2; ++h) {
-          c[h] = feature_class(verdict, nf, *reinterpret_cast<const u64*>(tile + (2 * lane + h) * 24 + 8 * word));
-#pragma unroll
-          for (u32 q = 0; q < 4; ++q) t[q] += c[h] == q ? 1 : 0;
-        }
-        if (cls_out) {                                        // wave-uniform
-          uint8_t* q = cls_out + (size_t)k * kTileRecs + 2 * lane;
-          if (cls16) *reinterpret_cast<uint16_t*>(q) = (uint16_t)(c[0] | (c[1] << 8));
-          else { q[0] = (uint8_t)c[0]; q[1] = (uint8_t)c[1]; }
-        }
-      });
-  if (acc) block_accumulate(t, acc, accl);                    // uniform over the grid
+      for (u32 q = 0; q < 4; ++q) t[q] += c[h] == q ? 1 : 0;
+    }
+    if (cls_out) store_class_pair(cls_out, k, lane, c[0], c[1]);   // wave-uniform
+  });
+  if (fa.acc) block_accumulate(t, fa.acc, accl);
 }
 
 // One thread per record: the rows peeled off the front of an 8- but not 16-byte aligned array and the n % 128 rest.
 extern "C" __global__ void __launch_bounds__(kBlock)
-ibu_k_feature_class_tail(const u64* __restrict__ recs, u64 row0, u64 row1, const uint8_t* __restrict__ verdict, u64 nf, u32 word,
-                         uint8_t* __restrict__ cls_out /*nullable*/, u64* __restrict__ acc) {
+ibu_k_feature_class_tail(const u64* __restrict__ recs, u64 row0, u64 row1, uint8_t* __restrict__ cls_out /*nullable*/, const FeatureClassArgs fa) {
   __shared__ u64 accl[kSortWaves * 4];
   const u64 i = row0 + (u64)blockIdx.x * kBlock + threadIdx.x;
   u64 t[4] = {0, 0, 0, 0};
   if (i < row1) {
-    const u32 c = feature_class(verdict, nf, recs[3 * i + word]);
+    const u32 c = feature_class(fa.verdict, fa.nf, recs[3 * i + fa.word]);
     if (cls_out) cls_out[i] = (uint8_t)c;
 #pragma unroll
     for (u32 q = 0; q < 4; ++q) t[q] = c == q ? 1 : 0;
   }
-  if (acc) block_accumulate(t, acc, accl);
+  if (fa.acc) block_accumulate(t, fa.acc, accl);
 }
 
 bool feature_args_ok(uint32_t feature_word, uint64_t n_features) {
@@ -188,17 +166,8 @@ hipError_t launch_feature_filter(const LaunchCfg& cfg, const void* recs, size_t 
                      (const u64*)d_umis, (const u64*)d_cells, (u64)n_features, limits, verdict, (u64*)acc);
   if (n == 0 || (!d_class && !class_totals)) return hipGetLastError();
   u64* racc = class_totals ? (u64*)acc + 4 : nullptr;
-  const Span sp[1] = {{recs, 24}};
-  launch_rows(cfg, sp, 1, n, kTileRecs,   // an 8-B aligned base peels exactly one record
-      [&](u64 row0, u64 row1) {
-        hipLaunchKernelGGL(ibu_k_feature_class_tail, dim3(tail_grid(row1 - row0)), dim3(kBlock), 0, st, (const u64*)recs, row0, row1,
-                           (const uint8_t*)verdict, (u64)n_features, feature_word, d_class, racc);
-      },
-      [&](size_t head, u32 ntiles) {
-        hipLaunchKernelGGL(ibu_k_feature_class, dim3(tiled_grid<ibu_k_feature_class>(cfg, ntiles)), dim3(kBlock), 0, st,
-                           adv((const uint8_t*)recs, 24 * head), ntiles, (const uint8_t*)verdict, (u64)n_features, feature_word,
-                           adv(d_class, head), racc);
-      });
+  launch_record_pass<ibu_k_feature_class, ibu_k_feature_class_tail>(cfg, recs, n, d_class,
+                                                                    FeatureClassArgs{verdict, (u64)n_features, feature_word, racc}, st);
   return hipGetLastError();
 }
 

@@ -140,67 +140,52 @@ __device__ __forceinline__ void wl_flush_totals(u32 cnt[4], u64* acc, u32 (*part
   }
 }
 
-struct CorRegs { u32x4 v[3]; };
+struct CorrectArgs { WlArgs wl; u64* acc; };     // acc: nullable, uniform over the grid
 
-// Tiled: the records arrive as three coalesced 16-byte loads per lane (next tile in flight), are re-tiled through the
-// wave's LDS slice, lane L owns records 2L and 2L+1.  Nothing of a record is stored but the 8 barcode bytes of a
-// corrected one; the class bytes of a tile leave as one 128-byte row.  Misses: the wave-cooperative neighbour search (the form
-// in which every lane searched its own record measured 2-4.7x slower: profiles/README.md r06_a).
+// Tiled (kcommon.hpp: sweep_records).  Nothing of a record is stored but the 8 barcode bytes of a corrected one.  Misses: the
+// wave-cooperative neighbour search (the form in which every lane searched its own record measured 2-4.7x slower:
+// profiles/README.md r06_a).
 extern "C" __global__ void __launch_bounds__(kBlock, 8)
-ibu_k_correct(uint8_t* __restrict__ recs, u32 ntiles, const WlArgs a, uint8_t* __restrict__ cls_out, u64* __restrict__ acc) {
+ibu_k_correct(uint8_t* __restrict__ recs, u32 ntiles, uint8_t* __restrict__ cls_out, const CorrectArgs ca) {
   __shared__ __attribute__((aligned(16))) uint8_t lds[kWavesPerBlock * kTileBytes];
   __shared__ u32 part[kWavesPerBlock][4];
   const u32 lane = threadIdx.x & (kWave - 1), wib = threadIdx.x >> 6;
   uint8_t* tile = lds + wib * kTileBytes;
+  const WlArgs& a = ca.wl;
   const u64 m = mask2(a.bc_len);
-  const bool cls16 = (reinterpret_cast<uintptr_t>(cls_out) & 1u) == 0;   // wave-uniform: two class bytes as one 16-bit store
   u32 cnt[4] = {0, 0, 0, 0};
-  sweep_tiles<CorRegs>(
-      tile_range(ntiles, wib),
-      [&](CorRegs& g, u32 t) {
-        const uint8_t* src = recs + (size_t)t * kTileBytes + 16 * lane;
+  sweep_records(recs, ntiles, tile, lane, wib, [&](u32 t) {
+    u64 bc[2], fix[2];
+    u32 c[2];
 #pragma unroll
-        for (int k = 0; k < 3; ++k) g.v[k] = ld16(src + 1024 * k);
-      },
-      [&](const CorRegs& g, u32 t) {
-        wave_lds_fence();
+    for (int h = 0; h < 2; ++h) {
+      bc[h] = rec_word(tile, lane, h);
+      c[h] = wl_lookup(a.table, a.mask, a.shift, a.has_ones, bc[h] & m) ? 0u : 3u;
+      fix[h] = 0;
+    }
+    if (a.search) {                                  // wave-uniform
 #pragma unroll
-        for (int k = 0; k < 3; ++k) *reinterpret_cast<u32x4*>(tile + 1024 * k + 16 * lane) = g.v[k];
-        wave_lds_fence();
-        u64 bc[2], fix[2];
-        u32 c[2];
+      for (int h = 0; h < 2; ++h) {
+        const u32 s = wl_search_wave(a, c[h] != 0, bc[h] & m, &fix[h], lane);
+        if (c[h] != 0) c[h] = s;
+      }
+    }
+    u64* r = reinterpret_cast<u64*>(recs + (size_t)t * kTileBytes) + 6 * lane;   // records 2L, 2L+1: words 6L and 6L+3
 #pragma unroll
-        for (int h = 0; h < 2; ++h) {
-          bc[h] = *reinterpret_cast<const u64*>(tile + (2 * lane + h) * 24);
-          c[h] = wl_lookup(a.table, a.mask, a.shift, a.has_ones, bc[h] & m) ? 0u : 3u;
-          fix[h] = 0;
-        }
-        if (a.search) {                              // wave-uniform
-#pragma unroll
-          for (int h = 0; h < 2; ++h) {
-            const u32 s = wl_search_wave(a, c[h] != 0, bc[h] & m, &fix[h], lane);
-            if (c[h] != 0) c[h] = s;
-          }
-        }
-        u64* r = reinterpret_cast<u64*>(recs + (size_t)t * kTileBytes) + 6 * lane;   // records 2L, 2L+1: words 6L and 6L+3
-#pragma unroll
-        for (int h = 0; h < 2; ++h) {
-          if (c[h] == 1) r[3 * h] = (bc[h] & ~m) | fix[h];
-          cnt[0] += c[h] == 0; cnt[1] += c[h] == 1; cnt[2] += c[h] == 2; cnt[3] += c[h] == 3;
-        }
-        if (cls_out) {                               // wave-uniform
-          uint8_t* q = cls_out + (size_t)t * kTileRecs + 2 * lane;
-          if (cls16) *reinterpret_cast<uint16_t*>(q) = (uint16_t)(c[0] | (c[1] << 8));
-          else { q[0] = (uint8_t)c[0]; q[1] = (uint8_t)c[1]; }
-        }
-      });
-  if (acc) wl_flush_totals(cnt, acc, part);          // uniform over the grid
+    for (int h = 0; h < 2; ++h) {
+      if (c[h] == 1) r[3 * h] = (bc[h] & ~m) | fix[h];
+      cnt[0] += c[h] == 0; cnt[1] += c[h] == 1; cnt[2] += c[h] == 2; cnt[3] += c[h] == 3;
+    }
+    if (cls_out) store_class_pair(cls_out, t, lane, c[0], c[1]);   // wave-uniform
+  });
+  if (ca.acc) wl_flush_totals(cnt, ca.acc, part);    // uniform over the grid
 }
 
 // One thread per record: the rows peeled off the front of an 8- but not 16-byte aligned array and the n % 128 rest.
 extern "C" __global__ void __launch_bounds__(kBlock)
-ibu_k_correct_tail(u64* __restrict__ recs, u64 row0, u64 n, const WlArgs a, uint8_t* __restrict__ cls_out, u64* __restrict__ acc) {
+ibu_k_correct_tail(u64* __restrict__ recs, u64 row0, u64 n, uint8_t* __restrict__ cls_out, const CorrectArgs ca) {
   __shared__ u32 part[kWavesPerBlock][4];
+  const WlArgs& a = ca.wl;
   const u64 i = row0 + (u64)blockIdx.x * kBlock + threadIdx.x;
   u32 cnt[4] = {0, 0, 0, 0};
   if (i < n) {
@@ -214,7 +199,7 @@ ibu_k_correct_tail(u64* __restrict__ recs, u64 row0, u64 n, const WlArgs a, uint
     if (cls_out) cls_out[i] = (uint8_t)c;
     cnt[0] = c == 0; cnt[1] = c == 1; cnt[2] = c == 2; cnt[3] = c == 3;
   }
-  if (acc) wl_flush_totals(cnt, acc, part);
+  if (ca.acc) wl_flush_totals(cnt, ca.acc, part);
 }
 
 // slots -> slot 0: one wave, lane = slot
@@ -315,55 +300,42 @@ __device__ __forceinline__ void ab_add(u64* __restrict__ counters, u64 slot, u64
   (void)__hip_atomic_fetch_add(counters + slot, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 
-// The shape of ibu_k_correct: lane L owns records 2L and 2L+1 of the wave's tile.  Grouped input (sorted records, a few hot
-// barcodes) would put the 128 adds of a tile on one address, so runs of equal slot inside the tile are merged first: a
-// record is a head where its slot differs from the record before it (across the lane seam by shuffle), a head's run ends at
-// the next head (from the two head ballots), and a head whose slot counts issues one atomic with the run's length.
+struct AbundanceArgs { WlArgs wl; u32 class_mask; u64* counters; };
+
+// Tiled (kcommon.hpp: sweep_records).  Grouped input (sorted records, a few hot barcodes) would put the 128 adds of a tile on one
+// address, so runs of equal slot inside the tile are merged first (kcommon.hpp: next_head; the record before a lane's first one
+// comes by shuffle), and a head whose slot counts issues one atomic with the run's length.
 extern "C" __global__ void __launch_bounds__(kBlock, 8)
-ibu_k_abundance_add(const uint8_t* __restrict__ recs, u32 ntiles, const WlArgs a, const uint8_t* __restrict__ cls, u32 class_mask,
-                    u64* __restrict__ counters) {
+ibu_k_abundance_add(const uint8_t* __restrict__ recs, u32 ntiles, const uint8_t* __restrict__ cls, const AbundanceArgs aa) {
   __shared__ __attribute__((aligned(16))) uint8_t lds[kWavesPerBlock * kTileBytes];
   const u32 lane = threadIdx.x & (kWave - 1), wib = threadIdx.x >> 6;
   uint8_t* tile = lds + wib * kTileBytes;
+  const WlArgs& a = aa.wl;
   const u64 m = mask2(a.bc_len);
-  const u64 above = ~((2ull << lane) - 1);           // the lanes above this one (none for lane 63: 2 << 63 wraps to 0)
-  sweep_tiles<CorRegs>(
-      tile_range(ntiles, wib),
-      [&](CorRegs& g, u32 t) {
-        const uint8_t* src = recs + (size_t)t * kTileBytes + 16 * lane;
+  sweep_records(recs, ntiles, tile, lane, wib, [&](u32 t) {
+    u64 s[2];
 #pragma unroll
-        for (int k = 0; k < 3; ++k) g.v[k] = ld16(src + 1024 * k);
-      },
-      [&](const CorRegs& g, u32 t) {
-        wave_lds_fence();
-#pragma unroll
-        for (int k = 0; k < 3; ++k) *reinterpret_cast<u32x4*>(tile + 1024 * k + 16 * lane) = g.v[k];
-        wave_lds_fence();
-        u64 s[2];
-#pragma unroll
-        for (int h = 0; h < 2; ++h) {
-          const u64 bc = *reinterpret_cast<const u64*>(tile + (2 * lane + h) * 24);
-          s[h] = ab_counted(cls, (u64)t * kTileRecs + 2 * lane + h, class_mask) ? wl_lookup_slot(a.table, a.mask, a.shift, a.has_ones, bc & m)
+    for (int h = 0; h < 2; ++h) {
+      const u64 bc = rec_word(tile, lane, h);
+      s[h] = ab_counted(cls, (u64)t * kTileRecs + 2 * lane + h, aa.class_mask) ? wl_lookup_slot(a.table, a.mask, a.shift, a.has_ones, bc & m)
                                                                                 : kNoSlot;
-        }
-        const u64 prev = shfl_up64(s[1], 1);
-        const bool head0 = lane == 0 || s[0] != prev, head1 = s[1] != s[0];
-        const u64 h0 = __ballot(head0) & above, h1 = __ballot(head1) & above;
-        const u32 n0 = h0 ? 2u * (u32)__builtin_ctzll(h0) : (u32)kTileRecs, n1 = h1 ? 2u * (u32)__builtin_ctzll(h1) + 1u : (u32)kTileRecs;
-        const u32 next = n0 < n1 ? n0 : n1;          // the first head behind this lane's two records, or the tile's end
-        if (head0 && s[0] != kNoSlot) ab_add(counters, s[0], head1 ? 1u : next - 2 * lane);
-        if (head1 && s[1] != kNoSlot) ab_add(counters, s[1], next - (2 * lane + 1));
-      });
+    }
+    const u64 prev = shfl_up64(s[1], 1);
+    const bool head0 = lane == 0 || s[0] != prev, head1 = s[1] != s[0];
+    const u32 next = next_head(__ballot(head0), __ballot(head1), lane, kTileRecs);
+    if (head0 && s[0] != kNoSlot) ab_add(aa.counters, s[0], head1 ? 1u : next - 2 * lane);
+    if (head1 && s[1] != kNoSlot) ab_add(aa.counters, s[1], next - (2 * lane + 1));
+  });
 }
 
 // One thread per record: the peeled head and the n % 128 rest.
 extern "C" __global__ void __launch_bounds__(kBlock)
-ibu_k_abundance_add_tail(const u64* __restrict__ recs, u64 row0, u64 n, const WlArgs a, const uint8_t* __restrict__ cls, u32 class_mask,
-                         u64* __restrict__ counters) {
+ibu_k_abundance_add_tail(const u64* __restrict__ recs, u64 row0, u64 n, const uint8_t* __restrict__ cls, const AbundanceArgs aa) {
+  const WlArgs& a = aa.wl;
   const u64 i = row0 + (u64)blockIdx.x * kBlock + threadIdx.x;
-  if (i >= n || !ab_counted(cls, i, class_mask)) return;
+  if (i >= n || !ab_counted(cls, i, aa.class_mask)) return;
   const u64 s = wl_lookup_slot(a.table, a.mask, a.shift, a.has_ones, recs[3 * i] & mask2(a.bc_len));
-  if (s != kNoSlot) ab_add(counters, s, 1);
+  if (s != kNoSlot) ab_add(aa.counters, s, 1);
 }
 
 // out[j] = the counter of codes[j]; 0 for a code that is not in the whitelist or has bits at or above 2*bc_len.
@@ -472,11 +444,14 @@ ibu_k_resolve_tail(u64* recs, uint8_t* cls, u64 row0, u64 row1, const WlArgs a, 
 static constexpr u32 kLabelMissing = 256, kLabelBins = 257;
 
 struct LabelArgs {
+  WlArgs wl;
   const uint8_t* labels;
   u32 match_mode;   // 0: class = label, or `missing` where not found; 1: 0 label == match, 1 another label, 2 not found
   u32 match, missing;
+  u64* acc;         // the histogram slots; nullable, uniform over the grid
 };
-__device__ __forceinline__ u32 label_bin(const WlArgs& a, const LabelArgs& l, u64 low) {
+__device__ __forceinline__ u32 label_bin(const LabelArgs& l, u64 low) {
+  const WlArgs& a = l.wl;
   const u64 s = wl_lookup_slot(a.table, a.mask, a.shift, a.has_ones, low);
   return s != kNoSlot ? (u32)l.labels[s] : kLabelMissing;
 }
@@ -500,65 +475,45 @@ __device__ __forceinline__ void label_hist_flush(const u64* hist, u64* __restric
   }
 }
 
-// The shape of ibu_k_abundance_add and the class store of ibu_k_correct.  HIST: the call asked for the histogram (acc != NULL).
+// Tiled (kcommon.hpp: sweep_records).  HIST: the call asked for the histogram (l.acc != NULL); runs of equal bin inside the tile are
+// merged as ibu_k_abundance_add merges runs of equal slot.
 template <bool HIST>
 __global__ void __launch_bounds__(kBlock, 8)
-ibu_k_label(const uint8_t* __restrict__ recs, u32 ntiles, const WlArgs a, const LabelArgs l, uint8_t* __restrict__ cls_out, u64* __restrict__ acc) {
+ibu_k_label(const uint8_t* __restrict__ recs, u32 ntiles, uint8_t* __restrict__ cls_out, const LabelArgs l) {
   __shared__ __attribute__((aligned(16))) uint8_t lds[kWavesPerBlock * kTileBytes];
   __shared__ u64 hist[HIST ? kLabelBins : 1];
   const u32 lane = threadIdx.x & (kWave - 1), wib = threadIdx.x >> 6;
   uint8_t* tile = lds + wib * kTileBytes;
-  const u64 m = mask2(a.bc_len);
-  const bool cls16 = (reinterpret_cast<uintptr_t>(cls_out) & 1u) == 0;   // wave-uniform: two class bytes as one 16-bit store
-  const u64 above = ~((2ull << lane) - 1);           // the lanes above this one (none for lane 63: 2 << 63 wraps to 0)
+  const u64 m = mask2(l.wl.bc_len);
   if constexpr (HIST) label_hist_clear(hist);
-  sweep_tiles<CorRegs>(
-      tile_range(ntiles, wib),
-      [&](CorRegs& g, u32 t) {
-        const uint8_t* src = recs + (size_t)t * kTileBytes + 16 * lane;
+  sweep_records(recs, ntiles, tile, lane, wib, [&](u32 t) {
+    u32 b[2];
 #pragma unroll
-        for (int k = 0; k < 3; ++k) g.v[k] = ld16(src + 1024 * k);
-      },
-      [&](const CorRegs& g, u32 t) {
-        wave_lds_fence();
-#pragma unroll
-        for (int k = 0; k < 3; ++k) *reinterpret_cast<u32x4*>(tile + 1024 * k + 16 * lane) = g.v[k];
-        wave_lds_fence();
-        u32 b[2];
-#pragma unroll
-        for (int h = 0; h < 2; ++h) b[h] = label_bin(a, l, *reinterpret_cast<const u64*>(tile + (2 * lane + h) * 24) & m);
-        if (cls_out) {                               // wave-uniform
-          const u32 c0 = label_class(l, b[0]), c1 = label_class(l, b[1]);
-          uint8_t* q = cls_out + (size_t)t * kTileRecs + 2 * lane;
-          if (cls16) *reinterpret_cast<uint16_t*>(q) = (uint16_t)(c0 | (c1 << 8));
-          else { q[0] = (uint8_t)c0; q[1] = (uint8_t)c1; }
-        }
-        if constexpr (HIST) {
-          const u32 prev = __shfl_up(b[1], 1);
-          const bool head0 = lane == 0 || b[0] != prev, head1 = b[1] != b[0];
-          const u64 h0 = __ballot(head0) & above, h1 = __ballot(head1) & above;
-          const u32 n0 = h0 ? 2u * (u32)__builtin_ctzll(h0) : (u32)kTileRecs, n1 = h1 ? 2u * (u32)__builtin_ctzll(h1) + 1u : (u32)kTileRecs;
-          const u32 next = n0 < n1 ? n0 : n1;        // the first head behind this lane's two records, or the tile's end
-          if (head0) label_hist_add(hist, b[0], head1 ? 1u : next - 2 * lane);
-          if (head1) label_hist_add(hist, b[1], next - (2 * lane + 1));
-        }
-      });
-  if constexpr (HIST) label_hist_flush(hist, acc);
+    for (int h = 0; h < 2; ++h) b[h] = label_bin(l, rec_word(tile, lane, h) & m);
+    if (cls_out) store_class_pair(cls_out, t, lane, label_class(l, b[0]), label_class(l, b[1]));   // wave-uniform
+    if constexpr (HIST) {
+      const u32 prev = __shfl_up(b[1], 1);
+      const bool head0 = lane == 0 || b[0] != prev, head1 = b[1] != b[0];
+      const u32 next = next_head(__ballot(head0), __ballot(head1), lane, kTileRecs);
+      if (head0) label_hist_add(hist, b[0], head1 ? 1u : next - 2 * lane);
+      if (head1) label_hist_add(hist, b[1], next - (2 * lane + 1));
+    }
+  });
+  if constexpr (HIST) label_hist_flush(hist, l.acc);
 }
 
-// One thread per record: the peeled head and the n % 128 rest.  acc (nullable) is uniform over the grid.
+// One thread per record: the peeled head and the n % 128 rest.
 extern "C" __global__ void __launch_bounds__(kBlock)
-ibu_k_label_tail(const u64* __restrict__ recs, u64 row0, u64 n, const WlArgs a, const LabelArgs l, uint8_t* __restrict__ cls_out,
-                 u64* __restrict__ acc) {
+ibu_k_label_tail(const u64* __restrict__ recs, u64 row0, u64 n, uint8_t* __restrict__ cls_out, const LabelArgs l) {
   __shared__ u64 hist[kLabelBins];
   const u64 i = row0 + (u64)blockIdx.x * kBlock + threadIdx.x;
-  if (acc) label_hist_clear(hist);
+  if (l.acc) label_hist_clear(hist);
   if (i < n) {
-    const u32 b = label_bin(a, l, recs[3 * i] & mask2(a.bc_len));
+    const u32 b = label_bin(l, recs[3 * i] & mask2(l.wl.bc_len));
     if (cls_out) cls_out[i] = (uint8_t)label_class(l, b);
-    if (acc) label_hist_add(hist, b, 1);
+    if (l.acc) label_hist_add(hist, b, 1);
   }
-  if (acc) label_hist_flush(hist, acc);
+  if (l.acc) label_hist_flush(hist, l.acc);
 }
 
 // slots -> slot 0: thread b sums bin b of every slot (it alone reads and writes bin b of slot 0)
@@ -636,16 +591,7 @@ hipError_t launch_correct(const LaunchCfg& cfg, const WhitelistTable& wl, void* 
   (void)hipGetLastError();
   if (n == 0) return hipSuccess;
   if (n / kTileRecs > 0xFFFFFFFFull) return hipErrorInvalidValue;
-  const WlArgs a = wl_args(wl, max_mismatches);
-  const Span sp[1] = {{recs, 24}};
-  launch_rows(cfg, sp, 1, n, kTileRecs,   // an 8-B aligned base peels exactly one record
-      [&](u64 row0, u64 row1) {
-        hipLaunchKernelGGL(ibu_k_correct_tail, dim3(tail_grid(row1 - row0)), dim3(kBlock), 0, st, (u64*)recs, row0, row1, a, d_class, (u64*)acc);
-      },
-      [&](size_t head, u32 ntiles) {
-        hipLaunchKernelGGL(ibu_k_correct, dim3(tiled_grid<ibu_k_correct>(cfg, ntiles)), dim3(kBlock), 0, st, adv((uint8_t*)recs, 24 * head),
-                           ntiles, a, adv(d_class, head), (u64*)acc);
-      });
+  launch_record_pass<ibu_k_correct, ibu_k_correct_tail>(cfg, recs, n, d_class, CorrectArgs{wl_args(wl, max_mismatches), (u64*)acc}, st);
   return hipGetLastError();
 }
 hipError_t launch_correct_fold(uint64_t* acc, hipStream_t st) {
@@ -659,17 +605,8 @@ hipError_t launch_abundance_add(const LaunchCfg& cfg, const WhitelistTable& wl, 
   (void)hipGetLastError();
   if (n == 0) return hipSuccess;
   if (n / kTileRecs > 0xFFFFFFFFull) return hipErrorInvalidValue;
-  const WlArgs a = wl_args(wl, 0);
-  const Span sp[1] = {{recs, 24}};
-  launch_rows(cfg, sp, 1, n, kTileRecs,   // an 8-B aligned base peels exactly one record
-      [&](u64 row0, u64 row1) {
-        hipLaunchKernelGGL(ibu_k_abundance_add_tail, dim3(tail_grid(row1 - row0)), dim3(kBlock), 0, st, (const u64*)recs, row0, row1, a, d_class,
-                           class_mask, (u64*)counters);
-      },
-      [&](size_t head, u32 ntiles) {
-        hipLaunchKernelGGL(ibu_k_abundance_add, dim3(tiled_grid<ibu_k_abundance_add>(cfg, ntiles)), dim3(kBlock), 0, st,
-                           adv((const uint8_t*)recs, 24 * head), ntiles, a, adv(d_class, head), class_mask, (u64*)counters);
-      });
+  launch_record_pass<ibu_k_abundance_add, ibu_k_abundance_add_tail>(cfg, recs, n, d_class, AbundanceArgs{wl_args(wl, 0), class_mask, (u64*)counters},
+                                                                    st);
   return hipGetLastError();
 }
 hipError_t launch_abundance_counts(const LaunchCfg& cfg, const WhitelistTable& wl, const uint64_t* counters, const uint64_t* codes, size_t k,
@@ -720,23 +657,9 @@ hipError_t launch_label_records(const LaunchCfg& cfg, const WhitelistTable& wl, 
   (void)hipGetLastError();
   if (n == 0 || (!d_class && !acc)) return hipSuccess;
   if (n / kTileRecs > 0xFFFFFFFFull) return hipErrorInvalidValue;
-  const WlArgs a = wl_args(wl, 0);
-  const LabelArgs l{labels, match_mode ? 1u : 0u, match, missing_class};
-  const Span sp[1] = {{recs, 24}};
-  launch_rows(cfg, sp, 1, n, kTileRecs,   // an 8-B aligned base peels exactly one record
-      [&](u64 row0, u64 row1) {
-        hipLaunchKernelGGL(ibu_k_label_tail, dim3(tail_grid(row1 - row0)), dim3(kBlock), 0, st, (const u64*)recs, row0, row1, a, l, d_class,
-                           (u64*)acc);
-      },
-      [&](size_t head, u32 ntiles) {
-        const uint8_t* r = adv((const uint8_t*)recs, 24 * head);
-        if (acc)
-          hipLaunchKernelGGL(ibu_k_label<true>, dim3(tiled_grid<ibu_k_label<true>>(cfg, ntiles)), dim3(kBlock), 0, st, r, ntiles, a, l,
-                             adv(d_class, head), (u64*)acc);
-        else
-          hipLaunchKernelGGL(ibu_k_label<false>, dim3(tiled_grid<ibu_k_label<false>>(cfg, ntiles)), dim3(kBlock), 0, st, r, ntiles, a, l,
-                             adv(d_class, head), (u64*)nullptr);
-      });
+  const LabelArgs l{wl_args(wl, 0), labels, match_mode ? 1u : 0u, match, missing_class, (u64*)acc};
+  if (acc) launch_record_pass<ibu_k_label<true>, ibu_k_label_tail>(cfg, recs, n, d_class, l, st);
+  else launch_record_pass<ibu_k_label<false>, ibu_k_label_tail>(cfg, recs, n, d_class, l, st);
   return hipGetLastError();
 }
 hipError_t launch_label_fold(uint64_t* acc, hipStream_t st) {

@@ -189,6 +189,53 @@ __device__ __forceinline__ void wave_lds_fence() {
   __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 }
 
+// ---- the per-record sweep ----------------------------------------------------------------------------------------------
+// A pass that reads every 24-byte record once and does one lookup or gather per record (correct, abundance, labels, the feature
+// classes): sweep_tiles over the wave's tiles, a tile arriving as three coalesced 16-byte loads per lane and re-tiled through the
+// wave's LDS slice `tile` (kTileBytes), after which lane L owns records 2L and 2L+1 (rec_word) and body(t) runs.  The rules at the
+// head of this file are kept HERE: nothing branches around the loads, and the fence pair keeps the stage behind the previous
+// body's reads and the body's reads behind the stage.  Whatever every thread of a workgroup must reach (a histogram clear, a
+// totals flush) stays in the kernel, around the call: a wave without a tile returns from the sweep at once.
+struct TileRegs { u32x4 v[3]; };
+template <class Body>
+__device__ __forceinline__ void sweep_records(const uint8_t* recs, u32 ntiles, uint8_t* tile, u32 lane, u32 wib, Body body) {
+  sweep_tiles<TileRegs>(
+      tile_range(ntiles, wib),
+      [&](TileRegs& g, u32 t) {
+        const uint8_t* src = recs + (size_t)t * kTileBytes + 16 * lane;
+#pragma unroll
+        for (int k = 0; k < 3; ++k) g.v[k] = ld16(src + 1024 * k);
+      },
+      [&](const TileRegs& g, u32 t) {
+        wave_lds_fence();
+#pragma unroll
+        for (int k = 0; k < 3; ++k) *reinterpret_cast<u32x4*>(tile + 1024 * k + 16 * lane) = g.v[k];
+        wave_lds_fence();
+        body(t);
+      });
+}
+// Word w (0 barcode, 1, 2) of record 2 * lane + h of the staged tile.
+__device__ __forceinline__ u64 rec_word(const uint8_t* tile, u32 lane, int h, u32 w = 0) {
+  return *reinterpret_cast<const u64*>(tile + (2 * lane + h) * 24 + 8 * w);
+}
+// The class bytes of this lane's two records of tile t (cls_out: the class of the sweep's first record, not NULL): a tile's 128
+// bytes leave as one row, at any alignment — one 16-bit store where the pointer is even, two byte stores where it is odd.
+__device__ __forceinline__ void store_class_pair(uint8_t* cls_out, u32 t, u32 lane, u32 c0, u32 c1) {
+  const bool cls16 = (reinterpret_cast<uintptr_t>(cls_out) & 1u) == 0;   // wave-uniform
+  uint8_t* q = cls_out + (size_t)t * kTileRecs + 2 * lane;
+  if (cls16) *reinterpret_cast<uint16_t*>(q) = (uint16_t)(c0 | (c1 << 8));
+  else { q[0] = (uint8_t)c0; q[1] = (uint8_t)c1; }
+}
+// Merging runs of equal keys among the positions of a wave, lane L holding positions 2L and 2L+1: a position is a HEAD where its
+// key differs from the one before it, and a head's run ends at the next head.  From the ballots of the heads at even and at odd
+// positions: the first head behind this lane's two positions, or `end` (the number of positions).  Keys stay with the caller.
+__device__ __forceinline__ u32 next_head(u64 even, u64 odd, u32 lane, u32 end) {
+  const u64 above = ~((2ull << lane) - 1);           // the lanes above this one (none for lane 63: 2 << 63 wraps to 0)
+  const u64 h0 = even & above, h1 = odd & above;
+  const u32 n0 = h0 ? 2u * (u32)__builtin_ctzll(h0) : end, n1 = h1 ? 2u * (u32)__builtin_ctzll(h1) + 1u : end;
+  return n0 < n1 ? n0 : n1;
+}
+
 // ---- bit order of the 2-bit codec ------------------------------------------------------------
 // Default (order 0, "LSB first"): base i of a sequence sits at bits [2i, 2i+1] of the code word, "ACGT" -> 0b11100100
 // (bitnuc's convention as recalled; nothing in the reference pins it: DESIGN.md §3).  The hedge (order 1, "MSB
@@ -543,6 +590,22 @@ template <auto Kernel>
 static inline u32 tiled_grid(const LaunchCfg& cfg, u32 ntiles) {
   static std::atomic<int> occ;
   return grid_for(ntiles, cfg.cus, resident_blocks<kBlock>(cfg, Kernel, 0, &occ));
+}
+// The launches of a per-record pass (sweep_records above) over n records; the limits on n are the callers'.  One parameter order:
+//   Tiled(recs as bytes, ntiles, class pointer advanced by the head, args)      Tail(recs as words, row0, row1, class pointer, args)
+// `args` is the pass's own by-value struct; d_class may be NULL where the pass allows it.
+template <class R, class A0, class... A> A0 kernel_arg0(R (*)(A0, A...));   // (declaration only) the type of a kernel's first parameter
+template <auto Tiled, auto Tail, class Recs, class Cls, class Args>
+static inline void launch_record_pass(const LaunchCfg& cfg, Recs* recs, size_t n, Cls* d_class, const Args& args, hipStream_t st) {
+  const Span sp[1] = {{recs, 24}};
+  launch_rows(cfg, sp, 1, n, kTileRecs,   // an 8-B aligned base peels exactly one record
+      [&](u64 row0, u64 row1) {
+        hipLaunchKernelGGL(Tail, dim3(tail_grid(row1 - row0)), dim3(kBlock), 0, st, (decltype(kernel_arg0(Tail)))recs, row0, row1, d_class, args);
+      },
+      [&](size_t head, u32 ntiles) {
+        hipLaunchKernelGGL(Tiled, dim3(tiled_grid<Tiled>(cfg, ntiles)), dim3(kBlock), 0, st, adv((decltype(kernel_arg0(Tiled)))recs, 24 * head),
+                           ntiles, adv(d_class, head), args);
+      });
 }
 // A grid-stride kernel over `items`: the workgroups that cover them once at per_block each, at most blocks_per_cu per CU, at least one.
 static inline u32 capped_grid(const LaunchCfg& cfg, u64 items, u64 per_block, u32 blocks_per_cu = 8) {
