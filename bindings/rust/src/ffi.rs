@@ -379,6 +379,8 @@ extern "C" {
                                 k: u32, points: *mut ibu_saturation_point_t, stream: *mut c_void) -> i32;
     pub fn ibu_select_records(ctx: *mut ibu_ctx_t, d_records: *const c_void, d_class: *const u8, n: usize, keep_mask: u32,
                               d_out: *mut c_void, cap: usize, n_out: *mut usize, stream: *mut c_void) -> i32;
+    pub fn ibu_partition_records(ctx: *mut ibu_ctx_t, d_records: *const c_void, d_class: *const u8, n: usize, part_of: *const u8, n_parts: u32,
+                                 d_out: *mut c_void, cap: usize, offsets: *mut u64, stream: *mut c_void) -> i32;
     pub fn ibu_bgzf_scan(buf: *const u8, len: usize, is_final: i32, blocks: *mut ibu_inflate_block_t, cap: usize, n_blocks: *mut usize,
                          consumed: *mut usize, out_bytes: *mut u64) -> i32;
     pub fn ibu_inflate_blocks_device(ctx: *mut ibu_ctx_t, d_comp: *const c_void, d_blocks: *const ibu_inflate_block_t, n: usize,

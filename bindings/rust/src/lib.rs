@@ -905,6 +905,20 @@ pub mod device {
             check(unsafe { ffi::ibu_select_records(self.raw, recs.ptr, class.ptr as *const u8, n, keep_mask, p, cap, &mut k, std::ptr::null_mut()) })?;
             Ok(k)
         }
+        /// Stable multi-way partition by class byte in one pass (`ibu_partition_records`): `part_of[c]` is the part of class byte
+        /// `c`, a value below `n_parts` or 255 (`IBU_PART_NONE`) for a class whose records are dropped; `None` is the identity below
+        /// `n_parts`.  `out` receives part 0, then part 1, ..., each in input order (ask with `out = None` first: it must hold
+        /// the records kept).  Returns the `n_parts + 1` offsets: part `p` is records `offsets[p] .. offsets[p + 1]` of `out`.
+        pub fn partition_records(&self, recs: &DeviceBuf, class: &DeviceBuf, n: usize, part_of: Option<&[u8; 256]>, n_parts: u32,
+                                 out: Option<&DeviceBuf>) -> Result<Vec<u64>> {
+            let mut offsets = vec![0u64; n_parts.min(255) as usize + 1];
+            let (p, cap) = out.map_or((std::ptr::null_mut(), 0usize), |b| (b.ptr, b.bytes / 24));
+            let map = part_of.map_or(std::ptr::null(), |m| m.as_ptr());
+            check(unsafe {
+                ffi::ibu_partition_records(self.raw, recs.ptr, class.ptr as *const u8, n, map, n_parts, p, cap, offsets.as_mut_ptr(), std::ptr::null_mut())
+            })?;
+            Ok(offsets)
+        }
         /// Device analogue of `load_to_vec`.
         pub fn load_to_device<P: AsRef<Path>>(&self, path: P) -> Result<(Header, *mut c_void, usize)> {
             let c = CString::new(path.as_ref().to_string_lossy().as_bytes()).unwrap();

@@ -14,7 +14,8 @@ other axis: features seen in too few cells) -> select_records -> pair_counts, or
 triple on the device) and write_matrix_market (the 10x directory, its text formatted on the device); for hashtag, antibody and guide
 libraries assign_features (one line per cell: its dominant feature, the runner-up, the row total and a class, from matrix_row_top
 and assign_rows over the entry table), and, to carry such a per-barcode verdict onto the records of any library with the same
-barcodes, labels_from_assignment -> label_records (-> select_records: one sample of a multiplexed library).
+barcodes, labels_from_assignment -> label_records (-> select_records: one sample of a multiplexed library; partition_records /
+partition_by_label: every sample at once, in one pass).
 """
 import copy
 import ctypes as C
@@ -48,6 +49,7 @@ BARCODE_RESOLVED = 4  # the class ibu_resolve_barcodes gives a record it resolve
 LABEL_MATCH = 1  # ibu_label_records flags (IBU_LABEL_MATCH)
 LABEL_IS, LABEL_OTHER, LABEL_MISSING = 0, 1, 2  # its classes in match mode (IBU_LABEL_*)
 LABEL_BINS = 257  # its histogram: the labels 0 .. 255, then the records not found (IBU_LABEL_BINS)
+PART_NONE = 255  # ibu_partition_records: the part_of entry of a class whose records are dropped (IBU_PART_NONE)
 #: the table of ibu_barcode_metrics: one numpy u64 column each, a row per barcode in input order
 BarcodeMetrics = namedtuple("BarcodeMetrics", "barcodes reads pairs triples set_reads set_triples")
 #: the totals of one ibu_filter_barcodes call (ibu_barcode_filter_counts_t without its reserved word); the by_class fields are 4-tuples
@@ -1562,6 +1564,64 @@ class Context:
         out = self.alloc(max(24 * n, 16))
         _check(lib.ibu_select_records(self._c, _dptr(d_records), _dptr(d_class), n, keep_mask, _dptr(out), n, C.byref(k), stream))
         return out, k.value
+
+    def partition_records(self, d_records, d_class, n, n_parts=None, part_of=None, out=None, stream=None):
+        """ibu_partition_records: a stable multi-way partition of n device records by class byte, in one pass -> (DeviceBuffer,
+        offsets as numpy u64[n_parts + 1]).  part_of (256 bytes, optional): the part of every class byte, a value below n_parts or
+        PART_NONE for a class whose records are dropped; None is the identity below n_parts.  n_parts (1 .. 255) may be left out
+        when part_of is given: one more than its largest part.  The buffer holds part 0, then part 1, ..., each in input order:
+        part p is records offsets[p] .. offsets[p + 1], and offsets[n_parts] records are kept.  out (optional): a DeviceBuffer to
+        write to, its capacity out.nbytes // 24 records; otherwise one with room for all n records is allocated, as select_records
+        does.  One count pass and one synchronisation; the records are valid once `stream` has run (the scatter may still be
+        queued on return)."""
+        if part_of is not None:
+            po = np.ascontiguousarray(part_of)
+            if po.shape != (256,) or po.dtype.kind not in "ui" or ((po < 0) | (po > 255)).any():
+                raise ValueError("part_of must hold 256 bytes")
+            po = po.astype(np.uint8)
+            if n_parts is None:
+                kept = po[po != PART_NONE]
+                n_parts = int(kept.max()) + 1 if kept.size else 1
+        elif n_parts is None:
+            raise ValueError("partition_records needs n_parts or part_of")
+        n_parts = _u32_arg("n_parts", n_parts)
+        offsets = (C.c_uint64 * (min(n_parts, 255) + 1))()
+        own = out is None
+        if own:
+            out = self.alloc(max(24 * n, 16))
+        cap = n if own else out.nbytes // 24
+        try:
+            _check(lib.ibu_partition_records(self._c, _dptr(d_records), _dptr(d_class), n,
+                                             None if part_of is None else po.ctypes.data_as(_lib.u8p), n_parts, _dptr(out), cap, offsets,
+                                             stream))
+        except BaseException:
+            if own:
+                out.free()
+            raise
+        return out, np.array(offsets, dtype=np.uint64)
+
+    def partition_by_label(self, lb, d_records, n, labels, stream=None):
+        """Every sample of a multiplexed library at once: one label_records call in plain mode and one partition_records call ->
+        (DeviceBuffer, offsets as numpy u64[len(labels) + 1]).  Part j holds the records whose barcode carries the label labels[j]
+        in the Labels table `lb`, in input order; records with any other label, and records whose barcode is no entry, are
+        dropped.  labels: 1 .. 255 distinct bytes (anything else raises ValueError before any device call)."""
+        labs = [int(v) for v in labels]
+        if not 1 <= len(labs) <= 255:
+            raise ValueError(f"labels holds {len(labs)} values; a partition has 1 .. 255 parts")
+        if any(not 0 <= v <= 255 for v in labs):
+            raise ValueError("a label is one byte")
+        if len(set(labs)) != len(labs):
+            raise ValueError("labels must be distinct")
+        missing = next(v for v in range(256) if v not in set(labs))   # at most 255 labels: a byte is free
+        part_of = np.full(256, PART_NONE, np.uint8)
+        part_of[labs] = np.arange(len(labs), dtype=np.uint8)
+        d_class = self.alloc(max(n, 16))
+        try:
+            self.label_records(lb, d_records, n, d_class=d_class, missing_class=missing, stream=stream)
+            return self.partition_records(d_records, d_class, n, n_parts=len(labs), part_of=part_of, stream=stream)
+        finally:
+            self.synchronize(stream)                             # the scatter reads the class bytes
+            d_class.free()
 
     def inflate_blocks(self, d_comp, blocks, d_out, stream=None):
         """ibu_inflate_blocks_device: the deflate blocks `blocks` (a ctypes array of ibu_inflate_block_t, or what bgzf_scan

@@ -212,6 +212,7 @@ SIGNATURES = {
     "ibu_saturation_curve": (i32, [vp, vp, sz, u64, u64, P(u64), u32, P(CSaturationPoint), vp]),
     "ibu_correct_barcodes": (i32, [vp, vp, vp, sz, u32, vp, P(CCorrectCounts), vp]),
     "ibu_select_records": (i32, [vp, vp, vp, sz, u32, vp, sz, P(sz), vp]),
+    "ibu_partition_records": (i32, [vp, vp, vp, sz, u8p, u32, vp, sz, P(u64), vp]),
     "ibu_abundance_create": (i32, [vp, vp, vp, P(vp)]),
     "ibu_abundance_reset": (i32, [vp, vp]),
     "ibu_abundance_info": (i32, [vp, P(sz)]),

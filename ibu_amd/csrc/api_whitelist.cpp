@@ -6,6 +6,7 @@
 #include <atomic>
 
 #include "ctx.hpp"
+#include "partition_plan.hpp"
 
 using namespace ibu;
 
@@ -377,5 +378,57 @@ extern "C" int32_t ibu_select_records(ibu_ctx_t* ctx, const void* d_records, con
   if (size_query) return IBU_OK;
   if (kept > cap) return err_capacity(kept, cap, "records kept", "n_out");
   IBU_HIP(launch_select_scatter(ctx->cfg, d_records, d_class, n, keep_mask & 0xFFu, ctx->d_sort_scratch, d_out, st));
+  return IBU_OK;
+}
+
+// The checks ibu_partition_records makes on its map: host arithmetic, before anything else is looked at.  part_of == NULL: the
+// identity below n_parts, IBU_PART_NONE above.
+static int32_t partition_map(const uint8_t* part_of, uint32_t n_parts, PartitionMap* map) {
+  if (n_parts < 1 || n_parts > kPartitionMaxParts)
+    return set_error(IBU_ERR_INVALID_ARG, n_parts, 0, 0, "Invalid argument: n_parts must be in 1 .. 255");
+  uint8_t m[256];
+  for (uint32_t c = 0; c < 256; ++c) {
+    const uint32_t p = part_of ? part_of[c] : (c < n_parts ? c : IBU_PART_NONE);
+    if (p >= n_parts && p != IBU_PART_NONE)
+      return set_error(IBU_ERR_INVALID_ARG, c, p, 0, "Invalid argument: part_of[%u] = %u is neither below n_parts nor IBU_PART_NONE", c, p);
+    m[c] = (uint8_t)p;
+  }
+  memcpy(map->w, m, sizeof m);
+  return IBU_OK;
+}
+extern "C" int32_t ibu_partition_records(ibu_ctx_t* ctx, const void* d_records, const uint8_t* d_class, size_t n, const uint8_t part_of[256],
+                                         uint32_t n_parts, void* d_out, size_t cap, uint64_t* offsets, void* stream) {
+  int32_t rc = check_ctx(ctx);
+  if (rc) return rc;
+  PartitionMap map;
+  if ((rc = partition_map(part_of, n_parts, &map)) != 0) return rc;
+  if (!offsets) return err_arg("offsets is NULL");
+  memset(offsets, 0, (n_parts + 1) * sizeof(uint64_t));
+  if (n == 0) return IBU_OK;
+  if ((rc = check_u64_ptr(d_records, "d_records")) != 0) return rc;
+  if (!d_class) return err_arg("d_class is NULL");
+  if ((rc = check_below_2_40(n, "partition_records", "records")) != 0) return rc;
+  const bool size_query = !d_out && cap == 0;
+  if (!size_query) {
+    if ((rc = check_u64_ptr(d_out, "d_out")) != 0) return rc;
+    const size_t cap_in = cap < n ? cap : n;   // no more than n records are ever written
+    const bool empty_inside = cap_in == 0 && d_out != d_records && ranges_overlap(d_out, 1, d_records, 24 * n);   // (as ibu_select_records)
+    if (ranges_overlap(d_out, 24 * cap_in, d_records, 24 * n) || empty_inside) return err_arg("d_out overlaps d_records");
+  }
+  const PartitionPlan pl = partition_plan(n, n_parts);
+  if (!pl.ok)
+    return set_error(IBU_ERR_INVALID_ARG, pl.entries, kPartitionMaxEntries, 0,
+                     "Invalid argument: partition_records: %llu parts x units is more than one scan takes (%llu): split the records",
+                     (unsigned long long)pl.entries, (unsigned long long)kPartitionMaxEntries);
+  hipStream_t st = pick_stream(ctx, stream);
+  rc = ensure_sort_scratch(ctx, pl.scratch_bytes);
+  if (rc) return rc;
+  IBU_HIP(launch_partition_count(ctx->cfg, d_class, n, n_parts, map, ctx->d_sort_scratch, ctx->sort_scratch_bytes, st));
+  IBU_HIP(read_back_words(ctx, static_cast<const uint64_t*>(ctx->d_sort_scratch) + 1 + pl.entries, n_parts + 1, st));
+  memcpy(offsets, ctx->h_pinned, (n_parts + 1) * sizeof(uint64_t));
+  const uint64_t kept = offsets[n_parts];
+  if (size_query) return IBU_OK;
+  if (kept > cap) return err_capacity(kept, cap, "records kept", "offsets[n_parts]");
+  IBU_HIP(launch_partition_scatter(ctx->cfg, d_records, d_class, n, n_parts, map, ctx->d_sort_scratch, d_out, st));
   return IBU_OK;
 }

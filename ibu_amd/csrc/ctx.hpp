@@ -12,7 +12,7 @@
 
 namespace ibu {
 
-constexpr size_t kPinnedWords = 128;   // ibu_ctx::h_pinned
+constexpr size_t kPinnedWords = 256;   // ibu_ctx::h_pinned (the most: ibu_partition_records, 255 part starts and the total)
 
 inline int32_t hip_fail(hipError_t e, const char* what) {
   if (e == hipErrorNoDevice || e == hipErrorInvalidDevice)
@@ -146,6 +146,12 @@ template <size_t WORDS>
 inline hipError_t read_back(ibu_ctx* ctx, const void* d_src, hipStream_t st) {
   static_assert(WORDS <= kPinnedWords, "the words come back through h_pinned");
   const hipError_t e = hipMemcpyAsync(ctx->h_pinned, d_src, WORDS * sizeof(uint64_t), hipMemcpyDeviceToHost, st);
+  return e != hipSuccess ? e : hipStreamSynchronize(st);
+}
+// ... for a number of words only the call knows (at most kPinnedWords: the caller's argument checks see to that).
+inline hipError_t read_back_words(ibu_ctx* ctx, const void* d_src, size_t words, hipStream_t st) {
+  if (words > kPinnedWords) return hipErrorInvalidValue;
+  const hipError_t e = hipMemcpyAsync(ctx->h_pinned, d_src, words * sizeof(uint64_t), hipMemcpyDeviceToHost, st);
   return e != hipSuccess ? e : hipStreamSynchronize(st);
 }
 }  // namespace ibu

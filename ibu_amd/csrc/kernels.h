@@ -262,6 +262,14 @@ hipError_t launch_select_count(const LaunchCfg&, const uint8_t* d_class, size_t 
                                hipStream_t st);
 hipError_t launch_select_scatter(const LaunchCfg&, const void* recs, const uint8_t* d_class, size_t n, uint32_t keep_mask,
                                  const void* scratch, void* out, hipStream_t st);
+// partition (ibu_partition_records; k_partition.hip, the plan in partition_plan.hpp): count + scan leave the total in scratch[0] (u64),
+// every (part, unit)'s output position behind it and, behind those, the n_parts part starts and the total once more — the n_parts + 1
+// words the caller reads back; scatter writes the records.  `map`: the part of every class byte, byte c of the 256 (255 = dropped).
+struct PartitionMap { uint32_t w[64]; };
+hipError_t launch_partition_count(const LaunchCfg&, const uint8_t* d_class, size_t n, uint32_t n_parts, const PartitionMap& map, void* scratch,
+                                  size_t scratch_bytes, hipStream_t st);
+hipError_t launch_partition_scatter(const LaunchCfg&, const void* recs, const uint8_t* d_class, size_t n, uint32_t n_parts,
+                                    const PartitionMap& map, const void* scratch, void* out, hipStream_t st);
 // the matrix export (ibu_matrix_rows, ibu_matrix_market_body; k_matrix.hip), on u64 columns of n entries.  `scratch`:
 // matrix_scratch_bytes(n) bytes, 8-byte aligned.  A count launcher (count + scan) leaves u64[4] at its front for the caller to read
 // back — [0 .. 2] the largest printed value of each column (text only), [3] the total: rows, or bytes of text — and every unit's

@@ -621,6 +621,15 @@ class Context {
     check(ibu_select_records(c_, d_recs, d_class, n, keep_mask, d_out, cap, &k, st));
     return k;
   }
+  // stable multi-way partition by class byte in one pass (ibu_partition_records): part_of (host, 256 bytes, or nullptr for the identity
+  // below n_parts) gives the part of every class byte, IBU_PART_NONE drops; d_out receives part 0, then part 1, ..., each in input
+  // order -> the n_parts + 1 offsets (part p is records offsets[p] .. offsets[p + 1] of d_out).  d_out == nullptr and cap == 0: only count
+  std::vector<uint64_t> partition_records(const void* d_recs, const uint8_t* d_class, size_t n, const uint8_t* part_of, uint32_t n_parts, void* d_out,
+                                          size_t cap, void* st = nullptr) {
+    std::vector<uint64_t> offsets((n_parts < 255 ? n_parts : 255) + 1, 0);
+    check(ibu_partition_records(c_, d_recs, d_class, n, part_of, n_parts, d_out, cap, offsets.data(), st));
+    return offsets;
+  }
   // load_to_vec, device form -> (header, device pointer owned by the caller: release with free(), n)
   std::tuple<Header, void*, size_t> load_to_device(const std::string& path, const RingConfig* ring = nullptr, StreamStats* stats = nullptr) {
     Header h; void* p = nullptr; size_t n = 0;

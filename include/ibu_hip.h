@@ -1000,6 +1000,33 @@ int32_t ibu_correct_barcodes(ibu_ctx_t* ctx, const ibu_whitelist_t* wl, void* d_
  * context's sort scratch (8 bytes per 2048 records). */
 int32_t ibu_select_records(ibu_ctx_t* ctx, const void* d_records, const uint8_t* d_class, size_t n, uint32_t keep_mask,
                            void* d_out, size_t cap, size_t* n_out, void* stream);
+/* Stable multi-way partition by class byte, in one pass over the records (k_partition.hip): every sample of a multiplexed library at
+ * once, where ibu_select_records keeps one subset per call and never a class above 7.  The reference has nothing like this; the
+ * semantics are this library's and are stated in full here (tests/partition_np.py states them in numpy).
+ * part_of (host, 256 bytes, nullable): part_of[c] is the part of class byte c — a value below n_parts, or IBU_PART_NONE (255) for a
+ * record that is dropped.  Several classes may map to one part.  NULL means the identity for c < n_parts and IBU_PART_NONE above.
+ * n_parts is 1 .. 255.  d_out (8-byte aligned; must not overlap d_records, by the test ibu_select_records makes) receives part 0,
+ * then part 1, and so on; within a part the records keep their input order, so every part of sorted input is still sorted, and the
+ * output bytes are fully determined by the input.  offsets (host, n_parts + 1 words, required): offsets[p] = the first record of
+ * part p in d_out, offsets[n_parts] = the number of records kept.
+ * Size query: d_out == NULL and cap == 0 fills offsets and writes nothing.  cap (records) smaller than offsets[n_parts]:
+ * IBU_ERR_INVALID_ARG with offsets filled and nothing written (detail.a = records kept, detail.b = cap); with a larger cap the
+ * bytes behind the last kept record are untouched.  n == 0 is OK: all offsets are 0 and nothing is touched.  n < 2^40.
+ * IBU_ERR_INVALID_ARG, with nothing touched: n_parts outside 1 .. 255; a part_of entry that is neither below n_parts nor 255
+ * (detail.a = the class, detail.b = the entry); offsets == NULL; with n > 0 a NULL or misaligned d_records, a NULL d_class, a
+ * misaligned or overlapping d_out (these leave offsets zeroed); more parts x units than one scan takes (below).
+ * Synchronises `stream` once (the offsets come back before anything is written); the scatter may still be queued on return.  The
+ * offsets pass through the context, as every small read-back does (the rule ibu_correct_barcodes states): of the calls in flight on
+ * ONE context at the same time, at most one may be such a call.
+ * Three kernels: count (a wave owns a UNIT of consecutive records and counts it per part in LDS), one exclusive scan of the
+ * part-major table of (part, unit) counts, scatter (a wave keeps its unit's running position per part in LDS; per 64 records the
+ * lanes of equal part find each other with the sort's match-any).  Reads 1 B of class per record twice and 24 B per kept record;
+ * writes 24 B per kept record.  The unit is max(2048, the power of two at or above 64 * n_parts) records, and the table lives in the
+ * context's sort scratch: 8 * (n_parts * ceil(n / unit) + n_parts + 2) bytes, at most n / 8 + 4096 for any n_parts.  The scan
+ * indexes the table with 32 bits: n_parts * ceil(n / unit) above 2^32 - 16385 is refused (255 parts: from 2.7e11 records). */
+#define IBU_PART_NONE 255u
+int32_t ibu_partition_records(ibu_ctx_t* ctx, const void* d_records, const uint8_t* d_class, size_t n, const uint8_t part_of[256],
+                              uint32_t n_parts, void* d_out, size_t cap, uint64_t* offsets, void* stream);
 /* Whitelist abundance and the resolution of ambiguous barcodes, on the device (k_whitelist.hip): what recovers the records that
  * ibu_correct_barcodes classes 2 (two or more whitelist entries one substitution away) with a prior, as Cell Ranger and STARsolo
  * (1MM_multi) do — the candidate that carries nearly all of the exactly matching reads among the candidates wins.  Records carry no

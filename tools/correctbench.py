@@ -15,7 +15,14 @@ and ibu_resolve_barcodes at 39/40.
 A leg of its own on the same arrays: per-barcode labels onto records.  Per configuration, in one process on one array and one
 whitelist (entry of rank r labelled r % 256), in read order and then on the same records SORTED: ibu_reduce (the plain 24-byte read),
 ibu_correct_barcodes(max_mismatches=0) with class bytes — the yardstick: the same read, one probe and a 1-byte write — and
-ibu_label_records with class bytes, with class bytes and the histogram, and with the histogram alone."""
+ibu_label_records with class bytes, with class bytes and the histogram, and with the histogram alone.
+  python tools/correctbench.py --partition [--records 1e9] [--whitelists 1e5] [--errors 0.02] [--rounds 5]
+A leg of its own on the same arrays: the multi-way partition by class byte.  Per configuration, in read order and then on the same
+records SORTED: ibu_device_copy of the array and ibu_select_records keeping every record of it (a class array of zeros) — the
+yardsticks: the same reads, the same 24-byte writes, the same unit walk — and, for S = 2, 8, 16 and 255 labels dealt evenly over the
+whitelist, ibu_partition_records on the class bytes of ibu_label_records in plain mode: the size query (count + scan) and the whole
+call, each with its one synchronisation inside; scatter_ms is the difference of the two medians.  For S = 8 also the chain the one
+call replaces: eight ibu_label_records(match) + ibu_select_records pairs, whose counts and record checksums must equal the parts."""
 import argparse
 import ctypes as C
 import json
@@ -36,6 +43,7 @@ def main():
     ap.add_argument("--random", type=float, default=0.01, help="share of uniform random barcodes (they always take the miss path)")
     ap.add_argument("--resolve", action="store_true", help="the abundance / resolve leg instead of the correct / select one")
     ap.add_argument("--labels", action="store_true", help="the label leg instead of the correct / select one")
+    ap.add_argument("--partition", action="store_true", help="the partition leg instead of the correct / select one")
     a = ap.parse_args()
     import torch                                             # before the library, as bench.py does
     torch.cuda.init()
@@ -100,6 +108,9 @@ def main():
                 continue
             if a.labels:
                 labels_leg(ia, ctx, torch, st, timed, stat, wl, codes, d, orig, out, d_cls, n, asked, bc_len, err, a)
+                continue
+            if a.partition:
+                partition_leg(ia, ctx, torch, st, timed, stat, wl, codes, d, orig, out, d_cls, n, asked, bc_len, err, a)
                 continue
             t_red, t_cor, t_sel, t_cpy = [], [], [], []
             counts = kept = None
@@ -204,6 +215,80 @@ def labels_leg(ia, ctx, torch, st, timed, stat, wl, codes, d, orig, out, d_cls, 
     result["found"] = int(hists["read_order"][:256].sum())
     result["not_found"] = int(hists["read_order"][256])
     result["sorted_histogram_equals_read_order"] = bool((hists["read_order"] == hists["sorted"]).all()) and int(hists["sorted"].sum()) == n
+    print(json.dumps(result), flush=True)
+    lb.close()
+
+
+def partition_leg(ia, ctx, torch, st, timed, stat, wl, codes, d, orig, out, d_cls, n, asked, bc_len, err, a):
+    w = len(codes)
+    unsigned = codes ^ torch.iinfo(torch.int64).min          # int64 order of this = unsigned order of the codes
+    rank = torch.argsort(torch.argsort(unsigned))
+    zeros = torch.zeros(n, dtype=torch.uint8, device="cuda")  # the class array of the select that keeps everything
+    torch.cuda.synchronize()
+    lb = wl.labels(fill=255)
+    result = {"leg": "partition", "n": n, "records_asked": asked, "bc_len": bc_len, "w": w, "errors": err, "random": a.random}
+    k_out = C.c_size_t()
+
+    def select(src, cls_ptr, mask, dst, cap):
+        ia._check(ia.lib.ibu_select_records(ctx._c, src.ptr, cls_ptr, n, mask, dst.ptr if dst is not None else None, cap, C.byref(k_out), st))
+        return k_out.value
+
+    def partition(src, parts, dst, offsets):
+        ia._check(ia.lib.ibu_partition_records(ctx._c, src.ptr, d_cls.ptr, n, None, parts, dst.ptr if dst is not None else None, n if dst is not None else 0,
+                                               offsets, st))
+
+    for order in ("read_order", "sorted"):
+        if order == "read_order":
+            ctx.copy(d, orig, 24 * n, stream=st)
+            recs, dst = d, out
+        else:
+            ctx.copy(out, orig, 24 * n, stream=st)
+            ctx.sort_records(out, d, n, stream=st)               # d is the destination from here on
+            recs, dst = out, d
+        t = {"copy": [], "select_all_query": [], "select_all": []}
+        for _ in range(a.rounds + 1):
+            t["copy"].append(timed(lambda: ctx.copy(dst, recs, 24 * n, stream=st)))
+            t["select_all_query"].append(timed(lambda: select(recs, zeros.data_ptr(), 1, None, 0)))
+            t["select_all"].append(timed(lambda: select(recs, zeros.data_ptr(), 1, dst, n)))
+        assert k_out.value == n
+        res = {k: stat(v) for k, v in t.items()}
+        sel = res["select_all"]["median_ms"]
+        for parts in (2, 8, 16, 255):
+            labs = (rank % parts).to(torch.uint8).contiguous()
+            torch.cuda.synchronize()
+            ia._check(ia.lib.ibu_labels_set(ctx._c, lb._c, codes.data_ptr(), labs.data_ptr(), w, None, st))
+            tl, tq, tp = [], [], []
+            offsets = (C.c_uint64 * (parts + 1))()
+            for _ in range(a.rounds + 1):
+                tl.append(timed(lambda: ctx.label_records(lb, recs, n, d_class=d_cls, stream=st)))
+                tq.append(timed(lambda: partition(recs, parts, None, offsets)))
+                tp.append(timed(lambda: partition(recs, parts, dst, offsets)))
+            off = list(offsets)
+            r = {"label_plain": stat(tl), "query": stat(tq), "partition": stat(tp), "kept": off[parts]}
+            r["scatter_ms"] = round(r["partition"]["median_ms"] - r["query"]["median_ms"], 3)
+            r["partition_over_select_all"] = round(r["partition"]["median_ms"] / sel, 3)
+            r["partition_over_copy"] = round(r["partition"]["median_ms"] / res["copy"]["median_ms"], 3)
+            if parts == 8:                                       # the chain the one call replaces; its outputs land in the columns' memory
+                ctx.synchronize(st)
+                sums = [ctx.reduce(ia.DeviceBuffer.wrap(ctx, dst.ptr + 24 * off[p], 24 * (off[p + 1] - off[p])), off[p + 1] - off[p]) for p in range(parts)]
+                tc, same = [], True
+                for rnd in range(a.rounds + 1):
+                    def chain():
+                        nonlocal same
+                        for p in range(parts):
+                            ctx.label_records(lb, recs, n, d_class=d_cls, match=p, stream=st)
+                            k = select(recs, d_cls.ptr, 1 << ia.LABEL_IS, dst, n)
+                            if rnd == 0:                         # (the warm-up round: checked, not timed)
+                                ctx.synchronize(st)
+                                same = same and k == off[p + 1] - off[p] and ctx.reduce(dst, k) == sums[p]
+                    tc.append(timed(chain))
+                r["chain_of_8_label_select_pairs"] = stat(tc)
+                r["chain_equals_partition"] = same
+                r["chain_over_label_plus_partition"] = round(r["chain_of_8_label_select_pairs"]["median_ms"] /
+                                                             (r["label_plain"]["median_ms"] + r["partition"]["median_ms"]), 3)
+                ctx.label_records(lb, recs, n, d_class=d_cls, stream=st)   # the class bytes of the plain mode again
+            res[f"S{parts}"] = r
+        result[order] = res
     print(json.dumps(result), flush=True)
     lb.close()
 
