@@ -261,15 +261,15 @@ extern "C" int32_t ibu_feature_metrics(ibu_ctx_t* ctx, const void* d_records, si
   if (flags & ~(uint32_t)IBU_FEATURE_ACCUMULATE) return err_arg("unknown bit in flags");
   if (feature_word == 2 && d_cells) return err_arg("d_cells needs feature_word 1: cells are not available on records sorted by (barcode, umi, index)");
   hipStream_t st = pick_stream(ctx, stream);
-  rc = ensure_runs_scratch(ctx, feature_run_scratch_bytes(0));
-  if (rc) return rc;
   if (!(flags & IBU_FEATURE_ACCUMULATE))
     for (uint64_t* col : {d_reads, d_umis, d_cells})
       if (col) IBU_HIP(hipMemsetAsync(col, 0, sizeof(uint64_t) * n_features, st));
-  uint64_t* acc = static_cast<uint64_t*>(ctx->d_runs_scratch);
-  IBU_HIP(launch_feature_count(ctx->cfg, d_records, n, feature_word, n_features, d_reads, d_umis, d_cells, acc, st));
-  if (!totals) return IBU_OK;
-  IBU_HIP(read_back<4>(ctx, acc, st));
+  const auto count = [&](uint64_t* acc) { return launch_feature_count(ctx->cfg, d_records, n, feature_word, n_features, d_reads, d_umis, d_cells, acc, st); };
+  if (!totals) {   // nothing to bring back: the launch stays asynchronous and touches no per-call state
+    IBU_HIP(count(nullptr));
+    return IBU_OK;
+  }
+  if ((rc = grid_totals<4>(ctx, st, count)) != 0) return rc;
   for (int k = 0; k < 4; ++k) totals[k] = ctx->h_pinned[k];
   return IBU_OK;
 }
@@ -314,10 +314,8 @@ extern "C" int32_t ibu_subsample_class(ibu_ctx_t* ctx, size_t n, uint64_t first_
     IBU_HIP(launch_subsample(ctx->cfg, n, base, threshold, d_class, nullptr, st));
     return IBU_OK;
   }
-  rc = ensure_sort_scratch(ctx, kSubsampleAccBytes);
+  rc = grid_totals<1>(ctx, st, [&](uint64_t* acc) { return launch_subsample(ctx->cfg, n, base, threshold, d_class, acc, st); });
   if (rc) return rc;
-  IBU_HIP(launch_subsample(ctx->cfg, n, base, threshold, d_class, static_cast<uint64_t*>(ctx->d_sort_scratch), st));
-  IBU_HIP(read_back<1>(ctx, ctx->d_sort_scratch, st));
   *n_kept = ctx->h_pinned[0];
   return IBU_OK;
 }
@@ -488,15 +486,14 @@ extern "C" int32_t ibu_assign_rows(ibu_ctx_t* ctx, const uint64_t* d_top_value, 
   if (counts) *counts = ibu_assign_counts_t{0, 0, 0, 0};   // (behind the last argument check: a refused call leaves the totals alone)
   if (n_rows == 0) return IBU_OK;
   hipStream_t st = pick_stream(ctx, stream);
-  uint64_t* acc = nullptr;
-  if (counts) {
-    if ((rc = ensure_sort_scratch(ctx, kAssignAccBytes)) != 0) return rc;
-    acc = static_cast<uint64_t*>(ctx->d_sort_scratch);
+  const auto assign = [&](uint64_t* acc) {
+    return launch_matrix_assign(ctx->cfg, d_top_value, d_next_value, d_row_sum, n_rows, rule->min_value, rule->num, rule->den, d_row_class, acc, st);
+  };
+  if (!counts) {   // nothing to bring back: the launch stays asynchronous and touches no per-call state
+    IBU_HIP(assign(nullptr));
+    return IBU_OK;
   }
-  IBU_HIP(launch_matrix_assign(ctx->cfg, d_top_value, d_next_value, d_row_sum, n_rows, rule->min_value, rule->num, rule->den, d_row_class,
-                               acc, st));
-  if (!counts) return IBU_OK;
-  IBU_HIP(read_back<3>(ctx, acc, st));
+  if ((rc = grid_totals<3>(ctx, st, assign)) != 0) return rc;
   counts->rows = n_rows;
   counts->assigned = ctx->h_pinned[IBU_ROW_ASSIGNED];
   counts->none = ctx->h_pinned[IBU_ROW_NONE];

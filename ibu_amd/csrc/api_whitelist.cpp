@@ -29,17 +29,6 @@ static int32_t no_ctx_error(const char* what) {
   if (count == 0) return set_error(IBU_ERR_NO_DEVICE, 0, 0, 0, "no HIP device: %s lives on a device context", what);
   return err_arg("ctx is NULL");
 }
-// The totals of a correct / resolve call that asks for them: the context's accumulator (allocated on first use) zeroed, the launch
-// on it, the fold, and the four totals read back into ctx->h_pinned[0..3].  Synchronises the stream.
-template <class Launch>
-static int32_t class_totals(ibu_ctx* ctx, hipStream_t st, Launch&& launch) {
-  if (!ctx->d_class_acc) IBU_HIP(ctx_malloc(ctx, reinterpret_cast<void**>(&ctx->d_class_acc), kCorrectAccBytes));
-  IBU_HIP(hipMemsetAsync(ctx->d_class_acc, 0, kCorrectAccBytes, st));
-  IBU_HIP(launch(ctx->d_class_acc));
-  IBU_HIP(launch_correct_fold(ctx->d_class_acc, st));
-  IBU_HIP(read_back<4>(ctx, ctx->d_class_acc, st));
-  return IBU_OK;
-}
 extern "C" int32_t ibu_whitelist_create(ibu_ctx_t* ctx, const uint64_t* d_codes, size_t w, uint32_t bc_len, void* stream,
                                         ibu_whitelist_t** out) {
   if (!ctx) return no_ctx_error("a whitelist");
@@ -111,7 +100,7 @@ extern "C" int32_t ibu_correct_barcodes(ibu_ctx_t* ctx, const ibu_whitelist_t* w
     IBU_HIP(correct(nullptr));
     return IBU_OK;
   }
-  if ((rc = class_totals(ctx, st, correct)) != 0) return rc;
+  if ((rc = grid_totals<4>(ctx, st, correct)) != 0) return rc;
   counts->exact = ctx->h_pinned[0];
   counts->corrected = ctx->h_pinned[1];
   counts->ambiguous = ctx->h_pinned[2];
@@ -225,7 +214,7 @@ extern "C" int32_t ibu_resolve_barcodes(ibu_ctx_t* ctx, const ibu_whitelist_t* w
     IBU_HIP(resolve(nullptr));
     return IBU_OK;
   }
-  if ((rc = class_totals(ctx, st, resolve)) != 0) return rc;
+  if ((rc = grid_totals<4>(ctx, st, resolve)) != 0) return rc;
   counts->examined = ctx->h_pinned[0];
   counts->resolved = ctx->h_pinned[1];
   counts->below_share = ctx->h_pinned[2];
@@ -294,14 +283,12 @@ extern "C" int32_t ibu_labels_set(ibu_ctx_t* ctx, ibu_labels_t* lb, const uint64
   if (n_skipped) *n_skipped = 0;
   if (k == 0) return IBU_OK;
   hipStream_t st = pick_stream(ctx, stream);
+  const auto set = [&](uint64_t* skipped) { return launch_labels_set(ctx->cfg, table_of(lb->wl), lb->d_labels, d_codes, d_labels, k, skipped, st); };
   if (!n_skipped) {   // nothing to bring back: the launch stays asynchronous and touches no per-call state
-    IBU_HIP(launch_labels_set(ctx->cfg, table_of(lb->wl), lb->d_labels, d_codes, d_labels, k, nullptr, st));
+    IBU_HIP(set(nullptr));
     return IBU_OK;
   }
-  if (!ctx->d_class_acc) IBU_HIP(ctx_malloc(ctx, reinterpret_cast<void**>(&ctx->d_class_acc), kCorrectAccBytes));
-  IBU_HIP(hipMemsetAsync(ctx->d_class_acc, 0, sizeof(uint64_t), st));
-  IBU_HIP(launch_labels_set(ctx->cfg, table_of(lb->wl), lb->d_labels, d_codes, d_labels, k, ctx->d_class_acc, st));
-  IBU_HIP(read_back<1>(ctx, ctx->d_class_acc, st));
+  if ((rc = grid_totals<1>(ctx, st, set)) != 0) return rc;
   *n_skipped = ctx->h_pinned[0];
   return IBU_OK;
 }

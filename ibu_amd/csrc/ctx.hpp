@@ -12,6 +12,7 @@
 
 namespace ibu {
 
+constexpr size_t kTotalsWords = kCorrectAccBytes / sizeof(uint64_t);   // ibu_ctx::d_totals_acc (the most: launch_correct's slots; every other call takes 1 to 4 words)
 constexpr size_t kPinnedWords = 256;   // ibu_ctx::h_pinned (the most: ibu_partition_records, 255 part starts and the total)
 
 inline int32_t hip_fail(hipError_t e, const char* what) {
@@ -59,7 +60,7 @@ struct ibu_ctx {
   uint64_t* d_status = nullptr;  // [first_bad_record, n_bad_records]
   uint64_t* d_acc = nullptr;     // [count, sum0..2, xor0..2, pad]
   uint32_t* d_flag = nullptr;    // sortedness flag
-  uint64_t* d_class_acc = nullptr;  // the totals of an ibu_correct_barcodes / ibu_resolve_barcodes call that asks for them (kCorrectAccBytes, on first use; such a call synchronises, so two never share it)
+  uint64_t* d_totals_acc = nullptr; // the grid totals of a call that asks for them (grid_totals below: kTotalsWords u64, on first use; such a call synchronises, so two never share it)
   uint64_t* d_label_acc = nullptr;  // the histogram slots of an ibu_label_records call that asks for `hist` (kLabelAccBytes, on first use; under the same rule)
   uint64_t* h_pinned = nullptr;  // kPinnedWords x u64 of pinned host memory for small read-backs
   void* d_sort_scratch = nullptr;
@@ -147,6 +148,17 @@ inline hipError_t read_back(ibu_ctx* ctx, const void* d_src, hipStream_t st) {
   static_assert(WORDS <= kPinnedWords, "the words come back through h_pinned");
   const hipError_t e = hipMemcpyAsync(ctx->h_pinned, d_src, WORDS * sizeof(uint64_t), hipMemcpyDeviceToHost, st);
   return e != hipSuccess ? e : hipStreamSynchronize(st);
+}
+// "Launch, then read K totals back" (kernels.h: grid totals): the context's accumulator, allocated on first use; launch(acc), which
+// zeroes it and adds into it; the K words read back into ctx->h_pinned[0 .. K - 1].  Synchronises the stream.  A call that asks for
+// no totals passes its launcher NULL instead and stays asynchronous.
+template <size_t K, class Launch>
+inline int32_t grid_totals(ibu_ctx* ctx, hipStream_t st, Launch&& launch) {
+  static_assert(K <= kTotalsWords, "the totals come back through d_totals_acc");
+  if (!ctx->d_totals_acc) IBU_HIP(ctx_malloc(ctx, reinterpret_cast<void**>(&ctx->d_totals_acc), kTotalsWords * sizeof(uint64_t)));
+  IBU_HIP(launch(ctx->d_totals_acc));
+  IBU_HIP(read_back<K>(ctx, ctx->d_totals_acc, st));
+  return IBU_OK;
 }
 // ... for a number of words only the call knows (at most kPinnedWords: the caller's argument checks see to that).
 inline hipError_t read_back_words(ibu_ctx* ctx, const void* d_src, size_t words, hipStream_t st) {

@@ -86,7 +86,7 @@ extern "C" void ibu_ctx_destroy(ibu_ctx_t* ctx) {
   if (ctx->d_status) (void)hipFree(ctx->d_status);
   if (ctx->d_acc) (void)hipFree(ctx->d_acc);
   if (ctx->d_flag) (void)hipFree(ctx->d_flag);
-  if (ctx->d_class_acc) (void)hipFree(ctx->d_class_acc);
+  if (ctx->d_totals_acc) (void)hipFree(ctx->d_totals_acc);
   if (ctx->d_label_acc) (void)hipFree(ctx->d_label_acc);
   if (ctx->h_pinned) (void)hipHostFree(ctx->h_pinned);
   if (ctx->h_part) (void)hipHostFree(ctx->h_part);

@@ -18,8 +18,6 @@
 
 namespace ibu {
 
-static_assert(kBlock == kSortThreads, "block_accumulate sums a workgroup of kSortThreads");
-
 __device__ __forceinline__ u64 lanes_below(u32 k) { return k >= 64u ? ~0ull : (1ull << k) - 1; }
 __device__ __forceinline__ void feat_add(u64* __restrict__ col, u64 f, u64 v) {   // no value comes back: a no-return atomic
   (void)__hip_atomic_fetch_add(col + f, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -61,7 +59,7 @@ struct FeatureSink : NoSink {
   }
 };
 
-// acc (block_accumulate): [0] reads in range, [1] umis in range, [2] cells in range, [3] reads out of range
+// acc (nullable, uniform over the grid; block_accumulate): [0] reads in range, [1] umis in range, [2] cells in range, [3] reads out of range
 extern "C" __global__ void __launch_bounds__(kSortThreads, 4)
 ibu_k_feature_count(const u64* __restrict__ recs, SegPlan sp, FeatureCols cols, u64* __restrict__ acc) {
   __shared__ __attribute__((aligned(16))) uint8_t lds[kSortWaves * kTileBytes];
@@ -74,7 +72,7 @@ ibu_k_feature_count(const u64* __restrict__ recs, SegPlan sp, FeatureCols cols, 
     runs_segment<2>(recs, sp, seg, lds + wib * kTileBytes, lane, 0, 0, c1, c2, sink);
   }
   u64 t[4] = {sink.t_reads, sink.t_umis, sink.t_cells, sink.t_out};
-  block_accumulate(t, acc, accl);
+  if (acc) block_accumulate(t, acc, accl);
 }
 
 // a NULL column counts as 0 everywhere (the entry point refuses a NULL column whose limits are not both 0)
@@ -105,7 +103,7 @@ struct FeatureClassArgs { const uint8_t* verdict; u64 nf; u32 word; u64* acc; };
 extern "C" __global__ void __launch_bounds__(kBlock, 8)
 ibu_k_feature_class(const uint8_t* __restrict__ recs, u32 ntiles, uint8_t* __restrict__ cls_out /*nullable*/, const FeatureClassArgs fa) {
   __shared__ __attribute__((aligned(16))) uint8_t lds[kWavesPerBlock * kTileBytes];
-  __shared__ u64 accl[kSortWaves * 4];
+  __shared__ u64 accl[kWavesPerBlock * 4];
   const u32 lane = threadIdx.x & (kWave - 1), wib = threadIdx.x >> 6;
   uint8_t* tile = lds + wib * kTileBytes;
   u64 t[4] = {0, 0, 0, 0};
@@ -125,7 +123,7 @@ ibu_k_feature_class(const uint8_t* __restrict__ recs, u32 ntiles, uint8_t* __res
 // One thread per record: the rows peeled off the front of an 8- but not 16-byte aligned array and the n % 128 rest.
 extern "C" __global__ void __launch_bounds__(kBlock)
 ibu_k_feature_class_tail(const u64* __restrict__ recs, u64 row0, u64 row1, uint8_t* __restrict__ cls_out /*nullable*/, const FeatureClassArgs fa) {
-  __shared__ u64 accl[kSortWaves * 4];
+  __shared__ u64 accl[kWavesPerBlock * 4];
   const u64 i = row0 + (u64)blockIdx.x * kBlock + threadIdx.x;
   u64 t[4] = {0, 0, 0, 0};
   if (i < row1) {
@@ -147,7 +145,7 @@ hipError_t launch_feature_count(const LaunchCfg& cfg, const void* recs, size_t n
                                 uint64_t* d_umis, uint64_t* d_cells, uint64_t* acc, hipStream_t st) {
   (void)hipGetLastError();
   if (n >= (1ull << 40) || !feature_args_ok(feature_word, n_features) || (feature_word == 2 && d_cells)) return hipErrorInvalidValue;
-  const hipError_t e = hipMemsetAsync(acc, 0, kFeatureAccBytes, st);
+  const hipError_t e = zero_totals(acc, 4, st);
   if (e != hipSuccess || n == 0) return e;
   const SegPlan sp = seg_plan(cfg, recs, n);
   hipLaunchKernelGGL(ibu_k_feature_count, seg_grid(sp), dim3(kSortThreads), 0, st, (const u64*)recs, sp,

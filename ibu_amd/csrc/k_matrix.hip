@@ -405,7 +405,7 @@ ibu_k_rowtop_finish(u32 nunits, const u64* __restrict__ units, const u64* __rest
 
 // ---- the class of a row ----------------------------------------------------------------------------------------------
 // ibu_assign_rows: elementwise over the columns ibu_matrix_row_top leaves.  The share test top * den >= num * sum is taken in 128 bits.
-// acc (nullable; zeroed by the launcher): rows per class [0 .. 2], one wave-reduced add per wave and class.
+// acc (nullable, uniform over the grid; block_accumulate): rows per class [0 .. 2].
 struct AssignRule { u64 min_value, num, den; };
 __device__ __forceinline__ bool mul_ge(u64 a, u64 b, u64 c, u64 d) {   // a * b >= c * d, exactly
   const u64 h1 = __umul64hi(a, b), h2 = __umul64hi(c, d);
@@ -414,6 +414,7 @@ __device__ __forceinline__ bool mul_ge(u64 a, u64 b, u64 c, u64 d) {   // a * b 
 extern "C" __global__ void __launch_bounds__(kBlock)
 ibu_k_rowtop_assign(const u64* __restrict__ top, const u64* __restrict__ next, const u64* __restrict__ sum, u64 rows, AssignRule rule,
                     uint8_t* __restrict__ cls_out /*nullable*/, u64* __restrict__ acc /*nullable*/) {
+  __shared__ u64 accl[kWavesPerBlock * 3];
   const u64 floor = rule.min_value ? rule.min_value : 1;
   u64 t[3] = {0, 0, 0};
   const u64 stride = (u64)gridDim.x * blockDim.x;
@@ -425,11 +426,7 @@ ibu_k_rowtop_assign(const u64* __restrict__ top, const u64* __restrict__ next, c
     for (u32 q = 0; q < 3; ++q) t[q] += c == q ? 1 : 0;
   }
   if (!acc) return;                                // uniform over the grid
-  wave_reduce(t, OpAdd{});
-  if ((threadIdx.x & (kWave - 1)) == 0)
-#pragma unroll
-    for (int q = 0; q < 3; ++q)
-      if (t[q]) atomicAdd(&acc[q], t[q]);
+  block_accumulate(t, acc, accl);
 }
 
 // ---- launchers -------------------------------------------------------------------------------------------------------
@@ -474,16 +471,12 @@ hipError_t launch_matrix_row_top(const LaunchCfg& cfg, const uint64_t* first, co
                      (u32)nunits, (const u64*)mtx_scan_array(scratch), (const u64*)part, out);
   return hipGetLastError();
 }
-// acc (nullable): kAssignAccBytes of device memory, 8-byte aligned, zeroed here; [0 .. 2] = the rows of class 0 .. 2.
 hipError_t launch_matrix_assign(const LaunchCfg& cfg, const uint64_t* top_value, const uint64_t* next_value, const uint64_t* row_sum,
                                 size_t rows, uint64_t min_value, uint64_t num, uint64_t den, uint8_t* d_class, uint64_t* acc, hipStream_t st) {
   (void)hipGetLastError();
   if (den == 0 || num > den || (!d_class && !acc)) return hipErrorInvalidValue;
-  if (acc) {
-    const hipError_t e = hipMemsetAsync(acc, 0, kAssignAccBytes, st);
-    if (e != hipSuccess) return e;
-  }
-  if (rows == 0) return hipSuccess;
+  const hipError_t e = zero_totals(acc, 3, st);
+  if (e != hipSuccess || rows == 0) return e;
   hipLaunchKernelGGL(ibu_k_rowtop_assign, dim3(capped_grid(cfg, rows, kBlock)), dim3(kBlock), 0, st, (const u64*)top_value,
                      (const u64*)next_value, (const u64*)row_sum, (u64)rows, AssignRule{min_value, num, den}, d_class, (u64*)acc);
   return hipGetLastError();

@@ -17,7 +17,7 @@
 //            there.  A run over all of 1e9 records is 122 071 scan entries, 120 rounds: the cost does not depend on run lengths.
 //   points   the 3 x K cumulative counts.
 // The subsample writes one class byte per row, sixteen rows per lane and dwordx4 store where the class array's alignment allows, bytes at
-// its two ends; the kept count goes through kReduceSlots slots, one atomic per workgroup.
+// its two ends; the kept count goes through block_accumulate, one atomic per workgroup.
 // Launchers: launch_subsample, launch_saturation (kernels.h); C ABI: ibu_subsample_class, ibu_saturation_curve (api_analysis.cpp).
 #include "runs_walk.hpp"
 
@@ -247,11 +247,10 @@ ibu_k_saturation_points(const u64* __restrict__ totals, u32 k, u64* __restrict__
 
 // ---- the subsample: class byte 0 (kept) where u(row) < threshold or the threshold is all ones, 1 (dropped) elsewhere -------------
 // `front` rows lie in front of the first 16-byte aligned class byte, `units` whole 16-row units behind them, fewer than 16 rows behind
-// those.  d_class == nullptr: the count alone.  acc (nullable): kReduceSlots u64, zeroed by the launcher.
+// those.  d_class == nullptr: the count alone.  acc (nullable, uniform over the grid; block_accumulate): [0] the kept rows.
 extern "C" __global__ void __launch_bounds__(kSortThreads)
 ibu_k_subsample(u64 n, u64 base, u64 threshold, u64 front, u64 units, uint8_t* __restrict__ d_class, u64* __restrict__ acc) {
-  __shared__ u32 wsum[kSortWaves];
-  const u32 lane = threadIdx.x & (kWave - 1), wib = threadIdx.x >> 6;
+  __shared__ u64 accl[kSortWaves];
   const bool all = threshold == ~0ull;
   u32 kept = 0;
   const u64 stride = (u64)gridDim.x * kSortThreads;
@@ -281,21 +280,8 @@ ibu_k_subsample(u64 n, u64 base, u64 threshold, u64 front, u64 units, uint8_t* _
     }
   }
   if (!acc) return;                                           // (uniform)
-  kept = wave_reduce(kept, OpAdd{});
-  if (lane == 0) wsum[wib] = kept;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    u64 s = 0;
-#pragma unroll
-    for (int w = 0; w < kSortWaves; ++w) s += wsum[w];
-    if (s) atomicAdd(&acc[blockIdx.x % kReduceSlots], s);
-  }
-}
-extern "C" __global__ void __launch_bounds__(kWave)
-ibu_k_subsample_fold(u64* __restrict__ acc) {                 // leaves the total in acc[0]
-  static_assert(kReduceSlots == kWave, "one lane per slot");
-  const u64 v = wave_reduce(acc[threadIdx.x], OpAdd{});
-  if (threadIdx.x == 0) acc[0] = v;
+  u64 t[1] = {kept};
+  block_accumulate(t, acc, accl);
 }
 
 uint64_t sample_base(uint64_t seed, uint64_t first_row) { return splitmix64(seed) + first_row; }
@@ -303,16 +289,13 @@ uint64_t sample_base(uint64_t seed, uint64_t first_row) { return splitmix64(seed
 hipError_t launch_subsample(const LaunchCfg& cfg, size_t n, uint64_t base, uint64_t threshold, uint8_t* d_class, uint64_t* acc, hipStream_t st) {
   (void)hipGetLastError();
   if (n == 0 || n >= (1ull << 40)) return hipErrorInvalidValue;
-  if (acc) {
-    const hipError_t e = hipMemsetAsync(acc, 0, kSubsampleAccBytes, st);
-    if (e != hipSuccess) return e;
-  }
+  const hipError_t e = zero_totals(acc, 1, st);
+  if (e != hipSuccess) return e;
   u64 front = d_class ? (u64)((16 - (reinterpret_cast<uintptr_t>(d_class) & 15u)) & 15u) : 0;
   front = front < n ? front : n;
   const u64 units = (n - front) / 16;
   hipLaunchKernelGGL(ibu_k_subsample, dim3(capped_grid(cfg, units, kSortThreads)), dim3(kSortThreads), 0, st, (u64)n, (u64)base, (u64)threshold, front, units,
                      d_class, (u64*)acc);
-  if (acc) hipLaunchKernelGGL(ibu_k_subsample_fold, dim3(1), dim3(kWave), 0, st, (u64*)acc);
   return hipGetLastError();
 }
 

@@ -121,8 +121,11 @@ __device__ __forceinline__ u32 wl_search_wave(const WlArgs& a, bool miss, u64 lo
   return cls;
 }
 
-// Totals of a workgroup: lane counters -> wave (shuffles) -> workgroup (LDS) -> one atomic per class and workgroup
-// into slot blockIdx % kReduceSlots of `acc` (kReduceSlots x 4 u64, folded by ibu_k_correct_fold).
+// The totals of ibu_k_correct and its tail, on the path they had before block_accumulate (kcommon.hpp) took over everywhere else:
+// lane counters -> wave (shuffles) -> workgroup (LDS) -> one atomic per class and workgroup into slot blockIdx % kReduceSlots of
+// `acc` (kReduceSlots x 4 u64, folded by ibu_k_correct_fold).  Kept because ibu_k_correct measured 0.5 % slower over 1e9 records
+// with block_accumulate behind its sweep, with no totals asked for: the sweep's register allocation moves with what follows it
+// (profiles/README.md r22_a).
 __device__ __forceinline__ void wl_flush_totals(u32 cnt[4], u64* acc, u32 (*part)[4]) {
   const u32 lane = threadIdx.x & (kWave - 1), wib = threadIdx.x >> 6;
 #pragma unroll
@@ -405,7 +408,7 @@ __device__ __forceinline__ u32 bytes_eq2(u32 w) {
 static constexpr u32 kResolveUnit = 16 * kWave;
 extern "C" __global__ void __launch_bounds__(kBlock, 8)
 ibu_k_resolve(u64* recs, uint8_t* cls, u32 nunits, const WlArgs a, const u64* __restrict__ counters, u64 num, u64 den, u64* __restrict__ acc) {
-  __shared__ u32 part[kWavesPerBlock][4];
+  __shared__ u64 accl[kWavesPerBlock * 4];
   const u32 lane = threadIdx.x & (kWave - 1), wib = threadIdx.x >> 6;
   u32 cnt[4] = {0, 0, 0, 0};
   const TileRange tr = tile_range(nunits, wib);
@@ -419,18 +422,20 @@ ibu_k_resolve(u64* recs, uint8_t* cls, u32 nunits, const WlArgs a, const u64* __
       m16 &= m16 - 1;
     }
   }
-  if (acc) wl_flush_totals(cnt, acc, part);          // uniform over the grid
+  u64 t[4] = {cnt[0], cnt[1], cnt[2], cnt[3]};
+  if (acc) block_accumulate(t, acc, accl);           // uniform over the grid
 }
 
 // One class byte per lane: the bytes in front of the first 16-byte boundary of the class array and the rest behind the last unit.
 extern "C" __global__ void __launch_bounds__(kBlock)
 ibu_k_resolve_tail(u64* recs, uint8_t* cls, u64 row0, u64 row1, const WlArgs a, const u64* __restrict__ counters, u64 num, u64 den,
                    u64* __restrict__ acc) {
-  __shared__ u32 part[kWavesPerBlock][4];
+  __shared__ u64 accl[kWavesPerBlock * 4];
   const u64 i = row0 + (u64)blockIdx.x * kBlock + threadIdx.x;
   u32 cnt[4] = {0, 0, 0, 0};
   resolve_round(a, counters, num, den, recs, cls, i < row1 && cls[i] == 2, i, threadIdx.x & (kWave - 1), cnt);
-  if (acc) wl_flush_totals(cnt, acc, part);
+  u64 t[4] = {cnt[0], cnt[1], cnt[2], cnt[3]};
+  if (acc) block_accumulate(t, acc, accl);
 }
 
 // =============================================================================================
@@ -526,10 +531,12 @@ extern "C" __global__ void ibu_k_label_fold(u64* acc) {
 }
 
 // The label of codes[j] becomes vals[j] (byte stores only); a code that is not in the whitelist or has bits at or above 2*bc_len
-// is skipped and, with skipped != NULL, counted there.
+// is skipped and, with skipped != NULL (uniform over the grid), counted there.  No thread leaves the loop by `return`: all of them
+// reach block_accumulate's barrier.
 extern "C" __global__ void __launch_bounds__(kBlock)
 ibu_k_labels_set(const u64* __restrict__ codes, const uint8_t* __restrict__ vals, u64 k, const WlArgs a, uint8_t* __restrict__ labels,
                  u64* __restrict__ skipped) {
+  __shared__ u64 accl[kWavesPerBlock];
   const u64 stride = (u64)gridDim.x * kBlock, m = mask2(a.bc_len);
   u32 miss = 0;
   for (u64 j = (u64)blockIdx.x * kBlock + threadIdx.x; j < k; j += stride) {
@@ -538,10 +545,8 @@ ibu_k_labels_set(const u64* __restrict__ codes, const uint8_t* __restrict__ vals
     if (s != kNoSlot) labels[s] = vals[j];
     else ++miss;
   }
-  if (skipped) {                                     // uniform over the grid
-    miss = wave_reduce(miss, OpAdd{});
-    if ((threadIdx.x & (kWave - 1)) == 0 && miss) atomicAdd(skipped, (u64)miss);
-  }
+  u64 t[1] = {miss};
+  if (skipped) block_accumulate(t, skipped, accl);
 }
 
 // out[j] = the label of codes[j]; `missing` for a code that is not in the whitelist or has bits at or above 2*bc_len.
@@ -589,14 +594,11 @@ static inline WlArgs wl_args(const WhitelistTable& wl, uint32_t search) {
 hipError_t launch_correct(const LaunchCfg& cfg, const WhitelistTable& wl, void* recs, size_t n, uint32_t max_mismatches, uint8_t* d_class,
                           uint64_t* acc, hipStream_t st) {
   (void)hipGetLastError();
-  if (n == 0) return hipSuccess;
   if (n / kTileRecs > 0xFFFFFFFFull) return hipErrorInvalidValue;
+  const hipError_t e = zero_totals(acc, kCorrectAccBytes / sizeof(u64), st);
+  if (e != hipSuccess || n == 0) return e;
   launch_record_pass<ibu_k_correct, ibu_k_correct_tail>(cfg, recs, n, d_class, CorrectArgs{wl_args(wl, max_mismatches), (u64*)acc}, st);
-  return hipGetLastError();
-}
-hipError_t launch_correct_fold(uint64_t* acc, hipStream_t st) {
-  (void)hipGetLastError();
-  hipLaunchKernelGGL(ibu_k_correct_fold, dim3(1), dim3(kReduceSlots), 0, st, (u64*)acc);
+  if (acc) hipLaunchKernelGGL(ibu_k_correct_fold, dim3(1), dim3(kReduceSlots), 0, st, (u64*)acc);
   return hipGetLastError();
 }
 
@@ -620,7 +622,8 @@ hipError_t launch_abundance_counts(const LaunchCfg& cfg, const WhitelistTable& w
 hipError_t launch_resolve(const LaunchCfg& cfg, const WhitelistTable& wl, const uint64_t* counters, void* recs, size_t n, uint64_t num,
                           uint64_t den, uint8_t* d_class, uint64_t* acc, hipStream_t st) {
   (void)hipGetLastError();
-  if (n == 0) return hipSuccess;
+  const hipError_t e = zero_totals(acc, 4, st);
+  if (e != hipSuccess || n == 0) return e;
   const WlArgs a = wl_args(wl, 1);
   const Span sp[1] = {{d_class, 1}};   // the split is the class bytes': those in front of the first 16-byte boundary are the head
   launch_rows(cfg, sp, 1, n, kResolveUnit,
@@ -639,7 +642,8 @@ static_assert(kLabelAccBytes == (size_t)kReduceSlots * kLabelBins * sizeof(u64),
 hipError_t launch_labels_set(const LaunchCfg& cfg, const WhitelistTable& wl, uint8_t* labels, const uint64_t* codes, const uint8_t* vals, size_t k,
                              uint64_t* skipped, hipStream_t st) {
   (void)hipGetLastError();
-  if (k == 0) return hipSuccess;
+  const hipError_t e = zero_totals(skipped, 1, st);
+  if (e != hipSuccess || k == 0) return e;
   hipLaunchKernelGGL(ibu_k_labels_set, dim3(capped_grid(cfg, k, kBlock)), dim3(kBlock), 0, st, (const u64*)codes, vals, (u64)k, wl_args(wl, 0),
                      labels, (u64*)skipped);
   return hipGetLastError();

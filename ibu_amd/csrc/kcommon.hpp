@@ -607,6 +607,10 @@ static inline void launch_record_pass(const LaunchCfg& cfg, Recs* recs, size_t n
                            ntiles, adv(d_class, head), args);
       });
 }
+// The launcher's half of the grid totals (kernels.h): the K words of a non-NULL acc zeroed on the stream.
+static inline hipError_t zero_totals(uint64_t* acc, size_t k, hipStream_t st) {
+  return acc ? hipMemsetAsync(acc, 0, k * sizeof(uint64_t), st) : hipSuccess;
+}
 // A grid-stride kernel over `items`: the workgroups that cover them once at per_block each, at most blocks_per_cu per CU, at least one.
 static inline u32 capped_grid(const LaunchCfg& cfg, u64 items, u64 per_block, u32 blocks_per_cu = 8) {
   u64 blocks = (items + per_block - 1) / per_block;
@@ -648,6 +652,24 @@ __device__ __forceinline__ void wave_reduce(T (&v)[K], Op op) {
   for (int m = 32; m >= 1; m >>= 1)
 #pragma unroll
     for (int k = 0; k < K; ++k) v[k] = op(v[k], shfl_xor_lanes(v[k], m));
+}
+// K totals of a workgroup of kBlock threads, one u64 per thread and total: per wave with shuffles, per workgroup in LDS, then one
+// atomic per non-zero total and workgroup into acc[k] (kernels.h: "Grid totals").  Every thread of the workgroup calls (a barrier).
+// Static indices only: t stays in registers.
+template <int K>
+__device__ __forceinline__ void block_accumulate(u64 (&t)[K], u64* acc, u64* lds /*[kWavesPerBlock][K]*/) {
+  const u32 lane = threadIdx.x & (kWave - 1), wib = threadIdx.x >> 6;
+  wave_reduce(t, OpAdd{});
+#pragma unroll
+  for (int k = 0; k < K; ++k)
+    if (lane == 0) lds[wib * K + k] = t[k];
+  __syncthreads();
+  if (threadIdx.x < K) {
+    u64 s = 0;
+#pragma unroll
+    for (int w = 0; w < kWavesPerBlock; ++w) s += lds[w * K + threadIdx.x];
+    if (s) atomicAdd(&acc[threadIdx.x], s);
+  }
 }
 // Inclusive scan: lane L gets op(.. op(op(v0, v1), v2) .., vL) for an associative op(front, back).
 template <class T, class Op>

@@ -41,6 +41,11 @@ static inline int resident_blocks(const LaunchCfg& cfg, K kernel, size_t dyn_lds
 }
 
 // All launchers are asynchronous on `st`, allocate nothing and never synchronise.
+// Grid totals.  Where a launcher hands K integer totals back, its `acc` argument (launch_labels_set: `skipped`) is nullable; when it
+// is not NULL it points to K u64 of device memory (launch_correct: kCorrectAccBytes), 8-byte aligned.  The launcher zeroes those
+// words on `st`, its kernels add into them (kcommon.hpp: block_accumulate, one atomic per non-zero total and workgroup), and the
+// totals are acc[0 .. K - 1] when the launcher's last kernel has run.  The host side of "launch, then read the K totals back" is grid_totals (ctx.hpp).  The passes that keep their acc
+// at the front of a run scratch they need anyway (molecules, cells, metrics, launch_feature_filter) say so where they are declared.
 hipError_t launch_decode(const LaunchCfg&, const void* recs, size_t n, uint32_t bc_len, uint32_t umi_len,
                          uint8_t* bc, uint8_t* umi, uint64_t* idx, hipStream_t st);
 hipError_t launch_encode(const LaunchCfg&, const uint8_t* bc, const uint8_t* umi, const uint64_t* idx,
@@ -181,11 +186,11 @@ hipError_t launch_metrics_filter(const LaunchCfg&, const void* recs, size_t n, c
                                  void* scratch, void* run_scratch, uint64_t barcodes, const MetricsLimits& limits, uint8_t* d_class,
                                  hipStream_t st);
 // per-feature metrics and the feature filter (ibu_feature_metrics, ibu_filter_features, k_features.hip).  The feature of a record is
-// the value of its word feature_word (1 or 2); 1 <= n_features <= 2^32.  `acc`: kFeatureAccBytes of device memory, 8-byte aligned,
-// zeroed by the launcher.  launch_feature_count ADDS into the columns (each nullable, n_features u64; d_cells only with
-// feature_word 1) and leaves u64[4] in acc: reads, umis and cells in range, reads out of range.  launch_feature_filter writes the
-// n_features verdict bytes, one class byte per record into d_class (nullable), and leaves in acc the features per verdict [0 .. 2]
-// and, with class_totals, the records per class [4 .. 7].
+// the value of its word feature_word (1 or 2); 1 <= n_features <= 2^32.  launch_feature_count ADDS into the columns (each nullable,
+// n_features u64; d_cells only with feature_word 1); its acc (grid totals, u64[4]): reads, umis and cells in range, reads out of
+// range.  launch_feature_filter writes the n_features verdict bytes and one class byte per record into d_class (nullable); its `acc`
+// is required: kFeatureAccBytes of device memory, 8-byte aligned, zeroed by the launcher, which leaves there the features per
+// verdict [0 .. 2] and, with class_totals, the records per class [4 .. 7].
 struct FeatureLimits {   // = ibu_feature_limits_t (ibu_hip.h)
   uint64_t min_reads, max_reads, min_umis, max_umis, min_cells, max_cells;
 };
@@ -200,9 +205,7 @@ hipError_t launch_feature_filter(const LaunchCfg&, const void* recs, size_t n, u
 // read subsampling and the saturation curve (ibu_subsample_class, ibu_saturation_curve, k_saturation.hip).  The number of a read is
 // splitmix64(base + row) with base = sample_base(seed, first_row); kept at a threshold: ibu_hip.h.
 uint64_t sample_base(uint64_t seed, uint64_t first_row);
-// One class byte per row into d_class (nullable: the count alone).  acc (nullable): kSubsampleAccBytes, 8-byte aligned; the launcher
-// zeroes it and leaves the number of kept rows in its first word.
-static constexpr size_t kSubsampleAccBytes = (size_t)kReduceSlots * sizeof(uint64_t);
+// One class byte per row into d_class (nullable: the count alone).  acc (grid totals, u64[1]): the number of kept rows.
 hipError_t launch_subsample(const LaunchCfg&, size_t n, uint64_t base, uint64_t threshold, uint8_t* d_class, uint64_t* acc, hipStream_t st);
 // The curve at k <= kSaturationMaxPoints non-decreasing thresholds (a host array), one read of the records.  Leaves u64[3][32] —
 // reads, barcodes, molecules of every point — saturation_points_offset() bytes into `scratch` (saturation_scratch_bytes(n) bytes,
@@ -229,15 +232,15 @@ size_t whitelist_slots(size_t w);
 // [1] distinct codes, [2] 1 = the all-ones key is among them.  `table` must be filled with 0xFF bytes.
 hipError_t launch_whitelist_build(const LaunchCfg&, const uint64_t* codes, size_t w, uint32_t bc_len, uint64_t* table, size_t slots,
                                   uint64_t* status, hipStream_t st);
-// acc (nullable): kReduceSlots x 4 u64, zeroed by the caller; launch_correct_fold leaves the four totals in its first four words.
+// acc (grid totals, u64[4]): the records of class 0 .. 3 — exact, corrected, ambiguous, unmatched.  The one acc that is larger than
+// its totals: kCorrectAccBytes, kReduceSlots x 4 u64, which the launcher zeroes and its last kernel folds into the first four words
+// (k_whitelist.hip: wl_flush_totals says why).
 static constexpr size_t kCorrectAccBytes = (size_t)kReduceSlots * 4 * sizeof(uint64_t);
 hipError_t launch_correct(const LaunchCfg&, const WhitelistTable& wl, void* recs, size_t n, uint32_t max_mismatches, uint8_t* d_class,
                           uint64_t* acc, hipStream_t st);
-hipError_t launch_correct_fold(uint64_t* acc, hipStream_t st);
 // abundance and resolve (ibu_abundance_add, ibu_abundance_counts, ibu_resolve_barcodes).  counters: wl.slots + 1 u64, one per table
 // slot and the last for the all-ones key.  add: d_class nullable (every record counts), otherwise the records whose class c < 8 has
-// bit c of class_mask set.  resolve: d_class required; acc (nullable) as for launch_correct — examined, resolved, below the share,
-// unseen — folded by launch_correct_fold.
+// bit c of class_mask set.  resolve: d_class required; acc (grid totals, u64[4]): examined, resolved, below the share, unseen.
 hipError_t launch_abundance_add(const LaunchCfg&, const WhitelistTable& wl, const void* recs, const uint8_t* d_class, size_t n,
                                 uint32_t class_mask, uint64_t* counters, hipStream_t st);
 hipError_t launch_abundance_counts(const LaunchCfg&, const WhitelistTable& wl, const uint64_t* counters, const uint64_t* codes, size_t k,
@@ -245,7 +248,7 @@ hipError_t launch_abundance_counts(const LaunchCfg&, const WhitelistTable& wl, c
 hipError_t launch_resolve(const LaunchCfg&, const WhitelistTable& wl, const uint64_t* counters, void* recs, size_t n, uint64_t num,
                           uint64_t den, uint8_t* d_class, uint64_t* acc, hipStream_t st);
 // labels (ibu_labels_set, ibu_labels_get, ibu_label_records).  labels: wl.slots + 1 bytes, one per table slot and the last for the
-// all-ones key.  set: skipped (nullable) = a device u64, zeroed by the caller, that gets the number of codes skipped.  label_records:
+// all-ones key.  set: skipped (grid totals, u64[1]): the number of codes skipped.  label_records:
 // d_class nullable; acc (nullable): kLabelAccBytes, zeroed by the caller — kReduceSlots x 257 u64, launch_label_fold leaves the 257
 // bins (the labels 0 .. 255, then the records not found) in its first 257 words.
 static constexpr size_t kLabelAccBytes = (size_t)kReduceSlots * 257 * sizeof(uint64_t);
@@ -288,10 +291,9 @@ hipError_t launch_matrix_text_write(const LaunchCfg&, const uint64_t* a, const u
 // launch_matrix_rows_count on the same `scratch`, row_top_scratch_bytes(n) bytes (the scan array, then 88 B per 2048 entries of
 // partial tuples): a reduce pass and a finishing pass for the rows that cross a unit seam; each output is nullable and gets one word
 // per row; `set` (nullable, then set_bits == 0): the bitmap of ibu_barcode_metrics over the values of `second`.
-// launch_matrix_assign: one class byte per row (nullable) and, in acc (nullable, kAssignAccBytes, zeroed by the launcher), u64[3] = the
-// rows of class 0, 1, 2; den >= 1 and num <= den.
+// launch_matrix_assign: one class byte per row (nullable); acc (grid totals, u64[3]): the rows of class 0, 1, 2; den >= 1 and
+// num <= den.
 size_t row_top_scratch_bytes(size_t n);
-static constexpr size_t kAssignAccBytes = 32;
 hipError_t launch_matrix_row_top(const LaunchCfg&, const uint64_t* first, const uint64_t* second, const uint64_t* values, size_t n,
                                  const uint64_t* set, uint64_t set_bits, void* scratch, size_t scratch_bytes, uint64_t* top_key,
                                  uint64_t* top_value, uint64_t* next_value, uint64_t* row_sum, uint64_t* row_entries, hipStream_t st);

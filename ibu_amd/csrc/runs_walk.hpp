@@ -1,8 +1,7 @@
 // runs_walk.hpp — the segment walk over SORTED records that k_aggregate.hip (barcode and pair counts) and k_molecules.hip (one index
 // per molecule) share: the cut of the rows into segments (SegPlan), the count scratch both address (RunsLayout), the walk itself
 // (runs_segment) with the sinks' interface (NoSink) and the sink that keeps the ballots for the class fill (BallotSink), the body of
-// every kernel that runs it (runs_kernel), and the totals of a workgroup (block_accumulate).  k_cells.hip (cell calling) and
-// k_saturation.hip (the saturation curve: a per-run minimum carried from tile to tile through NoSink::records) walk it too, and
+// every kernel that runs it (runs_kernel).  k_cells.hip (cell calling) and k_saturation.hip (the saturation curve: a per-run minimum carried from tile to tile through NoSink::records) walk it too, and
 // k_metrics.hip (per-barcode QC metrics: three levels of heads and a set test, through NoSink::words).
 #pragma once
 #include "kcommon.hpp"
@@ -12,6 +11,7 @@ namespace ibu {
 
 static constexpr int kSortThreads = 256;                      // one wave per segment, four waves per workgroup
 static constexpr int kSortWaves = kSortThreads / kWave;
+static_assert(kSortThreads == kBlock, "the kernels of the walk sum their totals with block_accumulate (kcommon.hpp): a workgroup of kBlock");
 static constexpr int kSegRecs = 8192;
 static constexpr u32 kStashHeads = 32;
 struct __attribute__((aligned(16))) RunStash { u64 barcode; u32 row_off; u32 pair_local; };
@@ -220,23 +220,5 @@ __device__ __forceinline__ void runs_kernel(const u64* __restrict__ recs, const 
 // The scan of per-segment counts (ibu_k_runs_scan, k_aggregate.hip): seg_heads u32[rows][nseg] -> seg_base u64[rows][nseg], the
 // exclusive prefix of every row, and totals[rows], the row sums.  One workgroup per row.
 void launch_runs_scan(const u32* seg_heads, u32 nseg, u32 rows, u64* seg_base, u64* totals, hipStream_t st);
-
-// K totals of a workgroup of kSortThreads, one u64 per thread and total: per wave with shuffles, per workgroup in LDS, then one
-// atomic per non-zero total and workgroup.  Every thread of the workgroup calls (a barrier).  Static indices only: t stays in registers.
-template <int K>
-__device__ __forceinline__ void block_accumulate(u64 (&t)[K], u64* acc, u64* lds /*[kSortWaves][K]*/) {
-  const u32 lane = threadIdx.x & (kWave - 1), wib = threadIdx.x >> 6;
-  wave_reduce(t, OpAdd{});
-#pragma unroll
-  for (int k = 0; k < K; ++k)
-    if (lane == 0) lds[wib * K + k] = t[k];
-  __syncthreads();
-  if (threadIdx.x < K) {
-    u64 s = 0;
-#pragma unroll
-    for (int w = 0; w < kSortWaves; ++w) s += lds[w * K + threadIdx.x];
-    if (s) atomicAdd(&acc[threadIdx.x], s);
-  }
-}
 
 }  // namespace ibu

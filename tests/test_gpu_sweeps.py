@@ -521,6 +521,44 @@ def _counts(cls):
     return {"exact": int(k[0]), "corrected": int(k[1]), "ambiguous": int(k[2]), "unmatched": int(k[3])}
 
 
+def _chain_case(ia, ctx, capfd, rng, wl, bc, bc_len, skew, cls_skew, head, what, every_other=2000):
+    """The chain of test_whitelist_chain on these barcodes, every result and every total against whitelist_np / resolve_np
+    -> the traced rows of (correct, the masked add, resolve), one launch split each."""
+    n = len(bc)
+    recs = rnp.records(rng, bc)
+    want, cls, counts = wnp.correct_records(recs, wl, bc_len, 1)
+    first_tile = np.bincount(cls[head:head + 128], minlength=4)
+    assert (first_tile > 0).all(), first_tile
+    # the counters: exact and corrected reads of these records, then `every_other` reads of every other whitelist entry in a second
+    # call, so that a pair of candidates is either lopsided (resolved) or even (below the share)
+    extra = rnp.records(rng, wnp.with_junk(rng, np.repeat(np.unique(wl)[::2], every_other), bc_len))
+    ab_np = rnp.add(rnp.add(rnp.Abundance(wl, bc_len), want, cls, 0b11), extra)
+    out_np, cls_np, tot_np = rnp.resolve(ab_np, want, cls, 3, 4)
+    assert tot_np["resolved"] > 0 and tot_np["below_share"] > 0 and tot_np["examined"] == counts["ambiguous"]
+    ar = _arena(ia, ctx, 24 * n, n)
+    try:
+        with _whitelist(ia, ctx, wl, bc_len) as h, h.abundance() as ab:
+            d, d_cls = ar.carve(24 * n, skew), ar.carve(n, cls_skew)
+            d.upload(recs)
+            got_counts, rows_c = _traced(ctx, capfd, lambda: ctx.correct_barcodes(h, d, n, 1, d_cls))
+            assert got_counts == counts == _counts(cls)
+            assert (d_cls.download(np.uint8, n) == cls).all() and d.download(count=24 * n).tobytes() == want.tobytes()
+            _, rows_a = _traced(ctx, capfd, lambda: ab.add(d, n, d_cls, 0b11))
+            d_extra = ctx.upload(extra)
+            ab.add(d_extra, len(extra))
+            codes = np.concatenate([np.unique(wl), np.unique(wl)[:64] ^ np.uint64(1)])
+            assert (ab.counts(codes) == rnp.counts(ab_np, codes)).all()
+            tot, rows_r = _traced(ctx, capfd, lambda: ctx.resolve_barcodes(h, ab, d, n, d_cls, (3, 4)))
+            d_extra.free()
+            ar.check(what)
+            assert tot == tot_np
+            assert (d_cls.download(np.uint8, n) == cls_np).all() and d.download(count=24 * n).tobytes() == out_np.tobytes()
+            assert len(rows_c) == len(rows_a) == len(rows_r) == 1
+            return rows_c, rows_a, rows_r
+    finally:
+        ar.free()
+
+
 @pytest.mark.parametrize("skew", SKEWS)
 @pytest.mark.parametrize("kernel", ["correct_add", "resolve"])
 def test_whitelist_chain(ia, ctx, capfd, cus, kernel, skew):
@@ -541,39 +579,35 @@ def test_whitelist_chain(ia, ctx, capfd, cus, kernel, skew):
     n, ntiles, plan = _shape("correct / abundance add" if kernel == "correct_add" else "resolve", cus, tile, head, base)
     rng = np.random.default_rng(0x1B00B00 + skew)
     wl, bc = rnp.make_case(rng, bc_len, w, n)
-    recs = rnp.records(rng, bc)
-    want, cls, counts = wnp.correct_records(recs, wl, bc_len, 1)
-    first_tile = np.bincount(cls[head:head + 128], minlength=4)
-    assert (first_tile > 0).all(), first_tile
-    # the counters: exact and corrected reads of these records, then 2000 reads of every other whitelist entry in a second call, so
-    # that a pair of candidates is either lopsided (resolved) or even (below the share)
-    extra = rnp.records(rng, wnp.with_junk(rng, np.repeat(np.unique(wl)[::2], 2000), bc_len))
-    ab_np = rnp.add(rnp.add(rnp.Abundance(wl, bc_len), want, cls, 0b11), extra)
-    out_np, cls_np, tot_np = rnp.resolve(ab_np, want, cls, 3, 4)
-    assert tot_np["resolved"] > 0 and tot_np["below_share"] > 0 and tot_np["examined"] == counts["ambiguous"]
-    ar = _arena(ia, ctx, 24 * n, n)
-    try:
-        with _whitelist(ia, ctx, wl, bc_len) as h, h.abundance() as ab:
-            d, d_cls = ar.carve(24 * n, skew), ar.carve(n, cls_skew)
-            d.upload(recs)
-            got_counts, rows_c = _traced(ctx, capfd, lambda: ctx.correct_barcodes(h, d, n, 1, d_cls))
-            assert got_counts == counts == _counts(cls)
-            assert (d_cls.download(np.uint8, n) == cls).all() and d.download(count=24 * n).tobytes() == want.tobytes()
-            _, rows_a = _traced(ctx, capfd, lambda: ab.add(d, n, d_cls, 0b11))
-            d_extra = ctx.upload(extra)
-            ab.add(d_extra, len(extra))
-            codes = np.concatenate([np.unique(wl), np.unique(wl)[:64] ^ np.uint64(1)])
-            assert (ab.counts(codes) == rnp.counts(ab_np, codes)).all()
-            tot, rows_r = _traced(ctx, capfd, lambda: ctx.resolve_barcodes(h, ab, d, n, d_cls, (3, 4)))
-            d_extra.free()
-            ar.check(f"whitelist chain {kernel}")
-            assert tot == tot_np
-            assert (d_cls.download(np.uint8, n) == cls_np).all() and d.download(count=24 * n).tobytes() == out_np.tobytes()
-            for r in (rows_c + rows_a if kernel == "correct_add" else rows_r):
-                assert r["tiled"] == ntiles * tile and r["head"] == head and r["rest"] == REST, r
-            assert len(rows_c) == len(rows_a) == len(rows_r) == 1
-    finally:
-        ar.free()
+    rows_c, rows_a, rows_r = _chain_case(ia, ctx, capfd, rng, wl, bc, bc_len, skew, cls_skew, head, f"whitelist chain {kernel}")
+    for r in (rows_c + rows_a if kernel == "correct_add" else rows_r):
+        assert r["tiled"] == ntiles * tile and r["head"] == head and r["rest"] == REST, r
+
+
+@pytest.mark.parametrize("skew", SKEWS)
+@pytest.mark.parametrize("shape", ["waves", "workgroups"])
+def test_whitelist_totals_of_waves_and_workgroups_without_a_tile(ia, ctx, capfd, cus, shape, skew):
+    """The totals of correct and resolve come through a workgroup barrier (k_whitelist.hip: wl_flush_totals; kcommon.hpp:
+    block_accumulate), so a wave that sweeps nothing must still reach it and a workgroup that sweeps nothing must add nothing.  The two shapes of tests/test_gpu_labels.py — waves: 61
+    tiles, three waves of the last workgroup get none; workgroups: 4 cus + 1 tiles, where the CU count is a multiple of 8 the last
+    workgroup gets none — each with a peeled head at skew 8 and a rest of 77 rows, so three launches add into one accumulator.  The
+    same chain as above on a whitelist of 1000 barcodes.  Two per cent of one-base errors give no ambiguous record at 7 885 records
+    (one planted pair among 1000 entries), so the barcodes are resolve_np.make_case's: 20 % one-base errors, 10 % midpoints of the
+    planted pairs, 10 % random — resolve has work in every case, which the chain asserts on the numpy side."""
+    bc_len, w, tile = 16, 1000, 128
+    ntiles = 61 if shape == "waves" else 4 * cus + 1
+    plan = sw.sweep_plan(cus, 1, ntiles)
+    empty_workgroups = [b for b in range(len(plan) // 4) if not any(plan[4 * b:4 * b + 4])]
+    if shape == "waves":
+        assert len(plan) == 64 and [k for k, tiles in enumerate(plan) if not tiles] == [61, 62, 63] and not empty_workgroups
+    else:
+        assert len(plan) == 4 * cus and bool(empty_workgroups) == (cus % 8 == 0), (cus, empty_workgroups)
+    head = 1 if skew else 0
+    n = head + ntiles * tile + REST
+    rng = np.random.default_rng([0x1B00B01, n, skew])
+    wl, bc = rnp.make_case(rng, bc_len, w, n)
+    rows_c, _, _ = _chain_case(ia, ctx, capfd, rng, wl, bc, bc_len, skew, 15 if skew else 0, head, f"whitelist totals {shape}", every_other=200)
+    assert rows_c[0]["tiled"] == ntiles * tile and rows_c[0]["head"] == head and rows_c[0]["rest"] == REST, rows_c
 
 
 # ---- the feature filter's class kernel -------------------------------------------------------------------------------

@@ -166,8 +166,7 @@ def test_kernels_are_in_the_code_object_without_scratch():
     import kernel_resources
     from ibu_amd import _lib
     ks = kernel_resources.all_kernels(_lib.SO_PATH)
-    for k in ("ibu_k_saturation_walk", "ibu_k_saturation_sum", "ibu_k_saturation_stitch", "ibu_k_saturation_points", "ibu_k_subsample",
-              "ibu_k_subsample_fold"):
+    for k in ("ibu_k_saturation_walk", "ibu_k_saturation_sum", "ibu_k_saturation_stitch", "ibu_k_saturation_points", "ibu_k_subsample"):
         assert k in ks, k
         assert ks[k].get("private_segment_fixed_size", 0) == 0 and not ks[k].get("uses_dynamic_stack", 0), (k, ks[k])
 
