@@ -94,9 +94,8 @@ extern "C" __global__ void ibu_k_runs_finish(const u64* __restrict__ starts, con
                                              u64 n_pairs, u64* __restrict__ counts, u64* __restrict__ uniq) {
   const u64 stride = (u64)gridDim.x * blockDim.x;
   for (u64 k = (u64)blockIdx.x * blockDim.x + threadIdx.x; k < n_runs; k += stride) {
-    const bool last = k + 1 == n_runs;
-    counts[k] = (last ? n : starts[k + 1]) - starts[k];
-    if (uniq) uniq[k] = (last ? n_pairs : pair_rank[k + 1]) - pair_rank[k];
+    counts[k] = closed_diff(starts, k, n_runs, n);
+    if (uniq) uniq[k] = closed_diff(pair_rank, k, n_runs, n_pairs);
   }
 }
 

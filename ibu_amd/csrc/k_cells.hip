@@ -34,21 +34,19 @@ struct CellEmit : BallotSink {                                // keeps the ballo
     starts[b] = row;                                          // first record of barcode b
     rank[b] = q;                                              // (barcode, umi) pairs that begin in front of it
   }
-  __device__ __forceinline__ void tile_run_ballots(u64 tile, u64 even, u64 odd) const { keep_tile(tile, even, odd); }
-  __device__ __forceinline__ void end_run_ballots(u32 which, u32 step, u64 m) const { keep_end(which, step, m); }
+  __device__ __forceinline__ void ballots(u64 at, bool tiled, u64 run_even, u64 run_odd, u64, u64) const { keep(at, tiled, run_even, run_odd); }
 };
 extern "C" __global__ void __launch_bounds__(kSortThreads, 8)
 ibu_k_cells_emit(const u64* __restrict__ recs, SegPlan sp, const u64* __restrict__ seg_base /*[2][nseg], scanned*/, u64* __restrict__ starts,
                  u64* __restrict__ rank, u64* __restrict__ masks /*nullable*/) {
-  runs_kernel<1>(recs, sp, seg_base, nullptr, CellEmit{{{}, masks, sp.main / kTileRecs}, starts, rank});
+  runs_kernel<1>(recs, sp, seg_base, nullptr, CellEmit{{{}, masks}, starts, rank});
 }
 
 extern "C" __global__ void __launch_bounds__(kSortThreads)
 ibu_k_cells_table(const u64* __restrict__ starts, const u64* __restrict__ rank, u64 nb, u64 n, u64 npairs, u32 by_reads, u64* __restrict__ metric) {
   const u64* src = by_reads ? starts : rank;
-  const u64 end = by_reads ? n : npairs;
   const u64 stride = (u64)gridDim.x * blockDim.x;
-  for (u64 b = (u64)blockIdx.x * blockDim.x + threadIdx.x; b < nb; b += stride) metric[b] = (b + 1 == nb ? end : src[b + 1]) - src[b];
+  for (u64 b = (u64)blockIdx.x * blockDim.x + threadIdx.x; b < nb; b += stride) metric[b] = closed_diff(src, b, nb, by_reads ? n : npairs);
 }
 
 // ---- rank selection: state u64[2] = (prefix: the digits decided so far, the rank that remains among the values under that prefix)
@@ -158,15 +156,14 @@ hipError_t launch_rank_select(const LaunchCfg& cfg, const uint64_t* values, uint
 // run scratch: acc u64[8] | selection work | starts u64[B] | rank u64[B] | metric u64[B] | verdict bytes
 struct CellLayout { size_t select, starts, rank, metric, verdict, bytes; };
 static CellLayout cell_layout(uint64_t nb) {
-  auto up = [](size_t x) { return (x + 15) & ~(size_t)15; };
   const size_t b = nb ? nb : 1;
   CellLayout L;
   L.select = 64;
-  L.starts = up(L.select + rank_select_work_bytes());
+  L.starts = align_up(L.select + rank_select_work_bytes(), 16);
   L.rank = L.starts + 8 * b;
   L.metric = L.rank + 8 * b;
   L.verdict = L.metric + 8 * b;
-  L.bytes = up(L.verdict + b + 4);
+  L.bytes = align_up(L.verdict + b + 4, 16);
   return L;
 }
 size_t cells_run_scratch_bytes(uint64_t barcodes) { return cell_layout(barcodes).bytes; }

@@ -1,7 +1,7 @@
 // k_features.hip — ibu_feature_metrics and ibu_filter_features: the other axis of the count matrix.  Per FEATURE (the value f of a
 // record's word feature_word, 1 or 2) its reads, its UMIs (triples) and the cells (pairs) it was seen in, and the filter that drops
 // the features seen in too few cells — include/ibu_hip.h has the rules in full.  Three kernels:
-//   count    the D = 2 walk of runs_walk.hpp with FeatureSink on NoSink::words.  Inside a step the records of a GROUP are adjacent
+//   count    the D = 2 walk of runs_walk.hpp with FeatureSink on NoSink::step.  Inside a step the records of a GROUP are adjacent
 //            (feature_word 1: a pair; 2: a triple; and whatever the step's first record continues), so the lane that holds a group's
 //            first record takes the group's extent and its triple heads from the step's head ballots — kcommon.hpp, next_head,
 //            as ibu_k_abundance_add merges the runs of a tile — and issues at most three 8-byte integer atomics into the
@@ -29,7 +29,6 @@ struct FeatureCols { u64* reads; u64* umis; u64* cells; u64 nf; u32 word; };   /
 // even positions alone and a distance of positions is twice a distance of records.
 struct FeatureSink : NoSink {
   FeatureCols c;
-  u32 lane;
   mutable u64 t_reads, t_umis, t_cells, t_out;                // per lane: in-range reads, umis, cells; reads out of range
   // the group of feature f over positions [pos, next): te / to = the step's ballots of triple heads at even / odd positions
   __device__ __forceinline__ void group(u64 f, u32 pos, u32 next, bool pair, bool pair_head, u64 te, u64 to) const {
@@ -48,29 +47,24 @@ struct FeatureSink : NoSink {
     // and the four of them live in scratch memory
     t_reads += in ? records : 0; t_umis += in ? heads : 0; t_cells += in && cell ? 1 : 0; t_out += in ? 0 : records;
   }
-  __device__ __forceinline__ void words(u64, const Rec& a, bool va, bool, bool a1, bool a2, const Rec& b, bool, bool b1, bool b2, bool pair) const {
-    const bool ga = va && (lane == 0 || (c.word == 1 ? a1 : a2));   // (wave-uniform choice) the step's first record begins a group too
-    const bool gb = pair && (c.word == 1 ? b1 : b2);
-    const u64 ge = __ballot(ga), go = __ballot(gb), te = __ballot(a2), to = __ballot(b2);
-    const u32 end = 2u * (u32)__popcll(__ballot(va));         // the valid lanes are the first ones
+  __device__ __forceinline__ void step(const WalkStep& s) const {
+    const u32 lane = s.lane;
+    const bool ga = s.va && (lane == 0 || (c.word == 1 ? s.a1 : s.a2));   // (wave-uniform choice) the step's first record begins a group too
+    const bool gb = s.pair && (c.word == 1 ? s.b1 : s.b2);
+    const u64 ge = __ballot(ga), go = __ballot(gb), te = __ballot(s.a2), to = __ballot(s.b2);
+    const u32 end = 2u * (u32)__popcll(__ballot(s.va));       // the valid lanes are the first ones
     const u32 next = next_head(ge, go, lane, end);            // the first group head behind this lane's records, or the step's end
-    if (ga) group(c.word == 1 ? a.w1 : a.w2, 2 * lane, gb ? 2 * lane + 1 : next, pair, a1, te, to);
-    if (gb) group(c.word == 1 ? b.w1 : b.w2, 2 * lane + 1, next, pair, b1, te, to);
+    if (ga) group(c.word == 1 ? s.a.w1 : s.a.w2, 2 * lane, gb ? 2 * lane + 1 : next, s.pair, s.a1, te, to);
+    if (gb) group(c.word == 1 ? s.b.w1 : s.b.w2, 2 * lane + 1, next, s.pair, s.b1, te, to);
   }
 };
 
 // acc (nullable, uniform over the grid; block_accumulate): [0] reads in range, [1] umis in range, [2] cells in range, [3] reads out of range
 extern "C" __global__ void __launch_bounds__(kSortThreads, 4)
 ibu_k_feature_count(const u64* __restrict__ recs, SegPlan sp, FeatureCols cols, u64* __restrict__ acc) {
-  __shared__ __attribute__((aligned(16))) uint8_t lds[kSortWaves * kTileBytes];
   __shared__ u64 accl[kSortWaves * 4];
-  const u32 lane = threadIdx.x & (kWave - 1), wib = threadIdx.x >> 6;
-  const u32 seg = wave_segment();
-  const FeatureSink sink{{}, cols, lane, 0, 0, 0, 0};
-  if (seg < sp.nseg) {                                        // wave-uniform; no return: every thread reaches the barrier below
-    u64 c1, c2;
-    runs_segment<2>(recs, sp, seg, lds + wib * kTileBytes, lane, 0, 0, c1, c2, sink);
-  }
+  const FeatureSink sink{{}, cols, 0, 0, 0, 0};
+  walk_wave<2>(recs, sp, nullptr, sink, [](u32, u32, SegCounts) {});   // (a wave without a segment comes back too: the barrier below)
   u64 t[4] = {sink.t_reads, sink.t_umis, sink.t_cells, sink.t_out};
   if (acc) block_accumulate(t, acc, accl);
 }
@@ -139,7 +133,7 @@ bool feature_args_ok(uint32_t feature_word, uint64_t n_features) {
   return (feature_word == 1 || feature_word == 2) && n_features >= 1 && n_features <= (1ull << 32);
 }
 // run scratch: acc u64[16] | verdict bytes (when the caller keeps no table of its own)
-size_t feature_run_scratch_bytes(uint64_t verdict_bytes) { return (kFeatureAccBytes + verdict_bytes + 15) & ~(size_t)15; }
+size_t feature_run_scratch_bytes(uint64_t verdict_bytes) { return align_up(kFeatureAccBytes + verdict_bytes, 16); }
 
 hipError_t launch_feature_count(const LaunchCfg& cfg, const void* recs, size_t n, uint32_t feature_word, uint64_t n_features, uint64_t* d_reads,
                                 uint64_t* d_umis, uint64_t* d_cells, uint64_t* acc, hipStream_t st) {

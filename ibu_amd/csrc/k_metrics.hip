@@ -3,7 +3,7 @@
 // equal (w0, w1), a triple a run of equal (w0, w1, w2); the set is a bitmap — include/ibu_hip.h has the rules in full.  The records
 // are read twice and nothing goes to the host between the steps but the barcode total:
 //   count    the D = 2 walk of runs_walk.hpp (its run heads are pair heads, its ranked heads triple heads) with MetricsSink on
-//            NoSink::words, the hook that brings the records' words and the barcode-head flag: five counters per segment — barcode
+//            NoSink::step, which brings the records' words and the barcode-head flag: five counters per segment — barcode
 //            heads, pair heads, triple heads, records in the set, triple heads in the set — carried in the sink from step to step
 //            as k_saturation.hip carries its state.  ibu_k_runs_scan of k_aggregate.hip turns the five rows into bases and totals; the totals go
 //            back to the host to size the table.
@@ -35,7 +35,7 @@ struct FeatureSet {
 template <bool EMIT>
 struct MetricsSink : BallotSink {
   FeatureSet set;
-  u64 lt_mask;
+  u64 lt_mask;                                                // (a member, not made from WalkStep::lane in the step: 78 VGPRs for 76 that way)
   u64* barcode /*nullable*/; u64* prefix; u64 nb;
   mutable u64 n0, n1, n2, n3, n4;                             // wave-uniform, carried from step to step
   mutable u64 bar_even, bar_odd;                              // the step's ballots of barcode heads
@@ -47,9 +47,10 @@ struct MetricsSink : BallotSink {
     prefix[3 * nb + k] = r3;
     prefix[4 * nb + k] = r4;
   }
-  __device__ __forceinline__ void words(u64 row, const Rec& a, bool va, bool a0, bool a1, bool a2, const Rec& b, bool b0, bool b1, bool b2,
-                                        bool pair) const {
-    const bool a3 = va && set.has(a), b3 = pair && set.has(b);
+  __device__ __forceinline__ void step(const WalkStep& s) const {
+    const Rec &a = s.a, &b = s.b;
+    const bool a0 = s.a0, a1 = s.a1, a2 = s.a2, b0 = s.b0, b1 = s.b1, b2 = s.b2;
+    const bool a3 = s.va && set.has(a), b3 = s.pair && set.has(b);
     const bool a4 = a3 && a2, b4 = b3 && b2;
     const u64 m0a = __ballot(a0), m0b = __ballot(b0), m1a = __ballot(a1), m1b = __ballot(b1), m2a = __ballot(a2), m2b = __ballot(b2);
     const u64 m3a = __ballot(a3), m3b = __ballot(b3), m4a = __ballot(a4), m4b = __ballot(b4);
@@ -61,8 +62,8 @@ struct MetricsSink : BallotSink {
         const u64 r2 = n2 + (u64)(__popcll(m2a & lt_mask) + __popcll(m2b & lt_mask));
         const u64 r3 = n3 + (u64)(__popcll(m3a & lt_mask) + __popcll(m3b & lt_mask));
         const u64 r4 = n4 + (u64)(__popcll(m4a & lt_mask) + __popcll(m4b & lt_mask));
-        if (a0) put(k, a.w0, row, r1, r2, r3, r4);
-        if (b0) put(k + (a0 ? 1 : 0), b.w0, row + 1, r1 + (a1 ? 1 : 0), r2 + (a2 ? 1 : 0), r3 + (a3 ? 1 : 0), r4 + (a4 ? 1 : 0));
+        if (a0) put(k, a.w0, s.row, r1, r2, r3, r4);
+        if (b0) put(k + (a0 ? 1 : 0), b.w0, s.row + 1, r1 + (a1 ? 1 : 0), r2 + (a2 ? 1 : 0), r3 + (a3 ? 1 : 0), r4 + (a4 ? 1 : 0));
       }
     }
     n0 += (u64)(__popcll(m0a) + __popcll(m0b));
@@ -71,9 +72,8 @@ struct MetricsSink : BallotSink {
     n3 += (u64)(__popcll(m3a) + __popcll(m3b));
     n4 += (u64)(__popcll(m4a) + __popcll(m4b));
   }
-  // the class fill wants the ballots of BARCODE heads, which the walk does not know: kept from `words` of the same step
-  __device__ __forceinline__ void tile_run_ballots(u64 tile, u64, u64) const { if constexpr (EMIT) keep_tile(tile, bar_even, bar_odd); }
-  __device__ __forceinline__ void end_run_ballots(u32 which, u32 step, u64) const { if constexpr (EMIT) keep_end(which, step, bar_even); }
+  // the class fill wants the ballots of BARCODE heads, which the walk does not take: kept from `step` of the same step
+  __device__ __forceinline__ void ballots(u64 at, bool tiled, u64, u64, u64, u64) const { if constexpr (EMIT) keep(at, tiled, bar_even, bar_odd); }
 };
 
 static constexpr u32 kMetricRows = 5;
@@ -81,39 +81,30 @@ static constexpr u32 kMetricRows = 5;
 // seg_heads: u32[5][nseg], the segment's five counters
 extern "C" __global__ void __launch_bounds__(kSortThreads, 4)
 ibu_k_metrics_count(const u64* __restrict__ recs, SegPlan sp, FeatureSet set, u32* __restrict__ seg_heads) {
-  __shared__ __attribute__((aligned(16))) uint8_t lds[kSortWaves * kTileBytes];
-  const u32 lane = threadIdx.x & (kWave - 1), wib = threadIdx.x >> 6;
-  const u32 seg = wave_segment();
-  if (seg >= sp.nseg) return;                                 // wave-uniform
-  const MetricsSink<false> sink{{{}, nullptr, 0}, set, 0, nullptr, nullptr, 0, 0, 0, 0, 0, 0, 0, 0};
-  u64 c1, c2;
-  runs_segment<2>(recs, sp, seg, lds + wib * kTileBytes, lane, 0, 0, c1, c2, sink);
-  if (lane == 0) {
+  const MetricsSink<false> sink{{{}, nullptr}, set, 0, nullptr, nullptr, 0, 0, 0, 0, 0, 0, 0, 0};
+  walk_wave<2>(recs, sp, nullptr, sink, [&](u32 seg, u32 lane, SegCounts) {
+    if (lane != 0) return;
     seg_heads[seg] = (u32)sink.n0;
     seg_heads[sp.nseg + seg] = (u32)sink.n1;
     seg_heads[2 * sp.nseg + seg] = (u32)sink.n2;
     seg_heads[3 * sp.nseg + seg] = (u32)sink.n3;
     seg_heads[4 * sp.nseg + seg] = (u32)sink.n4;
-  }
+  });
 }
 
 extern "C" __global__ void __launch_bounds__(kSortThreads, 4)
 ibu_k_metrics_emit(const u64* __restrict__ recs, SegPlan sp, FeatureSet set, const u64* __restrict__ base0, const u64* __restrict__ base14,
                    u64* __restrict__ barcode /*nullable*/, u64* __restrict__ prefix /*[5][nb]*/, u64 nb, u64* __restrict__ masks /*nullable*/) {
-  __shared__ __attribute__((aligned(16))) uint8_t lds[kSortWaves * kTileBytes];
-  const u32 lane = threadIdx.x & (kWave - 1), wib = threadIdx.x >> 6;
   const u32 seg = wave_segment();
-  if (seg >= sp.nseg) return;                                 // wave-uniform
-  const MetricsSink<true> sink{{{}, masks, sp.main / kTileRecs}, set, (1ull << lane) - 1, barcode, prefix, nb, base0[seg], base14[seg],
+  if (seg >= sp.nseg) return;                                 // wave-uniform: the five bases are read here, in front of the walk
+  const MetricsSink<true> sink{{{}, masks}, set, (1ull << (threadIdx.x & (kWave - 1))) - 1, barcode, prefix, nb, base0[seg], base14[seg],
                                base14[sp.nseg + seg], base14[2 * sp.nseg + seg], base14[3 * sp.nseg + seg], 0, 0};
-  u64 c1, c2;
-  runs_segment<2>(recs, sp, seg, lds + wib * kTileBytes, lane, 0, 0, c1, c2, sink);
+  walk_wave<2>(recs, sp, nullptr, sink, [](u32, u32, SegCounts) {});
 }
 
 // column c of barcode k: prefix[c][k + 1] - prefix[c][k]; the row behind the last barcode is (n, totals[1 .. 4])
 __device__ __forceinline__ u64 metric_at(const u64* __restrict__ prefix, u64 nb, u64 n, const u64* __restrict__ totals, u32 c, u64 k) {
-  const u64* col = prefix + (size_t)c * nb;
-  return (k + 1 == nb ? (c == 0 ? n : totals[c]) : col[k + 1]) - col[k];
+  return closed_diff(prefix + (size_t)c * nb, k, nb, c == 0 ? n : totals[c]);
 }
 extern "C" __global__ void __launch_bounds__(kSortThreads)
 ibu_k_metrics_table(const u64* __restrict__ prefix, u64 nb, u64 n, const u64* __restrict__ totals, u64* __restrict__ reads, u64* __restrict__ pairs,
@@ -180,7 +171,7 @@ static MetricsRunLayout metrics_run_layout(uint64_t nb) {
   MetricsRunLayout L;
   L.prefix = 128;
   L.verdict = L.prefix + kMetricRows * sizeof(u64) * b;
-  L.bytes = (L.verdict + b + 15) & ~(size_t)15;
+  L.bytes = align_up(L.verdict + b, 16);
   return L;
 }
 size_t metrics_scratch_bytes(size_t n) { return metrics_layout(n).bytes; }

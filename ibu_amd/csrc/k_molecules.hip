@@ -99,13 +99,12 @@ __device__ __forceinline__ void mol_tally(u64 (&t)[5], u32 cls, u64 reads, bool 
 struct MolEmit : BallotSink {                               // keeps the ballots of triple heads
   u64* table;
   __device__ __forceinline__ void head(u64, u64 c, u64 row, u64, u64, bool mol_head) const { table[c] = row | (mol_head ? kMolHead : 0); }
-  __device__ __forceinline__ void tile_ballots(u64 tile, u64 even, u64 odd) const { keep_tile(tile, even, odd); }
-  __device__ __forceinline__ void end_ballots(u32 which, u32 step, u64 m) const { keep_end(which, step, m); }
+  __device__ __forceinline__ void ballots(u64 at, bool tiled, u64, u64, u64 even, u64 odd) const { keep(at, tiled, even, odd); }
 };
 extern "C" __global__ void __launch_bounds__(kSortThreads, 8)
 ibu_k_molecules_emit(const u64* __restrict__ recs, SegPlan sp, const u64* __restrict__ seg_base /*[2][nseg], scanned*/, u64* __restrict__ table,
                      u64* __restrict__ masks /*nullable*/) {
-  runs_kernel<2>(recs, sp, seg_base, nullptr, MolEmit{{{}, masks, sp.main / kTileRecs}, table});
+  runs_kernel<2>(recs, sp, seg_base, nullptr, MolEmit{{{}, masks}, table});
 }
 
 // What a verdict block leaves for the chain scan: the aggregate of the candidates in front of its first molecule head (`lead`, all
@@ -266,13 +265,12 @@ static MolLayout mol_layout(uint64_t ncand) {
   MolLayout L;
   L.nblk = (u32)((ncand + kMolBlock - 1) / kMolBlock);
   const size_t nb = L.nblk ? L.nblk : 1;
-  auto up = [](size_t x) { return (x + 15) & ~(size_t)15; };
   L.table = 64;
-  L.verdict = up(L.table + 8 * (size_t)(ncand ? ncand : 1));
-  L.summary = up(L.verdict + (size_t)ncand + 4);
-  L.chain_start = up(L.summary + sizeof(MolSummary) * nb);
-  L.chain_full = up(L.chain_start + sizeof(u32) * nb);
-  L.bytes = up(L.chain_full + sizeof(MolFull) * nb);
+  L.verdict = align_up(L.table + 8 * (size_t)(ncand ? ncand : 1), 16);
+  L.summary = align_up(L.verdict + (size_t)ncand + 4, 16);
+  L.chain_start = align_up(L.summary + sizeof(MolSummary) * nb, 16);
+  L.chain_full = align_up(L.chain_start + sizeof(u32) * nb, 16);
+  L.bytes = align_up(L.chain_full + sizeof(MolFull) * nb, 16);
   return L;
 }
 size_t molecules_run_scratch_bytes(uint64_t candidates) { return mol_layout(candidates).bytes; }

@@ -106,18 +106,10 @@ ibu_k_swap_fields(const uint8_t* src, u32 ntiles, uint8_t* dst) {
   const u32 lane = threadIdx.x & (kWave - 1);
   const u32 wib = threadIdx.x >> 6;
   uint8_t* tile = lds + wib * kTileBytes;
-  sweep_tiles<RecRegs>(
-      tile_range(ntiles, wib),
-      [&](RecRegs& g, u32 t) {
-        const uint8_t* p = src + (size_t)t * kTileBytes + 16 * lane;
-#pragma unroll
-        for (int k = 0; k < 3; ++k) g.v[k] = ld16(p + 1024 * k);
-      },
-      [&](const RecRegs& g, u32 t) {
-        wave_lds_fence();
-#pragma unroll
-        for (int k = 0; k < 3; ++k) *reinterpret_cast<u32x4*>(tile + 1024 * k + 16 * lane) = g.v[k];
-        wave_lds_fence();
+  sweep_tiles<TileRegs>(
+      tile_range(ntiles, wib), [&](TileRegs& g, u32 t) { load_tile(g, src + (size_t)t * kTileBytes + 16 * lane); },
+      [&](const TileRegs& g, u32 t) {
+        land_tile(tile, g, lane);
 #pragma unroll
         for (int h = 0; h < 2; ++h) {
           u64* r = reinterpret_cast<u64*>(tile + (lane + 64 * h) * 24);

@@ -76,14 +76,15 @@ __device__ __forceinline__ u32 sat_tally(u32 bin, bool valid, u32 lane, u32 nbit
 struct SatSink : NoSink {
   const u64* T;                                               // the wave's thresholds in LDS
   u64 base, end;                                              // u(row) = splitmix64(base + row); the first row behind the segment
-  u32 lane, nbits;                                            // 2^nbits >= K + 1
+  u32 lane, nbits;                                            // 2^nbits >= K + 1.  (its own lane and end, not WalkStep's lane and va: 82 VGPRs for 80 with those)
   // carried from step to step (wave-uniform but for `lead` and the tallies)
   mutable u32 open1, open2;                                   // the min of the run open at the end of the rows walked so far
   mutable u32 seen1, seen2;                                   // kSatFlag once the segment has had a head
   mutable u32 lead1, lead2;                                   // in the one lane that met the segment's first head: the min in front of it
   mutable u32 reads, runs1, runs2;                            // lane j: reads / closed runs of bin j
-  __device__ __forceinline__ void records(u64 row, bool a1, bool a2, bool b1, bool b2, bool pair) const {
-    const bool va = row < end;
+  __device__ __forceinline__ void step(const WalkStep& s) const {
+    const u64 row = s.row;
+    const bool va = row < end, a1 = s.a1, a2 = s.a2, b1 = s.b1, b2 = s.b2, pair = s.pair;
     const u32 ba = va ? sat_bin(T, splitmix64(base + row), nbits) : kSatNone;
     const u32 bb = pair ? sat_bin(T, splitmix64(base + row + 1), nbits) : kSatNone;
     reads += sat_tally(ba, va, lane, nbits);
@@ -138,32 +139,30 @@ struct SatThresholds { u64 t[kSaturationMaxPoints]; };        // the entries beh
 extern "C" __global__ void __launch_bounds__(kSortThreads, 4)
 ibu_k_saturation_walk(const u64* __restrict__ recs, SegPlan sp, SatThresholds th, u32 nbits, u64 base, u32* __restrict__ hist /*[nseg][kSatRow]*/,
                       u32* __restrict__ summary /*[nseg][2]*/) {
-  __shared__ __attribute__((aligned(16))) uint8_t lds[kSortWaves * kTileBytes];
   __shared__ u64 search[kSortWaves][kSatSearch];
   const u32 lane = threadIdx.x & (kWave - 1), wib = threadIdx.x >> 6;
-  const u32 seg = wave_segment();
-  if (seg >= sp.nseg) return;                                 // wave-uniform
   u64 mine = ~0ull;
 #pragma unroll
   for (u32 j = 0; j < kSaturationMaxPoints; ++j) mine = lane == j ? th.t[j] : mine;   // (static indices: the thresholds stay kernel arguments)
   search[wib][lane] = mine;
   wave_lds_fence();
+  const u32 seg = wave_segment();
   const u64 stop = sp.head + sp.main, first = seg_first_row(sp, seg);
   const u64 end = seg == 0 ? sp.head : seg == sp.nseg - 1 ? sp.n : (first + kSegRecs < stop ? first + kSegRecs : stop);
   const SatSink sink{{}, search[wib], base, end, lane, nbits, kSatNone, kSatNone, 0, 0, kSatNone, kSatNone, 0, 0, 0};
-  u64 c1, c2;
-  runs_segment<1>(recs, sp, seg, lds + wib * kTileBytes, lane, 0, 0, c1, c2, sink);
-  const u32 lead1 = wave_reduce(sink.lead1, OpMin{}), lead2 = wave_reduce(sink.lead2, OpMin{});
-  u32* row = hist + (size_t)seg * kSatRow;
-  if (lane < kSatBins) {                                      // (the counters above bin K are never read: sat_tally)
-    row[lane] = sink.reads;
-    row[kSatBins + lane] = sink.runs1;
-    row[2 * kSatBins + lane] = sink.runs2;
-  }
-  if (lane == 0) {
-    summary[2 * (size_t)seg] = sat_summary(sink.seen1, lead1, sink.open1);
-    summary[2 * (size_t)seg + 1] = sat_summary(sink.seen2, lead2, sink.open2);
-  }
+  walk_wave<1>(recs, sp, nullptr, sink, [&](u32 seg, u32 lane, SegCounts) {   // (the walk's seg and lane from here on)
+    const u32 lead1 = wave_reduce(sink.lead1, OpMin{}), lead2 = wave_reduce(sink.lead2, OpMin{});
+    u32* row = hist + (size_t)seg * kSatRow;
+    if (lane < kSatBins) {                                    // (the counters above bin K are never read: sat_tally)
+      row[lane] = sink.reads;
+      row[kSatBins + lane] = sink.runs1;
+      row[2 * kSatBins + lane] = sink.runs2;
+    }
+    if (lane == 0) {
+      summary[2 * (size_t)seg] = sat_summary(sink.seen1, lead1, sink.open1);
+      summary[2 * (size_t)seg + 1] = sat_summary(sink.seen2, lead2, sink.open2);
+    }
+  });
 }
 
 // totals: u64[3][kSatBins] (reads, barcodes, molecules by bin), zeroed by the launcher
@@ -307,7 +306,7 @@ static SatLayout sat_layout(size_t n) {
   SatLayout L;
   L.points = 1024;
   L.summary = 2048;
-  L.hist = (L.summary + 2 * sizeof(u32) * cap + 15) & ~(size_t)15;
+  L.hist = align_up(L.summary + 2 * sizeof(u32) * cap, 16);
   L.bytes = L.hist + sizeof(u32) * kSatRow * cap;
   return L;
 }

@@ -196,21 +196,25 @@ __device__ __forceinline__ void wave_lds_fence() {
 // head of this file are kept HERE: nothing branches around the loads, and the fence pair keeps the stage behind the previous
 // body's reads and the body's reads behind the stage.  Whatever every thread of a workgroup must reach (a histogram clear, a
 // totals flush) stays in the kernel, around the call: a wave without a tile returns from the sweep at once.
+// The STAGE, written once (the segment walk of runs_walk.hpp uses it too): load_tile issues a tile's three loads, src = the tile's
+// first byte + 16 * lane; land_tile puts them in the slice between the two fences.
 struct TileRegs { u32x4 v[3]; };
+__device__ __forceinline__ void load_tile(TileRegs& g, const uint8_t* src) {
+  g.v[0] = ld16(src); g.v[1] = ld16(src + 1024); g.v[2] = ld16(src + 2048);
+}
+__device__ __forceinline__ void land_tile(uint8_t* tile, const TileRegs& g, u32 lane) {
+  wave_lds_fence();
+  *reinterpret_cast<u32x4*>(tile + 16 * lane) = g.v[0];
+  *reinterpret_cast<u32x4*>(tile + 1024 + 16 * lane) = g.v[1];
+  *reinterpret_cast<u32x4*>(tile + 2048 + 16 * lane) = g.v[2];
+  wave_lds_fence();
+}
 template <class Body>
 __device__ __forceinline__ void sweep_records(const uint8_t* recs, u32 ntiles, uint8_t* tile, u32 lane, u32 wib, Body body) {
   sweep_tiles<TileRegs>(
-      tile_range(ntiles, wib),
-      [&](TileRegs& g, u32 t) {
-        const uint8_t* src = recs + (size_t)t * kTileBytes + 16 * lane;
-#pragma unroll
-        for (int k = 0; k < 3; ++k) g.v[k] = ld16(src + 1024 * k);
-      },
+      tile_range(ntiles, wib), [&](TileRegs& g, u32 t) { load_tile(g, recs + (size_t)t * kTileBytes + 16 * lane); },
       [&](const TileRegs& g, u32 t) {
-        wave_lds_fence();
-#pragma unroll
-        for (int k = 0; k < 3; ++k) *reinterpret_cast<u32x4*>(tile + 1024 * k + 16 * lane) = g.v[k];
-        wave_lds_fence();
+        land_tile(tile, g, lane);
         body(t);
       });
 }
@@ -534,6 +538,7 @@ static inline u32 grid_for(u32 ntiles, int cus, int blocks_per_cu) {
   return need < cap ? (need ? need : 1) : cap;
 }
 static inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
+static inline size_t align_up(size_t x, size_t a) { return (x + a - 1) & ~(a - 1); }   // a: a power of two (the scratch layouts)
 
 // Peeling.  The tiled kernels need every array 16-B aligned.  A resident shard that starts at an odd record of a
 // larger buffer (perfectly legal: the reference's split gives `per = len / n`, mmap.rs:297-307) is 8-B but not 16-B

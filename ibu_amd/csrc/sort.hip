@@ -74,15 +74,14 @@ static SortLayout sort_layout(const LaunchCfg& cfg, size_t n, int tile) {
   L.tpb = tiles_per_block(nt);
   L.nblocks = (u32)((nt + L.tpb - 1) / L.tpb);
   L.idx64 = n >= (1ull << 32) || cfg.sort_idx64;             // cfg.sort_idx64: a test knob (the 64-bit index kernels at small sizes)
-  auto up = [](size_t x) { return (x + 255) & ~(size_t)255; };
   size_t o = kCensusBytes;                                   // the census slots sit in front
-  L.misc = o; o = up(o + kMiscBytes);
-  L.binbase = o; o = up(o + 8 * kBins);
-  L.blocksum = o; o = up(o + 4 * (size_t)L.nblocks * kBins);
-  L.blockoff = o; o = up(o + 8 * (size_t)L.nblocks * kBins);
-  L.counts = o; o = up(o + 2 * (size_t)nt * kBins);
-  L.pos = o; o = up(o + (L.idx64 ? 8 : 4) * (size_t)nt * kBins);
-  L.digits = o; o = up(o + (size_t)nt * tile + 1024);
+  L.misc = o; o = align_up(o + kMiscBytes, 256);
+  L.binbase = o; o = align_up(o + 8 * kBins, 256);
+  L.blocksum = o; o = align_up(o + 4 * (size_t)L.nblocks * kBins, 256);
+  L.blockoff = o; o = align_up(o + 8 * (size_t)L.nblocks * kBins, 256);
+  L.counts = o; o = align_up(o + 2 * (size_t)nt * kBins, 256);
+  L.pos = o; o = align_up(o + (L.idx64 ? 8 : 4) * (size_t)nt * kBins, 256);
+  L.digits = o; o = align_up(o + (size_t)nt * tile + 1024, 256);
   L.total = o;
   return L;
 }
